@@ -6,22 +6,27 @@ batch = 8 pairs per GPU, symmetric, synthetic N(0,1) images and seeded synthetic
 pretrained weights / datasets offline).  Precision = the arithmetic that timing script really
 runs (--dtype mixed, the default): its amp_dtype=bfloat16 reaches DINOv2 only
 (roma_models.py:183-188), VGG / decoder / refiners autocast to float16 (encoders.py:7,
-matcher.py:46,341) - ROMA_MIXED.  All-bfloat16 (--dtype bf16) is timed under other_configs.  A "step" = one match() over one batch,
+matcher.py:46,341) - ROMA_MIXED.  All-bfloat16 (--dtype bf16) is timed under other_configs (--full).  A "step" = one match() over one batch,
 inputs already resident in HBM.  N > 1: one process per GPU, pairs sharded 8 per GPU (weak
 scaling), the only collective is the RCCL gather of the results.
 
     python bench.py                                           # N = 1, 50 timed steps after 10 warm-ups
+    python bench.py --full                                    # the same, plus every extra measurement listed below
     python bench.py --gpus 8 --steps 20 --warmup 3            # re-executes itself under torch.distributed.run
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 20 --warmup 3
     python bench.py --config coarse --batch 1                 # BASELINE config 2 (coarse-only 560, B = 1)
     python bench.py --gpus 2 --dry                            # CPU / gloo: launch + shard + gather logic only
+    python bench.py --dump-outputs out/                       # also write the last timed step's outputs as .npy
 
-Rank 0 prints ONE JSON line.  Besides the driver contract it carries
-  roofline      dominant kernel: algorithmic FLOP/s (or B/s) from per-launch HIP events on the launch stream
-  kernels       every instrumented kernel (GEMMs, attention, local correlation, grid-sample warp, ...)
-  parity        the timed configuration's outputs against the committed reference golden (tools/parity_metrics.py)
-  cpu_baseline  the CPU oracle on the host cores: 1 warm-up + 3 timed calls, median
+A plain run sets up, warms up, times --steps steps, writes the outputs if --dump-outputs is given and prints ONE JSON line
+(rank 0).  With --full (off by default) the line also carries
+  roofline        dominant kernel: algorithmic FLOP/s (or B/s) from per-launch HIP events on the launch stream
+  kernels         every instrumented kernel (GEMMs, attention, local correlation, grid-sample warp, ...)
+  parity          the timed configuration's outputs against the committed reference golden (tools/parity_metrics.py)
+  other_configs   BASELINE configs 2 and 5 and the f16 / all-bf16 storage modes, each timed and parity-gated
+  cpu_baseline    the CPU oracle on the host cores: 1 warm-up + 3 timed calls, median
+each of which the matching --no-* option still switches off.
 """
 import argparse
 import ctypes as C
@@ -41,6 +46,30 @@ sys.path.insert(0, ROOT)
 PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3}  # dense MFMA peaks, /opt/skills/guides/MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
 PMC_SUMMARIES = ("profiles/r06_pmc_summary.json", "profiles/r05_pmc_summary.json", "profiles/r04_pmc_summary.json", "profiles/r03_pmc_summary.json", "profiles/r02_pmc_summary.json", "profiles/r01_pmc_summary.json")
+DUMP_FULL_LIMIT = 48 << 20   # --dump-outputs: outputs up to this many bytes are written whole
+DUMP_SAMPLE_PIXELS = 1 << 21  # otherwise this many pixels, the same seeded choice in every run
+DUMP_SEED = 0
+
+
+def dump_outputs(warp, cert, directory):
+    """--dump-outputs: what match() returned in the last timed step.  Small outputs are written whole (warp.npy [B, H, 2W, 4],
+    certainty.npy [B, H, 2W], float32).  Larger ones (the default workload: 239 MB) are written as the same seeded sample of
+    pixels of both (warp_sample.npy [P, 4], certainty_sample.npy [P], float32) plus the float64 sum of every row of the
+    whole output (warp_rowsum.npy [B, H, 4], certainty_rowsum.npy [B, H]), so that a change anywhere still shows."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    warp, cert = warp.float(), cert.float()
+    if (warp.numel() + cert.numel()) * 4 <= DUMP_FULL_LIMIT:
+        arrays = {"warp": warp, "certainty": cert}
+    else:
+        n_pix = cert.numel()
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_pix, size=min(DUMP_SAMPLE_PIXELS, n_pix), replace=False))
+        idx = torch.from_numpy(idx).to(warp.device)
+        arrays = {"warp_sample": warp.reshape(n_pix, -1)[idx], "certainty_sample": cert.reshape(-1)[idx],
+                  "warp_rowsum": warp.double().sum(dim=2), "certainty_rowsum": cert.double().sum(dim=2)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a.cpu().numpy())
+    return sorted(arrays)
 
 
 def pmc_traffic(kernel):
@@ -125,11 +154,17 @@ def main():
     ap.add_argument("--upsample", type=int, default=864)
     ap.add_argument("--streams", type=int, default=2, choices=[1, 2],
                     help="sub-batch HIP streams per GPU (2 = the library default: two half-batches, DESIGN.md section 4)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the extra measurements: roofline / per-kernel instrumented passes, "
+                         "parity against the reference golden, the other BASELINE configurations and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (warp, certainty) to DIR/<name>.npy; outputs above "
+                         f"{DUMP_FULL_LIMIT >> 20} MiB are written as a fixed seeded pixel sample plus float64 row sums")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the extra legs of the default run: BASELINE configs 2 (coarse-only B = 1) and 5 (f32 B = 8, "
+                    help="--full: skip the extra legs of the default configuration: BASELINE configs 2 (coarse-only B = 1) and 5 (f32 B = 8, "
                          "indoor weights) and the f16 storage mode, each with its own roofline object")
     ap.add_argument("--cpu-baseline-reps", type=int, default=3)
     ap.add_argument("--dry", action="store_true", help="CPU-only launch-logic check: gloo backend, stand-in match()")
@@ -257,6 +292,8 @@ def main():
         solo_all = [float(x.item()) for x in solo_all]
     step_ms = [e0.elapsed_time(e1) for e0, e1 in evs]
     finite = bool(torch.isfinite(out[1]).all()) if out[1] is not None else True
+    # before any --full leg runs the model again: the files hold exactly what the last timed step returned
+    dumped = dump_outputs(out[0], out[1], args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     what = (f"{args.coarse}->{args.upsample}, symmetric, upsample_preds" if full else f"{args.coarse} coarse-only, symmetric")
     policy = {"mixed": "precision policy of the reference's bf16 timing script: bfloat16 DINOv2 + float16 autocast for VGG / decoder / "
@@ -282,6 +319,8 @@ def main():
     }
     if step_ms:
         result["ms_per_step_median_hip_events"] = statistics.median(step_ms)
+    if dumped:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "files": [n + ".npy" for n in dumped]}
     if world > 1:
         result["rccl_ranks"] = world
         result["pairs_per_s_per_rank"] = per_rank
@@ -349,7 +388,7 @@ def main():
                    for k, x in sorted(prof.items(), key=lambda kv: -kv[1]["total_ms"])}
         return roof, kernels
 
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         result["roofline"], result["kernels"] = instrumented_pass(model, step, max(1, min(3, args.steps)), args.streams == 2)
         if full and args.dtype != "f32":
             # ---- the regime a TRAINED matcher produces: smooth (coherent) warps.  The random-weight benchmark model's coarse
@@ -378,7 +417,7 @@ def main():
                         "the warp regime of a trained matcher; only the warp-dependent kernels are listed",
                 "kernels": {k: v for k, v in kc.items() if k.startswith("local_corr") or k.startswith("refiner_input")}}
 
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         # ---- parity of the timed configuration (rank 0's shard = seeds 0 / 1) against the reference's own output
         gold = os.path.join(ROOT, "tests", "golden", "match_full8.npz" if full else "match_full_coarse.npz")
         default_cfg = args.coarse == 560 and (not full or args.upsample == 864) and args.batch == (8 if full else 1)
@@ -415,7 +454,7 @@ def main():
             result["parity"] = None
 
     default_run = full and args.dtype == "mixed" and args.coarse == 560 and args.upsample == 864 and args.batch == 8
-    if rank == 0 and world == 1 and default_run and not args.no_other_configs:
+    if rank == 0 and world == 1 and default_run and args.full and not args.no_other_configs:
         # ---- the other single-GPU configurations of BASELINE.json, as nested objects of the same JSON line (they are NOT
         # the metric): each builds its own handle, is timed like the main loop (synchronise / K steps / synchronise) and
         # gets its own instrumented pass.
@@ -475,7 +514,7 @@ def main():
             "all_bf16_storage_b8": side_config("bf16", True, 8, 10, 3, 0, 1, "match_full8.npz"),
         }
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # ---- CPU baseline: the oracle (CPU restatement of the reference; the reference itself is not on the GPU box) on
         # the host cores, ONE symmetric pair of the same workload per call: 1 warm-up + N timed calls, median
         from oracle import roma_oracle

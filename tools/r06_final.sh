@@ -13,9 +13,9 @@ echo "== full GPU suite"
 timeout 1700 python -m pytest tests -m gpu -q 2>&1 | tail -30 > "$OUT/pytest_gpu.log"; tail -5 "$OUT/pytest_gpu.log"
 cp gpurun_out/parity_report.json "$OUT/" 2>/dev/null
 echo "== bench (default)"
-timeout 900 python bench.py --steps 20 --warmup 3 > "$OUT/bench_mixed.json" 2> "$OUT/bench_mixed.err"; tail -1 "$OUT/bench_mixed.err" | cut -c1-200; cut -c1-300 "$OUT/bench_mixed.json"
+timeout 900 python bench.py --full --steps 20 --warmup 3 > "$OUT/bench_mixed.json" 2> "$OUT/bench_mixed.err"; tail -1 "$OUT/bench_mixed.err" | cut -c1-200; cut -c1-300 "$OUT/bench_mixed.json"
 echo "== bench, one stream"
-timeout 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-other-configs --streams 1 > "$OUT/bench_mixed_1stream.json" 2> "$OUT/bench_mixed_1stream.err"; cut -c1-240 "$OUT/bench_mixed_1stream.json"
+timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-other-configs --streams 1 > "$OUT/bench_mixed_1stream.json" 2> "$OUT/bench_mixed_1stream.err"; cut -c1-240 "$OUT/bench_mixed_1stream.json"
 echo "== kernel trace of the bench (one stream: per-kernel stats)"
 cd /tmp
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- python "$REPO/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-roofline --no-parity --no-other-configs --streams 1 > "$OUT/prof.log" 2>&1

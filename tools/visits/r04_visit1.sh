@@ -18,7 +18,7 @@ for s in 1 0; do
 done
 echo "== bench A/B (schedule 1, 0, 1)"
 for s in 1 0 1; do
-  ROMA_GEMM8P_SCHED=$s timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench_sched$s.json" 2> "$OUT/bench_sched$s.err"
+  ROMA_GEMM8P_SCHED=$s timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench_sched$s.json" 2> "$OUT/bench_sched$s.err"
   python - "$OUT/bench_sched$s.json" $s <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1]))
@@ -29,7 +29,7 @@ PY
 done
 echo "== ROMA_MIXED (bf16 DINOv2 in libroma_hip.so + binary16 elsewhere): parity gates, bench"
 timeout 900 python -m pytest tests/test_gpu_parity.py -q -x -k "mixed" 2>&1 | tail -8
-timeout 400 python bench.py --dtype mixed --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$OUT/bench_mixed.json" 2> "$OUT/bench_mixed.err"
+timeout 400 python bench.py --full --dtype mixed --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$OUT/bench_mixed.json" 2> "$OUT/bench_mixed.err"
 python - "$OUT/bench_mixed.json" <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1]))

@@ -11,7 +11,7 @@ echo "== reproducibility + mixed parity tests"
 timeout 900 python -m pytest tests/test_gpu_parity.py -q -k "reproducible or mixed" 2>&1 | tail -5
 echo "== bench bf16 / mixed"
 for dt in bf16 mixed; do
-  timeout 400 python bench.py --dtype $dt --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$OUT/bench_$dt.json" 2> "$OUT/bench_$dt.err"
+  timeout 400 python bench.py --full --dtype $dt --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs > "$OUT/bench_$dt.json" 2> "$OUT/bench_$dt.err"
   python - "$OUT/bench_$dt.json" $dt <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1]))

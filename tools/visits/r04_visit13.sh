@@ -10,7 +10,7 @@ echo "== yardstick ws1x1 on / off"
 for w in 1 0; do ROMA_WS1X1=$w timeout 300 python tools/bench_vendor_gemm.py 2>&1 | grep "stride 4" | cut -c1-170; done
 echo "== bench A/B ws1x1 1, 0, 1"
 for w in 1 0 1; do
-  ROMA_WS1X1=$w timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench_ws$w.json" 2> "$OUT/bench_ws$w.err"
+  ROMA_WS1X1=$w timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench_ws$w.json" 2> "$OUT/bench_ws$w.err"
   python - "$OUT/bench_ws$w.json" $w <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1]))

@@ -7,7 +7,7 @@ echo "== ws1x1 tests"
 timeout 900 python -m pytest tests/test_gpu_ops.py -q -x -k "ws1x1" 2>&1 | tail -4
 for w in 1 3 0; do echo "== ROMA_WS1X1=$w"; ROMA_WS1X1=$w timeout 300 python tools/bench_vendor_gemm.py 2>&1 | grep "stride 4" | cut -c1-110; done
 for w in 1 0 1; do
-  ROMA_WS1X1=$w timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench_ws$w.json" 2> "$OUT/bench_ws$w.err"
+  ROMA_WS1X1=$w timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench_ws$w.json" 2> "$OUT/bench_ws$w.err"
   python - "$OUT/bench_ws$w.json" $w <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1]))

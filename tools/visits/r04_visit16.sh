@@ -23,7 +23,7 @@ for k in 1 0; do
 timeout 400 python bench.py --steps 20 --warmup 5 --dtype mixed --no-cpu-baseline --no-other-configs --no-parity --no-roofline --stream-skew $k 2>/dev/null | python -c "import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('mixed skew $k pairs/s',round(r['value'],2),'ms',round(r['ms_per_step'],3))"
 done
 echo "== kernel table with the new GELU (instrumented pass)"
-timeout 400 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
+timeout 400 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
 python - "$OUT/bench_full.json" <<'PY'
 import json,sys
 r=json.load(open(sys.argv[1]))

@@ -3,7 +3,7 @@
 set -u
 export TMPDIR=/tmp
 timeout 600 env ROMA_ATTN_OCC4=1 python -m pytest tests/test_gpu_ops.py -q -x -k "attention" 2>&1 | tail -2
-run() { timeout 400 env "$@" python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity 2>/dev/null | python -c "
+run() { timeout 400 env "$@" python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=r['kernels']

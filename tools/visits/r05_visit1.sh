@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/v1; mkdir -p "$OUT"
 timeout 1700 python -m pytest tests -m gpu -q -x 2>&1 | tail -15 | tee "$OUT/pytest_gpu.log"
 timeout 600 python -m pytest tests/test_gpu_match.py tests/test_gpu_tiny.py -q -s -k "paths or forward_apis or from_path" 2>&1 | grep -i "max|\|passed\|failed\|forward APIs" | cut -c1-400 | tee "$OUT/new_tests.log"
-timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity > "$OUT/bench.json" 2> "$OUT/bench.err"
 python - <<'P'
 import json
 r=json.loads(open("gpurun_out/v1/bench.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ OUT=$PWD/gpurun_out/v14; mkdir -p "$OUT"
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_match.py -q -x 2>&1 | tail -3 | tee "$OUT/tests.log"
 timeout 600 python -m pytest tests/test_gpu_ops.py -q -x -k "conv3x3 or gemm" 2>&1 | tail -2 | tee -a "$OUT/tests.log"
 for ko in 1 0 1 0; do
-ROMA_CONV_KORDER=$ko timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity 2>/dev/null | python -c "
+ROMA_CONV_KORDER=$ko timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs --no-parity 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('korder=$ko pairs/s',round(r['value'],2),'ms',round(r['ms_per_step'],3),{n:(round(v['ms_per_step'],3),round(v.get('TFLOP/s',0),1)) for n,v in r['kernels'].items() if 'conv3x3,relu' in n})" | tee -a "$OUT/bench.log"

@@ -7,7 +7,7 @@ OUT=$PWD/gpurun_out/v7; mkdir -p "$OUT"
 timeout 600 python -m pytest tests/test_gpu_ops.py -q -x -k "refiner_block_final or refiner_block_fused or refiner_block_repeated" 2>&1 | tail -5 | tee "$OUT/tests.log"
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_match.py -q -x 2>&1 | tail -4 | tee -a "$OUT/tests.log"
 for c in 1 0 1; do
-ROMA_COMPOSE_OUT=$c timeout 400 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
+ROMA_COMPOSE_OUT=$c timeout 400 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-other-configs 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1])
 p=r['parity']

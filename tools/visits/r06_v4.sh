@@ -13,7 +13,7 @@ done; done
 echo "== full GPU suite"
 timeout 1700 python -m pytest tests -m gpu -q -x 2>&1 | tail -15 | tee "$OUT/pytest_gpu.log"
 echo "== kernels (one instrumented pass)"
-timeout 300 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-other-configs > "$OUT/bench_kernels.json" 2>/dev/null
+timeout 300 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-parity --no-other-configs > "$OUT/bench_kernels.json" 2>/dev/null
 python - "$OUT/bench_kernels.json" <<'P'
 import json, sys
 d = json.load(open(sys.argv[1]))
