@@ -305,6 +305,21 @@ int roma_op_mutual_nn_fill(const float* a, long na, const float* b, long nb, con
 long roma_op_multinomial_workspace(long n, long k);
 int roma_op_multinomial(const float* weights, long n, long k, unsigned long long seed, long long* out_indices, void* workspace,
                         long workspace_bytes, void* stream);
+/* Batched RANSAC - the robust estimation the reference's demos run on sample() output through OpenCV:
+ * cv2.findHomography(A, B, RANSAC) (model 0: 4-point DLT, one-sided reprojection error in image B) and
+ * cv2.findFundamentalMat(A, B, FM_RANSAC) (model 1: 7-point solver, up to 3 models per sample, max of the two point-to-epipolar-line
+ * distances).  Plain RANSAC in rounds of 256 hypotheses per pair with OpenCV's adaptive iteration count, optionally followed by
+ * up to 3 least-squares refits on the inliers (refine != 0); the algorithm is restated in tools/geometry_ref.py.
+ * kpts_a, kpts_b DEVICE f32 [B, N, 2] pixel coordinates; counts DEVICE int32 [B] rows per pair (NULL: N; rows at or beyond
+ * counts[b] are never read); seeds DEVICE u64 [B] (the samples of pair b depend on seeds[b] only).  Outputs, all DEVICE:
+ * model f64 [B, 3, 3] mapping A to B (x_B ~ H x_A, x_B^T F x_A = 0; [2][2] = 1, or unit Frobenius norm where |[2][2]| < 1e-12
+ * of it; zeros where no model), mask u8 [B, N] inliers of the returned model, ok u8 [B], info int32 [B, 6] = {rounds run,
+ * winning hypothesis, its root, its inlier count, final inlier count, pair valid}.  No host synchronisation.
+ * workspace: device memory of roma_op_ransac_workspace(B, N) bytes. */
+long roma_op_ransac_workspace(int B, int N);
+int roma_op_ransac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
+                   int N, float threshold, double confidence, int max_iters, int refine, double* out_model, unsigned char* out_mask,
+                   unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes, void* stream);
 /* ---- Tiny RoMa (romatch/models/tiny.py), matcher side; the XFeat backbone is the caller's (model_zoo/__init__.py:24-27).
  * All tensors f32, channels-last unless noted.  corr_volume (tiny.py:182-196) = roma_op_gemm with A = feats of image B
  * [H1*W1, C], W = feats of image A [H0*W0, C], alpha = 1/sqrt(C), batch = pairs: cv [B, H1*W1, H0*W0]. */

@@ -21,6 +21,7 @@
 #include "tiny.h"
 #include "vit.h"
 #include "sampling.h"
+#include "geometry.h"
 
 namespace roma {
 static thread_local std::string g_err;
@@ -522,6 +523,14 @@ long roma_op_multinomial_workspace(long n, long k) { return (long)multinomial_wo
 int roma_op_multinomial(const float* weights, long n, long k, unsigned long long seed, long long* out_indices, void* workspace,
                         long workspace_bytes, void* stream) {
   return multinomial_launch(weights, n, k, seed, out_indices, workspace, (size_t)workspace_bytes, S(stream));
+}
+// ---- batched RANSAC (geometry.hip)
+long roma_op_ransac_workspace(int B, int N) { return (long)ransac_workspace_bytes(B, N); }
+int roma_op_ransac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
+                   int N, float threshold, double confidence, int max_iters, int refine, double* out_model, unsigned char* out_mask,
+                   unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes, void* stream) {
+  return ransac_launch(model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, refine, out_model, out_mask,
+                       out_ok, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
 }
 // ---- Tiny RoMa matcher side (tiny.hip)
 int roma_op_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, void* stream) {

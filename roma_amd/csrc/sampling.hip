@@ -29,12 +29,6 @@ struct SelState {  // lives at the head of the workspace
   unsigned pad[3];
 };
 
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
-
 __global__ __launch_bounds__(256) void race_keys_kernel(const float* __restrict__ w, long n, uint64_t seed, float* __restrict__ keys,
                                                         SelState* st) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
