@@ -320,6 +320,34 @@ long roma_op_ransac_workspace(int B, int N);
 int roma_op_ransac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
                    int N, float threshold, double confidence, int max_iters, int refine, double* out_model, unsigned char* out_mask,
                    unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes, void* stream);
+/* Essential matrix and relative pose - the tail of the reference's pose benchmarks (romatch/utils/utils.py estimate_pose):
+ * cv2.findEssentialMat(A, B, K, RANSAC, prob, threshold, maxIters) and cv2.recoverPose.  Algorithm restated in
+ * tools/essential_ref.py.  roma_op_essential: Nister's five-point solver (up to 10 models per sample, real roots by Sturm
+ * bisection), Sampson test (x_B^T E x_A)^2 < thr^2 (|E x_A|_{1,2}^2 + |E^T x_B|_{1,2}^2), plain RANSAC in rounds of 256
+ * hypotheses per pair with OpenCV's adaptive iteration count, no refinement.  kpts_a, kpts_b DEVICE f32 [B, N, 2]; counts,
+ * seeds as for roma_op_ransac; camera_matrix DEVICE f64 [B, 3, 3] or NULL (identity: the points are normalised already),
+ * applied as OpenCV does: x_n = ((x - cx) / fx, (y - cy) / fy), threshold / ((fx + fy) / 2).  Outputs, all DEVICE: E f64
+ * [B, 3, 3] on normalised points (unit Frobenius norm, largest-magnitude entry positive; zeros where no model), mask u8 [B, N],
+ * ok u8 [B], info int32 [B, 5] = {rounds run, winning hypothesis, its root, inlier count, pair valid}.  No host
+ * synchronisation.  workspace: device memory of roma_op_essential_workspace(B, N) bytes. */
+long roma_op_essential_workspace(int B, int N);
+int roma_op_essential(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                      const double* camera_matrix, int B, int N, float threshold, double prob, int max_iters, double* out_e,
+                      unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes,
+                      void* stream);
+/* The five-point solver alone: x0, x1 DEVICE f64 [S, 5, 2] (x1^T E x0 = 0) -> E DEVICE f64 [S, 10, 3, 3] (solutions in ascending
+ * order of Nister's z, unused slots 0), n DEVICE int32 [S]. */
+int roma_op_essential_minimal(const double* x0, const double* x1, int S, double* out_e, int* out_n, void* stream);
+/* cv2.recoverPose(E, A, B, K, distance_thresh, mask): the four decompositions (R1, t), (R2, t), (R1, -t), (R2, -t) of E (SVD with
+ * OpenCV's det(U), det(V^T) > 0 fix-up, t = U[:, 2]), linear triangulation of the masked rows, a row counts for a candidate if
+ * its depth is positive and below distance_thresh in both cameras; the candidate with the most rows wins (ties: the earlier).
+ * E DEVICE f64 [B, 3, 3]; kpts as above; mask DEVICE u8 [B, N] or NULL (every row); counts, camera_matrix as above.
+ * Outputs, all DEVICE: n_good int32 [B], R f64 [B, 3, 3], t f64 [B, 3], mask_good u8 [B, N].  workspace: device memory of
+ * roma_op_recover_pose_workspace(B, N) bytes. */
+long roma_op_recover_pose_workspace(int B, int N);
+int roma_op_recover_pose(const double* E, const float* kpts_a, const float* kpts_b, const unsigned char* mask, const int* counts,
+                         const double* camera_matrix, int B, int N, double distance_thresh, int* out_n_good, double* out_r,
+                         double* out_t, unsigned char* out_mask, void* workspace, long workspace_bytes, void* stream);
 /* ---- Tiny RoMa (romatch/models/tiny.py), matcher side; the XFeat backbone is the caller's (model_zoo/__init__.py:24-27).
  * All tensors f32, channels-last unless noted.  corr_volume (tiny.py:182-196) = roma_op_gemm with A = feats of image B
  * [H1*W1, C], W = feats of image A [H0*W0, C], alpha = 1/sqrt(C), batch = pairs: cv [B, H1*W1, H0*W0]. */

@@ -2,14 +2,16 @@
 
 Public surface mirrors the reference package (`romatch/__init__.py:2`): model factories and the
 local-correlation operator, plus the post-processing of `sample()` output (robust homography /
-fundamental-matrix estimation).  Everything numerical runs in libroma_hip.so (hand-written HIP, gfx950).
+fundamental / essential-matrix estimation, relative pose).  Everything numerical runs in libroma_hip.so (hand-written HIP, gfx950).
 """
 from .matcher import RegressionMatcher, roma_indoor, roma_model, roma_outdoor  # noqa: F401
 from .local_correlation import local_corr, local_correlation  # noqa: F401
 from .kde import kde  # noqa: F401
 from .sampling import multinomial  # noqa: F401
-from .geometry import find_fundamental, find_homography  # noqa: F401
+from .geometry import (essential_minimal, estimate_pose, estimate_pose_uncalibrated, find_essential, find_fundamental,  # noqa: F401
+                       find_homography, recover_pose)
 from .tiny import TinyRoMa, tiny_roma_v1_outdoor  # noqa: F401
 
 __all__ = ["RegressionMatcher", "roma_model", "roma_outdoor", "roma_indoor", "local_corr", "local_correlation", "kde",
-           "multinomial", "find_homography", "find_fundamental", "TinyRoMa", "tiny_roma_v1_outdoor"]
+           "multinomial", "find_homography", "find_fundamental", "find_essential", "recover_pose", "estimate_pose",
+           "estimate_pose_uncalibrated", "essential_minimal", "TinyRoMa", "tiny_roma_v1_outdoor"]

@@ -21,6 +21,7 @@
 #include "tiny.h"
 #include "vit.h"
 #include "sampling.h"
+#include "essential.h"
 #include "geometry.h"
 
 namespace roma {
@@ -531,6 +532,25 @@ int roma_op_ransac(int model, const float* kpts_a, const float* kpts_b, const in
                    unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes, void* stream) {
   return ransac_launch(model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, refine, out_model, out_mask,
                        out_ok, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+// ---- essential matrix and recoverPose (essential.hip)
+long roma_op_essential_workspace(int B, int N) { return (long)essential_workspace_bytes(B, N); }
+int roma_op_essential(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                      const double* camera_matrix, int B, int N, float threshold, double prob, int max_iters, double* out_e,
+                      unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes,
+                      void* stream) {
+  return essential_launch(kpts_a, kpts_b, counts, seeds, camera_matrix, B, N, threshold, prob, max_iters, out_e, out_mask, out_ok,
+                          out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+int roma_op_essential_minimal(const double* x0, const double* x1, int S_, double* out_e, int* out_n, void* stream) {
+  return essential_minimal_launch(x0, x1, S_, out_e, out_n, S(stream));
+}
+long roma_op_recover_pose_workspace(int B, int N) { return (long)recover_pose_workspace_bytes(B, N); }
+int roma_op_recover_pose(const double* E, const float* kpts_a, const float* kpts_b, const unsigned char* mask, const int* counts,
+                         const double* camera_matrix, int B, int N, double distance_thresh, int* out_n_good, double* out_r,
+                         double* out_t, unsigned char* out_mask, void* workspace, long workspace_bytes, void* stream) {
+  return recover_pose_launch(E, kpts_a, kpts_b, mask, counts, camera_matrix, B, N, distance_thresh, out_n_good, out_r, out_t,
+                             out_mask, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
 }
 // ---- Tiny RoMa matcher side (tiny.hip)
 int roma_op_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, void* stream) {

@@ -1,0 +1,1037 @@
+// Batched essential-matrix RANSAC and recoverPose on the device - what the reference's pose benchmarks run on sample() output
+// through OpenCV (romatch/utils/utils.py estimate_pose): cv2.findEssentialMat(..., RANSAC) around the five-point solver, then
+// cv2.recoverPose.  tools/essential_ref.py restates this file in numpy float64 step by step and is the oracle of the GPU tests.
+//
+// findEssentialMat, per pair b (counts[b] rows; later rows are never read):
+//   1. ess_norm_kernel: x_n = ((x - cx) / fx, (y - cy) / fy) in f64 (identity without a camera matrix), f32 copies (non-finite
+//      rows as NaN), thr_n = thr / ((fx + fy) / 2).  No Hartley normalisation: it would break the essential constraints.
+//   2. rounds of RANSAC_ROUND hypotheses, enqueued ceil(max_iters / ROUND) times, no host synchronisation:
+//      ess_hyp_kernel    16 lanes per hypothesis: sample (the counter-based stream of ransac_common.h at S = 5), Nister's
+//                        five-point solver in f64 (below), up to 10 models
+//      ess_score_kernel  one wave per hypothesis: Sampson test of its models in f32, popc(ballot) counts
+//      ess_select_kernel per pair: arg-max (ties: lowest (h, root)), OpenCV's adaptive iteration count, done flag.
+//   3. ess_mask_kernel + ess_finish_kernel: final mask, E, ok, round / winner info.  No refinement (OpenCV has none here).
+// The five-point solver (D. Nister, PAMI 2004): null space X, Y, Z, W of the 5 x 9 epipolar system (Gauss-Jordan, then modified
+// Gram-Schmidt: an orthonormal basis keeps the elimination below well conditioned), the ten cubic constraints det E = 0 and
+// 2 E E^T E - tr(E E^T) E = 0 of E = x X + y Y + z Z + W as a 10 x 20 matrix (one row per lane), Gauss-Jordan on its ten
+// leading columns (row swaps and pivot rows by shuffles), the degree-10 polynomial in z as the determinant of Nister's 3 x 3
+// polynomial matrix, its real roots by Sturm-sequence bisection with a fixed schedule from Fujiwara's bound (one root per lane,
+// ascending: a root's index is its rank) and NEWTON polishing steps, x and y from the two rows of B(z) with the largest cross
+// product, then GN_STEPS Gauss-Newton steps of (x, y, z) on the ten cubic constraints themselves (the elimination loses digits
+// on some samples; the refinement recovers them), E normalised with its largest-magnitude entry positive.
+// recoverPose: ess_decompose_kernel (one-sided Jacobi SVD of E per pair, OpenCV's det fix-up, the four candidates),
+// ess_cheirality_kernel (grid (point blocks, pair): triangulation for all four candidates, per-block counts, no atomics),
+// ess_pose_kernel (candidate with most good points, ties to the earlier one; R, t, n_good, mask).
+// Every flag and counter of the workspace is written with plain stores by one kernel and read by a later launch on the same
+// stream.  Results are bit-identical from run to run and independent of B.
+#include "essential.h"
+#include "geometry.h"
+#include "ransac_common.h"
+
+// the scoring arithmetic is written with explicit fmaf; nothing else is fused (tools/essential_ref.py evaluates the same
+// expressions in f64)
+#pragma clang fp contract(off)
+
+namespace roma {
+namespace {
+
+constexpr int R = RANSAC_ROUND;
+constexpr int MAXR = ESSENTIAL_MAX_ROOTS;
+constexpr int G = 16;                     // lanes per hypothesis in the solver
+constexpr int GPB = 256 / G;              // hypotheses per solver workgroup
+constexpr int LDS_BASIS = 0, LDS_TAIL = 36, LDS_CHAIN = 96, LDS_PER = 162;  // doubles per hypothesis
+constexpr int BISECT = 64;                // bisection steps per root
+constexpr int NEWTON = 3;                 // Newton steps on the polynomial after bisection
+constexpr double NEWTON_REACH = 1e-3;     // relative length of a Newton step that is still taken
+constexpr int GN_STEPS = 3;               // Gauss-Newton steps of (x, y, z) on the cubic constraints
+constexpr double GN_REACH = 1e-2;         // relative length of a Gauss-Newton step that is still taken
+constexpr double E_PIVOT_EPS = 1e-10;     // |pivot| of the 10 x 20 elimination (unit-norm null basis)
+constexpr int SVD_SWEEPS = 20;
+constexpr double SVD_TOL = 4 * DBL_EPSILON;
+static_assert(R % GPB == 0, "a solver workgroup must not straddle two pairs");
+
+struct EState {
+  double fx, fy, cx, cy;        // x_n = (x - c) / f
+  double cur[9];                // current model
+  alignas(16) float curf[12];   // f32 copy the scoring reads
+  float thr2;                   // thr_n^2
+  int n;                        // rows of the pair: counts[b] clamped to [0, N]
+  int valid;                    // enough finite rows for a sample, camera matrix usable
+  int best;                     // inlier count of the current model (-1: none yet)
+  int best_h, best_root;        // winning minimal sample and its root
+  int needed;                   // adaptive iteration count
+  int rounds;                   // rounds executed
+  int done;                     // sampling finished for this pair
+};
+
+// ------------------------------------------------------------------------------------------------------------ scoring (f32)
+// p = (x0, y0, x1, y1) normalised.  Sampson test in multiplication form: (x1^T E x0)^2 < thr^2 (|E x0|_{1,2}^2 + |E^T x1|_{1,2}^2)
+__device__ __forceinline__ bool inlier_e(const float* m, float4 p, float t2) {
+  const float lx = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
+  const float ly = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
+  const float lz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
+  const float d = fmaf(p.z, lx, fmaf(p.w, ly, lz));
+  const float kx = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
+  const float ky = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
+  return d * d < t2 * (fmaf(lx, lx, ly * ly) + fmaf(kx, kx, ky * ky));
+}
+
+// ------------------------------------------------------------------------------------------------------------ five-point solver
+// Nister's column order of the cubic constraints: x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1
+__host__ __device__ constexpr int mono(int ex, int ey, int ez) {
+  switch (ex * 16 + ey * 4 + ez) {
+    case 48: return 0;
+    case 12: return 1;
+    case 36: return 2;
+    case 24: return 3;
+    case 33: return 4;
+    case 32: return 5;
+    case 9: return 6;
+    case 8: return 7;
+    case 21: return 8;
+    case 20: return 9;
+    case 18: return 10;
+    case 17: return 11;
+    case 16: return 12;
+    case 6: return 13;
+    case 5: return 14;
+    case 4: return 15;
+    case 3: return 16;
+    case 2: return 17;
+    case 1: return 18;
+    default: return 19;
+  }
+}
+
+// acc += s p q r for three linear polynomials (coefficients of x, y, z, 1)
+__device__ __forceinline__ void add_triple(double (&acc)[20], double s, const double* p, const double* q, const double* r) {
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const double pq = s * (p[a] * q[b]);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int k = mono((a == 0) + (b == 0) + (c == 0), (a == 1) + (b == 1) + (c == 1), (a == 2) + (b == 2) + (c == 2));
+        acc[k] = acc[k] + pq * r[c];
+      }
+    }
+  }
+}
+
+template <int NA, int NB>
+__device__ __forceinline__ void pmul(const double (&a)[NA], const double (&b)[NB], double (&c)[NA + NB - 1]) {
+#pragma unroll
+  for (int k = 0; k < NA + NB - 1; ++k) c[k] = 0;
+#pragma unroll
+  for (int i = 0; i < NA; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) c[i + j] = c[i + j] + a[i] * b[j];
+}
+
+template <int N>
+__device__ __forceinline__ double horner(const double* c, double t) {  // c ascending, N coefficients
+  double v = c[N - 1];
+#pragma unroll
+  for (int i = N - 2; i >= 0; --i) v = v * t + c[i];
+  return v;
+}
+
+// Nister's 3 x 3 matrix B(z) of <k> = <e> - z <f>, <l> = <g> - z <h>, <m> = <i> - z <j> (rows 4 .. 9 of the reduced
+// constraints, columns 10 .. 19): row r = (x coefficient deg 3, y coefficient deg 3, constant deg 4), ascending in z
+__device__ __forceinline__ void nister_rows(const double* tail, double (&bx)[3][4], double (&by)[3][4], double (&b1)[3][5]) {
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double* e = tail + 20 * r;
+    const double* f = e + 10;
+    bx[r][0] = e[2]; bx[r][1] = e[1] - f[2]; bx[r][2] = e[0] - f[1]; bx[r][3] = -f[0];
+    by[r][0] = e[5]; by[r][1] = e[4] - f[5]; by[r][2] = e[3] - f[4]; by[r][3] = -f[3];
+    b1[r][0] = e[9]; b1[r][1] = e[8] - f[9]; b1[r][2] = e[7] - f[8]; b1[r][3] = e[6] - f[7]; b1[r][4] = -f[6];
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void scale_max(double (&p)[N]) {  // divide by the largest magnitude (a positive factor)
+  double m = 0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) m = fmax(m, fabs(p[i]));
+  const double inv = 1.0 / m;
+#pragma unroll
+  for (int i = 0; i < N; ++i) p[i] = p[i] * inv;
+}
+
+// p_next = -rem(a, b) for deg a = N - 1, deg b = N - 2 (generic degree drop), scaled to unit maximum
+// p_next = -rem(a, b) for deg a = N - 1, deg b = N - 2 (generic degree drop), scaled to unit maximum
+template <int N>
+__device__ __forceinline__ void sturm_next(const double (&a)[N], const double (&b)[N - 1], double (&r)[N - 2]) {
+  const double q1 = a[N - 1] / b[N - 2];
+  const double q0 = (a[N - 2] - q1 * b[N - 3]) / b[N - 2];
+  r[0] = -(a[0] - q0 * b[0]);
+#pragma unroll
+  for (int i = 1; i < N - 2; ++i) r[i] = -((a[i] - q1 * b[i - 1]) - q0 * b[i]);
+  scale_max(r);
+}
+
+template <int N>
+__device__ __forceinline__ void store_poly(double* dst, const double (&p)[N], bool w) {
+  if (w) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) dst[i] = p[i];
+  }
+}
+
+// the chain after a (element 11 - N, N coefficients) and b: element j = 13 - N at offset 11 j - j (j - 1) / 2
+template <int N>
+__device__ __forceinline__ void sturm_build(const double (&a)[N], const double (&b)[N - 1], double* ch, bool w, double (&lead)[11],
+                                            bool& fin) {
+  if constexpr (N >= 3) {
+    double r[N - 2];
+    sturm_next<N>(a, b, r);
+    constexpr int j = 13 - N;
+    store_poly(ch + 11 * j - j * (j - 1) / 2, r, w);
+    lead[j] = r[N - 3];
+#pragma unroll
+    for (int i = 0; i < N - 2; ++i) fin = fin && isfinite(r[i]);
+    sturm_build<N - 1>(b, r, ch, w, lead, fin);
+  }
+}
+
+// sign changes of the Sturm chain (degrees 10 .. 0, ascending coefficients from offset 0) at t, zeros skipped
+__device__ __forceinline__ int sturm_changes(const double* ch, double t) {
+  int c = 0;
+  double last = 0;
+  int off = 0;
+#pragma unroll
+  for (int k = 0; k <= 10; ++k) {
+    const int n = 11 - k;
+    double v = ch[off + n - 1];
+    for (int i = n - 2; i >= 0; --i) v = v * t + ch[off + i];
+    if (v != 0) {
+      if (last != 0 && ((v < 0) != (last < 0))) ++c;
+      last = v;
+    }
+    off += n;
+  }
+  return c;
+}
+
+__device__ __forceinline__ void mm3(const double* a, const double* b, double* c) {  // c = a b
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[3 * i + j] = (a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j]) + a[3 * i + 2] * b[6 + j];
+}
+
+__device__ __forceinline__ void mmt3(const double* a, const double* b, double* c) {  // c = a b^T
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[3 * i + j] = (a[3 * i] * b[3 * j] + a[3 * i + 1] * b[3 * j + 1]) + a[3 * i + 2] * b[3 * j + 2];
+}
+
+__device__ __forceinline__ double det3e(const double* f) {
+  return f[0] * (f[4] * f[8] - f[5] * f[7]) - f[1] * (f[3] * f[8] - f[5] * f[6]) + f[2] * (f[3] * f[7] - f[4] * f[6]);
+}
+
+// GN_STEPS Gauss-Newton steps of (x, y, z) on the ten cubic constraints of E = x X + y Y + z Z + W themselves (not on the
+// eliminated polynomial, whose roots carry the elimination's rounding); a step longer than GN_REACH (1 + max |x, y, z|) or not
+// finite is not taken.  3 x 3 normal equations by Cramer's rule.  basis: the group's LDS basis (entry q: x, y, z, 1 coefficients).
+__device__ __forceinline__ void refine_xyz(const double* basis, double& x, double& y, double& z) {
+  for (int it = 0; it < GN_STEPS; ++it) {
+    double E[9], EEt[9], M[9], r[10], J[3][10];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) E[q] = ((x * basis[4 * q] + y * basis[4 * q + 1]) + z * basis[4 * q + 2]) + basis[4 * q + 3];
+    mmt3(E, E, EEt);
+    const double tr = (EEt[0] + EEt[4]) + EEt[8];
+    mm3(EEt, E, M);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) r[q] = 2.0 * M[q] - tr * E[q];
+    r[9] = det3e(E);
+    const double cof[9] = {E[4] * E[8] - E[5] * E[7], E[5] * E[6] - E[3] * E[8], E[3] * E[7] - E[4] * E[6],
+                           E[2] * E[7] - E[1] * E[8], E[0] * E[8] - E[2] * E[6], E[1] * E[6] - E[0] * E[7],
+                           E[1] * E[5] - E[2] * E[4], E[2] * E[3] - E[0] * E[5], E[0] * E[4] - E[1] * E[3]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double D[9], t1[9], t2[9], a1[9], a2[9], a3[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q) D[q] = basis[4 * q + k];
+      mmt3(D, E, t1);
+      mm3(t1, E, a1);
+      mmt3(E, D, t2);
+      mm3(t2, E, a2);
+      mm3(EEt, D, a3);
+      double ip = 0, dd = 0;
+#pragma unroll
+      for (int q = 0; q < 9; ++q) { ip += D[q] * E[q]; dd += cof[q] * D[q]; }
+#pragma unroll
+      for (int q = 0; q < 9; ++q) J[k][q] = (2.0 * ((a1[q] + a2[q]) + a3[q]) - (2.0 * ip) * E[q]) - tr * D[q];
+      J[k][9] = dd;
+    }
+    double A[9], g[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      double gi = 0;
+#pragma unroll
+      for (int q = 0; q < 10; ++q) gi += J[i][q] * r[q];
+      g[i] = gi;
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        double a = 0;
+#pragma unroll
+        for (int q = 0; q < 10; ++q) a += J[i][q] * J[j][q];
+        A[3 * i + j] = a;
+      }
+    }
+    const double det = det3e(A);
+    double st[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      double Ak[9];
+#pragma unroll
+      for (int q = 0; q < 9; ++q) Ak[q] = q % 3 == k ? g[q / 3] : A[q];
+      st[k] = -det3e(Ak) / det;
+    }
+    const double big = 1.0 + fmax(fmax(fabs(x), fabs(y)), fabs(z));
+    const bool take = isfinite(st[0]) && isfinite(st[1]) && isfinite(st[2]) &&
+                      fmax(fmax(fabs(st[0]), fabs(st[1])), fabs(st[2])) <= GN_REACH * big;
+    x = take ? x + st[0] : x;
+    y = take ? y + st[1] : y;
+    z = take ? z + st[2] : z;
+  }
+}
+
+// One hypothesis on the G lanes of a group (gl = lane in the group); every lane of the workgroup must call it (barriers).
+// Returns this lane's model in e (valid: a real root whose E is finite), its rank among the group's valid models and their
+// number.  sm: the group's LDS_PER doubles.
+__device__ __forceinline__ void solve_e_group(const double (&xa)[5], const double (&ya)[5], const double (&xb)[5], const double (&yb)[5], bool act,
+                              double* sm, int gl, double (&e)[9], int& rank, int& nsol) {
+  // null space of the 5 x 9 system x1^T E x0 = 0 (every lane, registers); basis X, Y, Z, W = free columns 5 .. 8, unit norm
+  {
+    double a[5][9];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+      const double x = xa[k], y = ya[k], u = xb[k], v = yb[k];
+      a[k][0] = u * x; a[k][1] = u * y; a[k][2] = u; a[k][3] = v * x; a[k][4] = v * y; a[k][5] = v;
+      a[k][6] = x; a[k][7] = y; a[k][8] = 1;
+    }
+    act = gauss_jordan(a) && act;
+    double v[4][9];
+#pragma unroll
+    for (int f = 0; f < 4; ++f) {  // modified Gram-Schmidt in the order X, Y, Z, W
+#pragma unroll
+      for (int k = 0; k < 5; ++k) v[f][k] = -a[k][5 + f];
+#pragma unroll
+      for (int k = 5; k < 9; ++k) v[f][k] = k == 5 + f ? 1.0 : 0.0;
+#pragma unroll
+      for (int g = 0; g < f; ++g) {
+        double d = 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) d += v[f][k] * v[g][k];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) v[f][k] = v[f][k] - d * v[g][k];
+      }
+      double s = 0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) s += v[f][k] * v[f][k];
+      const double inv = 1.0 / sqrt(s);
+#pragma unroll
+      for (int k = 0; k < 9; ++k) v[f][k] = v[f][k] * inv;
+      if (gl == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) sm[LDS_BASIS + 4 * k + f] = v[f][k];  // entry k of E: (x, y, z, 1) coefficients
+      }
+    }
+  }
+  __syncthreads();
+  // row gl of the 10 x 20 constraint matrix: 2 (E E^T E)_ij - tr(E E^T) E_ij for gl = 3 i + j < 9, det E for gl = 9
+  double acc[20];
+#pragma unroll
+  for (int k = 0; k < 20; ++k) acc[k] = 0;
+  const double* P = sm + LDS_BASIS;
+  if (gl < 9) {
+    const int i = gl / 3, j = gl % 3;
+    for (int k = 0; k < 3; ++k)
+      for (int l = 0; l < 3; ++l) {
+        add_triple(acc, 2.0, P + 4 * (3 * i + l), P + 4 * (3 * k + l), P + 4 * (3 * k + j));
+        add_triple(acc, -1.0, P + 4 * (3 * k + l), P + 4 * (3 * k + l), P + 4 * (3 * i + j));
+      }
+  } else if (gl == 9) {
+    constexpr int perm[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {1, 0, 2}, {2, 1, 0}};
+    for (int q = 0; q < 6; ++q)
+      add_triple(acc, q < 3 ? 1.0 : -1.0, P + 4 * perm[q][0], P + 4 * (3 + perm[q][1]), P + 4 * (6 + perm[q][2]));
+  }
+  // Gauss-Jordan on columns 0 .. 9 with partial pivoting (first maximum); lane r holds row r
+#pragma unroll
+  for (int k = 0; k < 10; ++k) {
+    double v = gl >= k && gl < 10 ? fabs(acc[k]) : -1.0;
+    int p = gl;
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) {
+      const double ov = __shfl_xor(v, off, G);
+      const int op = __shfl_xor(p, off, G);
+      if (ov > v || (ov == v && op < p)) { v = ov; p = op; }
+    }
+    act = act && v > E_PIVOT_EPS;
+    const int src = gl == k ? p : gl == p ? k : gl;
+#pragma unroll
+    for (int c = 0; c < 20; ++c) acc[c] = __shfl(acc[c], src, G);
+    const double inv = 1.0 / __shfl(acc[k], k, G);
+    if (gl == k) {
+#pragma unroll
+      for (int c = 0; c < 20; ++c) acc[c] = acc[c] * inv;
+    }
+    const double f = acc[k];
+#pragma unroll
+    for (int c = 0; c < 20; ++c) {
+      const double rk = __shfl(acc[c], k, G);
+      if (gl != k) acc[c] = acc[c] - f * rk;
+    }
+  }
+  if (gl >= 4 && gl < 10) {
+#pragma unroll
+    for (int c = 0; c < 10; ++c) sm[LDS_TAIL + 10 * (gl - 4) + c] = acc[10 + c];
+  }
+  __syncthreads();
+  // degree-10 polynomial det B(z) and its Sturm chain (every lane the same values; lane 0 stores the chain)
+  double bx[3][4], by[3][4], b1[3][5];
+  nister_rows(sm + LDS_TAIL, bx, by, b1);
+  double lead[11];
+  bool fin = true;
+  double bound;
+  {
+    double u0[8], u1[8], v0[8], v1[8], w0[7], w1[7];
+    pmul(by[1], b1[2], u0);
+    pmul(b1[1], by[2], u1);
+    pmul(bx[1], b1[2], v0);
+    pmul(b1[1], bx[2], v1);
+    pmul(bx[1], by[2], w0);
+    pmul(by[1], bx[2], w1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) { u0[i] = u0[i] - u1[i]; v0[i] = v0[i] - v1[i]; }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) w0[i] = w0[i] - w1[i];
+    double p0[11], q0[11], q1[11], p1[10];
+    pmul(bx[0], u0, p0);
+    pmul(by[0], v0, q0);
+    pmul(b1[0], w0, q1);
+#pragma unroll
+    for (int i = 0; i < 11; ++i) p0[i] = (p0[i] - q0[i]) + q1[i];
+    scale_max(p0);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) p1[i] = (i + 1) * p0[i + 1];
+    scale_max(p1);
+    double* ch = sm + LDS_CHAIN;
+    store_poly(ch, p0, gl == 0);
+    store_poly(ch + 11, p1, gl == 0);
+    lead[0] = p0[10];
+    lead[1] = p1[9];
+#pragma unroll
+    for (int i = 0; i < 11; ++i) fin = fin && isfinite(p0[i]);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) fin = fin && isfinite(p1[i]);
+    sturm_build<11>(p0, p1, ch, gl == 0, lead, fin);
+    bound = 0;
+#pragma unroll
+    for (int i = 1; i <= 10; ++i) bound = fmax(bound, pow(fabs(p0[10 - i] / p0[10]), 1.0 / i));
+    bound = 2.0 * bound;  // Fujiwara's bound of the roots: 2 max_i |a_{10-i} / a_10|^(1/i)
+  }
+  // sign changes at -inf and +inf from the leading coefficients (degree of element j: 10 - j)
+  int vneg = 0, vpos = 0;
+  {
+    double ln = 0, lp = 0;
+#pragma unroll
+    for (int j = 0; j <= 10; ++j) {
+      fin = fin && lead[j] != 0;
+      const double a = lead[j], an = (10 - j) % 2 ? -a : a;
+      if (lp != 0 && ((a < 0) != (lp < 0))) ++vpos;
+      if (ln != 0 && ((an < 0) != (ln < 0))) ++vneg;
+      lp = a;
+      ln = an;
+    }
+  }
+  fin = fin && isfinite(bound);
+  const int nroots = fin && act ? min(max(vneg - vpos, 0), MAXR) : 0;
+  __syncthreads();
+  // root gl (ascending) by bisection on the number of roots in (-inf, t]
+  double lo = -bound, hi = bound;
+  for (int it = 0; it < BISECT; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    const bool up = vneg - sturm_changes(sm + LDS_CHAIN, mid) >= gl + 1;
+    lo = up ? lo : mid;
+    hi = up ? mid : hi;
+  }
+  double z = 0.5 * (lo + hi);
+  {  // Newton polish on p0; a step longer than NEWTON_REACH (1 + |z|) is not taken
+    const double* p0 = sm + LDS_CHAIN;
+    for (int it = 0; it < NEWTON; ++it) {
+      double v = p0[10], d = 10 * p0[10];
+#pragma unroll
+      for (int i = 9; i >= 0; --i) {
+        v = v * z + p0[i];
+        if (i > 0) d = d * z + i * p0[i];
+      }
+      const double z1 = z - v / d;
+      z = isfinite(z1) && fabs(z1 - z) <= NEWTON_REACH * (1.0 + fabs(z)) ? z1 : z;
+    }
+  }
+  // x, y from the null vector of B(z): the cross product of two rows with the largest |w| (first on ties)
+  double rx[3], ry[3], r1[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) { rx[r] = horner<4>(bx[r], z); ry[r] = horner<4>(by[r], z); r1[r] = horner<5>(b1[r], z); }
+  double c0 = 0, c1 = 0, c2 = 0;
+#pragma unroll
+  for (int pr = 0; pr < 3; ++pr) {
+    const int a = pr == 2 ? 1 : 0, b = pr == 0 ? 1 : 2;
+    const double d0 = ry[a] * r1[b] - r1[a] * ry[b], d1 = r1[a] * rx[b] - rx[a] * r1[b], d2 = rx[a] * ry[b] - ry[a] * rx[b];
+    if (fabs(d2) > fabs(c2)) { c0 = d0; c1 = d1; c2 = d2; }
+  }
+  double x = c0 / c2, y = c1 / c2;
+  refine_xyz(sm + LDS_BASIS, x, y, z);
+  double s = 0;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    const double* b = sm + LDS_BASIS + 4 * q;
+    e[q] = ((x * b[0] + y * b[1]) + z * b[2]) + b[3];
+    s += e[q] * e[q];
+  }
+  const double inv = 1.0 / sqrt(s);
+  int big = 0;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    e[q] = e[q] * inv;
+    if (fabs(e[q]) > fabs(e[big])) big = q;
+  }
+  bool valid = gl < nroots;
+  double sg = 1.0;
+#pragma unroll
+  for (int q = 0; q < 9; ++q) {
+    valid = valid && isfinite(e[q]);
+    if (q == big && e[q] < 0) sg = -1.0;
+  }
+#pragma unroll
+  for (int q = 0; q < 9; ++q) e[q] = e[q] * sg;
+  const unsigned long long bal = __ballot(valid);
+  const unsigned gm = (unsigned)(bal >> (threadIdx.x & 63 & ~(G - 1))) & ((1u << G) - 1);
+  rank = valid ? __popc(gm & ((1u << gl) - 1)) : -1;
+  nsol = __popc(gm);
+  __syncthreads();  // the group's LDS is reused by the caller's next hypothesis
+}
+
+// ------------------------------------------------------------------------------------------------------------ RANSAC kernels
+__global__ __launch_bounds__(256) void ess_norm_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
+                                                       const int* __restrict__ counts, const double* __restrict__ K, int N, float thr,
+                                                       int max_iters, EState* __restrict__ st, float4* __restrict__ pts) {
+  __shared__ double sh[256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  const int n = counts ? min(max(counts[b], 0), N) : N;
+  const float2* A = ka + (long)b * N;
+  const float2* Bp = kb + (long)b * N;
+  double fx = 1, fy = 1, cx = 0, cy = 0;
+  if (K) {
+    const double* k = K + (long)b * 9;
+    fx = k[0]; cx = k[2]; fy = k[4]; cy = k[5];
+  }
+  const double thr_n = (double)thr / ((fx + fy) * 0.5);
+  double cnt = 0;
+  for (int i = t; i < n; i += 256) {
+    const float2 a = A[i], q = Bp[i];
+    const bool f = finite_row(a.x, a.y, q.x, q.y);
+    cnt += f ? 1 : 0;
+    float4 o = make_float4(NAN, NAN, NAN, NAN);
+    if (f) o = make_float4((float)((a.x - cx) / fx), (float)((a.y - cy) / fy), (float)((q.x - cx) / fx), (float)((q.y - cy) / fy));
+    pts[(long)b * N + i] = o;
+  }
+  cnt = block_sum(cnt, sh);
+  const bool valid = cnt >= 5 && fx != 0 && fy != 0 && isfinite(fx) && isfinite(fy) && isfinite(cx) && isfinite(cy) && thr_n > 0 &&
+                     isfinite(thr_n);
+  if (t == 0) {
+    EState& S = st[b];
+    S.fx = fx; S.fy = fy; S.cx = cx; S.cy = cy;
+    S.thr2 = (float)(thr_n * thr_n);
+    S.n = n;
+    S.valid = valid ? 1 : 0;
+    S.best = -1; S.best_h = -1; S.best_root = -1;
+    S.needed = max_iters;
+    S.rounds = 0;
+    S.done = valid ? 0 : 1;
+    for (int k = 0; k < 9; ++k) S.cur[k] = 0;
+    for (int k = 0; k < 12; ++k) S.curf[k] = 0;
+  }
+}
+
+// G lanes per (pair, hypothesis of the round); grid B * R / GPB
+__global__ __launch_bounds__(256) void ess_hyp_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb, int N,
+                                                      const unsigned long long* __restrict__ seeds, const EState* __restrict__ st,
+                                                      int round, double* __restrict__ slot_d, float* __restrict__ slot_f,
+                                                      int* __restrict__ slot_n) {
+  __shared__ double sm[GPB * LDS_PER];
+  const int grp = threadIdx.x / G, gl = threadIdx.x % G;
+  const int g = blockIdx.x * GPB + grp, b = g / R;
+  const EState& P = st[b];
+  if (P.done) return;  // uniform over the workgroup: its hypotheses belong to one pair
+  const int h = round * R + g % R;
+  int idx[5];
+  bool act = draw_sample<5>(seeds[b], h, P.n, idx);
+  double xa[5], ya[5], xb[5], yb[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const float2 a = act ? ka[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
+    const float2 q = act ? kb[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
+    act = act && finite_row(a.x, a.y, q.x, q.y);
+    xa[k] = (a.x - P.cx) / P.fx; ya[k] = (a.y - P.cy) / P.fy;
+    xb[k] = (q.x - P.cx) / P.fx; yb[k] = (q.y - P.cy) / P.fy;
+  }
+  double e[9];
+  int rank, nsol;
+  solve_e_group(xa, ya, xb, yb, act, sm + grp * LDS_PER, gl, e, rank, nsol);
+  if (rank >= 0) {
+    const long o = (long)g * MAXR + rank;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) slot_d[o * 9 + k] = e[k];
+    float4* f = reinterpret_cast<float4*>(slot_f + o * 12);
+    f[0] = make_float4((float)e[0], (float)e[1], (float)e[2], (float)e[3]);
+    f[1] = make_float4((float)e[4], (float)e[5], (float)e[6], (float)e[7]);
+    f[2] = make_float4((float)e[8], 0.f, 0.f, 0.f);
+  }
+  if (gl == 0) slot_n[g] = nsol;
+}
+
+// one wave per (pair, hypothesis): its models (wave-uniform coefficients) against the pair's points
+__global__ __launch_bounds__(256) void ess_score_kernel(const float4* __restrict__ pts, int N, const EState* __restrict__ st,
+                                                        const float* __restrict__ slot_f, const int* __restrict__ slot_n,
+                                                        int* __restrict__ slot_cnt) {
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = g / R;
+  const EState& P = st[b];
+  if (P.done) return;
+  const int nm = slot_n[g];
+  const float* mf = slot_f + (long)g * MAXR * 12;
+  const float4* Pp = pts + (long)b * N;
+  const int n = P.n;
+  const float t2 = P.thr2;
+  int c[MAXR];
+#pragma unroll
+  for (int r = 0; r < MAXR; ++r) c[r] = 0;
+  if (nm > 0) {
+    for (int i0 = 0; i0 < n; i0 += 64) {
+      const int i = i0 + lane;
+      const float4 p = i < n ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
+#pragma unroll
+      for (int r = 0; r < MAXR; ++r)
+        if (r < nm) c[r] += __popcll(__ballot(inlier_e(mf + 12 * r, p, t2)));
+    }
+  }
+  if (lane == 0) {
+    int* o = slot_cnt + (long)g * MAXR;
+#pragma unroll
+    for (int r = 0; r < MAXR; ++r) o[r] = r < nm ? c[r] : -1;
+  }
+}
+
+// one workgroup per pair: best (count, lowest slot) of the round, running best, adaptive iteration count, done flag
+__global__ __launch_bounds__(256) void ess_select_kernel(EState* __restrict__ st, int round, double conf, int max_iters,
+                                                         const double* __restrict__ slot_d, const int* __restrict__ slot_cnt) {
+  __shared__ int sc[256], si[256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  EState& P = st[b];
+  if (P.done) return;
+  const int* cnt = slot_cnt + (long)b * R * MAXR;
+  int bc = -1, bi = 0x7fffffff;
+  for (int k = t; k < R * MAXR; k += 256) {
+    const int c = cnt[k];
+    if (c > bc) { bc = c; bi = k; }  // k ascends: ties keep the lower slot
+  }
+  sc[t] = bc;
+  si[t] = bi;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      const int c = sc[t + w], i = si[t + w];
+      if (c > sc[t] || (c == sc[t] && i < si[t])) { sc[t] = c; si[t] = i; }
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    const int c = sc[0], k = si[0];
+    if (c > P.best) {  // strictly: an earlier round's model keeps a tie
+      P.best = c;
+      P.best_h = round * R + k / MAXR;
+      P.best_root = k % MAXR;
+      const double* m = slot_d + ((long)b * R * MAXR + k) * 9;
+      for (int q = 0; q < 9; ++q) P.cur[q] = m[q];
+      for (int q = 0; q < 9; ++q) P.curf[q] = (float)P.cur[q];
+      P.needed = update_num_iters(conf, (double)c / P.n, 5, max_iters);
+    }
+    P.rounds = round + 1;
+    const long drawn = (long)(round + 1) * R;
+    P.done = drawn >= (long)min(max_iters, P.needed) ? 1 : 0;
+  }
+}
+
+// mask[b, i] = inlier of the winning model (rows beyond counts[b], and pairs without a model: 0); grid (ceil(N / 256), B)
+__global__ __launch_bounds__(256) void ess_mask_kernel(const float4* __restrict__ pts, int N, const EState* __restrict__ st,
+                                                       unsigned char* __restrict__ mask) {
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const EState& P = st[b];
+  bool in = false;
+  if (P.best > 0 && i < P.n) in = inlier_e(P.curf, pts[(long)b * N + i], P.thr2);
+  mask[(long)b * N + i] = in ? 1 : 0;
+}
+
+__global__ __launch_bounds__(64) void ess_finish_kernel(int B, const EState* __restrict__ st, double* __restrict__ out,
+                                                        unsigned char* __restrict__ ok, int* __restrict__ info) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const EState& P = st[b];
+  const bool good = P.valid && P.best > 0;
+  for (int k = 0; k < 9; ++k) out[(long)b * 9 + k] = good ? P.cur[k] : 0.0;
+  ok[b] = good ? 1 : 0;
+  int* o = info + (long)b * ESSENTIAL_INFO;
+  o[0] = P.rounds;
+  o[1] = P.best_h;
+  o[2] = P.best_root;
+  o[3] = P.best;
+  o[4] = P.valid;
+}
+
+// the solver alone on caller samples; grid ceil(S / GPB)
+__global__ __launch_bounds__(256) void ess_minimal_kernel(const double* __restrict__ x0, const double* __restrict__ x1, int S,
+                                                          double* __restrict__ out_e, int* __restrict__ out_n) {
+  __shared__ double sm[GPB * LDS_PER];
+  const int grp = threadIdx.x / G, gl = threadIdx.x % G;
+  const int s = blockIdx.x * GPB + grp;
+  const bool act = s < S;
+  double xa[5], ya[5], xb[5], yb[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    const long o = ((long)(act ? s : 0) * 5 + k) * 2;
+    xa[k] = x0[o]; ya[k] = x0[o + 1]; xb[k] = x1[o]; yb[k] = x1[o + 1];
+  }
+  double e[9];
+  int rank, nsol;
+  solve_e_group(xa, ya, xb, yb, act, sm + grp * LDS_PER, gl, e, rank, nsol);
+  if (!act) return;
+  if (rank >= 0) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out_e[((long)s * MAXR + rank) * 9 + k] = e[k];
+  }
+  if (gl >= nsol && gl < MAXR) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out_e[((long)s * MAXR + gl) * 9 + k] = 0.0;
+  }
+  if (gl == 0) out_n[s] = nsol;
+}
+
+// ------------------------------------------------------------------------------------------------------------ recoverPose
+struct PoseState {
+  double cand[4][12];           // (R row-major, t) of the four candidates: (R1, t), (R2, t), (R1, -t), (R2, -t)
+  double fx, fy, cx, cy;
+  int n, valid;
+};
+
+__device__ __forceinline__ void mat3(const double* a, const double* b, double* c) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[3 * i + j] = (a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j]) + a[3 * i + 2] * b[6 + j];
+}
+
+// one thread per pair: E = U S V^T by one-sided Jacobi on the columns of E (A V = U S), singular values descending,
+// u3 = u1 x u2 (v3 signed to match where s3 > 0), OpenCV's fix-up (det(U), det(V) > 0), W = [[0, 1, 0], [-1, 0, 0], [0, 0, 1]],
+// R1 = U W V^T, R2 = U W^T V^T, t = U[:, 2]
+__global__ __launch_bounds__(64) void ess_decompose_kernel(const double* __restrict__ E, const int* __restrict__ counts,
+                                                           const double* __restrict__ K, int B, int N, PoseState* __restrict__ st) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  double a[3][3], v[3][3];  // a[j] = column j
+  bool fin = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      a[j][i] = E[(long)b * 9 + 3 * i + j];
+      fin = fin && isfinite(a[j][i]);
+      v[j][i] = i == j ? 1.0 : 0.0;
+    }
+  for (int sweep = 0; sweep < SVD_SWEEPS && fin; ++sweep) {
+    bool rot = false;
+#pragma unroll
+    for (int pq = 0; pq < 3; ++pq) {
+      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+      double al = 0, be = 0, ga = 0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        al += a[p][k] * a[p][k];
+        be += a[q][k] * a[q][k];
+        ga += a[p][k] * a[q][k];
+      }
+      if (fabs(ga) > SVD_TOL * sqrt(al * be)) {
+        const double zz = (be - al) / (2 * ga);
+        const double tn = copysign(1.0, zz) / (fabs(zz) + sqrt(1 + zz * zz));
+        const double c = 1 / sqrt(1 + tn * tn), s = c * tn;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double ap = a[p][k], aq = a[q][k], vp = v[p][k], vq = v[q][k];
+          a[p][k] = c * ap - s * aq;
+          a[q][k] = s * ap + c * aq;
+          v[p][k] = c * vp - s * vq;
+          v[q][k] = s * vp + c * vq;
+        }
+        rot = true;
+      }
+    }
+    if (!rot) break;
+  }
+  double sg[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) sg[j] = sqrt(a[j][0] * a[j][0] + a[j][1] * a[j][1] + a[j][2] * a[j][2]);
+  // sort descending (columns of A and V together)
+#pragma unroll
+  for (int pass = 0; pass < 3; ++pass) {
+    const int p = pass == 1 ? 1 : 0, q = p + 1;
+    if (sg[q] > sg[p]) {
+      double t = sg[p]; sg[p] = sg[q]; sg[q] = t;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        t = a[p][k]; a[p][k] = a[q][k]; a[q][k] = t;
+        t = v[p][k]; v[p][k] = v[q][k]; v[q][k] = t;
+      }
+    }
+  }
+  double U[9], Vt[9];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    U[3 * k] = a[0][k] / sg[0];
+    U[3 * k + 1] = a[1][k] / sg[1];
+  }
+  U[2] = U[3] * U[7] - U[6] * U[4];
+  U[5] = U[6] * U[1] - U[0] * U[7];
+  U[8] = U[0] * U[4] - U[3] * U[1];
+  const double d3 = a[2][0] * U[2] + a[2][1] * U[5] + a[2][2] * U[8];
+  const double s3 = d3 < 0 ? -1.0 : 1.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    Vt[k] = v[0][k];
+    Vt[3 + k] = v[1][k];
+    Vt[6 + k] = s3 * v[2][k];
+  }
+  const double dv = Vt[0] * (Vt[4] * Vt[8] - Vt[5] * Vt[7]) - Vt[1] * (Vt[3] * Vt[8] - Vt[5] * Vt[6]) +
+                    Vt[2] * (Vt[3] * Vt[7] - Vt[4] * Vt[6]);
+  if (dv < 0) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Vt[k] = -Vt[k];
+  }
+  const double W[9] = {0, 1, 0, -1, 0, 0, 0, 0, 1}, Wt[9] = {0, -1, 0, 1, 0, 0, 0, 0, 1};
+  double tmp[9], R1[9], R2[9];
+  mat3(U, W, tmp);
+  mat3(tmp, Vt, R1);
+  mat3(U, Wt, tmp);
+  mat3(tmp, Vt, R2);
+  bool ok = fin && sg[1] > 0;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) ok = ok && isfinite(R1[k]) && isfinite(R2[k]) && isfinite(U[k]);
+  PoseState& P = st[b];
+  for (int c = 0; c < 4; ++c) {
+    const double* Rc = c % 2 == 0 ? R1 : R2;
+    const double ts = c < 2 ? 1.0 : -1.0;
+    for (int k = 0; k < 9; ++k) P.cand[c][k] = Rc[k];
+    for (int k = 0; k < 3; ++k) P.cand[c][9 + k] = ts * U[3 * k + 2];
+  }
+  double fx = 1, fy = 1, cx = 0, cy = 0;
+  if (K) {
+    const double* k = K + (long)b * 9;
+    fx = k[0]; cx = k[2]; fy = k[4]; cy = k[5];
+  }
+  P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy;
+  P.n = counts ? min(max(counts[b], 0), N) : N;
+  P.valid = ok && fx != 0 && fy != 0 && isfinite(fx) && isfinite(fy) && isfinite(cx) && isfinite(cy) ? 1 : 0;
+}
+
+// linear triangulation with P0 = [I | 0], P1 = [R | t] and the point on the ray of camera 0, X = (lam x0, w): (lam, w) is the
+// smallest eigenvector of M^T M for the two equations of camera 1, M = [[u R3.x0 - R1.x0, u t3 - t1], [v R3.x0 - R2.x0, v t3 - t2]].
+// OpenCV's cheirality rule: Q2 Q3 = lam w > 0, then depth lam / w and depth (R X)_3 / w in camera 1 both in (0, dist).
+__device__ __forceinline__ bool cheiral(const double* c, double x, double y, double u, double v, double dist) {
+  const double r1 = (c[0] * x + c[1] * y) + c[2], r2 = (c[3] * x + c[4] * y) + c[5], r3 = (c[6] * x + c[7] * y) + c[8];
+  const double a1 = u * r3 - r1, b1 = u * c[11] - c[9];
+  const double a2 = v * r3 - r2, b2 = v * c[11] - c[10];
+  const double p = a1 * a1 + a2 * a2, q = a1 * b1 + a2 * b2, r = b1 * b1 + b2 * b2;
+  const double hd = (p - r) * 0.5;
+  const double mu = (p + r) * 0.5 - sqrt(hd * hd + q * q);
+  const double lam = p >= r ? q : mu - r;
+  const double w = p >= r ? mu - p : q;
+  if (!(lam * w > 0)) return false;
+  const double z0 = lam / w, z1 = (lam * r3 + w * c[11]) / w;
+  return z0 < dist && z1 > 0 && z1 < dist;
+}
+
+// grid (ceil(N / 256), B): good flags of the four candidates per point, per-block counts
+__global__ __launch_bounds__(256) void ess_cheirality_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
+                                                             const unsigned char* __restrict__ mask, int N, double dist,
+                                                             const PoseState* __restrict__ st, unsigned char* __restrict__ flags,
+                                                             int* __restrict__ partial) {
+  __shared__ int sh[4][4];
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const PoseState& P = st[b];
+  int bits = 0;
+  if (P.valid && i < P.n && (!mask || mask[(long)b * N + i])) {
+    const float2 a = ka[(long)b * N + i], q = kb[(long)b * N + i];
+    if (finite_row(a.x, a.y, q.x, q.y)) {
+      const double x = (a.x - P.cx) / P.fx, y = (a.y - P.cy) / P.fy, u = (q.x - P.cx) / P.fx, v = (q.y - P.cy) / P.fy;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) bits |= cheiral(P.cand[c], x, y, u, v, dist) ? 1 << c : 0;
+    }
+  }
+  if (i < N) flags[(long)b * N + i] = (unsigned char)bits;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int n = __popcll(__ballot((bits >> c) & 1));
+    if (lane == 0) sh[wave][c] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int c = threadIdx.x;
+    partial[((long)b * gridDim.x + blockIdx.x) * 4 + c] = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
+  }
+}
+
+// one workgroup per pair: candidate with the most good points (ties: the earlier one), R, t, n_good, mask_good
+__global__ __launch_bounds__(256) void ess_pose_kernel(int N, int nblk, const PoseState* __restrict__ st,
+                                                       const unsigned char* __restrict__ flags, const int* __restrict__ partial,
+                                                       int* __restrict__ out_n, double* __restrict__ out_r, double* __restrict__ out_t,
+                                                       unsigned char* __restrict__ out_mask) {
+  __shared__ int best;
+  const int b = blockIdx.x, t = threadIdx.x;
+  const PoseState& P = st[b];
+  if (t == 0) {
+    int cnt[4] = {0, 0, 0, 0};
+    for (int k = 0; k < nblk; ++k)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) cnt[c] += partial[((long)b * nblk + k) * 4 + c];
+    int bc = 0;
+#pragma unroll
+    for (int c = 1; c < 4; ++c)
+      if (cnt[c] > cnt[bc]) bc = c;
+    best = bc;
+    const bool ok = P.valid;
+    out_n[b] = ok ? cnt[bc] : 0;
+    for (int k = 0; k < 9; ++k) out_r[(long)b * 9 + k] = ok ? P.cand[bc][k] : 0.0;
+    for (int k = 0; k < 3; ++k) out_t[(long)b * 3 + k] = ok ? P.cand[bc][9 + k] : 0.0;
+  }
+  __syncthreads();
+  const int c = best;
+  for (int i = t; i < N; i += 256) out_mask[(long)b * N + i] = (unsigned char)((flags[(long)b * N + i] >> c) & 1);
+}
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+struct Carve {
+  EState* st;
+  float4* pts;
+  double* slot_d;
+  float* slot_f;
+  int *slot_n, *slot_cnt;
+  size_t bytes;
+};
+
+Carve carve(void* ws, int B, int N) {
+  Carve c;
+  char* p = static_cast<char*>(ws);
+  size_t o = 0;
+  c.st = reinterpret_cast<EState*>(p + o); o = align256(o + sizeof(EState) * B);
+  c.pts = reinterpret_cast<float4*>(p + o); o = align256(o + sizeof(float4) * (size_t)B * N);
+  c.slot_d = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * 9 * MAXR * (size_t)B * R);
+  c.slot_f = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * 12 * MAXR * (size_t)B * R);
+  c.slot_n = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * (size_t)B * R);
+  c.slot_cnt = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * MAXR * (size_t)B * R);
+  c.bytes = o + 256;  // slack: the caller's base need not be 256-aligned
+  return c;
+}
+
+struct PoseCarve {
+  PoseState* st;
+  unsigned char* flags;
+  int* partial;
+  size_t bytes;
+};
+
+PoseCarve pose_carve(void* ws, int B, int N) {
+  PoseCarve c;
+  char* p = static_cast<char*>(ws);
+  size_t o = 0;
+  const size_t nblk = (N + 255) / 256;
+  c.st = reinterpret_cast<PoseState*>(p + o); o = align256(o + sizeof(PoseState) * B);
+  c.flags = reinterpret_cast<unsigned char*>(p + o); o = align256(o + (size_t)B * N);
+  c.partial = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * 4 * nblk * B);
+  c.bytes = o + 256;
+  return c;
+}
+
+template <typename T>
+T align_base(void* ws) {
+  return reinterpret_cast<T>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
+}
+
+}  // namespace
+
+size_t essential_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? carve(nullptr, B, N).bytes : 0; }
+
+int essential_launch(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K,
+                     int B, int N, float threshold, double prob, int max_iters, double* out_e, unsigned char* out_mask,
+                     unsigned char* out_ok, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
+  ROMA_REQUIRE(kpts_a && kpts_b && seeds && out_e && out_mask && out_ok && out_info && ws, "essential: null pointer");
+  ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), "essential: need 0 < B <= 65536, 0 < N, B * N < 2^31");
+  ROMA_REQUIRE(max_iters > 0, "essential: max_iters must be positive");
+  ROMA_REQUIRE(threshold > 0 && isfinite(threshold), "essential: threshold must be positive and finite");
+  ROMA_REQUIRE(prob >= 0 && prob <= 1, "essential: prob must lie in [0, 1]");
+  ROMA_REQUIRE(ws_bytes >= essential_workspace_bytes(B, N), "essential: workspace too small (roma_op_essential_workspace)");
+  const Carve c = carve(align_base<void*>(ws), B, N);
+  const float2* ka = reinterpret_cast<const float2*>(kpts_a);
+  const float2* kb = reinterpret_cast<const float2*>(kpts_b);
+  hipLaunchKernelGGL(ess_norm_kernel, dim3(B), dim3(256), 0, s, ka, kb, counts, K, N, threshold, max_iters, c.st, c.pts);
+  ROMA_LAUNCH_CHECK();
+  const int rounds = (max_iters + R - 1) / R;
+  for (int r = 0; r < rounds; ++r) {
+    hipLaunchKernelGGL(ess_hyp_kernel, dim3(B * R / GPB), dim3(256), 0, s, ka, kb, N, seeds, c.st, r, c.slot_d, c.slot_f, c.slot_n);
+    ROMA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ess_score_kernel, dim3(B * R / 4), dim3(256), 0, s, c.pts, N, c.st, c.slot_f, c.slot_n, c.slot_cnt);
+    ROMA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ess_select_kernel, dim3(B), dim3(256), 0, s, c.st, r, prob, max_iters, c.slot_d, c.slot_cnt);
+    ROMA_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(ess_mask_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, c.pts, N, c.st, out_mask);
+  ROMA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ess_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, out_e, out_ok, out_info);
+  ROMA_LAUNCH_CHECK();
+  return 0;
+}
+
+int essential_minimal_launch(const double* x0, const double* x1, int S, double* out_e, int* out_n, hipStream_t s) {
+  ROMA_REQUIRE(x0 && x1 && out_e && out_n, "essential_minimal: null pointer");
+  ROMA_REQUIRE(S > 0 && S <= (1 << 24), "essential_minimal: need 0 < S <= 2^24");
+  hipLaunchKernelGGL(ess_minimal_kernel, dim3((S + GPB - 1) / GPB), dim3(256), 0, s, x0, x1, S, out_e, out_n);
+  ROMA_LAUNCH_CHECK();
+  return 0;
+}
+
+size_t recover_pose_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? pose_carve(nullptr, B, N).bytes : 0; }
+
+int recover_pose_launch(const double* E, const float* kpts_a, const float* kpts_b, const unsigned char* mask, const int* counts,
+                        const double* K, int B, int N, double distance_thresh, int* out_n, double* out_r, double* out_t,
+                        unsigned char* out_mask, void* ws, size_t ws_bytes, hipStream_t s) {
+  ROMA_REQUIRE(E && kpts_a && kpts_b && out_n && out_r && out_t && out_mask && ws, "recover_pose: null pointer");
+  ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), "recover_pose: need 0 < B <= 65536, 0 < N, B * N < 2^31");
+  ROMA_REQUIRE(distance_thresh > 0, "recover_pose: distance_thresh must be positive");
+  ROMA_REQUIRE(ws_bytes >= recover_pose_workspace_bytes(B, N), "recover_pose: workspace too small (roma_op_recover_pose_workspace)");
+  const PoseCarve c = pose_carve(align_base<void*>(ws), B, N);
+  const int nblk = (N + 255) / 256;
+  hipLaunchKernelGGL(ess_decompose_kernel, dim3((B + 63) / 64), dim3(64), 0, s, E, counts, K, B, N, c.st);
+  ROMA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ess_cheirality_kernel, dim3(nblk, B), dim3(256), 0, s, reinterpret_cast<const float2*>(kpts_a),
+                     reinterpret_cast<const float2*>(kpts_b), mask, N, distance_thresh, c.st, c.flags, c.partial);
+  ROMA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ess_pose_kernel, dim3(B), dim3(256), 0, s, N, nblk, c.st, c.flags, c.partial, out_n, out_r, out_t, out_mask);
+  ROMA_LAUNCH_CHECK();
+  return 0;
+}
+
+}  // namespace roma

@@ -17,7 +17,7 @@
 // Every flag and counter of the workspace is written with plain stores by one kernel and read by a later launch on the same
 // stream: no atomics and no hand-off inside a launch.  Results are bit-identical from run to run and independent of B.
 #include "geometry.h"
-#include "sampling.h"
+#include "ransac_common.h"
 
 #include <float.h>
 #include <math.h>
@@ -31,11 +31,9 @@ namespace {
 
 constexpr int R = RANSAC_ROUND;
 constexpr int MAX_ROOTS = 3;          // model slots per hypothesis
-constexpr int MAX_TRY = 64;           // redraws of one sample index before the sample is given up
 constexpr int REFINE_ITERS = 3;
 constexpr int JACOBI_SWEEPS = 15;
 constexpr double COLLINEAR_EPS = 1e-4;  // |sin| of a triple's angle below which the triple counts as collinear
-constexpr double PIVOT_EPS = 1e-6;      // |pivot| of the minimal solvers' elimination (normalised coordinates)
 constexpr double CUBIC_EPS = 1e-12;     // relative size below which a leading coefficient of the cubic is zero
 constexpr double JACOBI_TOL = 4 * DBL_EPSILON;
 
@@ -126,44 +124,6 @@ __device__ __forceinline__ bool all_finite(const double* m) {
 #pragma unroll
   for (int k = 0; k < 9; ++k) ok &= isfinite(m[k]);
   return ok;
-}
-
-// Gauss-Jordan elimination with partial pivoting (first maximum) of the pivot columns 0 .. ROWS-1; rows swapped by selects
-// so the matrix stays in registers.  false if a pivot is not above PIVOT_EPS in magnitude.
-template <int ROWS, int COLS>
-__device__ __forceinline__ bool gauss_jordan(double (&a)[ROWS][COLS]) {
-#pragma unroll
-  for (int k = 0; k < ROWS; ++k) {
-    int p = k;
-    double big = fabs(a[k][k]);
-#pragma unroll
-    for (int r = k + 1; r < ROWS; ++r) {
-      const double v = fabs(a[r][k]);
-      if (v > big) { big = v; p = r; }
-    }
-    if (!(big > PIVOT_EPS)) return false;
-#pragma unroll
-    for (int r = k + 1; r < ROWS; ++r) {
-      const bool sw = r == p;
-#pragma unroll
-      for (int c = 0; c < COLS; ++c) {
-        const double t = a[k][c];
-        a[k][c] = sw ? a[r][c] : t;
-        a[r][c] = sw ? t : a[r][c];
-      }
-    }
-    const double inv = 1.0 / a[k][k];
-#pragma unroll
-    for (int c = 0; c < COLS; ++c) a[k][c] = a[k][c] * inv;
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      if (r == k) continue;
-      const double f = a[r][k];
-#pragma unroll
-      for (int c = 0; c < COLS; ++c) a[r][c] = a[r][c] - f * a[k][c];
-    }
-  }
-  return true;
 }
 
 // real roots of c3 x^3 + c2 x^2 + c1 x + c0, ascending; their number (0 .. 3).  Closed form (trigonometric / Cardano), then
@@ -298,63 +258,6 @@ __device__ int solve_f(const double* xa, const double* ya, const double* xb, con
     ++n;
   }
   return n;
-}
-
-// ------------------------------------------------------------------------------------------------------------ sampling
-// draw j of hypothesis h: index mix64(key_h + G2 (c + 1)) mod n with c = j, j + S, j + 2S, ... until it differs from the
-// draws before it; key_h = mix64(seed + G1 (h + 1)).  Depends on (seed, h) only.
-template <int S>
-__device__ __forceinline__ bool draw_sample(uint64_t seed, int h, int n, int (&idx)[S]) {
-  const uint64_t key = mix64(seed + 0x9e3779b97f4a7c15ull * (uint64_t)(h + 1));
-#pragma unroll
-  for (int j = 0; j < S; ++j) {
-    bool got = false;
-    for (int t = 0; t < MAX_TRY && !got; ++t) {
-      const uint64_t c = (uint64_t)(j + t * S);
-      const int v = (int)(mix64(key + 0xd1b54a32d192ed03ull * (c + 1)) % (uint64_t)n);
-      bool dup = false;
-#pragma unroll
-      for (int k = 0; k < j; ++k) dup |= idx[k] == v;
-      if (!dup) {
-        idx[j] = v;
-        got = true;
-      }
-    }
-    if (!got) return false;
-  }
-  return true;
-}
-
-// OpenCV's RANSACUpdateNumIters with the ceiling of the ratio: hypotheses needed so that, with inlier ratio w, a sample of
-// s inliers has been drawn with probability conf
-__device__ int update_num_iters(double conf, double w, int s, int max_iters) {
-  conf = fmin(fmax(conf, 0.0), 1.0);
-  w = fmin(fmax(w, 0.0), 1.0);
-  double ws = 1;
-  for (int k = 0; k < s; ++k) ws *= w;
-  const double num = log(fmax(1 - conf, DBL_MIN));
-  double denom = 1 - ws;
-  if (denom < DBL_MIN) return 0;
-  denom = log(denom);
-  if (denom >= 0 || -num >= max_iters * (-denom)) return max_iters;
-  return (int)ceil(num / denom);
-}
-
-// ------------------------------------------------------------------------------------------------------------ reductions
-__device__ __forceinline__ double block_sum(double v, double* sh) {  // 256 threads, fixed tree
-  const int t = threadIdx.x;
-  __syncthreads();
-  sh[t] = v;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) sh[t] = sh[t] + sh[t + s];
-    __syncthreads();
-  }
-  return sh[0];
-}
-
-__device__ __forceinline__ bool finite_row(float a0, float a1, float b0, float b1) {
-  return isfinite(a0) && isfinite(a1) && isfinite(b0) && isfinite(b1);
 }
 
 // ------------------------------------------------------------------------------------------------------------ kernels

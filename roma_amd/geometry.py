@@ -8,6 +8,11 @@ for it, and there is no Levenberg-Marquardt polish.  The algorithm is restated i
 
 Both models map A to B in pixel coordinates: x_B ~ H x_A and x_B^T F x_A = 0, like OpenCV's (points1 = A, points2 = B).  H and F
 are scaled so that [2, 2] = 1 (unit Frobenius norm where |[2, 2]| < 1e-12 of it); F has rank 2.
+
+The relative pose of the reference's pose benchmarks (romatch/utils/utils.py estimate_pose: cv2.findEssentialMat + cv2.recoverPose)
+runs on the device as well (`roma_op_essential` / `roma_op_recover_pose`, csrc/essential.hip): `find_essential`, `recover_pose`,
+`estimate_pose`, `estimate_pose_uncalibrated` and the five-point solver alone, `essential_minimal`.  Restated in numpy float64 by
+tools/essential_ref.py.
 """
 from __future__ import annotations
 
@@ -112,3 +117,212 @@ def find_fundamental(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.9
     kpts_A, kpts_B: [N, 2] -> (F [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
     [B, N, 2] -> (F [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
     return _front(FUNDAMENTAL, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts)
+
+
+# ---------------------------------------------------------------------------------------------------- essential matrix and pose
+ESSENTIAL_MAX_ROOTS = 10  # solutions of one five-point sample (csrc/essential.h)
+
+
+def _pair_batch(kpts_A, kpts_B):
+    a, b = _as_batch(kpts_A, "kpts_A"), _as_batch(kpts_B, "kpts_B")
+    a = a[None] if a.dim() == 2 else a
+    b = b[None] if b.dim() == 2 else b
+    if a.shape != b.shape or a.dim() != 3:
+        raise ValueError(f"roma_amd.geometry: kpts_A {tuple(kpts_A.shape)} and kpts_B {tuple(kpts_B.shape)} differ in shape")
+    if a.device != b.device:
+        raise ValueError("roma_amd.geometry: kpts_A and kpts_B live on different devices")
+    return a, b
+
+
+def _cameras(camera_matrix, B, dev):
+    """[B, 3, 3] float64 device camera matrices, or None (identity)"""
+    if camera_matrix is None:
+        return None
+    K = torch.as_tensor(camera_matrix).to(device=dev, dtype=torch.float64)
+    if K.shape == (3, 3):
+        K = K[None].expand(B, 3, 3)
+    if K.shape != (B, 3, 3):
+        raise ValueError(f"roma_amd.geometry: camera_matrix must be [3, 3] or [{B}, 3, 3], got {tuple(K.shape)}")
+    return K.contiguous()
+
+
+def _counts(counts, B, dev):
+    if counts is None:
+        return None
+    counts = torch.as_tensor(counts).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    if counts.shape[0] != B:
+        raise ValueError(f"roma_amd.geometry: counts has {counts.shape[0]} entries for {B} pairs")
+    return counts
+
+
+def _seeds(seed, B, dev):
+    if seed is None:
+        seeds = torch.randint(0, 2 ** 62, (B,), dtype=torch.int64)  # CPU generator: no device synchronisation
+    elif isinstance(seed, torch.Tensor):
+        seeds = seed.reshape(-1).to(torch.int64)
+        if seeds.shape[0] != B:
+            raise ValueError(f"roma_amd.geometry: {seeds.shape[0]} seeds for {B} pairs")
+    else:
+        seeds = torch.full((B,), int(seed), dtype=torch.int64)
+    return seeds.to(dev).contiguous()  # read as uint64 by the kernels
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None):
+    """Batched cv2.findEssentialMat, no host synchronisation.  Returns (E [B, 3, 3] float64, mask [B, N] bool, ok [B] bool,
+    info [B, 5] int32) with info = (rounds run, winning hypothesis, its root, inlier count, pair valid)."""
+    a, b = _pair_batch(kpts_A, kpts_B)
+    if not (threshold > 0) or not (0 <= prob <= 1) or int(max_iters) <= 0:
+        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= prob <= 1, max_iters > 0")
+    B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
+    E = torch.zeros((B, 3, 3), device=dev, dtype=torch.float64)
+    mask = torch.zeros((B, N), device=dev, dtype=torch.bool)
+    ok = torch.zeros((B,), device=dev, dtype=torch.bool)
+    info = torch.zeros((B, 5), device=dev, dtype=torch.int32)
+    if B == 0:
+        return E, mask, ok, info
+    K, counts, seeds = _cameras(camera_matrix, B, dev), _counts(counts, B, dev), _seeds(seed, B, dev)
+    if N < 5:  # no pair can hold a minimal sample: nothing to launch
+        return E, mask, ok, info
+    lib = _lib.load()
+    nws = int(lib.roma_op_essential_workspace(B, N))
+    ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(lib.roma_op_essential(_ptr(a), _ptr(b), _ptr(counts), _ptr(seeds), _ptr(K), B, N, float(threshold), float(prob),
+                                         int(max_iters), _ptr(E), _ptr(mask), _ptr(ok), _ptr(info), _ptr(ws), nws,
+                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return E, mask, ok, info
+
+
+def find_essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None):
+    """cv2.findEssentialMat(kpts_A, kpts_B, camera_matrix, cv2.RANSAC, prob, threshold, max_iters) on the device: Nister's
+    five-point hypotheses (up to 10 models each), inliers whose Sampson distance is below the threshold, no refinement.
+    camera_matrix None means identity (the points are normalised already, as the reference calls it); a [3, 3] or [B, 3, 3]
+    matrix normalises x_n = ((x - cx) / fx, (y - cy) / fy) and divides the threshold by (fx + fy) / 2, like OpenCV.  E relates
+    the normalised points (x_B^T E x_A = 0), has unit Frobenius norm and its largest-magnitude entry positive.
+
+    kpts_A, kpts_B: [N, 2] -> (E [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
+    [B, N, 2] -> (E [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
+    single = isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2
+    E, mask, ok, _ = essential(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, counts)
+    if not single:
+        return E, mask, ok
+    if not bool(ok[0]):  # the one synchronisation of the single-pair form
+        return None, None
+    return E[0], mask[0]
+
+
+def recover_pose(E, kpts_A, kpts_B, mask=None, camera_matrix=None, distance_thresh=1e9, counts=None):
+    """cv2.recoverPose(E, kpts_A, kpts_B, camera_matrix, distance_thresh, mask) on the device.  The four decompositions
+    (R1, t), (R2, t), (R1, -t), (R2, -t) of E (SVD with OpenCV's det(U), det(V^T) > 0 fix-up, t = U[:, 2]; E need not be exactly
+    essential), linear triangulation of the masked rows, a row is good for a candidate if its depth is positive and below
+    distance_thresh in both cameras; the candidate with the most good rows wins, ties to the earlier one.
+
+    E [3, 3] with kpts [N, 2] -> (n_good int, R [3, 3] float64, t [3, 1] float64, mask_good [N] bool);
+    E [B, 3, 3] with kpts [B, N, 2] -> (n_good [B] int32, R [B, 3, 3], t [B, 3, 1], mask_good [B, N]), no synchronisation."""
+    single = isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2
+    a, b = _pair_batch(kpts_A, kpts_B)
+    B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
+    if not isinstance(E, torch.Tensor) or not E.is_cuda:
+        raise _lib.RomaHipError("roma_amd.geometry: E must be a tensor on a HIP device; there is no CPU fallback")
+    E = E.detach().to(device=dev, dtype=torch.float64).reshape(-1, 3, 3).contiguous()
+    if E.shape[0] != B:
+        raise ValueError(f"roma_amd.geometry: {E.shape[0]} matrices E for {B} pairs")
+    if not (distance_thresh > 0):
+        raise ValueError("roma_amd.geometry: distance_thresh must be positive")
+    if mask is not None:
+        mask = torch.as_tensor(mask).to(device=dev).reshape(B, N).to(torch.uint8).contiguous()
+    K, counts = _cameras(camera_matrix, B, dev), _counts(counts, B, dev)
+    n_good = torch.zeros((B,), device=dev, dtype=torch.int32)
+    R = torch.zeros((B, 3, 3), device=dev, dtype=torch.float64)
+    t = torch.zeros((B, 3, 1), device=dev, dtype=torch.float64)
+    good = torch.zeros((B, N), device=dev, dtype=torch.bool)
+    if B > 0 and N > 0:
+        lib = _lib.load()
+        nws = int(lib.roma_op_recover_pose_workspace(B, N))
+        ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            _lib.check(lib.roma_op_recover_pose(_ptr(E), _ptr(a), _ptr(b), _ptr(mask), _ptr(counts), _ptr(K), B, N,
+                                                float(distance_thresh), _ptr(n_good), _ptr(R), _ptr(t), _ptr(good), _ptr(ws), nws,
+                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    if single:
+        return int(n_good[0]), R[0], t[0], good[0]
+    return n_good, R, t, good
+
+
+def essential_minimal(x0, x1):
+    """The five-point solver alone on caller-chosen samples: x0, x1 [S, 5, 2] normalised points (x1^T E x0 = 0) ->
+    (E [S, 10, 3, 3] float64, n [S] int32); solution r < n[s] of sample s is E[s, r], in ascending order of Nister's z, unit
+    Frobenius norm, largest-magnitude entry positive; unused slots are zero."""
+    for name, x in (("x0", x0), ("x1", x1)):
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise _lib.RomaHipError(f"roma_amd.geometry: {name} must be a tensor on a HIP device; there is no CPU fallback")
+        if x.dim() != 3 or tuple(x.shape[1:]) != (5, 2):
+            raise ValueError(f"roma_amd.geometry: {name} must be [S, 5, 2], got {tuple(x.shape)}")
+    if x0.shape != x1.shape:
+        raise ValueError("roma_amd.geometry: x0 and x1 differ in shape")
+    S, dev = int(x0.shape[0]), x0.device
+    a = x0.detach().to(torch.float64).contiguous()
+    b = x1.detach().to(device=dev, dtype=torch.float64).contiguous()
+    E = torch.zeros((S, ESSENTIAL_MAX_ROOTS, 3, 3), device=dev, dtype=torch.float64)
+    n = torch.zeros((S,), device=dev, dtype=torch.int32)
+    if S > 0:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().roma_op_essential_minimal(_ptr(a), _ptr(b), S, _ptr(E), _ptr(n),
+                                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return E, n
+
+
+def _normalise_pose_points(kpts, K):
+    """the reference's normalisation (utils.py:38-39): inverse of K[:2, :2] (skew included) after the principal point, f64"""
+    k = kpts.to(torch.float64) - K[:, None, :2, 2]
+    a, b, c, d = K[:, 0, 0, None], K[:, 0, 1, None], K[:, 1, 0, None], K[:, 1, 1, None]
+    det = a * d - b * c  # closed-form 2 x 2 inverse: torch.linalg.inv would read its error flag back to the host
+    return torch.stack(((d * k[..., 0] - b * k[..., 1]) / det, (a * k[..., 1] - c * k[..., 0]) / det), dim=-1)
+
+
+def _pose_inputs(kpts0, kpts1, K0, K1, counts):
+    a, b = _pair_batch(kpts0, kpts1)
+    B, dev = int(a.shape[0]), a.device
+    K0, K1 = _cameras(K0, B, dev), _cameras(K1, B, dev)
+    if K0 is None or K1 is None:
+        raise ValueError("roma_amd.geometry: K0 and K1 are required")
+    return a, b, K0, K1, _counts(counts, B, dev)
+
+
+def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=1000, seed=None, counts=None):
+    """romatch/utils/utils.py:30-51 on the device: normalise with the inverse of K[:2, :2] and the principal point (f64), then
+    find_essential (identity camera, threshold norm_thresh, prob conf) and recover_pose.
+
+    [N, 2] -> (R [3, 3], t [3, 1], mask [N] bool) or None (also for fewer than 5 rows); [B, N, 2] -> (R [B, 3, 3],
+    t [B, 3, 1], mask [B, N], ok [B]) with no host synchronisation.  mask is what the reference returns: cv2.recoverPose rewrites the RANSAC mask in place, so it holds
+    the RANSAC inliers that pass the cheirality test of the chosen candidate (tools/pose_geometry.estimate_pose returns the plain
+    RANSAC mask instead)."""
+    single = isinstance(kpts0, torch.Tensor) and kpts0.dim() == 2
+    a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
+    x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
+    E, inl, ok, _ = essential(x0, x1, None, conf, norm_thresh, max_iters, seed, counts)
+    n, R, t, good = recover_pose(E, x0, x1, inl, None, 1e9, counts)
+    ok = ok & (n > 0)
+    if not single:
+        return R, t, good, ok
+    return (R[0], t[0], good[0]) if bool(ok[0]) else None  # the one synchronisation of the single-pair form
+
+
+def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=10000, seed=None, counts=None):
+    """romatch/utils/utils.py:53-74 on the device: find_fundamental on the pixels (threshold norm_thresh in pixels, as the
+    reference passes it; plain RANSAC + LO standing in for USAC_ACCURATE), E = K1^T F K0, then recover_pose on the normalised
+    points.  Returns as estimate_pose."""
+    single = isinstance(kpts0, torch.Tensor) and kpts0.dim() == 2
+    a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
+    F, inl, ok, _ = ransac(FUNDAMENTAL, a, b, norm_thresh, conf, max_iters, seed, True, counts)
+    E = K1.transpose(1, 2) @ F @ K0
+    x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
+    n, R, t, good = recover_pose(E, x0, x1, inl, None, 1e9, counts)
+    ok = ok & (n > 0)
+    if not single:
+        return R, t, good, ok
+    return (R[0], t[0], good[0]) if bool(ok[0]) else None  # the one synchronisation of the single-pair form

@@ -142,12 +142,16 @@ def ground_truth_matches(data):
 
 
 # ------------------------------------------------------------------------------------------- MegaDepth-1500 pose benchmark
-def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200):
+def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200, pose="host"):
     """megadepth_pose_estimation_benchmark.py:25-116 over an iterable of pairs
     {im_A, im_B (what model.match takes: paths, PIL images or [3, H, W] tensors), K1, K2 [3, 3], T_1to2 [3, 4] or [4, 4],
     size_A = (w1, h1), size_B = (w2, h2) of the ORIGINAL images}: per pair one `match`, then `repeats` x {`sample` 5 000
     matches, pixel coordinates at the 1 200-pixel scale, shuffle, `estimate_pose` at 0.5 px / mean focal, pose error};
-    failures count as 90 degrees.  Returns the reference's dictionary (auc_5/10/20, map_5/10/20)."""
+    failures count as 90 degrees.  Returns the reference's dictionary (auc_5/10/20, map_5/10/20).
+    pose="host": tools/pose_geometry.estimate_pose per call (numpy); pose="device": a pair's `repeats` calls as one batched
+    roma_amd.estimate_pose (B = repeats, one seed per repeat), read back once per pair."""
+    if pose not in ("host", "device"):
+        raise ValueError(f"pose must be 'host' or 'device', got {pose!r}")
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pose_geometry as PG
@@ -164,6 +168,11 @@ def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200):
         K1, K2 = K1.copy(), K2.copy()
         K1[:2] *= s1
         K2[:2] *= s2
+        norm_threshold = 0.5 / (np.mean(np.abs(K1[:2, :2])) + np.mean(np.abs(K2[:2, :2])))
+        if pose == "device":
+            tot_e_pose += _device_pose_errors(model, dense_matches, dense_certainty, num, repeats, (h1, w1, h2, w2), K1, K2,
+                                              norm_threshold, R, t, rng)
+            continue
         for _ in range(repeats):
             sparse, _ = model.sample(dense_matches, dense_certainty, num)
             k1, k2 = model.to_pixel_coordinates(sparse, h1, w1, h2, w2)
@@ -171,7 +180,6 @@ def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200):
             sh = rng.permutation(len(k1))
             k1, k2 = k1[sh], k2[sh]
             try:
-                norm_threshold = 0.5 / (np.mean(np.abs(K1[:2, :2])) + np.mean(np.abs(K2[:2, :2])))
                 R_est, t_est, _ = PG.estimate_pose(k1, k2, K1, K2, norm_threshold, conf=0.99999, rng=rng)
                 e_t, e_R = PG.compute_pose_error(np.concatenate((R_est, t_est), axis=-1), R, t)
             except Exception as e:  # estimate_pose returned None (too few matches / no model), like the reference's except
@@ -183,6 +191,38 @@ def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200):
     acc = [(tot < th).mean() for th in (5, 10, 15, 20)]
     return {"auc_5": auc[0], "auc_10": auc[1], "auc_20": auc[2], "map_5": acc[0], "map_10": float(np.mean(acc[:2])),
             "map_20": float(np.mean(acc))}
+
+
+def _device_pose_errors(model, dense_matches, dense_certainty, num, repeats, hw, K1, K2, norm_threshold, R, t, rng):
+    """one pair's `repeats` pose estimates as one batched roma_amd.estimate_pose: [max(e_t, e_R)] per repeat"""
+    import numpy as np
+    from roma_amd import estimate_pose
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import pose_geometry as PG
+    ka, kb, counts = [], [], []
+    for _ in range(repeats):
+        sparse, _ = model.sample(dense_matches, dense_certainty, num)
+        k1, k2 = model.to_pixel_coordinates(sparse, *hw)
+        sh = torch.as_tensor(rng.permutation(len(k1)), device=k1.device)
+        ka.append(k1[sh].float())
+        kb.append(k2[sh].float())
+        counts.append(len(k1))
+    n = max(counts)
+    a = torch.full((repeats, n, 2), float("nan"), device=ka[0].device)
+    b = torch.full((repeats, n, 2), float("nan"), device=ka[0].device)
+    for i in range(repeats):
+        a[i, :counts[i]], b[i, :counts[i]] = ka[i], kb[i]
+    seeds = torch.as_tensor(rng.integers(0, 2 ** 62, repeats), dtype=torch.int64)
+    R_est, t_est, _, ok = estimate_pose(a, b, K1, K2, norm_threshold, 0.99999, 1000, seed=seeds, counts=counts)
+    R_est, t_est, ok = R_est.cpu().numpy(), t_est.cpu().numpy(), ok.cpu().numpy()
+    out = []
+    for i in range(repeats):
+        if not ok[i]:  # no model (too few matches), like the reference's except
+            out.append(90)
+            continue
+        e_t, e_R = PG.compute_pose_error(np.concatenate((R_est[i], t_est[i]), axis=-1), R, t)
+        out.append(max(e_t, e_R))
+    return out
 
 
 def check_acceptance_pose(results):
@@ -229,6 +269,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--synthetic", type=int, default=0, help="number of synthetic planar batches (of 2 pairs) to run")
     ap.add_argument("--synthetic-pose", type=int, default=0, help="number of synthetic pairs for the pose (MegaDepth-1500) loop")
+    ap.add_argument("--device-pose", action="store_true", help="pose loop: batched roma_amd.estimate_pose instead of the host path")
     ap.add_argument("--megadepth", default=None, help="data root of the MegaDepth test split (reference: data/megadepth)")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--dinov2", default=None)
@@ -256,7 +297,7 @@ def main():
             pairs.append({"im_A": d["im_A"].to("cuda:0"), "im_B": d["im_B"].to("cuda:0"), "K1": d["K1"][0].numpy(),
                           "K2": d["K2"][0].numpy(), "T_1to2": d["T_1to2"][0].numpy(), "size_A": (args.res, args.res),
                           "size_B": (args.res, args.res)})
-        res = pose_benchmark(model, pairs)
+        res = pose_benchmark(model, pairs, pose="device" if args.device_pose else "host")
         print(json.dumps({"pose_results": res, "acceptance_on_megadepth1500": {k: v[0] for k, v in ACCEPTANCE_POSE.items()},
                           "note": "synthetic planar scenes" + ("" if args.weights else ", RANDOM weights: plumbing check only")}))
         return
