@@ -1,4 +1,4 @@
-// Batched essential-matrix RANSAC (five-point solver) and recoverPose on the device - see essential.hip.
+// Batched essential-matrix RANSAC (five-point solver) and recoverPose on the device - see essential.hip and ransac.h.
 #pragma once
 #include "common.h"
 

@@ -1,16 +1,14 @@
-// Batched essential-matrix RANSAC and recoverPose on the device - what the reference's pose benchmarks run on sample() output
-// through OpenCV (romatch/utils/utils.py estimate_pose): cv2.findEssentialMat(..., RANSAC) around the five-point solver, then
-// cv2.recoverPose.  tools/essential_ref.py restates this file in numpy float64 step by step and is the oracle of the GPU tests.
+// The essential-matrix (E) model of the device RANSAC (ransac.h) and recoverPose - what the reference's pose benchmarks run on
+// sample() output through OpenCV (romatch/utils/utils.py estimate_pose): cv2.findEssentialMat(..., RANSAC) around the
+// five-point solver, then cv2.recoverPose.  tools/essential_ref.py restates this file in numpy float64 step by step.
 //
-// findEssentialMat, per pair b (counts[b] rows; later rows are never read):
-//   1. ess_norm_kernel: x_n = ((x - cx) / fx, (y - cy) / fy) in f64 (identity without a camera matrix), f32 copies (non-finite
-//      rows as NaN), thr_n = thr / ((fx + fy) / 2).  No Hartley normalisation: it would break the essential constraints.
-//   2. rounds of RANSAC_ROUND hypotheses, enqueued ceil(max_iters / ROUND) times, no host synchronisation:
-//      ess_hyp_kernel    16 lanes per hypothesis: sample (the counter-based stream of ransac_common.h at S = 5), Nister's
-//                        five-point solver in f64 (below), up to 10 models
-//      ess_score_kernel  one wave per hypothesis: Sampson test of its models in f32, popc(ballot) counts
-//      ess_select_kernel per pair: arg-max (ties: lowest (h, root)), OpenCV's adaptive iteration count, done flag.
-//   3. ess_mask_kernel + ess_finish_kernel: final mask, E, ok, round / winner info.  No refinement (OpenCV has none here).
+// What E adds to the shared pipeline (Essential):
+//   normalise   x_n = ((x - cx) / fx, (y - cy) / fy) in f64 (identity without a camera matrix), thr_n = thr / ((fx + fy) / 2).
+//               No Hartley normalisation: it would break the essential constraints.
+//   hypothesis  16 lanes per hypothesis: Nister's five-point solver in f64 (below), up to 10 slots.
+//   inlier      f32 Sampson test.
+//   finish      E as found, info of ESSENTIAL_INFO ints.  No refinement (OpenCV has none here).
+//
 // The five-point solver (D. Nister, PAMI 2004): null space X, Y, Z, W of the 5 x 9 epipolar system (Gauss-Jordan, then modified
 // Gram-Schmidt: an orthonormal basis keeps the elimination below well conditioned), the ten cubic constraints det E = 0 and
 // 2 E E^T E - tr(E E^T) E = 0 of E = x X + y Y + z Z + W as a 10 x 20 matrix (one row per lane), Gauss-Jordan on its ten
@@ -22,20 +20,14 @@
 // recoverPose: ess_decompose_kernel (one-sided Jacobi SVD of E per pair, OpenCV's det fix-up, the four candidates),
 // ess_cheirality_kernel (grid (point blocks, pair): triangulation for all four candidates, per-block counts, no atomics),
 // ess_pose_kernel (candidate with most good points, ties to the earlier one; R, t, n_good, mask).
-// Every flag and counter of the workspace is written with plain stores by one kernel and read by a later launch on the same
-// stream.  Results are bit-identical from run to run and independent of B.
+// As in the RANSAC pipeline, every flag and count of recoverPose's workspace is written with plain stores by one kernel and read
+// by a later launch on the same stream.  Results are bit-identical from run to run and independent of B.
 #include "essential.h"
-#include "geometry.h"
-#include "ransac_common.h"
-
-// the scoring arithmetic is written with explicit fmaf; nothing else is fused (tools/essential_ref.py evaluates the same
-// expressions in f64)
-#pragma clang fp contract(off)
+#include "ransac.h"
 
 namespace roma {
 namespace {
 
-constexpr int R = RANSAC_ROUND;
 constexpr int MAXR = ESSENTIAL_MAX_ROOTS;
 constexpr int G = 16;                     // lanes per hypothesis in the solver
 constexpr int GPB = 256 / G;              // hypotheses per solver workgroup
@@ -48,21 +40,6 @@ constexpr double GN_REACH = 1e-2;         // relative length of a Gauss-Newton s
 constexpr double E_PIVOT_EPS = 1e-10;     // |pivot| of the 10 x 20 elimination (unit-norm null basis)
 constexpr int SVD_SWEEPS = 20;
 constexpr double SVD_TOL = 4 * DBL_EPSILON;
-static_assert(R % GPB == 0, "a solver workgroup must not straddle two pairs");
-
-struct EState {
-  double fx, fy, cx, cy;        // x_n = (x - c) / f
-  double cur[9];                // current model
-  alignas(16) float curf[12];   // f32 copy the scoring reads
-  float thr2;                   // thr_n^2
-  int n;                        // rows of the pair: counts[b] clamped to [0, N]
-  int valid;                    // enough finite rows for a sample, camera matrix usable
-  int best;                     // inlier count of the current model (-1: none yet)
-  int best_h, best_root;        // winning minimal sample and its root
-  int needed;                   // adaptive iteration count
-  int rounds;                   // rounds executed
-  int done;                     // sampling finished for this pair
-};
 
 // ------------------------------------------------------------------------------------------------------------ scoring (f32)
 // p = (x0, y0, x1, y1) normalised.  Sampson test in multiplication form: (x1^T E x0)^2 < thr^2 (|E x0|_{1,2}^2 + |E^T x1|_{1,2}^2)
@@ -161,7 +138,6 @@ __device__ __forceinline__ void scale_max(double (&p)[N]) {  // divide by the la
 }
 
 // p_next = -rem(a, b) for deg a = N - 1, deg b = N - 2 (generic degree drop), scaled to unit maximum
-// p_next = -rem(a, b) for deg a = N - 1, deg b = N - 2 (generic degree drop), scaled to unit maximum
 template <int N>
 __device__ __forceinline__ void sturm_next(const double (&a)[N], const double (&b)[N - 1], double (&r)[N - 2]) {
   const double q1 = a[N - 1] / b[N - 2];
@@ -215,22 +191,11 @@ __device__ __forceinline__ int sturm_changes(const double* ch, double t) {
   return c;
 }
 
-__device__ __forceinline__ void mm3(const double* a, const double* b, double* c) {  // c = a b
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c[3 * i + j] = (a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j]) + a[3 * i + 2] * b[6 + j];
-}
-
 __device__ __forceinline__ void mmt3(const double* a, const double* b, double* c) {  // c = a b^T
 #pragma unroll
   for (int i = 0; i < 3; ++i)
 #pragma unroll
     for (int j = 0; j < 3; ++j) c[3 * i + j] = (a[3 * i] * b[3 * j] + a[3 * i + 1] * b[3 * j + 1]) + a[3 * i + 2] * b[3 * j + 2];
-}
-
-__device__ __forceinline__ double det3e(const double* f) {
-  return f[0] * (f[4] * f[8] - f[5] * f[7]) - f[1] * (f[3] * f[8] - f[5] * f[6]) + f[2] * (f[3] * f[7] - f[4] * f[6]);
 }
 
 // GN_STEPS Gauss-Newton steps of (x, y, z) on the ten cubic constraints of E = x X + y Y + z Z + W themselves (not on the
@@ -243,10 +208,10 @@ __device__ __forceinline__ void refine_xyz(const double* basis, double& x, doubl
     for (int q = 0; q < 9; ++q) E[q] = ((x * basis[4 * q] + y * basis[4 * q + 1]) + z * basis[4 * q + 2]) + basis[4 * q + 3];
     mmt3(E, E, EEt);
     const double tr = (EEt[0] + EEt[4]) + EEt[8];
-    mm3(EEt, E, M);
+    mat3(EEt, E, M);
 #pragma unroll
     for (int q = 0; q < 9; ++q) r[q] = 2.0 * M[q] - tr * E[q];
-    r[9] = det3e(E);
+    r[9] = det3(E);
     const double cof[9] = {E[4] * E[8] - E[5] * E[7], E[5] * E[6] - E[3] * E[8], E[3] * E[7] - E[4] * E[6],
                            E[2] * E[7] - E[1] * E[8], E[0] * E[8] - E[2] * E[6], E[1] * E[6] - E[0] * E[7],
                            E[1] * E[5] - E[2] * E[4], E[2] * E[3] - E[0] * E[5], E[0] * E[4] - E[1] * E[3]};
@@ -256,10 +221,10 @@ __device__ __forceinline__ void refine_xyz(const double* basis, double& x, doubl
 #pragma unroll
       for (int q = 0; q < 9; ++q) D[q] = basis[4 * q + k];
       mmt3(D, E, t1);
-      mm3(t1, E, a1);
+      mat3(t1, E, a1);
       mmt3(E, D, t2);
-      mm3(t2, E, a2);
-      mm3(EEt, D, a3);
+      mat3(t2, E, a2);
+      mat3(EEt, D, a3);
       double ip = 0, dd = 0;
 #pragma unroll
       for (int q = 0; q < 9; ++q) { ip += D[q] * E[q]; dd += cof[q] * D[q]; }
@@ -282,14 +247,14 @@ __device__ __forceinline__ void refine_xyz(const double* basis, double& x, doubl
         A[3 * i + j] = a;
       }
     }
-    const double det = det3e(A);
+    const double det = det3(A);
     double st[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       double Ak[9];
 #pragma unroll
       for (int q = 0; q < 9; ++q) Ak[q] = q % 3 == k ? g[q / 3] : A[q];
-      st[k] = -det3e(Ak) / det;
+      st[k] = -det3(Ak) / det;
     }
     const double big = 1.0 + fmax(fmax(fabs(x), fabs(y)), fabs(z));
     const bool take = isfinite(st[0]) && isfinite(st[1]) && isfinite(st[2]) &&
@@ -517,182 +482,66 @@ __device__ __forceinline__ void solve_e_group(const double (&xa)[5], const doubl
   __syncthreads();  // the group's LDS is reused by the caller's next hypothesis
 }
 
-// ------------------------------------------------------------------------------------------------------------ RANSAC kernels
-__global__ __launch_bounds__(256) void ess_norm_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
-                                                       const int* __restrict__ counts, const double* __restrict__ K, int N, float thr,
-                                                       int max_iters, EState* __restrict__ st, float4* __restrict__ pts) {
-  __shared__ double sh[256];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const int n = counts ? min(max(counts[b], 0), N) : N;
-  const float2* A = ka + (long)b * N;
-  const float2* Bp = kb + (long)b * N;
-  double fx = 1, fy = 1, cx = 0, cy = 0;
-  if (K) {
-    const double* k = K + (long)b * 9;
-    fx = k[0]; cx = k[2]; fy = k[4]; cy = k[5];
-  }
-  const double thr_n = (double)thr / ((fx + fy) * 0.5);
-  double cnt = 0;
-  for (int i = t; i < n; i += 256) {
-    const float2 a = A[i], q = Bp[i];
-    const bool f = finite_row(a.x, a.y, q.x, q.y);
-    cnt += f ? 1 : 0;
-    float4 o = make_float4(NAN, NAN, NAN, NAN);
-    if (f) o = make_float4((float)((a.x - cx) / fx), (float)((a.y - cy) / fy), (float)((q.x - cx) / fx), (float)((q.y - cy) / fy));
-    pts[(long)b * N + i] = o;
-  }
-  cnt = block_sum(cnt, sh);
-  const bool valid = cnt >= 5 && fx != 0 && fy != 0 && isfinite(fx) && isfinite(fy) && isfinite(cx) && isfinite(cy) && thr_n > 0 &&
-                     isfinite(thr_n);
-  if (t == 0) {
-    EState& S = st[b];
-    S.fx = fx; S.fy = fy; S.cx = cx; S.cy = cy;
-    S.thr2 = (float)(thr_n * thr_n);
-    S.n = n;
-    S.valid = valid ? 1 : 0;
-    S.best = -1; S.best_h = -1; S.best_root = -1;
-    S.needed = max_iters;
-    S.rounds = 0;
-    S.done = valid ? 0 : 1;
-    for (int k = 0; k < 9; ++k) S.cur[k] = 0;
-    for (int k = 0; k < 12; ++k) S.curf[k] = 0;
-  }
-}
-
-// G lanes per (pair, hypothesis of the round); grid B * R / GPB
-__global__ __launch_bounds__(256) void ess_hyp_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb, int N,
-                                                      const unsigned long long* __restrict__ seeds, const EState* __restrict__ st,
-                                                      int round, double* __restrict__ slot_d, float* __restrict__ slot_f,
-                                                      int* __restrict__ slot_n) {
-  __shared__ double sm[GPB * LDS_PER];
-  const int grp = threadIdx.x / G, gl = threadIdx.x % G;
-  const int g = blockIdx.x * GPB + grp, b = g / R;
-  const EState& P = st[b];
-  if (P.done) return;  // uniform over the workgroup: its hypotheses belong to one pair
-  const int h = round * R + g % R;
-  int idx[5];
-  bool act = draw_sample<5>(seeds[b], h, P.n, idx);
-  double xa[5], ya[5], xb[5], yb[5];
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const float2 a = act ? ka[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
-    const float2 q = act ? kb[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
-    act = act && finite_row(a.x, a.y, q.x, q.y);
-    xa[k] = (a.x - P.cx) / P.fx; ya[k] = (a.y - P.cy) / P.fy;
-    xb[k] = (q.x - P.cx) / P.fx; yb[k] = (q.y - P.cy) / P.fy;
-  }
-  double e[9];
-  int rank, nsol;
-  solve_e_group(xa, ya, xb, yb, act, sm + grp * LDS_PER, gl, e, rank, nsol);
-  if (rank >= 0) {
-    const long o = (long)g * MAXR + rank;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) slot_d[o * 9 + k] = e[k];
-    float4* f = reinterpret_cast<float4*>(slot_f + o * 12);
-    f[0] = make_float4((float)e[0], (float)e[1], (float)e[2], (float)e[3]);
-    f[1] = make_float4((float)e[4], (float)e[5], (float)e[6], (float)e[7]);
-    f[2] = make_float4((float)e[8], 0.f, 0.f, 0.f);
-  }
-  if (gl == 0) slot_n[g] = nsol;
-}
-
-// one wave per (pair, hypothesis): its models (wave-uniform coefficients) against the pair's points
-__global__ __launch_bounds__(256) void ess_score_kernel(const float4* __restrict__ pts, int N, const EState* __restrict__ st,
-                                                        const float* __restrict__ slot_f, const int* __restrict__ slot_n,
-                                                        int* __restrict__ slot_cnt) {
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = g / R;
-  const EState& P = st[b];
-  if (P.done) return;
-  const int nm = slot_n[g];
-  const float* mf = slot_f + (long)g * MAXR * 12;
-  const float4* Pp = pts + (long)b * N;
-  const int n = P.n;
-  const float t2 = P.thr2;
-  int c[MAXR];
-#pragma unroll
-  for (int r = 0; r < MAXR; ++r) c[r] = 0;
-  if (nm > 0) {
-    for (int i0 = 0; i0 < n; i0 += 64) {
-      const int i = i0 + lane;
-      const float4 p = i < n ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
-#pragma unroll
-      for (int r = 0; r < MAXR; ++r)
-        if (r < nm) c[r] += __popcll(__ballot(inlier_e(mf + 12 * r, p, t2)));
+// ------------------------------------------------------------------------------------------------------------ model policy
+struct Essential {
+  struct Norm {
+    double fx, fy, cx, cy;  // x_n = (x - c) / f
+    __device__ void apply(float2 a, float2 q, double& xa, double& ya, double& xb, double& yb) const {
+      xa = (a.x - cx) / fx; ya = (a.y - cy) / fy;
+      xb = (q.x - cx) / fx; yb = (q.y - cy) / fy;
     }
-  }
-  if (lane == 0) {
-    int* o = slot_cnt + (long)g * MAXR;
-#pragma unroll
-    for (int r = 0; r < MAXR; ++r) o[r] = r < nm ? c[r] : -1;
-  }
-}
+  };
+  static constexpr int S = 5, SLOTS = MAXR, HYP_THREADS = 256, HYP_LANES = G, REFINE_ITERS = 0, INFO = ESSENTIAL_INFO;
+  static constexpr bool SCORE_EVERY_SLOT = false;  // 10 slots, a few of them used: score only those
 
-// one workgroup per pair: best (count, lowest slot) of the round, running best, adaptive iteration count, done flag
-__global__ __launch_bounds__(256) void ess_select_kernel(EState* __restrict__ st, int round, double conf, int max_iters,
-                                                         const double* __restrict__ slot_d, const int* __restrict__ slot_cnt) {
-  __shared__ int sc[256], si[256];
-  const int b = blockIdx.x, t = threadIdx.x;
-  EState& P = st[b];
-  if (P.done) return;
-  const int* cnt = slot_cnt + (long)b * R * MAXR;
-  int bc = -1, bi = 0x7fffffff;
-  for (int k = t; k < R * MAXR; k += 256) {
-    const int c = cnt[k];
-    if (c > bc) { bc = c; bi = k; }  // k ascends: ties keep the lower slot
-  }
-  sc[t] = bc;
-  si[t] = bi;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      const int c = sc[t + w], i = si[t + w];
-      if (c > sc[t] || (c == sc[t] && i < si[t])) { sc[t] = c; si[t] = i; }
+  // every thread of the workgroup: the pair's camera; pts written for every row; one threshold (t2a == t2b)
+  __device__ static bool normalise(const float2* A, const float2* Bp, int n, const double* K, float thr, double* sh, float4* pts,
+                                   Norm& nm, float& t2a, float& t2b) {
+    const int t = threadIdx.x;
+    double fx = 1, fy = 1, cx = 0, cy = 0;
+    if (K) {
+      fx = K[0]; cx = K[2]; fy = K[4]; cy = K[5];
     }
-    __syncthreads();
-  }
-  if (t == 0) {
-    const int c = sc[0], k = si[0];
-    if (c > P.best) {  // strictly: an earlier round's model keeps a tie
-      P.best = c;
-      P.best_h = round * R + k / MAXR;
-      P.best_root = k % MAXR;
-      const double* m = slot_d + ((long)b * R * MAXR + k) * 9;
-      for (int q = 0; q < 9; ++q) P.cur[q] = m[q];
-      for (int q = 0; q < 9; ++q) P.curf[q] = (float)P.cur[q];
-      P.needed = update_num_iters(conf, (double)c / P.n, 5, max_iters);
+    const double thr_n = (double)thr / ((fx + fy) * 0.5);
+    double cnt = 0;
+    for (int i = t; i < n; i += 256) {
+      const float2 a = A[i], q = Bp[i];
+      const bool f = finite_row(a.x, a.y, q.x, q.y);
+      cnt += f ? 1 : 0;
+      float4 o = make_float4(NAN, NAN, NAN, NAN);
+      if (f) o = make_float4((float)((a.x - cx) / fx), (float)((a.y - cy) / fy), (float)((q.x - cx) / fx), (float)((q.y - cy) / fy));
+      pts[i] = o;
     }
-    P.rounds = round + 1;
-    const long drawn = (long)(round + 1) * R;
-    P.done = drawn >= (long)min(max_iters, P.needed) ? 1 : 0;
+    cnt = block_sum(cnt, sh);
+    nm.fx = fx; nm.fy = fy; nm.cx = cx; nm.cy = cy;
+    t2a = t2b = (float)(thr_n * thr_n);
+    return cnt >= S && fx != 0 && fy != 0 && isfinite(fx) && isfinite(fy) && isfinite(cx) && isfinite(cy) && thr_n > 0 &&
+           isfinite(thr_n);
   }
-}
 
-// mask[b, i] = inlier of the winning model (rows beyond counts[b], and pairs without a model: 0); grid (ceil(N / 256), B)
-__global__ __launch_bounds__(256) void ess_mask_kernel(const float4* __restrict__ pts, int N, const EState* __restrict__ st,
-                                                       unsigned char* __restrict__ mask) {
-  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  const EState& P = st[b];
-  bool in = false;
-  if (P.best > 0 && i < P.n) in = inlier_e(P.curf, pts[(long)b * N + i], P.thr2);
-  mask[(long)b * N + i] = in ? 1 : 0;
-}
+  // the G lanes of a group: the hypothesis' valid models in slots 0 .. nsol - 1
+  __device__ static void hypothesis(const double (&xa)[5], const double (&ya)[5], const double (&xb)[5], const double (&yb)[5],
+                                    bool act, int g, int gl, const Slots& sl) {
+    __shared__ double sm[GPB * LDS_PER];
+    double e[9];
+    int rank, nsol;
+    solve_e_group(xa, ya, xb, yb, act, sm + (threadIdx.x / G) * LDS_PER, gl, e, rank, nsol);
+    if (rank >= 0) store_model(e, (long)g * MAXR + rank, sl);
+    if (gl == 0) sl.n[g] = nsol;
+  }
 
-__global__ __launch_bounds__(64) void ess_finish_kernel(int B, const EState* __restrict__ st, double* __restrict__ out,
-                                                        unsigned char* __restrict__ ok, int* __restrict__ info) {
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  const EState& P = st[b];
-  const bool good = P.valid && P.best > 0;
-  for (int k = 0; k < 9; ++k) out[(long)b * 9 + k] = good ? P.cur[k] : 0.0;
-  ok[b] = good ? 1 : 0;
-  int* o = info + (long)b * ESSENTIAL_INFO;
-  o[0] = P.rounds;
-  o[1] = P.best_h;
-  o[2] = P.best_root;
-  o[3] = P.best;
-  o[4] = P.valid;
-}
+  __device__ static bool inlier(const float* m, float4 p, float t2, float) { return inlier_e(m, p, t2); }
+
+  // E as found; info = {rounds, best_h, best_root, best, valid}
+  __device__ static void finish(const PairState<Essential>& P, bool good, double* out, int* info) {
+    for (int k = 0; k < 9; ++k) out[k] = good ? P.cur[k] : 0.0;
+    info[0] = P.rounds;
+    info[1] = P.best_h;
+    info[2] = P.best_root;
+    info[3] = P.best;
+    info[4] = P.valid;
+  }
+};
 
 // the solver alone on caller samples; grid ceil(S / GPB)
 __global__ __launch_bounds__(256) void ess_minimal_kernel(const double* __restrict__ x0, const double* __restrict__ x1, int S,
@@ -728,13 +577,6 @@ struct PoseState {
   double fx, fy, cx, cy;
   int n, valid;
 };
-
-__device__ __forceinline__ void mat3(const double* a, const double* b, double* c) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c[3 * i + j] = (a[3 * i] * b[j] + a[3 * i + 1] * b[3 + j]) + a[3 * i + 2] * b[6 + j];
-}
 
 // one thread per pair: E = U S V^T by one-sided Jacobi on the columns of E (A V = U S), singular values descending,
 // u3 = u1 x u2 (v3 signed to match where s3 > 0), OpenCV's fix-up (det(U), det(V) > 0), W = [[0, 1, 0], [-1, 0, 0], [0, 0, 1]],
@@ -922,31 +764,6 @@ __global__ __launch_bounds__(256) void ess_pose_kernel(int N, int nblk, const Po
   for (int i = t; i < N; i += 256) out_mask[(long)b * N + i] = (unsigned char)((flags[(long)b * N + i] >> c) & 1);
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-struct Carve {
-  EState* st;
-  float4* pts;
-  double* slot_d;
-  float* slot_f;
-  int *slot_n, *slot_cnt;
-  size_t bytes;
-};
-
-Carve carve(void* ws, int B, int N) {
-  Carve c;
-  char* p = static_cast<char*>(ws);
-  size_t o = 0;
-  c.st = reinterpret_cast<EState*>(p + o); o = align256(o + sizeof(EState) * B);
-  c.pts = reinterpret_cast<float4*>(p + o); o = align256(o + sizeof(float4) * (size_t)B * N);
-  c.slot_d = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * 9 * MAXR * (size_t)B * R);
-  c.slot_f = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * 12 * MAXR * (size_t)B * R);
-  c.slot_n = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * (size_t)B * R);
-  c.slot_cnt = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * MAXR * (size_t)B * R);
-  c.bytes = o + 256;  // slack: the caller's base need not be 256-aligned
-  return c;
-}
-
 struct PoseCarve {
   PoseState* st;
   unsigned char* flags;
@@ -966,43 +783,18 @@ PoseCarve pose_carve(void* ws, int B, int N) {
   return c;
 }
 
-template <typename T>
-T align_base(void* ws) {
-  return reinterpret_cast<T>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-}
-
 }  // namespace
 
-size_t essential_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? carve(nullptr, B, N).bytes : 0; }
+size_t essential_workspace_bytes(int B, int N) { return workspace_bytes<Essential>(B, N); }
 
 int essential_launch(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K,
                      int B, int N, float threshold, double prob, int max_iters, double* out_e, unsigned char* out_mask,
                      unsigned char* out_ok, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
-  ROMA_REQUIRE(kpts_a && kpts_b && seeds && out_e && out_mask && out_ok && out_info && ws, "essential: null pointer");
-  ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), "essential: need 0 < B <= 65536, 0 < N, B * N < 2^31");
-  ROMA_REQUIRE(max_iters > 0, "essential: max_iters must be positive");
-  ROMA_REQUIRE(threshold > 0 && isfinite(threshold), "essential: threshold must be positive and finite");
-  ROMA_REQUIRE(prob >= 0 && prob <= 1, "essential: prob must lie in [0, 1]");
-  ROMA_REQUIRE(ws_bytes >= essential_workspace_bytes(B, N), "essential: workspace too small (roma_op_essential_workspace)");
-  const Carve c = carve(align_base<void*>(ws), B, N);
-  const float2* ka = reinterpret_cast<const float2*>(kpts_a);
-  const float2* kb = reinterpret_cast<const float2*>(kpts_b);
-  hipLaunchKernelGGL(ess_norm_kernel, dim3(B), dim3(256), 0, s, ka, kb, counts, K, N, threshold, max_iters, c.st, c.pts);
-  ROMA_LAUNCH_CHECK();
-  const int rounds = (max_iters + R - 1) / R;
-  for (int r = 0; r < rounds; ++r) {
-    hipLaunchKernelGGL(ess_hyp_kernel, dim3(B * R / GPB), dim3(256), 0, s, ka, kb, N, seeds, c.st, r, c.slot_d, c.slot_f, c.slot_n);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ess_score_kernel, dim3(B * R / 4), dim3(256), 0, s, c.pts, N, c.st, c.slot_f, c.slot_n, c.slot_cnt);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ess_select_kernel, dim3(B), dim3(256), 0, s, c.st, r, prob, max_iters, c.slot_d, c.slot_cnt);
-    ROMA_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(ess_mask_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, c.pts, N, c.st, out_mask);
-  ROMA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ess_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, out_e, out_ok, out_info);
-  ROMA_LAUNCH_CHECK();
-  return 0;
+  if (check_args("essential", "prob", kpts_a && kpts_b && seeds && out_e && out_mask && out_ok && out_info && ws, B, N, threshold,
+                 prob, max_iters, ws_bytes, essential_workspace_bytes(B, N)))
+    return -1;
+  return ransac_run<Essential>(kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, false, out_e, out_mask, out_ok,
+                               out_info, ws, s);
 }
 
 int essential_minimal_launch(const double* x0, const double* x1, int S, double* out_e, int* out_n, hipStream_t s) {

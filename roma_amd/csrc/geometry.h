@@ -1,10 +1,9 @@
-// Batched RANSAC on the device: homography (4-point DLT) and fundamental matrix (7-point) - see geometry.hip.
+// Batched RANSAC on the device: homography (4-point DLT) and fundamental matrix (7-point) - see geometry.hip and ransac.h.
 #pragma once
 #include "common.h"
 
 namespace roma {
 constexpr int RANSAC_HOMOGRAPHY = 0, RANSAC_FUNDAMENTAL = 1;
-constexpr int RANSAC_ROUND = 256;      // hypotheses per pair and round (tools/geometry_ref.py: ROUND)
 constexpr int RANSAC_INFO = 6;         // ints per pair in out_info
 size_t ransac_workspace_bytes(int B, int N);
 // kpts_a / kpts_b [B, N, 2] f32 pixels; counts [B] int32 (NULL: N rows each); seeds [B] u64.  Outputs: model [B, 3, 3] f64,

@@ -24,7 +24,7 @@ from . import _lib
 
 HOMOGRAPHY, FUNDAMENTAL = 0, 1
 SAMPLE_SIZE = {HOMOGRAPHY: 4, FUNDAMENTAL: 7}
-ROUND = 256  # hypotheses per pair and round (csrc/geometry.h RANSAC_ROUND)
+ROUND = 256  # hypotheses per pair and round (csrc/ransac.h RANSAC_ROUND)
 
 
 def _as_batch(k: torch.Tensor, name: str) -> torch.Tensor:
@@ -35,92 +35,6 @@ def _as_batch(k: torch.Tensor, name: str) -> torch.Tensor:
     if k.dtype not in (torch.float32, torch.float64):
         raise ValueError(f"roma_amd.geometry: {name} must be float32 or float64, got {k.dtype}")
     return k.detach().to(torch.float32).contiguous()
-
-
-def ransac(model: int, kpts_A: torch.Tensor, kpts_B: torch.Tensor, threshold: float, confidence: float, max_iters: int,
-           seed=None, refine: bool = True, counts=None):
-    """Batched robust estimation, no host synchronisation.  kpts [B, N, 2] device pixel coordinates; counts [B] rows per pair
-    (rows at or beyond counts[b] are never read); seed an int (every pair), a [B] tensor (one per pair) or None (drawn from
-    torch's CPU generator).  Returns (M [B, 3, 3] float64, mask [B, N] bool, ok [B] bool, info [B, 6] int32) with
-    info = (rounds run, winning hypothesis, its root, its inlier count, final inlier count, pair valid)."""
-    a, b = _as_batch(kpts_A, "kpts_A"), _as_batch(kpts_B, "kpts_B")
-    a = a[None] if a.dim() == 2 else a
-    b = b[None] if b.dim() == 2 else b
-    if a.shape != b.shape or a.dim() != 3:
-        raise ValueError(f"roma_amd.geometry: kpts_A {tuple(kpts_A.shape)} and kpts_B {tuple(kpts_B.shape)} differ in shape")
-    if a.device != b.device:
-        raise ValueError("roma_amd.geometry: kpts_A and kpts_B live on different devices")
-    if model not in SAMPLE_SIZE:
-        raise ValueError(f"roma_amd.geometry: unknown model {model}")
-    if not (threshold > 0) or not (0 <= confidence <= 1) or int(max_iters) <= 0:
-        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= confidence <= 1, max_iters > 0")
-    B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
-    M = torch.zeros((B, 3, 3), device=dev, dtype=torch.float64)
-    mask = torch.zeros((B, N), device=dev, dtype=torch.bool)
-    ok = torch.zeros((B,), device=dev, dtype=torch.bool)
-    info = torch.zeros((B, 6), device=dev, dtype=torch.int32)
-    if B == 0:
-        return M, mask, ok, info
-    if counts is not None:
-        counts = torch.as_tensor(counts).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
-        if counts.shape[0] != B:
-            raise ValueError(f"roma_amd.geometry: counts has {counts.shape[0]} entries for {B} pairs")
-    if seed is None:
-        seeds = torch.randint(0, 2 ** 62, (B,), dtype=torch.int64)  # CPU generator: no device synchronisation
-    elif isinstance(seed, torch.Tensor):
-        seeds = seed.reshape(-1).to(torch.int64)
-        if seeds.shape[0] != B:
-            raise ValueError(f"roma_amd.geometry: {seeds.shape[0]} seeds for {B} pairs")
-    else:
-        seeds = torch.full((B,), int(seed), dtype=torch.int64)
-    seeds = seeds.to(dev).contiguous()  # read as uint64 by the kernels
-    if N < SAMPLE_SIZE[model]:  # no pair can hold a minimal sample: nothing to launch
-        return M, mask, ok, info
-    lib = _lib.load()
-    nws = int(lib.roma_op_ransac_workspace(B, N))
-    ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        _lib.check(lib.roma_op_ransac(int(model), C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
-                                      C.c_void_p(counts.data_ptr() if counts is not None else 0), C.c_void_p(seeds.data_ptr()), B, N,
-                                      float(threshold), float(confidence), int(max_iters), 1 if refine else 0,
-                                      C.c_void_p(M.data_ptr()), C.c_void_p(mask.data_ptr()), C.c_void_p(ok.data_ptr()),
-                                      C.c_void_p(info.data_ptr()), C.c_void_p(ws.data_ptr()), nws,
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    return M, mask, ok, info
-
-
-def _front(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, refine, counts):
-    single = isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2
-    M, mask, ok, _ = ransac(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, refine, counts)
-    if not single:
-        return M, mask, ok
-    if not bool(ok[0]):  # the one synchronisation of the single-pair form (OpenCV returns None)
-        return None, None
-    return M[0], mask[0]
-
-
-def find_homography(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.995, max_iters=2000, seed=None, refine=True,
-                    counts=None):
-    """cv2.findHomography(kpts_A, kpts_B, cv2.RANSAC, ransac_reproj_threshold, maxIters=max_iters, confidence=confidence) on the
-    device: 4-point DLT hypotheses (OpenCV's checkSubset), inliers |H x_A - x_B| < threshold in image B.
-
-    kpts_A, kpts_B: [N, 2] -> (H [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
-    [B, N, 2] -> (H [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
-    return _front(HOMOGRAPHY, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts)
-
-
-def find_fundamental(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.99, max_iters=1000, seed=None, refine=True,
-                     counts=None):
-    """cv2.findFundamentalMat(kpts_A, kpts_B, cv2.FM_RANSAC, ransac_reproj_threshold, confidence, max_iters) on the device:
-    7-point hypotheses (up to 3 models each), inliers whose distances to both epipolar lines are below the threshold.
-
-    kpts_A, kpts_B: [N, 2] -> (F [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
-    [B, N, 2] -> (F [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
-    return _front(FUNDAMENTAL, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts)
-
-
-# ---------------------------------------------------------------------------------------------------- essential matrix and pose
-ESSENTIAL_MAX_ROOTS = 10  # solutions of one five-point sample (csrc/essential.h)
 
 
 def _pair_batch(kpts_A, kpts_B):
@@ -171,30 +85,92 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr() if t is not None else 0)
 
 
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _robust(op, a, s, ninfo, seed, counts, head, tail):
+    """what ransac() and essential() share after their own checks: zeroed outputs (M [B, 3, 3] float64, mask [B, N] bool,
+    ok [B] bool, info [B, ninfo] int32), counts and seeds on the device, then roma_op_<op>(*head(counts, seeds), B, N, *tail,
+    outputs, workspace, stream) with the tensors of head passed as pointers.  Nothing is launched for B == 0 or N < s, where no
+    pair can hold a minimal sample."""
+    B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
+    outs = (torch.zeros((B, 3, 3), device=dev, dtype=torch.float64), torch.zeros((B, N), device=dev, dtype=torch.bool),
+            torch.zeros((B,), device=dev, dtype=torch.bool), torch.zeros((B, ninfo), device=dev, dtype=torch.int32))
+    if B == 0:
+        return outs
+    counts, seeds = _counts(counts, B, dev), _seeds(seed, B, dev)
+    front = head(counts, seeds)  # holds its tensors until the launch is enqueued
+    if N < s:
+        return outs
+    lib = _lib.load()
+    nws = int(getattr(lib, f"roma_op_{op}_workspace")(B, N))
+    ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, f"roma_op_{op}")(*(x if isinstance(x, int) else _ptr(x) for x in front), B, N, *tail,
+                                                 *map(_ptr, outs), _ptr(ws), nws, _stream(dev)))
+    return outs
+
+
+def ransac(model: int, kpts_A: torch.Tensor, kpts_B: torch.Tensor, threshold: float, confidence: float, max_iters: int,
+           seed=None, refine: bool = True, counts=None):
+    """Batched robust estimation, no host synchronisation.  kpts [B, N, 2] device pixel coordinates; counts [B] rows per pair
+    (rows at or beyond counts[b] are never read); seed an int (every pair), a [B] tensor (one per pair) or None (drawn from
+    torch's CPU generator).  Returns (M [B, 3, 3] float64, mask [B, N] bool, ok [B] bool, info [B, 6] int32) with
+    info = (rounds run, winning hypothesis, its root, its inlier count, final inlier count, pair valid)."""
+    a, b = _pair_batch(kpts_A, kpts_B)
+    if model not in SAMPLE_SIZE:
+        raise ValueError(f"roma_amd.geometry: unknown model {model}")
+    if not (threshold > 0) or not (0 <= confidence <= 1) or int(max_iters) <= 0:
+        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= confidence <= 1, max_iters > 0")
+    return _robust("ransac", a, SAMPLE_SIZE[model], 6, seed, counts,
+                   lambda counts, seeds: (int(model), a, b, counts, seeds),
+                   (float(threshold), float(confidence), int(max_iters), 1 if refine else 0))
+
+
+def _front(kpts_A, outs, ok, none):
+    """what the public functions return: for a batch outs + (ok,); for a single pair ([N, 2] kpts) the first entry of each of
+    outs, or `none` when no model was found - the one host synchronisation of the single-pair forms (OpenCV returns None)"""
+    if not (isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2):
+        return (*outs, ok)
+    return tuple(o[0] for o in outs) if bool(ok[0]) else none
+
+
+def find_homography(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.995, max_iters=2000, seed=None, refine=True,
+                    counts=None):
+    """cv2.findHomography(kpts_A, kpts_B, cv2.RANSAC, ransac_reproj_threshold, maxIters=max_iters, confidence=confidence) on the
+    device: 4-point DLT hypotheses (OpenCV's checkSubset), inliers |H x_A - x_B| < threshold in image B.
+
+    kpts_A, kpts_B: [N, 2] -> (H [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
+    [B, N, 2] -> (H [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
+    M, mask, ok, _ = ransac(HOMOGRAPHY, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts)
+    return _front(kpts_A, (M, mask), ok, (None, None))
+
+
+def find_fundamental(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.99, max_iters=1000, seed=None, refine=True,
+                     counts=None):
+    """cv2.findFundamentalMat(kpts_A, kpts_B, cv2.FM_RANSAC, ransac_reproj_threshold, confidence, max_iters) on the device:
+    7-point hypotheses (up to 3 models each), inliers whose distances to both epipolar lines are below the threshold.
+
+    kpts_A, kpts_B: [N, 2] -> (F [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
+    [B, N, 2] -> (F [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
+    M, mask, ok, _ = ransac(FUNDAMENTAL, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts)
+    return _front(kpts_A, (M, mask), ok, (None, None))
+
+
+# ---------------------------------------------------------------------------------------------------- essential matrix and pose
+ESSENTIAL_MAX_ROOTS = 10  # solutions of one five-point sample (csrc/essential.h)
+
+
 def essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None):
     """Batched cv2.findEssentialMat, no host synchronisation.  Returns (E [B, 3, 3] float64, mask [B, N] bool, ok [B] bool,
     info [B, 5] int32) with info = (rounds run, winning hypothesis, its root, inlier count, pair valid)."""
     a, b = _pair_batch(kpts_A, kpts_B)
     if not (threshold > 0) or not (0 <= prob <= 1) or int(max_iters) <= 0:
         raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= prob <= 1, max_iters > 0")
-    B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
-    E = torch.zeros((B, 3, 3), device=dev, dtype=torch.float64)
-    mask = torch.zeros((B, N), device=dev, dtype=torch.bool)
-    ok = torch.zeros((B,), device=dev, dtype=torch.bool)
-    info = torch.zeros((B, 5), device=dev, dtype=torch.int32)
-    if B == 0:
-        return E, mask, ok, info
-    K, counts, seeds = _cameras(camera_matrix, B, dev), _counts(counts, B, dev), _seeds(seed, B, dev)
-    if N < 5:  # no pair can hold a minimal sample: nothing to launch
-        return E, mask, ok, info
-    lib = _lib.load()
-    nws = int(lib.roma_op_essential_workspace(B, N))
-    ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        _lib.check(lib.roma_op_essential(_ptr(a), _ptr(b), _ptr(counts), _ptr(seeds), _ptr(K), B, N, float(threshold), float(prob),
-                                         int(max_iters), _ptr(E), _ptr(mask), _ptr(ok), _ptr(info), _ptr(ws), nws,
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-    return E, mask, ok, info
+    return _robust("essential", a, 5, 5, seed, counts,
+                   lambda counts, seeds: (a, b, counts, seeds, _cameras(camera_matrix, int(a.shape[0]), a.device)),
+                   (float(threshold), float(prob), int(max_iters)))
 
 
 def find_essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None):
@@ -206,13 +182,8 @@ def find_essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0
 
     kpts_A, kpts_B: [N, 2] -> (E [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
     [B, N, 2] -> (E [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
-    single = isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2
     E, mask, ok, _ = essential(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, counts)
-    if not single:
-        return E, mask, ok
-    if not bool(ok[0]):  # the one synchronisation of the single-pair form
-        return None, None
-    return E[0], mask[0]
+    return _front(kpts_A, (E, mask), ok, (None, None))
 
 
 def recover_pose(E, kpts_A, kpts_B, mask=None, camera_matrix=None, distance_thresh=1e9, counts=None):
@@ -247,7 +218,7 @@ def recover_pose(E, kpts_A, kpts_B, mask=None, camera_matrix=None, distance_thre
         with torch.cuda.device(dev):
             _lib.check(lib.roma_op_recover_pose(_ptr(E), _ptr(a), _ptr(b), _ptr(mask), _ptr(counts), _ptr(K), B, N,
                                                 float(distance_thresh), _ptr(n_good), _ptr(R), _ptr(t), _ptr(good), _ptr(ws), nws,
-                                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                                _stream(dev)))
     if single:
         return int(n_good[0]), R[0], t[0], good[0]
     return n_good, R, t, good
@@ -272,7 +243,7 @@ def essential_minimal(x0, x1):
     if S > 0:
         with torch.cuda.device(dev):
             _lib.check(_lib.load().roma_op_essential_minimal(_ptr(a), _ptr(b), S, _ptr(E), _ptr(n),
-                                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                                             _stream(dev)))
     return E, n
 
 
@@ -301,28 +272,20 @@ def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=100
     t [B, 3, 1], mask [B, N], ok [B]) with no host synchronisation.  mask is what the reference returns: cv2.recoverPose rewrites the RANSAC mask in place, so it holds
     the RANSAC inliers that pass the cheirality test of the chosen candidate (tools/pose_geometry.estimate_pose returns the plain
     RANSAC mask instead)."""
-    single = isinstance(kpts0, torch.Tensor) and kpts0.dim() == 2
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
     x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
     E, inl, ok, _ = essential(x0, x1, None, conf, norm_thresh, max_iters, seed, counts)
     n, R, t, good = recover_pose(E, x0, x1, inl, None, 1e9, counts)
-    ok = ok & (n > 0)
-    if not single:
-        return R, t, good, ok
-    return (R[0], t[0], good[0]) if bool(ok[0]) else None  # the one synchronisation of the single-pair form
+    return _front(kpts0, (R, t, good), ok & (n > 0), None)
 
 
 def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=10000, seed=None, counts=None):
     """romatch/utils/utils.py:53-74 on the device: find_fundamental on the pixels (threshold norm_thresh in pixels, as the
     reference passes it; plain RANSAC + LO standing in for USAC_ACCURATE), E = K1^T F K0, then recover_pose on the normalised
     points.  Returns as estimate_pose."""
-    single = isinstance(kpts0, torch.Tensor) and kpts0.dim() == 2
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
     F, inl, ok, _ = ransac(FUNDAMENTAL, a, b, norm_thresh, conf, max_iters, seed, True, counts)
     E = K1.transpose(1, 2) @ F @ K0
     x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
     n, R, t, good = recover_pose(E, x0, x1, inl, None, 1e9, counts)
-    ok = ok & (n > 0)
-    if not single:
-        return R, t, good, ok
-    return (R[0], t[0], good[0]) if bool(ok[0]) else None  # the one synchronisation of the single-pair form
+    return _front(kpts0, (R, t, good), ok & (n > 0), None)

@@ -1,6 +1,7 @@
 """numpy float64 restatement of the device essential-matrix RANSAC and recoverPose (roma_amd/csrc/essential.hip,
 `roma_amd.find_essential` / `recover_pose` / `estimate_pose`): the oracle of tests/test_gpu_essential.py, as
-tools/geometry_ref.py is for H and F (whose sampling stream, Gauss-Jordan and iteration formula this file imports).
+tools/geometry_ref.py is for H and F (whose round loop - sampling stream, selection, iteration count and stop - and
+Gauss-Jordan this file imports).
 
 Same algorithm step by step: normalisation x_n = ((x - cx) / fx, (y - cy) / fy) (identity without a camera matrix), threshold
 / ((fx + fy) / 2); hypotheses in rounds of ROUND per pair drawn by the same counter-based generator at S = 5; Nister's
@@ -25,7 +26,6 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import geometry_ref as gr  # noqa: E402
 
-ROUND = gr.ROUND
 MAX_ROOTS = 10
 BISECT = 64
 NEWTON = 3
@@ -304,28 +304,10 @@ def ransac(pa, pb, thr, prob, max_iters, seed, K=None):
     with np.errstate(invalid="ignore"):
         xa, xb = _normalise(pa, K), _normalise(pb, K)
     t2 = thr_n * thr_n
-    best, cur, needed = -1, None, max_iters
-    for r in range((max_iters + ROUND - 1) // ROUND):
-        hs = np.arange(r * ROUND, (r + 1) * ROUND)
-        idx, drawn = gr.draw_samples(seed, hs, n, 5)
-        idx = np.where(drawn[:, None], idx, 0)
-        ok = drawn & fin[idx].all(axis=1)
-        models = np.zeros((ROUND, MAX_ROOTS, 3, 3))
-        nm = np.zeros(ROUND, dtype=np.int64)
-        sel = np.nonzero(ok)[0]
-        if len(sel):
-            models[sel], nm[sel] = five_point(xa[idx[sel]], xb[idx[sel]])
-        counts = inliers(models, xa, xb, t2).sum(axis=1).reshape(ROUND, MAX_ROOTS)
-        counts = np.where(np.arange(MAX_ROOTS)[None, :] < nm[:, None], counts, -1).reshape(-1)
-        k = int(np.argmax(counts))
-        if counts[k] > best:
-            best = int(counts[k])
-            out.update(best_h=r * ROUND + k // MAX_ROOTS, best_root=k % MAX_ROOTS)
-            cur = models.reshape(-1, 3, 3)[k].copy()
-            needed = gr.update_num_iters(prob, best / n, 5, max_iters)
-        out["rounds"] = r + 1
-        if (r + 1) * ROUND >= min(max_iters, needed):
-            break
+    best, cur, best_h, best_root, rounds = gr.round_loop(n, 5, MAX_ROOTS, fin, seed, prob, max_iters,
+                                                         lambda idx: five_point(xa[idx], xb[idx]),
+                                                         lambda M: inliers(M, xa, xb, t2).sum(axis=1))
+    out.update(rounds=rounds, best_h=best_h, best_root=best_root)
     if best <= 0:
         return out
     out.update(E=cur, mask=inliers(cur[None], xa, xb, t2)[0], ok=True, best=best)

@@ -25,6 +25,7 @@ PIVOT_EPS = 1e-6
 CUBIC_EPS = 1e-12
 SAMPLE = {HOMOGRAPHY: 4, FUNDAMENTAL: 7}
 REFIT_MIN = {HOMOGRAPHY: 4, FUNDAMENTAL: 8}
+SLOTS = {HOMOGRAPHY: 1, FUNDAMENTAL: MAX_ROOTS}  # models per hypothesis
 _G1, _G2 = np.uint64(0x9E3779B97F4A7C15), np.uint64(0xD1B54A32D192ED03)
 
 
@@ -230,6 +231,36 @@ def update_num_iters(conf, w, s, max_iters):
     return int(math.ceil(num / denom))
 
 
+def round_loop(n, s, slots, fin, seed, conf, max_iters, solve, count):
+    """the sampling rounds of one pair, as every model runs them (csrc/ransac.h): ROUND hypotheses per round drawn by
+    draw_samples; solve(idx [k, s]) -> (models [k, slots, 3, 3], number of models [k]) on the samples that were drawn and hold
+    finite rows only; count(models [K, 3, 3]) -> inlier counts [K], -1 for unused slots; the largest count (ties: lowest
+    (h, slot)) replaces the current model if it is strictly larger; OpenCV's adaptive iteration count; stop once ROUND * rounds
+    reaches it or max_iters.  Returns (best count, current model or None, best_h, best_root, rounds)."""
+    best, cur, best_h, best_root, needed, rounds = -1, None, -1, -1, max_iters, 0
+    for r in range((max_iters + ROUND - 1) // ROUND):
+        hs = np.arange(r * ROUND, (r + 1) * ROUND)
+        idx, drawn = draw_samples(seed, hs, n, s)
+        idx = np.where(drawn[:, None], idx, 0)
+        ok = drawn & fin[idx].all(axis=1)
+        models = np.zeros((ROUND, slots, 3, 3))
+        nm = np.zeros(ROUND, dtype=np.int64)
+        sel = np.nonzero(ok)[0]
+        if len(sel):
+            models[sel], nm[sel] = solve(idx[sel])
+        counts = count(models.reshape(-1, 3, 3)).reshape(ROUND, slots)
+        counts = np.where(np.arange(slots)[None, :] < nm[:, None], counts, -1).reshape(-1)
+        k = int(np.argmax(counts))
+        if counts[k] > best:
+            best, best_h, best_root = int(counts[k]), r * ROUND + k // slots, k % slots
+            cur = models.reshape(-1, 3, 3)[k].copy()
+            needed = update_num_iters(conf, best / n, s, max_iters)
+        rounds = r + 1
+        if rounds * ROUND >= min(max_iters, needed):
+            break
+    return best, cur, best_h, best_root, rounds
+
+
 def refit(model, xa, xb):
     """least-squares model on normalised inliers: smallest eigenvector of the 9 x 9 normal equations (rank 2 for F)"""
     x, y, u, v = xa[:, 0], xa[:, 1], xb[:, 0], xb[:, 1]
@@ -261,34 +292,16 @@ def ransac(model, pa, pb, thr, conf, max_iters, seed, refine=True):
     with np.errstate(invalid="ignore"):
         xa, xb = (pa - ca) * sa, (pb - cb) * sb
     t2a, t2b = (thr * sa) ** 2, (thr * sb) ** 2
-    best, cur, needed = -1, None, max_iters
-    for r in range((max_iters + ROUND - 1) // ROUND):
-        hs = np.arange(r * ROUND, (r + 1) * ROUND)
-        idx, drawn = draw_samples(seed, hs, n, s)
-        idx = np.where(drawn[:, None], idx, 0)
-        ok = drawn & fin[idx].all(axis=1)
-        sa_, sb_ = xa[idx], xb[idx]
-        models = np.zeros((ROUND, MAX_ROOTS, 3, 3))
-        nm = np.zeros(ROUND, dtype=np.int64)
-        sel = np.nonzero(ok)[0]
-        if len(sel):
-            if model == HOMOGRAPHY:
-                H, hok = solve_h(sa_[sel], sb_[sel])
-                models[sel, 0], nm[sel] = H, hok.astype(np.int64)
-            else:
-                F, fn = solve_f(sa_[sel], sb_[sel])
-                models[sel], nm[sel] = F, fn
-        counts = inliers(model, models, xa, xb, t2a, t2b).sum(axis=1).reshape(ROUND, MAX_ROOTS)
-        counts = np.where(np.arange(MAX_ROOTS)[None, :] < nm[:, None], counts, -1).reshape(-1)
-        k = int(np.argmax(counts))
-        if counts[k] > best:
-            best = int(counts[k])
-            out.update(best_min=best, best_h=r * ROUND + k // MAX_ROOTS, best_root=k % MAX_ROOTS)
-            cur = models.reshape(-1, 3, 3)[k].copy()
-            needed = update_num_iters(conf, best / n, s, max_iters)
-        out["rounds"] = r + 1
-        if (r + 1) * ROUND >= min(max_iters, needed):
-            break
+
+    def solve(idx):
+        if model == HOMOGRAPHY:
+            H, ok = solve_h(xa[idx], xb[idx])
+            return H[:, None], ok.astype(np.int64)
+        return solve_f(xa[idx], xb[idx])
+
+    best, cur, best_h, best_root, rounds = round_loop(n, s, SLOTS[model], fin, seed, conf, max_iters, solve,
+                                                      lambda M: inliers(model, M, xa, xb, t2a, t2b).sum(axis=1))
+    out.update(rounds=rounds, best_h=best_h, best_root=best_root, best_min=best)
     if best <= 0:
         return out
     if refine:

@@ -21,6 +21,18 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from audit_asm_reads import extract_code_object as code_object  # noqa: E402
 
 
+def strip_args(nm):
+    """the demangled name without its trailing argument list; parentheses inside the name, as in `(anonymous namespace)`, stay"""
+    if not nm.endswith(")"):
+        return nm
+    depth = 0
+    for i in range(len(nm) - 1, -1, -1):
+        depth += {")": 1, "(": -1}.get(nm[i], 0)
+        if depth == 0:
+            return nm[:i]
+    return nm
+
+
 def kernels(obj):
     """[{name, vgpr, agpr, sgpr, spill, scratch, lds}] of one host object"""
     notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", code_object(obj)], capture_output=True, text=True,
@@ -35,7 +47,7 @@ def kernels(obj):
         sym = g("name", "?")
         nm = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
         nm = nm.replace("void roma::", "").replace("unsigned short", "bf16")
-        nm = re.sub(r"\(.*\)$", "", nm)
+        nm = strip_args(nm)
         out.append({"name": nm, "vgpr": int(g("vgpr_count")), "agpr": int(g("agpr_count")), "sgpr": int(g("sgpr_count")),
                     "spill": int(g("vgpr_spill_count")), "sgpr_spill": int(g("sgpr_spill_count")),
                     "scratch": int(g("private_segment_fixed_size")), "lds": int(g("group_segment_fixed_size"))})
