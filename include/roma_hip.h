@@ -348,6 +348,24 @@ long roma_op_recover_pose_workspace(int B, int N);
 int roma_op_recover_pose(const double* E, const float* kpts_a, const float* kpts_b, const unsigned char* mask, const int* counts,
                          const double* camera_matrix, int B, int N, double distance_thresh, int* out_n_good, double* out_r,
                          double* out_t, unsigned char* out_mask, void* workspace, long workspace_bytes, void* stream);
+/* Nonlinear refinement of a relative pose: a Levenberg-Marquardt fit of (R, t) to the Sampson error of E = [t]x R under a
+ * hard-truncated loss sum min(r^2, thr^2) - what the final refinement of PoseLib's estimate_relative_pose is (the reference's
+ * megadepth_pose_estimation_benchmark_poselib.py); it follows roma_op_essential + roma_op_recover_pose, whose pose is the winning
+ * five-point sample's.  Algorithm restated in tools/pose_refine_ref.py: five parameters (R <- exp([w]x) R, t on the unit sphere),
+ * analytic Jacobian over the active rows (r^2 < thr^2), (H + lambda diag H) delta = -g by Cholesky, lambda from 1e-3, a step is
+ * kept only if it lowers the truncated cost (else lambda x 10, at most 10 retries).  It stops after max_steps accepted steps, on a
+ * step shorter than 1e-10, with fewer than 5 active rows or when H + lambda diag H is not positive definite; the pose so far is
+ * returned, so the cost never rises and a pose is never lost.  R DEVICE f64 [B, 3, 3], t DEVICE f64 [B, 3]; kpts_a, kpts_b
+ * DEVICE f32 [B, N, 2] NORMALISED points; counts as for roma_op_ransac; valid DEVICE u8 [B] or NULL (every pair): pairs to fit,
+ * the others are copied through; thr in normalised units.  Outputs, all DEVICE: R f64 [B, 3, 3], t f64 [B, 3] (the input bits
+ * when no step was accepted), mask u8 [B, N] (r^2 < thr^2 under the returned pose and positive depth in both cameras by
+ * recoverPose's triangulation; zeros for a pair that is not fitted), info int32 [B, 4] = {accepted steps, cost evaluations,
+ * active rows at the end, pair fitted}.  One workgroup per pair runs the whole loop in one launch: no host synchronisation,
+ * bit-identical from run to run and independent of B.  workspace: device memory of roma_op_refine_pose_workspace(B, N) bytes. */
+long roma_op_refine_pose_workspace(int B, int N);
+int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
+                        const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
+                        unsigned char* out_mask, int* out_info, void* workspace, long workspace_bytes, void* stream);
 /* ---- Tiny RoMa (romatch/models/tiny.py), matcher side; the XFeat backbone is the caller's (model_zoo/__init__.py:24-27).
  * All tensors f32, channels-last unless noted.  corr_volume (tiny.py:182-196) = roma_op_gemm with A = feats of image B
  * [H1*W1, C], W = feats of image A [H0*W0, C], alpha = 1/sqrt(C), batch = pairs: cv [B, H1*W1, H0*W0]. */

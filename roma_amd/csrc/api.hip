@@ -22,6 +22,7 @@
 #include "vit.h"
 #include "sampling.h"
 #include "essential.h"
+#include "pose_refine.h"
 #include "geometry.h"
 
 namespace roma {
@@ -551,6 +552,14 @@ int roma_op_recover_pose(const double* E, const float* kpts_a, const float* kpts
                          double* out_t, unsigned char* out_mask, void* workspace, long workspace_bytes, void* stream) {
   return recover_pose_launch(E, kpts_a, kpts_b, mask, counts, camera_matrix, B, N, distance_thresh, out_n_good, out_r, out_t,
                              out_mask, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+// ---- relative-pose refinement (pose_refine.hip)
+long roma_op_refine_pose_workspace(int B, int N) { return (long)refine_pose_workspace_bytes(B, N); }
+int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
+                        const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
+                        unsigned char* out_mask, int* out_info, void* workspace, long workspace_bytes, void* stream) {
+  return refine_pose_launch(R, t, kpts_a, kpts_b, counts, valid, B, N, thr, max_steps, out_r, out_t, out_mask, out_info, workspace,
+                            (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
 }
 // ---- Tiny RoMa matcher side (tiny.hip)
 int roma_op_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, void* stream) {

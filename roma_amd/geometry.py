@@ -12,7 +12,8 @@ are scaled so that [2, 2] = 1 (unit Frobenius norm where |[2, 2]| < 1e-12 of it)
 The relative pose of the reference's pose benchmarks (romatch/utils/utils.py estimate_pose: cv2.findEssentialMat + cv2.recoverPose)
 runs on the device as well (`roma_op_essential` / `roma_op_recover_pose`, csrc/essential.hip): `find_essential`, `recover_pose`,
 `estimate_pose`, `estimate_pose_uncalibrated` and the five-point solver alone, `essential_minimal`.  Restated in numpy float64 by
-tools/essential_ref.py.
+tools/essential_ref.py.  `refine_pose` (`roma_op_refine_pose`, csrc/pose_refine.hip) fits the recovered pose to its inliers by
+Levenberg-Marquardt on the truncated Sampson error, as the reference's PoseLib benchmark does; restated by tools/pose_refine_ref.py.
 """
 from __future__ import annotations
 
@@ -264,28 +265,115 @@ def _pose_inputs(kpts0, kpts1, K0, K1, counts):
     return a, b, K0, K1, _counts(counts, B, dev)
 
 
-def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=1000, seed=None, counts=None):
+def _pose_tensor(x, name, B, shape, dev):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise _lib.RomaHipError(f"roma_amd.geometry: {name} must be a tensor on a HIP device; there is no CPU fallback")
+    x = x.detach().to(device=dev, dtype=torch.float64)
+    if x.numel() != B * shape[0] * shape[1]:
+        raise ValueError(f"roma_amd.geometry: {name} must hold {B} x {shape}, got {tuple(x.shape)}")
+    return x.reshape(B, *shape).contiguous()
+
+
+def _refine_normalised(R, t, x0, x1, thr, max_steps, counts, valid):
+    """roma_op_refine_pose on normalised points [B, N, 2] (read as f32): (R [B, 3, 3], t [B, 3, 1], mask [B, N] bool,
+    info [B, 4] int32).  Nothing is launched for B == 0 or N < 5: every pair comes back untouched."""
+    a, b = _pair_batch(x0, x1)
+    B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
+    R, t = _pose_tensor(R, "R", B, (3, 3), dev), _pose_tensor(t, "t", B, (3, 1), dev)
+    if not (thr > 0) or int(max_steps) < 0:
+        raise ValueError("roma_amd.geometry: need norm_thresh > 0, max_steps >= 0")
+    counts = _counts(counts, B, dev)
+    if valid is not None:
+        valid = torch.as_tensor(valid).to(device=dev).reshape(-1).to(torch.uint8).contiguous()
+        if valid.shape[0] != B:
+            raise ValueError(f"roma_amd.geometry: valid has {valid.shape[0]} entries for {B} pairs")
+    mask = torch.zeros((B, N), device=dev, dtype=torch.bool)
+    info = torch.zeros((B, 4), device=dev, dtype=torch.int32)
+    if B == 0 or N < 5:
+        return R.clone(), t.clone(), mask, info
+    out_R, out_t = torch.empty_like(R), torch.empty_like(t)
+    lib = _lib.load()
+    nws = int(lib.roma_op_refine_pose_workspace(B, N))
+    ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(lib.roma_op_refine_pose(_ptr(R), _ptr(t), _ptr(a), _ptr(b), _ptr(counts), _ptr(valid), B, N, float(thr),
+                                           int(max_steps), _ptr(out_R), _ptr(out_t), _ptr(mask), _ptr(info), _ptr(ws), nws,
+                                           _stream(dev)))
+    return out_R, out_t, mask, info
+
+
+def refine_pose(R, t, kpts0, kpts1, K0, K1, norm_thresh, max_steps=25, counts=None, valid=None):
+    """Nonlinear refinement of a relative pose on the device (roma_op_refine_pose, csrc/pose_refine.hip): a Levenberg-Marquardt
+    fit of (R, t) to the Sampson error of E = [t]x R under the truncated loss sum min(r^2, norm_thresh^2) - what the final
+    refinement of poselib.estimate_relative_pose is (the reference's megadepth_pose_estimation_benchmark_poselib.py); restated
+    in numpy float64 by tools/pose_refine_ref.py.  The pixel keypoints are normalised as in estimate_pose; norm_thresh is the
+    threshold estimate_pose takes.  At most max_steps accepted steps; a fit that cannot move (no or fewer than 5 rows inside
+    the threshold, a singular system) returns its input, so the truncated cost never rises and a pose is never lost.
+
+    R [3, 3], t [3, 1] with kpts [N, 2] -> (R [3, 3] float64, t [3, 1] float64, mask [N] bool, info [4] int32);
+    R [B, 3, 3], t [B, 3, 1] with kpts [B, N, 2] -> (R [B, 3, 3], t [B, 3, 1], mask [B, N], info [B, 4]).  No host
+    synchronisation in either form.  mask: rows whose Sampson error is below norm_thresh under the returned pose and whose
+    depth is positive in both cameras (the triangulation of recover_pose); info = (accepted steps, cost evaluations, active
+    rows at the end, pair fitted).  valid [B] bool marks the pairs to fit; the others, and pairs of fewer than 5 rows, come
+    back untouched with an empty mask and info[3] = 0.  See `ransac` for counts."""
+    single = isinstance(kpts0, torch.Tensor) and kpts0.dim() == 2
+    a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
+    x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
+    out = _refine_normalised(R, t, x0, x1, norm_thresh, max_steps, counts, valid)
+    return tuple(o[0] for o in out) if single else out
+
+
+def _refined(R, t, good, ok, x0, x1, thr, counts):
+    """the refine=True tail of estimate_pose*: pairs without a pose are passed as not valid and keep what they had"""
+    R, t, mask, info = _refine_normalised(R, t, x0, x1, thr, 25, counts, ok)
+    return R, t, torch.where(info[:, 3:4] > 0, mask, good)
+
+
+def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=1000, seed=None, counts=None, refine=False):
     """romatch/utils/utils.py:30-51 on the device: normalise with the inverse of K[:2, :2] and the principal point (f64), then
     find_essential (identity camera, threshold norm_thresh, prob conf) and recover_pose.
 
     [N, 2] -> (R [3, 3], t [3, 1], mask [N] bool) or None (also for fewer than 5 rows); [B, N, 2] -> (R [B, 3, 3],
     t [B, 3, 1], mask [B, N], ok [B]) with no host synchronisation.  mask is what the reference returns: cv2.recoverPose rewrites the RANSAC mask in place, so it holds
     the RANSAC inliers that pass the cheirality test of the chosen candidate (tools/pose_geometry.estimate_pose returns the plain
-    RANSAC mask instead)."""
+    RANSAC mask instead).
+
+    refine=True: the recovered pose, which is the winning five-point sample's, then goes through `refine_pose` (threshold
+    norm_thresh, 25 steps; pairs without a pose are left alone) and mask is the refined one.  The default leaves every output
+    as it was before the keyword existed."""
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
     x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
     E, inl, ok, _ = essential(x0, x1, None, conf, norm_thresh, max_iters, seed, counts)
     n, R, t, good = recover_pose(E, x0, x1, inl, None, 1e9, counts)
-    return _front(kpts0, (R, t, good), ok & (n > 0), None)
+    ok = ok & (n > 0)
+    if refine:
+        R, t, good = _refined(R, t, good, ok, x0, x1, norm_thresh, counts)
+    return _front(kpts0, (R, t, good), ok, None)
 
 
-def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=10000, seed=None, counts=None):
+def _mean_focal(K0, K1):
+    """mean of fx, fy of both cameras as a Python float; host arithmetic when the matrices were given on the host"""
+    f = [torch.as_tensor(K).to(torch.float64).reshape(-1, 3, 3)[:, (0, 1), (0, 1)].mean() for K in (K0, K1)]
+    return 0.5 * (float(f[0]) + float(f[1]))
+
+
+def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=10000, seed=None, counts=None,
+                               refine=False):
     """romatch/utils/utils.py:53-74 on the device: find_fundamental on the pixels (threshold norm_thresh in pixels, as the
     reference passes it; plain RANSAC + LO standing in for USAC_ACCURATE), E = K1^T F K0, then recover_pose on the normalised
-    points.  Returns as estimate_pose."""
+    points.  Returns as estimate_pose.
+
+    refine=True: as in estimate_pose.  The refinement works on normalised points, so it gets norm_thresh divided by the mean of
+    the four focal lengths (fx, fy of K0 and of K1; over all pairs where the matrices are [B, 3, 3]).  That mean is a host
+    number: camera matrices given on the host (numpy, CPU tensors) cost nothing, matrices that live on the device are read back
+    once, which is the one host synchronisation of this option."""
+    focal = _mean_focal(K0, K1) if refine else None
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
     F, inl, ok, _ = ransac(FUNDAMENTAL, a, b, norm_thresh, conf, max_iters, seed, True, counts)
     E = K1.transpose(1, 2) @ F @ K0
     x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
     n, R, t, good = recover_pose(E, x0, x1, inl, None, 1e9, counts)
-    return _front(kpts0, (R, t, good), ok & (n > 0), None)
+    ok = ok & (n > 0)
+    if refine:
+        R, t, good = _refined(R, t, good, ok, x0, x1, norm_thresh / focal, counts)
+    return _front(kpts0, (R, t, good), ok, None)

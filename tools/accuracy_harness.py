@@ -142,16 +142,20 @@ def ground_truth_matches(data):
 
 
 # ------------------------------------------------------------------------------------------- MegaDepth-1500 pose benchmark
-def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200, pose="host"):
+def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200, pose="host", refine=False):
     """megadepth_pose_estimation_benchmark.py:25-116 over an iterable of pairs
     {im_A, im_B (what model.match takes: paths, PIL images or [3, H, W] tensors), K1, K2 [3, 3], T_1to2 [3, 4] or [4, 4],
     size_A = (w1, h1), size_B = (w2, h2) of the ORIGINAL images}: per pair one `match`, then `repeats` x {`sample` 5 000
     matches, pixel coordinates at the 1 200-pixel scale, shuffle, `estimate_pose` at 0.5 px / mean focal, pose error};
     failures count as 90 degrees.  Returns the reference's dictionary (auc_5/10/20, map_5/10/20).
     pose="host": tools/pose_geometry.estimate_pose per call (numpy); pose="device": a pair's `repeats` calls as one batched
-    roma_amd.estimate_pose (B = repeats, one seed per repeat), read back once per pair."""
+    roma_amd.estimate_pose (B = repeats, one seed per repeat), read back once per pair.  refine=True (pose="device" only):
+    estimate_pose(..., refine=True), the Levenberg-Marquardt fit on the truncated Sampson error that the reference's PoseLib
+    benchmark (megadepth_pose_estimation_benchmark_poselib.py) gets from poselib.estimate_relative_pose."""
     if pose not in ("host", "device"):
         raise ValueError(f"pose must be 'host' or 'device', got {pose!r}")
+    if refine and pose != "device":
+        raise ValueError("refine=True needs pose='device': the host path has no refinement")
     import numpy as np
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import pose_geometry as PG
@@ -171,7 +175,7 @@ def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200, pos
         norm_threshold = 0.5 / (np.mean(np.abs(K1[:2, :2])) + np.mean(np.abs(K2[:2, :2])))
         if pose == "device":
             tot_e_pose += _device_pose_errors(model, dense_matches, dense_certainty, num, repeats, (h1, w1, h2, w2), K1, K2,
-                                              norm_threshold, R, t, rng)
+                                              norm_threshold, R, t, rng, refine)
             continue
         for _ in range(repeats):
             sparse, _ = model.sample(dense_matches, dense_certainty, num)
@@ -193,7 +197,7 @@ def pose_benchmark(model, pairs, seed=0, num=5000, repeats=5, max_side=1200, pos
             "map_20": float(np.mean(acc))}
 
 
-def _device_pose_errors(model, dense_matches, dense_certainty, num, repeats, hw, K1, K2, norm_threshold, R, t, rng):
+def _device_pose_errors(model, dense_matches, dense_certainty, num, repeats, hw, K1, K2, norm_threshold, R, t, rng, refine=False):
     """one pair's `repeats` pose estimates as one batched roma_amd.estimate_pose: [max(e_t, e_R)] per repeat"""
     import numpy as np
     from roma_amd import estimate_pose
@@ -213,7 +217,8 @@ def _device_pose_errors(model, dense_matches, dense_certainty, num, repeats, hw,
     for i in range(repeats):
         a[i, :counts[i]], b[i, :counts[i]] = ka[i], kb[i]
     seeds = torch.as_tensor(rng.integers(0, 2 ** 62, repeats), dtype=torch.int64)
-    R_est, t_est, _, ok = estimate_pose(a, b, K1, K2, norm_threshold, 0.99999, 1000, seed=seeds, counts=counts)
+    kw = {"refine": True} if refine else {}
+    R_est, t_est, _, ok = estimate_pose(a, b, K1, K2, norm_threshold, 0.99999, 1000, seed=seeds, counts=counts, **kw)
     R_est, t_est, ok = R_est.cpu().numpy(), t_est.cpu().numpy(), ok.cpu().numpy()
     out = []
     for i in range(repeats):
@@ -270,6 +275,7 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, help="number of synthetic planar batches (of 2 pairs) to run")
     ap.add_argument("--synthetic-pose", type=int, default=0, help="number of synthetic pairs for the pose (MegaDepth-1500) loop")
     ap.add_argument("--device-pose", action="store_true", help="pose loop: batched roma_amd.estimate_pose instead of the host path")
+    ap.add_argument("--refine-pose", action="store_true", help="with --device-pose: estimate_pose(..., refine=True)")
     ap.add_argument("--megadepth", default=None, help="data root of the MegaDepth test split (reference: data/megadepth)")
     ap.add_argument("--weights", default=None)
     ap.add_argument("--dinov2", default=None)
@@ -297,7 +303,7 @@ def main():
             pairs.append({"im_A": d["im_A"].to("cuda:0"), "im_B": d["im_B"].to("cuda:0"), "K1": d["K1"][0].numpy(),
                           "K2": d["K2"][0].numpy(), "T_1to2": d["T_1to2"][0].numpy(), "size_A": (args.res, args.res),
                           "size_B": (args.res, args.res)})
-        res = pose_benchmark(model, pairs, pose="device" if args.device_pose else "host")
+        res = pose_benchmark(model, pairs, pose="device" if args.device_pose else "host", refine=args.refine_pose)
         print(json.dumps({"pose_results": res, "acceptance_on_megadepth1500": {k: v[0] for k, v in ACCEPTANCE_POSE.items()},
                           "note": "synthetic planar scenes" + ("" if args.weights else ", RANDOM weights: plumbing check only")}))
         return

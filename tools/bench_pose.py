@@ -6,7 +6,10 @@ reference's MegaDepth-1500 benchmark: B = 8 pairs, N = 5 000 matches, threshold 
 Per configuration one JSON line: ms per batched estimate_pose call (device events, after warm-up), rounds executed per pair,
 hypothesis-point evaluations per second (hypotheses the score kernel ran x points; a hypothesis carries up to 10 models) and the host numpy path
 tools/pose_geometry.estimate_pose on the same pairs, one after the other - a CPU number, for scale only.
-Usage: python tools/bench_pose.py [--iters 20] [--no-cpu]
+--refine adds, after each configuration's line, one line for estimate_pose(..., refine=True) (the Levenberg-Marquardt fit of
+csrc/pose_refine.hip after the RANSAC): ms per call, the added ms over the plain call timed next to it, steps and cost
+evaluations per pair.
+Usage: python tools/bench_pose.py [--iters 20] [--no-cpu] [--refine]
 """
 import argparse
 import json
@@ -60,16 +63,57 @@ def run(name, a, b, K, iters, cpu):
     return res
 
 
+def _timed(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters, out
+
+
+def run_refined(name, a, b, K, iters):
+    """the refined leg: plain and refined calls timed alternately (three rounds each, the medians), and the fit's own counters"""
+    from roma_amd.geometry import estimate_pose, refine_pose
+    thr = 0.5 / float(np.mean([K[0, 0], K[1, 1]]))
+    da = torch.tensor(a, dtype=torch.float32, device="cuda:0")
+    db = torch.tensor(b, dtype=torch.float32, device="cuda:0")
+    seeds = torch.arange(len(a), dtype=torch.int64) + 1
+    plain = lambda: estimate_pose(da, db, K, K, thr, 0.99999, 1000, seed=seeds)  # noqa: E731
+    fitted = lambda: estimate_pose(da, db, K, K, thr, 0.99999, 1000, seed=seeds, refine=True)  # noqa: E731
+    for _ in range(3):
+        plain()
+        fitted()
+    torch.cuda.synchronize()
+    ms_p, ms_r = [], []
+    for _ in range(3):
+        ms_p.append(_timed(plain, iters)[0])
+        ms_r.append(_timed(fitted, iters)[0])
+    R, t, mask, ok = plain()
+    ms_fit, (_, _, _, info) = _timed(lambda: refine_pose(R, t, da, db, K, K, thr, valid=ok), iters)
+    info = info.cpu().numpy()
+    res = {"config": name + " refine=True", "B": int(a.shape[0]), "N": int(a.shape[1]), "threshold": thr, "max_steps": 25,
+           "ms_per_call": round(float(np.median(ms_r)), 4), "ms_per_plain_call": round(float(np.median(ms_p)), 4),
+           "added_ms": round(float(np.median(ms_r) - np.median(ms_p)), 4), "refine_pose_alone_ms": round(ms_fit, 4),
+           "steps_per_pair": info[:, 0].tolist(), "cost_evals_per_pair": info[:, 1].tolist(), "active_rows_per_pair": info[:, 2].tolist()}
+    print(json.dumps(res), flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true", help="skip the host reference timing")
+    ap.add_argument("--refine", action="store_true", help="add the estimate_pose(..., refine=True) leg")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_pose.py measures the device path: it needs a GPU"
     K = synthetic_relief_pair(480, 640, seed=0)["K1"]
     for frac in (0.0, 0.3, 0.5):
         a, b = relief_batch(8, 5000, frac)
         run(f"estimate_pose megadepth outliers={frac}", a, b, K, args.iters, not args.no_cpu)
+        if args.refine:
+            run_refined(f"estimate_pose megadepth outliers={frac}", a, b, K, args.iters)
 
 
 if __name__ == "__main__":
