@@ -320,6 +320,20 @@ long roma_op_ransac_workspace(int B, int N);
 int roma_op_ransac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
                    int N, float threshold, double confidence, int max_iters, int refine, double* out_model, unsigned char* out_mask,
                    unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes, void* stream);
+/* The same batched RANSAC with MAGSAC++ scoring (Barath et al., CVPR 2020; nu = 4), restated in tools/magsac_ref.py - what
+ * demo_fundamental asks OpenCV for with USAC_MAGSAC, defined as there (not OpenCV's implementation).  threshold tau is the largest
+ * residual that counts as an inlier; a model's score is the sum over the pair's rows of the MAGSAC++ loss of its pixel residual
+ * (model 0: reprojection error in image B; model 1: Sampson distance), lower is better; then up to lo_iters (0 .. 64) IRLS steps
+ * with the MAGSAC++ weights, each kept only if the score drops.  Inputs as for roma_op_ransac.  Outputs, all DEVICE: model, mask
+ * (residual < threshold under the returned model), ok as for roma_op_ransac; info int32 [B, 7] = {rounds run, winning hypothesis,
+ * its root, inliers of the winning minimal model, final inliers, pair valid, LO steps accepted}; score f64 [B, 2] = {sum of the
+ * loss of the winning minimal model, final sum: that less the accepted LO steps' gains} (0 where no model).  No host
+ * synchronisation.
+ * workspace: device memory of roma_op_magsac_workspace(B, N) bytes. */
+long roma_op_magsac_workspace(int B, int N);
+int roma_op_magsac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
+                   int N, float threshold, double confidence, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask,
+                   unsigned char* out_ok, int* out_info, double* out_score, void* workspace, long workspace_bytes, void* stream);
 /* Essential matrix and relative pose - the tail of the reference's pose benchmarks (romatch/utils/utils.py estimate_pose):
  * cv2.findEssentialMat(A, B, K, RANSAC, prob, threshold, maxIters) and cv2.recoverPose.  Algorithm restated in
  * tools/essential_ref.py.  roma_op_essential: Nister's five-point solver (up to 10 models per sample, real roots by Sturm

@@ -92,6 +92,8 @@ SIGNATURES = {
     "roma_op_multinomial": (_i, [_vp, _l, _l, C.c_ulonglong, _vp, _vp, _l, _vp]),
     "roma_op_ransac_workspace": (_l, [_i, _i]),
     "roma_op_ransac": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "roma_op_magsac_workspace": (_l, [_i, _i]),
+    "roma_op_magsac": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_essential_workspace": (_l, [_i, _i]),
     "roma_op_essential": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_essential_minimal": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),

@@ -534,6 +534,13 @@ int roma_op_ransac(int model, const float* kpts_a, const float* kpts_b, const in
   return ransac_launch(model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, refine, out_model, out_mask,
                        out_ok, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
 }
+long roma_op_magsac_workspace(int B, int N) { return (long)magsac_workspace_bytes(B, N); }
+int roma_op_magsac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
+                   int N, float threshold, double confidence, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask,
+                   unsigned char* out_ok, int* out_info, double* out_score, void* workspace, long workspace_bytes, void* stream) {
+  return magsac_launch(model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, lo_iters, out_model, out_mask,
+                       out_ok, out_info, out_score, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
 // ---- essential matrix and recoverPose (essential.hip)
 long roma_op_essential_workspace(int B, int N) { return (long)essential_workspace_bytes(B, N); }
 int roma_op_essential(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,

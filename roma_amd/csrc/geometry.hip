@@ -11,6 +11,8 @@
 //   refit       up to REFINE_ITERS times: 9 x 9 normal equations in f64 on the current inliers (fixed-order tree reduction),
 //               smallest eigenvector by one-sided Jacobi on one wave; rank 2 for F.
 //   finish      de-normalised in f64 (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scaled so that [2, 2] = 1; info of RANSAC_INFO ints.
+//   residual2   (MAGSAC++, magsac_run) f32 squared pixel residuals: reprojection error in image B (H), Sampson distance (F).
+//   wrefit      (MAGSAC++) the refit's normal equations weighted by the MAGSAC++ weights of the current model (one IRLS step).
 #include "geometry.h"
 #include "ransac.h"
 
@@ -42,6 +44,40 @@ __device__ __forceinline__ bool inlier_f(const float* m, float4 p, float t2a, fl
   const float ky = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
   const float d2 = d * d;
   return d2 < t2b * fmaf(lx, lx, ly * ly) && d2 < t2a * fmaf(kx, kx, ky * ky);
+}
+
+// squared pixel residuals of the MAGSAC++ scoring from the normalised points; sa2, sb2 the squared scales x_n = (x - c) s.
+// Each is split into terms linear in the model (res_terms_*) and the squared residual formed from them (r2_from_*), so that
+// magsac_accept_kernel can evaluate a candidate as current + difference on the same rows.
+// H: forward reprojection error in image B, |e|^2 / (p_z^2 s_b^2) with the terms of inlier_h; terms (e_x, e_y, p_z).
+__device__ __forceinline__ void res_terms_h(const float* m, float4 p, float (&t)[3]) {
+  const float px = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
+  const float py = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
+  const float pz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
+  t[0] = fmaf(-p.z, pz, px);
+  t[1] = fmaf(-p.w, pz, py);
+  t[2] = pz;
+}
+
+__device__ __forceinline__ float r2_from_h(const float (&t)[3], float, float sb2) {
+  return fmaf(t[0], t[0], t[1] * t[1]) / (t[2] * t[2] * sb2);
+}
+
+// F: Sampson distance d^2 / (s_b^2 |F x_a|_{1,2}^2 + s_a^2 |F^T x_b|_{1,2}^2), exact in pixels (x_b^T F x_a = x_nb^T F_n x_na);
+// terms (d, l_x, l_y, k_x, k_y)
+__device__ __forceinline__ void res_terms_f(const float* m, float4 p, float (&t)[5]) {
+  const float lx = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
+  const float ly = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
+  const float lz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
+  t[0] = fmaf(p.z, lx, fmaf(p.w, ly, lz));
+  t[1] = lx;
+  t[2] = ly;
+  t[3] = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
+  t[4] = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
+}
+
+__device__ __forceinline__ float r2_from_f(const float (&t)[5], float sa2, float sb2) {
+  return t[0] * t[0] / fmaf(sb2, fmaf(t[1], t[1], t[2] * t[2]), sa2 * fmaf(t[3], t[3], t[4] * t[4]));
 }
 
 // ------------------------------------------------------------------------------------------------------------ f64 helpers
@@ -264,6 +300,11 @@ struct Hartley {
   // point loop, where a branch per slot reloads them (35 % slower for F); unused slots hold zeros and their counts are dropped
   static constexpr bool SCORE_EVERY_SLOT = true;
 
+  __device__ static void res_scales(const Norm& nm, float& sa2, float& sb2) {  // the scales of M::residual2
+    sa2 = (float)(nm.sa * nm.sa);
+    sb2 = (float)(nm.sb * nm.sb);
+  }
+
   // every thread of the workgroup: the pair's normalisation; pts written only for a valid pair
   __device__ static bool normalise(const float2* A, const float2* Bp, int n, const double*, float thr, double* sh, float4* pts,
                                    Norm& nm, float& t2a, float& t2b) {
@@ -319,13 +360,18 @@ struct Hartley {
     }
   }
 
-  // least-squares refit on the current mask (normalised DLT / normalised 8-point + rank 2); A, Bp, mask: the pair's rows
-  __device__ static void refit(const float2* A, const float2* Bp, PairState<Model>& P, const unsigned char* mask) {
+  // least-squares refit (normalised DLT / normalised 8-point + rank 2); A, Bp: the pair's rows.  W = false: the rows of the
+  // current mask, with at least REFIT_MIN inliers (RANSAC refinement).  W = true: the MAGSAC++ IRLS step - the normal equations
+  // weighted by w(V) of the current model over the rows of positive weight, at least REFIT_MIN of them; pts: the pair's
+  // normalised f32 rows the scoring reads.
+  template <bool W>
+  __device__ static void fit(const float2* A, const float2* Bp, PairState<Model>& P, const unsigned char* mask, const float4* pts,
+                             const MagState* S) {
     __shared__ double red[4][45];
     __shared__ double M[9][9];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (P.stop) return;
-    if (P.best < Model::REFIT_MIN) {
+    if (W ? P.best_h < 0 : P.best < Model::REFIT_MIN) {
       if (t == 0) { P.stop = 1; P.cand_ok = 0; }
       return;
     }
@@ -333,8 +379,18 @@ struct Hartley {
 #pragma unroll
     for (int e = 0; e < 45; ++e) acc[e] = 0;
     const double cax = P.nrm.ca[0], cay = P.nrm.ca[1], cbx = P.nrm.cb[0], cby = P.nrm.cb[1], sa = P.nrm.sa, sb = P.nrm.sb;
+    int npos = 0;
     for (int i = t; i < P.n; i += 256) {
-      if (!mask[i]) continue;
+      double wt = 1;
+      if constexpr (W) {
+        float w;
+        magsac_rho(Model::residual2(P.curf, pts[i], S->sa2, S->sb2) * S->vs, w);
+        if (!(w > 0.f)) continue;
+        ++npos;
+        wt = w;
+      } else {
+        if (!mask[i]) continue;
+      }
       const float2 a = A[i], q = Bp[i];
       const double x = (a.x - cax) * sa, y = (a.y - cay) * sa, u = (q.x - cbx) * sb, v = (q.y - cby) * sb;
       if (Model::MODEL == RANSAC_HOMOGRAPHY) {
@@ -344,14 +400,30 @@ struct Hartley {
 #pragma unroll
         for (int p = 0; p < 9; ++p)
 #pragma unroll
-          for (int q2 = p; q2 < 9; ++q2, ++e) acc[e] += r1[p] * r1[q2] + r2[p] * r2[q2];
+          for (int q2 = p; q2 < 9; ++q2, ++e) {
+            if constexpr (W) acc[e] += wt * (r1[p] * r1[q2] + r2[p] * r2[q2]);
+            else acc[e] += r1[p] * r1[q2] + r2[p] * r2[q2];
+          }
       } else {
         const double r1[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1};
         int e = 0;
 #pragma unroll
         for (int p = 0; p < 9; ++p)
 #pragma unroll
-          for (int q2 = p; q2 < 9; ++q2, ++e) acc[e] += r1[p] * r1[q2];
+          for (int q2 = p; q2 < 9; ++q2, ++e) {
+            if constexpr (W) acc[e] += wt * (r1[p] * r1[q2]);
+            else acc[e] += r1[p] * r1[q2];
+          }
+      }
+    }
+    if constexpr (W) {  // rows of positive weight over the workgroup
+      __shared__ int cnt[4];
+      for (int off = 32; off > 0; off >>= 1) npos += __shfl_xor(npos, off);
+      if (lane == 0) cnt[wave] = npos;
+      __syncthreads();
+      if (((cnt[0] + cnt[1]) + cnt[2]) + cnt[3] < Model::REFIT_MIN) {
+        if (t == 0) { P.stop = 1; P.cand_ok = 0; }
+        return;
       }
     }
 #pragma unroll
@@ -410,6 +482,14 @@ struct Hartley {
     }
   }
 
+  __device__ static void refit(const float2* A, const float2* Bp, PairState<Model>& P, const unsigned char* mask) {
+    fit<false>(A, Bp, P, mask, nullptr, nullptr);
+  }
+
+  __device__ static void wrefit(const float2* A, const float2* Bp, const float4* pts, PairState<Model>& P, const MagState& S) {
+    fit<true>(A, Bp, P, nullptr, pts, &S);
+  }
+
   // de-normalise (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scale; info = {rounds, best_h, best_root, best_min, best, valid}
   __device__ static void finish(const PairState<Model>& P, bool good, double* out, int* info) {
     const Norm& q = P.nrm;
@@ -445,6 +525,14 @@ struct Hartley {
 struct Homography : Hartley<Homography> {
   static constexpr int MODEL = RANSAC_HOMOGRAPHY, S = 4, SLOTS = 1, REFIT_MIN = 4;
   __device__ static bool inlier(const float* m, float4 p, float t2a, float t2b) { return inlier_h(m, p, t2a, t2b); }
+  static constexpr int NT = 3;  // residual terms linear in the model
+  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) { res_terms_h(m, p, t); }
+  __device__ static float r2_from(const float (&t)[NT], float sa2, float sb2) { return r2_from_h(t, sa2, sb2); }
+  __device__ static float residual2(const float* m, float4 p, float sa2, float sb2) {
+    float t[NT];
+    res_terms_h(m, p, t);
+    return r2_from_h(t, sa2, sb2);
+  }
   __device__ static int solve(const double* xa, const double* ya, const double* xb, const double* yb, double (&m)[SLOTS][9]) {
     return solve_h(xa, ya, xb, yb, m);
   }
@@ -453,6 +541,14 @@ struct Homography : Hartley<Homography> {
 struct Fundamental : Hartley<Fundamental> {
   static constexpr int MODEL = RANSAC_FUNDAMENTAL, S = 7, SLOTS = 3, REFIT_MIN = 8;
   __device__ static bool inlier(const float* m, float4 p, float t2a, float t2b) { return inlier_f(m, p, t2a, t2b); }
+  static constexpr int NT = 5;
+  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) { res_terms_f(m, p, t); }
+  __device__ static float r2_from(const float (&t)[NT], float sa2, float sb2) { return r2_from_f(t, sa2, sb2); }
+  __device__ static float residual2(const float* m, float4 p, float sa2, float sb2) {
+    float t[NT];
+    res_terms_f(m, p, t);
+    return r2_from_f(t, sa2, sb2);
+  }
   __device__ static int solve(const double* xa, const double* ya, const double* xb, const double* yb, double (&m)[SLOTS][9]) {
     return solve_f(xa, ya, xb, yb, m);
   }
@@ -476,6 +572,26 @@ int ransac_launch(int model, const float* kpts_a, const float* kpts_b, const int
                                       out_model, out_mask, out_ok, out_info, ws, s)
              : ransac_run<Fundamental>(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, refine,
                                        out_model, out_mask, out_ok, out_info, ws, s);
+}
+
+size_t magsac_workspace_bytes(int B, int N) {
+  return std::max(magsac_workspace_bytes<Homography>(B, N), magsac_workspace_bytes<Fundamental>(B, N));
+}
+
+int magsac_launch(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
+                  int N, float threshold, double confidence, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask,
+                  unsigned char* out_ok, int* out_info, double* out_score, void* ws, size_t ws_bytes, hipStream_t s) {
+  ROMA_REQUIRE(model == RANSAC_HOMOGRAPHY || model == RANSAC_FUNDAMENTAL, "magsac: model must be 0 (homography) or 1 (fundamental)");
+  if (check_args("magsac", "confidence",
+                 kpts_a && kpts_b && seeds && out_model && out_mask && out_ok && out_info && out_score && ws, B, N, threshold,
+                 confidence, max_iters, ws_bytes, magsac_workspace_bytes(B, N)))
+    return -1;
+  ROMA_REQUIRE(lo_iters >= 0 && lo_iters <= MAGSAC_MAX_LO, "magsac: lo_iters must lie in [0, 64]");
+  return model == RANSAC_HOMOGRAPHY
+             ? magsac_run<Homography>(kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, lo_iters, out_model,
+                                      out_mask, out_ok, out_info, out_score, ws, s)
+             : magsac_run<Fundamental>(kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, lo_iters, out_model,
+                                       out_mask, out_ok, out_info, out_score, ws, s);
 }
 
 }  // namespace roma

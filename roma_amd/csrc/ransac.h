@@ -15,6 +15,7 @@
 //      model), ransac_refit_kernel (M::refit: a least-squares candidate), ransac_accept_kernel (re-score; the candidate is kept
 //      if its inlier count is not lower, else refinement stops).
 //   4. ransac_mask_kernel + ransac_finish_kernel: final mask, ok flag, M::finish (model in pixel terms, info row).
+// magsac_run (below) is the same pipeline with MAGSAC++ scoring and IRLS local optimisation (tools/magsac_ref.py).
 // Every flag and counter of the workspace is written with plain stores by one kernel and read by a later launch on the same
 // stream: no atomics and no hand-off inside a launch.  Results are bit-identical from run to run and independent of B.
 #pragma once
@@ -460,6 +461,339 @@ int ransac_run(const float* kpts_a, const float* kpts_b, const int* counts, cons
   hipLaunchKernelGGL(ransac_mask_kernel<M>, mgrid, dim3(256), 0, s, c.pts, N, c.st, out_mask);
   ROMA_LAUNCH_CHECK();
   hipLaunchKernelGGL(ransac_finish_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, out_model, out_ok, out_info);
+  ROMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ MAGSAC++
+// The same pipeline with MAGSAC++ scoring (Barath et al., CVPR 2020; nu = 4; tools/magsac_ref.py restates it): a model's score
+// is the sum over the pair's rows of the loss rho(V), V = r^2 k^2 / (2 tau^2) with r the model's pixel residual (M::residual2)
+// and tau the threshold; lower is better.  Sampling rounds, hypotheses and slots are those above (ransac_norm_kernel and
+// ransac_hyp_kernel are shared); what changes:
+//   magsac_score_kernel  one wave per hypothesis: compensated f32 sum of rho per slot (lane partials over rows i = lane mod 64
+//                        ascending, then a fixed butterfly), and the count r < tau for the adaptive iteration count
+//   magsac_select_kernel arg-min (ties: lowest (h, slot)); the running best changes only on a strictly smaller score
+//   lo_iters times magsac_refit_kernel (M::wrefit: IRLS step, weights w(V) of the current model) and magsac_accept_kernel (the
+//   candidate is kept only if its score is strictly lower - the gain measured paired, on the same rows - else LO stops); then
+//   the mask r < tau and magsac_finish_kernel.
+constexpr double MAGSAC_K2 = 13.276704135987625;      // 0.99 quantile of chi^2 with 4 DoF
+constexpr float MAGSAC_VK = 6.638352067993813f;       // k^2 / 2
+constexpr float MAGSAC_GK = 0.003611260617758621f;    // Gamma(3/2, V_k)
+constexpr float MAGSAC_RHO_MAX = 1.3015316073311316f; // gamma(5/2, V_k): the loss of an outlier and of a non-finite row
+constexpr float HALF_SQRT_PI = 0.886226925452758f;    // Gamma(3/2)
+
+// rho(V) = gamma(5/2, V) + V (Gamma(3/2, V) - Gamma(3/2, V_k)) and w(V) = Gamma(3/2, V) - Gamma(3/2, V_k) for V < V_k; (RHO_MAX, 0)
+// beyond and for NaN.  Gamma(3/2, V) = sqrt(pi) / 2 erfc(sqrt V) + sqrt(V) e^-V, gamma(3/2, V) = Gamma(3/2) - Gamma(3/2, V),
+// gamma(5/2, V) = 3/2 gamma(3/2, V) - V^{3/2} e^-V.
+__device__ __forceinline__ float magsac_rho(float V, float& w) {
+  if (!(V < MAGSAC_VK)) {
+    w = 0.f;
+    return MAGSAC_RHO_MAX;
+  }
+  const float s = sqrtf(V), se = s * expf(-V);
+  const float G = fmaf(HALF_SQRT_PI, erfcf(s), se);
+  const float g52 = fmaf(1.5f, HALF_SQRT_PI - G, -(V * se));
+  w = G - MAGSAC_GK;
+  return fmaf(V, w, g52);
+}
+
+struct MagState {               // per pair, next to PairState
+  float sa2, sb2;               // squared normalisation scales M::residual2 divides by
+  float vs;                     // k^2 / (2 tau^2): V = r^2 vs
+  float t2;                     // tau^2: inlier r^2 < t2
+  float score;                  // sum of rho of the running best of the sampling rounds (+inf: none yet)
+  float score_min;              // sum of rho of the winning minimal model
+  int lo_steps;                 // LO steps accepted
+  double gain;                  // what the accepted LO steps lowered the sum of rho by (magsac_accept_kernel)
+};
+
+template <class M>
+struct MagCarve {
+  Carve<M> c;                   // the RANSAC carve: pair states, points, slots (cnt: inlier counts per slot)
+  MagState* ms;
+  float* sc;                    // sum of rho per slot, +inf if unused [B * R * SLOTS]
+  size_t bytes;
+};
+
+template <class M>
+MagCarve<M> magsac_carve(void* ws, int B, int N) {
+  MagCarve<M> m;
+  m.c = carve<M>(ws, B, N);
+  char* p = static_cast<char*>(ws);
+  size_t o = m.c.bytes - 256;
+  m.ms = reinterpret_cast<MagState*>(p + o); o = align256(o + sizeof(MagState) * B);
+  m.sc = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * M::SLOTS * (size_t)B * R);
+  m.bytes = o + 256;
+  return m;
+}
+
+template <class M>
+size_t magsac_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? magsac_carve<M>(nullptr, B, N).bytes : 0; }
+
+// s + x with its rounding error added to the compensation c (Knuth's TwoSum: exact, whatever the order of s and x)
+__device__ __forceinline__ void two_sum(float& s, float& c, float x) {
+  const float t = s + x, bp = t - s;
+  c += (s - (t - bp)) + (x - bp);
+  s = t;
+}
+
+// the wave's total of the lanes' compensated sums (s, c): a fixed butterfly; both lanes of a pair compute the same
+// (sum, compensation), so every lane ends with the same value
+__device__ __forceinline__ float wave_total(float s, float c) {
+  for (int off = 32; off > 0; off >>= 1) {
+    const float so = __shfl_xor(s, off), co = __shfl_xor(c, off);
+    c = c + co;
+    two_sum(s, c, so);
+  }
+  return s + c;
+}
+
+// one wave: sum of rho of SL models (wave-uniform coefficients mf, the first nm used) over rows 0 .. n-1, and their inlier counts.
+// Compensated f32 sums (TwoSum): a plain f32 sum of thousands of rows resolves no change below ~1e-7 of the total, which is
+// larger than what a late IRLS step gains, and LO would stop on rounding.
+template <class M, int SL>
+__device__ __forceinline__ void magsac_sums(const float* mf, int nm, const float4* __restrict__ Pp, int n, const MagState& S,
+                                            int lane, float (&acc)[SL], int (&c)[SL]) {
+  const float sa2 = S.sa2, sb2 = S.sb2, vs = S.vs, t2 = S.t2;
+  float cmp[SL];
+#pragma unroll
+  for (int r = 0; r < SL; ++r) { acc[r] = 0.f; cmp[r] = 0.f; c[r] = 0; }
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    const int i = i0 + lane;
+    const bool row = i < n;
+    const float4 p = row ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
+#pragma unroll
+    for (int r = 0; r < SL; ++r) {
+      if (M::SCORE_EVERY_SLOT || r < nm) {
+        const float r2 = M::residual2(mf + 12 * r, p, sa2, sb2);
+        c[r] += __popcll(__ballot(r2 < t2));
+        float w;
+        const float rho = magsac_rho(r2 * vs, w);
+        two_sum(acc[r], cmp[r], row ? rho : 0.f);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < SL; ++r) acc[r] = wave_total(acc[r], cmp[r]);
+}
+
+// one thread per pair: residual scales, V scale, threshold
+template <class M>
+__global__ __launch_bounds__(64) void magsac_init_kernel(int B, float thr, const PairState<M>* __restrict__ st,
+                                                         MagState* __restrict__ ms) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  MagState& S = ms[b];
+  M::res_scales(st[b].nrm, S.sa2, S.sb2);
+  const double t2 = (double)thr * thr;
+  S.vs = (float)(MAGSAC_K2 / (2 * t2));
+  S.t2 = (float)t2;
+  S.score = INFINITY;
+  S.score_min = INFINITY;
+  S.lo_steps = 0;
+  S.gain = 0.0;
+}
+
+// one wave per (pair, hypothesis)
+template <class M>
+__global__ __launch_bounds__(256) void magsac_score_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
+                                                           const MagState* __restrict__ ms, Slots sl, float* __restrict__ sc) {
+  constexpr int SL = M::SLOTS;
+  const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = g / R;
+  const PairState<M>& P = st[b];
+  if (P.done) return;
+  const int nm = sl.n[g];
+  float acc[SL];
+  int c[SL];
+#pragma unroll
+  for (int r = 0; r < SL; ++r) { acc[r] = 0.f; c[r] = 0; }
+  if (nm > 0) magsac_sums<M, SL>(sl.f + (long)g * SL * 12, nm, pts + (long)b * N, P.n, ms[b], lane, acc, c);
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < SL; ++r) {
+      sc[(long)g * SL + r] = r < nm ? acc[r] : INFINITY;
+      sl.cnt[(long)g * SL + r] = r < nm ? c[r] : -1;
+    }
+  }
+}
+
+// one workgroup per pair: smallest score of the round (lowest slot on ties), running best, adaptive iteration count, done flag
+template <class M>
+__global__ __launch_bounds__(256) void magsac_select_kernel(PairState<M>* __restrict__ st, MagState* __restrict__ ms, int round,
+                                                            double conf, int max_iters, Slots sl, const float* __restrict__ sc) {
+  constexpr int SL = M::SLOTS;
+  __shared__ float ss[256];
+  __shared__ int si[256];
+  const int b = blockIdx.x, t = threadIdx.x;
+  PairState<M>& P = st[b];
+  if (P.done) return;
+  const float* s = sc + (long)b * R * SL;
+  float bs = INFINITY;
+  int bi = 0x7fffffff;
+  for (int k = t; k < R * SL; k += 256) {
+    const float v = s[k];
+    if (v < bs) { bs = v; bi = k; }  // k ascends: ties keep the lower slot
+  }
+  ss[t] = bs;
+  si[t] = bi;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) {
+      const float v = ss[t + w];
+      const int i = si[t + w];
+      if (v < ss[t] || (v == ss[t] && i < si[t])) { ss[t] = v; si[t] = i; }
+    }
+    __syncthreads();
+  }
+  if (t == 0) {
+    MagState& S = ms[b];
+    const float v = ss[0];
+    const int k = si[0];
+    if (v < S.score) {  // strictly: an earlier round's model keeps a tie
+      S.score = v;
+      S.score_min = v;
+      const int c = sl.cnt[(long)b * R * SL + k];
+      P.best = c;
+      P.best_min = c;
+      P.best_h = round * R + k / SL;
+      P.best_root = k % SL;
+      const double* m = sl.d + ((long)b * R * SL + k) * 9;
+      for (int q = 0; q < 9; ++q) P.cur[q] = m[q];
+      to_f32(P.cur, P.curf);
+      P.needed = update_num_iters(conf, (double)c / P.n, M::S, max_iters);
+    }
+    P.rounds = round + 1;
+    const long drawn = (long)(round + 1) * R;
+    P.done = drawn >= (long)min(max_iters, P.needed) ? 1 : 0;
+  }
+}
+
+// one workgroup per pair: an IRLS candidate from the MAGSAC++ weights of the current model (M::wrefit)
+template <class M>
+__global__ __launch_bounds__(256) void magsac_refit_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
+                                                           const float4* __restrict__ pts, int N, PairState<M>* __restrict__ st,
+                                                           const MagState* __restrict__ ms) {
+  const long o = (long)blockIdx.x * N;
+  M::wrefit(ka + o, kb + o, pts + o, st[blockIdx.x], ms[blockIdx.x]);
+}
+
+// one wave per pair: keep the candidate if its sum of rho is strictly lower than the current model's, else stop.  The gain
+// sum(rho_cur - rho_cand) is measured on the same rows in one pass, the candidate's residual terms as the current model's
+// plus those of the f32 difference (cand - cur): rounding the two models to f32 separately moves each sum by far more than a
+// late IRLS step gains (an inlier's residual is a small difference of O(1) normalised terms), and paired this way the shared
+// part of that error cancels.  The inlier count is the candidate's own (what the mask kernel evaluates).
+template <class M>
+__global__ __launch_bounds__(64) void magsac_accept_kernel(const float4* __restrict__ pts, int N, PairState<M>* __restrict__ st,
+                                                           MagState* __restrict__ ms) {
+  constexpr int NT = M::NT;
+  const int b = blockIdx.x, lane = threadIdx.x;
+  PairState<M>& P = st[b];
+  if (P.stop || !P.cand_ok) return;
+  MagState& S = ms[b];
+  float dm[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) dm[k] = (float)(P.cand[k] - P.cur[k]);
+  const float4* Pp = pts + (long)b * N;
+  const int n = P.n;
+  const float sa2 = S.sa2, sb2 = S.sb2, vs = S.vs, t2 = S.t2;
+  float g = 0.f, gc = 0.f;
+  int c = 0;
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    const int i = i0 + lane;
+    const bool row = i < n;
+    const float4 p = row ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
+    float tu[NT], td[NT], tc[NT];
+    M::res_terms(P.curf, p, tu);
+    M::res_terms(dm, p, td);
+#pragma unroll
+    for (int k = 0; k < NT; ++k) tc[k] = tu[k] + td[k];
+    float w;
+    const float ru = magsac_rho(M::r2_from(tu, sa2, sb2) * vs, w);
+    const float rc = magsac_rho(M::r2_from(tc, sa2, sb2) * vs, w);
+    two_sum(g, gc, row ? ru - rc : 0.f);
+    c += __popcll(__ballot(M::residual2(P.candf, p, sa2, sb2) < t2));
+  }
+  g = wave_total(g, gc);
+  if (lane == 0) {
+    if (g > 0.f) {
+      S.gain = S.gain + (double)g;
+      S.lo_steps = S.lo_steps + 1;
+      P.best = c;
+      for (int k = 0; k < 9; ++k) P.cur[k] = P.cand[k];
+      for (int k = 0; k < 12; ++k) P.curf[k] = P.candf[k];
+    } else {
+      P.stop = 1;
+    }
+    P.cand_ok = 0;
+  }
+}
+
+// mask[b, i] = r < tau under the current model (rows beyond counts[b], and pairs without inliers: 0); grid (ceil(N / 256), B)
+template <class M>
+__global__ __launch_bounds__(256) void magsac_mask_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
+                                                          const MagState* __restrict__ ms, unsigned char* __restrict__ mask) {
+  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const PairState<M>& P = st[b];
+  bool in = false;
+  if (P.best > 0 && i < P.n) {
+    const MagState& S = ms[b];
+    in = M::residual2(P.curf, pts[(long)b * N + i], S.sa2, S.sb2) < S.t2;
+  }
+  mask[(long)b * N + i] = in ? 1 : 0;
+}
+
+// one thread per pair: ok flag, M::finish (model, the first M::INFO entries of the info row), LO steps, scores (the final sum
+// of rho is the winning minimal model's less the gains of the accepted LO steps)
+template <class M>
+__global__ __launch_bounds__(64) void magsac_finish_kernel(int B, const PairState<M>* __restrict__ st, const MagState* __restrict__ ms,
+                                                           double* __restrict__ out, unsigned char* __restrict__ ok,
+                                                           int* __restrict__ info, double* __restrict__ score) {
+  const int b = blockIdx.x * 64 + threadIdx.x;
+  if (b >= B) return;
+  const PairState<M>& P = st[b];
+  const MagState& S = ms[b];
+  const bool good = P.valid && P.best > 0;
+  M::finish(P, good, out + (long)b * 9, info + (long)b * (M::INFO + 1));
+  info[(long)b * (M::INFO + 1) + M::INFO] = S.lo_steps;
+  const bool found = P.best_h >= 0;
+  score[2 * (long)b] = found ? (double)S.score_min : 0.0;
+  score[2 * (long)b + 1] = found ? (double)S.score_min - S.gain : 0.0;
+  ok[b] = good ? 1 : 0;
+}
+
+template <class M>
+int magsac_run(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B, int N, float thr,
+               double conf, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask, unsigned char* out_ok,
+               int* out_info, double* out_score, void* ws, hipStream_t s) {
+  const MagCarve<M> w = magsac_carve<M>(align_base<void*>(ws), B, N);
+  const Carve<M>& c = w.c;
+  const float2* ka = reinterpret_cast<const float2*>(kpts_a);
+  const float2* kb = reinterpret_cast<const float2*>(kpts_b);
+  hipLaunchKernelGGL(ransac_norm_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, counts, nullptr, N, thr, max_iters, c.st, c.pts);
+  ROMA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(magsac_init_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, thr, c.st, w.ms);
+  ROMA_LAUNCH_CHECK();
+  const int rounds = (max_iters + R - 1) / R;
+  for (int r = 0; r < rounds; ++r) {
+    hipLaunchKernelGGL(ransac_hyp_kernel<M>, dim3(B * R * M::HYP_LANES / M::HYP_THREADS), dim3(M::HYP_THREADS), 0, s, ka, kb, N,
+                       seeds, c.st, r, c.sl);
+    ROMA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(magsac_score_kernel<M>, dim3(B * R / 4), dim3(256), 0, s, c.pts, N, c.st, w.ms, c.sl, w.sc);
+    ROMA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(magsac_select_kernel<M>, dim3(B), dim3(256), 0, s, c.st, w.ms, r, conf, max_iters, c.sl, w.sc);
+    ROMA_LAUNCH_CHECK();
+  }
+  for (int it = 0; it < lo_iters; ++it) {
+    hipLaunchKernelGGL(magsac_refit_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, c.pts, N, c.st, w.ms);
+    ROMA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(magsac_accept_kernel<M>, dim3(B), dim3(64), 0, s, c.pts, N, c.st, w.ms);
+    ROMA_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(magsac_mask_kernel<M>, dim3((N + 255) / 256, B), dim3(256), 0, s, c.pts, N, c.st, w.ms, out_mask);
+  ROMA_LAUNCH_CHECK();
+  hipLaunchKernelGGL(magsac_finish_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, w.ms, out_model, out_ok, out_info,
+                     out_score);
   ROMA_LAUNCH_CHECK();
   return 0;
 }

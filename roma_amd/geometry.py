@@ -3,8 +3,10 @@ OpenCV - cv2.findHomography(..., cv2.RANSAC) (benchmarks/hpatches_sequences_homo
 cv2.findFundamentalMat(..., cv2.FM_RANSAC) (demo/demo_fundamental.py) - batched over pairs, in HIP (csrc/geometry.hip).
 
 Plain RANSAC with OpenCV's adaptive iteration count, followed (refine=True) by up to three least-squares refits on the inliers
-(local optimisation).  OpenCV's USAC_MAGSAC scoring, which demo_fundamental uses, is not restated: plain RANSAC + LO stands in
-for it, and there is no Levenberg-Marquardt polish.  The algorithm is restated in numpy float64 by tools/geometry_ref.py.
+(local optimisation), and no Levenberg-Marquardt polish.  The algorithm is restated in numpy float64 by tools/geometry_ref.py.
+method="magsac" (`magsac`, `roma_op_magsac`) keeps the sampling and scores each model by the MAGSAC++ loss (Barath et al.,
+CVPR 2020, nu = 4) instead of its inlier count, then runs IRLS steps with the MAGSAC++ weights - what demo_fundamental asks
+OpenCV for with USAC_MAGSAC, as the paper defines it (not OpenCV's implementation); restated by tools/magsac_ref.py.
 
 Both models map A to B in pixel coordinates: x_B ~ H x_A and x_B^T F x_A = 0, like OpenCV's (points1 = A, points2 = B).  H and F
 are scaled so that [2, 2] = 1 (unit Frobenius norm where |[2, 2]| < 1e-12 of it); F has rank 2.
@@ -90,14 +92,16 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _robust(op, a, s, ninfo, seed, counts, head, tail):
-    """what ransac() and essential() share after their own checks: zeroed outputs (M [B, 3, 3] float64, mask [B, N] bool,
-    ok [B] bool, info [B, ninfo] int32), counts and seeds on the device, then roma_op_<op>(*head(counts, seeds), B, N, *tail,
-    outputs, workspace, stream) with the tensors of head passed as pointers.  Nothing is launched for B == 0 or N < s, where no
-    pair can hold a minimal sample."""
+def _robust(op, a, s, ninfo, seed, counts, head, tail, nscore=0):
+    """what ransac(), magsac() and essential() share after their own checks: zeroed outputs (M [B, 3, 3] float64, mask [B, N]
+    bool, ok [B] bool, info [B, ninfo] int32, and score [B, nscore] float64 if nscore), counts and seeds on the device, then
+    roma_op_<op>(*head(counts, seeds), B, N, *tail, outputs, workspace, stream) with the tensors of head passed as pointers.
+    Nothing is launched for B == 0 or N < s, where no pair can hold a minimal sample."""
     B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
     outs = (torch.zeros((B, 3, 3), device=dev, dtype=torch.float64), torch.zeros((B, N), device=dev, dtype=torch.bool),
             torch.zeros((B,), device=dev, dtype=torch.bool), torch.zeros((B, ninfo), device=dev, dtype=torch.int32))
+    if nscore:
+        outs = outs + (torch.zeros((B, nscore), device=dev, dtype=torch.float64),)
     if B == 0:
         return outs
     counts, seeds = _counts(counts, B, dev), _seeds(seed, B, dev)
@@ -129,6 +133,42 @@ def ransac(model: int, kpts_A: torch.Tensor, kpts_B: torch.Tensor, threshold: fl
                    (float(threshold), float(confidence), int(max_iters), 1 if refine else 0))
 
 
+MAGSAC_MAX_LO = 64  # csrc/geometry.h
+
+
+def magsac(model: int, kpts_A: torch.Tensor, kpts_B: torch.Tensor, threshold: float, confidence: float, max_iters: int,
+           seed=None, lo_iters: int = 10, counts=None):
+    """Batched robust estimation with MAGSAC++ scoring (roma_op_magsac; Barath et al., CVPR 2020, nu = 4, as restated in
+    tools/magsac_ref.py - not OpenCV's USAC_MAGSAC implementation), no host synchronisation.  The sampling of `ransac` (same
+    samples, minimal solvers and adaptive iteration count), but each model is scored by the sum over the pair's rows of the
+    MAGSAC++ loss of its pixel residual (H: reprojection error in image B; F: Sampson distance) and the smallest score wins; then
+    up to lo_iters IRLS steps with the MAGSAC++ weights, each kept only if the score drops.  threshold is the largest residual
+    that counts as an inlier (sigma_max = threshold / sqrt(13.2767), the 0.99 quantile of chi^2 with 4 DoF).
+
+    Inputs as for `ransac`.  Returns (M [B, 3, 3] float64, mask [B, N] bool (residual < threshold), ok [B] bool,
+    info [B, 7] int32, score [B, 2] float64) with info = (rounds run, winning hypothesis, its root, inliers of the winning minimal
+    model, final inliers, pair valid, LO steps accepted) and score = (loss of the winning minimal model, final loss: that less the gains of the accepted LO steps)."""
+    a, b = _pair_batch(kpts_A, kpts_B)
+    if model not in SAMPLE_SIZE:
+        raise ValueError(f"roma_amd.geometry: unknown model {model}")
+    if not (threshold > 0) or not (0 <= confidence <= 1) or int(max_iters) <= 0:
+        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= confidence <= 1, max_iters > 0")
+    if not (0 <= int(lo_iters) <= MAGSAC_MAX_LO):
+        raise ValueError(f"roma_amd.geometry: lo_iters must lie in [0, {MAGSAC_MAX_LO}]")
+    return _robust("magsac", a, SAMPLE_SIZE[model], 7, seed, counts,
+                   lambda counts, seeds: (int(model), a, b, counts, seeds),
+                   (float(threshold), float(confidence), int(max_iters), int(lo_iters)), nscore=2)
+
+
+def _estimate(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, refine, counts, method):
+    """(M, mask, ok) of `ransac` (method "ransac") or `magsac` (method "magsac"; refine=False means lo_iters=0)"""
+    if method == "ransac":
+        return ransac(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, refine, counts)[:3]
+    if method == "magsac":
+        return magsac(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, 10 if refine else 0, counts)[:3]
+    raise ValueError(f"roma_amd.geometry: method must be 'ransac' or 'magsac', got {method!r}")
+
+
 def _front(kpts_A, outs, ok, none):
     """what the public functions return: for a batch outs + (ok,); for a single pair ([N, 2] kpts) the first entry of each of
     outs, or `none` when no model was found - the one host synchronisation of the single-pair forms (OpenCV returns None)"""
@@ -138,24 +178,29 @@ def _front(kpts_A, outs, ok, none):
 
 
 def find_homography(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.995, max_iters=2000, seed=None, refine=True,
-                    counts=None):
+                    counts=None, method="ransac"):
     """cv2.findHomography(kpts_A, kpts_B, cv2.RANSAC, ransac_reproj_threshold, maxIters=max_iters, confidence=confidence) on the
     device: 4-point DLT hypotheses (OpenCV's checkSubset), inliers |H x_A - x_B| < threshold in image B.
+    method="magsac": the same sampling with MAGSAC++ scoring and IRLS local optimisation (`magsac`; refine=False: lo_iters=0).
 
     kpts_A, kpts_B: [N, 2] -> (H [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
     [B, N, 2] -> (H [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
-    M, mask, ok, _ = ransac(HOMOGRAPHY, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts)
+    M, mask, ok = _estimate(HOMOGRAPHY, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts,
+                            method)
     return _front(kpts_A, (M, mask), ok, (None, None))
 
 
 def find_fundamental(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.99, max_iters=1000, seed=None, refine=True,
-                     counts=None):
+                     counts=None, method="ransac"):
     """cv2.findFundamentalMat(kpts_A, kpts_B, cv2.FM_RANSAC, ransac_reproj_threshold, confidence, max_iters) on the device:
     7-point hypotheses (up to 3 models each), inliers whose distances to both epipolar lines are below the threshold.
+    method="magsac": the same sampling with MAGSAC++ scoring of the Sampson distance and IRLS local optimisation (`magsac`;
+    refine=False: lo_iters=0) - what demo_fundamental's cv2.USAC_MAGSAC call asks for, as MAGSAC++ is defined in the paper.
 
     kpts_A, kpts_B: [N, 2] -> (F [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
     [B, N, 2] -> (F [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
-    M, mask, ok, _ = ransac(FUNDAMENTAL, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts)
+    M, mask, ok = _estimate(FUNDAMENTAL, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts,
+                            method)
     return _front(kpts_A, (M, mask), ok, (None, None))
 
 

@@ -5,10 +5,12 @@
   * find_homography at B = 8, N = 5 000 with the HPatches benchmark's settings (threshold 3 min(w, h) / 480 at 864^2,
     confidence 0.99999, OpenCV's default 2 000 iterations), 0.5 px noise and 30 % outliers.
 
-Per configuration one JSON line: ms per batched call (device events, after warm-up), model-point evaluations per second (the
-hypotheses the score kernel ran x models per hypothesis x points), rounds executed per pair, and the same work through
-tools/geometry_ref.py on the host (numpy f64, one pair after the other) - a CPU number, for scale only.
-Usage: python tools/bench_geometry.py [--iters 20] [--no-cpu]
+Each configuration runs twice at the same settings: plain RANSAC + LO (`ransac`, the default of find_*) and MAGSAC++ scoring
+with IRLS local optimisation (`magsac`, method="magsac").  Per leg one JSON line: ms per batched call (device events, after
+warm-up), model-point evaluations per second (the hypotheses the score kernel ran x models per hypothesis x points), rounds
+executed per pair, and the same work through tools/geometry_ref.py / tools/magsac_ref.py on the host (numpy f64, one pair after
+the other) - a CPU number, for scale only.
+Usage: python tools/bench_geometry.py [--iters 20] [--no-cpu] [--method ransac|magsac|both]
 """
 import argparse
 import json
@@ -23,6 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import geometry_ref as gr  # noqa: E402
+import magsac_ref as mr  # noqa: E402
 from accuracy_harness import synthetic_relief_pair  # noqa: E402
 
 
@@ -54,33 +57,40 @@ def homography_batch(B, N, outlier_frac, seed=0, size=864):
     return a, b
 
 
-def run(name, model, a, b, thr, conf, max_iters, iters, cpu):
-    from roma_amd.geometry import ransac
+def run(name, model, a, b, thr, conf, max_iters, iters, cpu, method="ransac"):
+    from roma_amd.geometry import magsac, ransac
     da = torch.tensor(a, dtype=torch.float32, device="cuda:0")
     db = torch.tensor(b, dtype=torch.float32, device="cuda:0")
     seeds = torch.arange(len(a), dtype=torch.int64) + 1
+    fn = ransac if method == "ransac" else magsac
+
+    def call():
+        return fn(model, da, db, thr, conf, max_iters, seed=seeds)[:4]
     for _ in range(3):
-        M, mask, ok, info = ransac(model, da, db, thr, conf, max_iters, seed=seeds)
+        M, mask, ok, info = call()
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(iters):
-        M, mask, ok, info = ransac(model, da, db, thr, conf, max_iters, seed=seeds)
+        M, mask, ok, info = call()
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / iters
     info = info.cpu().numpy()
     roots = gr.MAX_ROOTS if model == gr.FUNDAMENTAL else 1
     evals = float(info[:, 0].sum()) * gr.ROUND * roots * a.shape[1]
-    res = {"config": name, "B": int(a.shape[0]), "N": int(a.shape[1]), "threshold": thr, "confidence": conf, "max_iters": max_iters,
+    res = {"config": name, "method": method, "B": int(a.shape[0]), "N": int(a.shape[1]), "threshold": thr, "confidence": conf, "max_iters": max_iters,
            "ms_per_call": round(ms, 4), "model_point_evals_per_s": evals / (ms * 1e-3), "rounds_per_pair": info[:, 0].tolist(),
            "inliers_per_pair": info[:, 4].tolist(), "ok": ok.cpu().tolist()}
     if cpu:
         t = time.perf_counter()
         rounds = []
         for i in range(len(a)):
-            r = gr.ransac(model, a[i].astype(np.float32).astype(np.float64), b[i].astype(np.float32).astype(np.float64), thr, conf,
-                          max_iters, i + 1, True)
+            pa, pb = a[i].astype(np.float32).astype(np.float64), b[i].astype(np.float32).astype(np.float64)
+            if method == "ransac":
+                r = gr.ransac(model, pa, pb, thr, conf, max_iters, i + 1, True)
+            else:
+                r = mr.magsac(model, pa, pb, thr, conf, max_iters, i + 1)
             rounds.append(r["rounds"])
         res["cpu_numpy_reference_ms_per_call"] = round((time.perf_counter() - t) * 1e3, 1)
         res["cpu_reference_rounds_per_pair"] = rounds
@@ -92,15 +102,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true", help="skip the host reference timing")
+    ap.add_argument("--method", choices=("ransac", "magsac", "both"), default="both")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_geometry.py measures the device path: it needs a GPU"
+    methods = ("ransac", "magsac") if args.method == "both" else (args.method,)
     B = 8
     for frac in (0.0, 0.3):
         a, b = relief_batch(B, 10000, frac)
-        run(f"find_fundamental demo_fundamental outliers={frac}", gr.FUNDAMENTAL, a, b, 0.2, 0.999999, 10000, args.iters,
-            not args.no_cpu)
+        for m in methods:
+            run(f"find_fundamental demo_fundamental outliers={frac}", gr.FUNDAMENTAL, a, b, 0.2, 0.999999, 10000, args.iters,
+                not args.no_cpu, m)
     a, b = homography_batch(B, 5000, 0.3)
-    run("find_homography hpatches outliers=0.3", gr.HOMOGRAPHY, a, b, 3 * 864 / 480, 0.99999, 2000, args.iters, not args.no_cpu)
+    for m in methods:
+        run("find_homography hpatches outliers=0.3", gr.HOMOGRAPHY, a, b, 3 * 864 / 480, 0.99999, 2000, args.iters, not args.no_cpu,
+            m)
 
 
 if __name__ == "__main__":
