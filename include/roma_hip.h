@@ -380,6 +380,26 @@ long roma_op_refine_pose_workspace(int B, int N);
 int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
                         const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
                         unsigned char* out_mask, int* out_info, void* workspace, long workspace_bytes, void* stream);
+/* Nonlinear refinement of a homography (model 0) or a fundamental matrix (model 1): a Levenberg-Marquardt fit under the
+ * hard-truncated loss sum min(|r|^2, thr^2) of the forward reprojection error in image B (H: what cv2.findHomography(..., RANSAC)
+ * ends with) or of the Sampson distance (F: what PoseLib's estimate_fundamental ends with); it follows roma_op_ransac /
+ * roma_op_magsac, whose last step is an algebraic least-squares refit.  Algorithm restated in tools/model_refine_ref.py: the fit
+ * runs in the Hartley-normalised coordinates of the pair's finite rows with residuals in pixels; H keeps its largest entry fixed
+ * and updates the other eight, F = U diag(1, sigma, 0) V^T is updated on (U, V, sigma) and has rank 2 at every iterate; the loop
+ * (lambda, retries, stopping rules) is roma_op_refine_pose's, with at least 4 (H) or 7 (F) active rows.  The active set is
+ * re-evaluated with every cost, not frozen to a RANSAC mask.  M DEVICE f64 [B, 3, 3] in pixel coordinates (x_B ~ H x_A,
+ * x_B^T F x_A = 0); kpts_a, kpts_b DEVICE f32 [B, N, 2] pixels; counts as for roma_op_ransac; valid DEVICE u8 [B] or NULL (every
+ * pair): pairs to fit, the others are copied through; thr > 0 in pixels (inf: plain least squares over the finite rows).
+ * Outputs, all DEVICE: M f64 [B, 3, 3] (scaled like roma_op_ransac's; the input bits when no step was accepted), mask u8 [B, N]
+ * (|r|^2 < thr^2 under the returned model; zeros for a pair that is not fitted), info int32 [B, 4] = {accepted steps, cost
+ * evaluations, active rows at the end, pair fitted}, cost f64 [B, 2] = {truncated cost at the start, at the end} in px^2 (NaN
+ * for a pair that is not fitted).  One workgroup per pair runs the whole loop in one launch: no host synchronisation,
+ * bit-identical from run to run and independent of B.  B == 0 launches nothing.  workspace: device memory of
+ * roma_op_refine_model_workspace(B, N) bytes. */
+long roma_op_refine_model_workspace(int B, int N);
+int roma_op_refine_model(int model, const double* M, const float* kpts_a, const float* kpts_b, const int* counts,
+                         const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_m, unsigned char* out_mask,
+                         int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream);
 /* ---- Tiny RoMa (romatch/models/tiny.py), matcher side; the XFeat backbone is the caller's (model_zoo/__init__.py:24-27).
  * All tensors f32, channels-last unless noted.  corr_volume (tiny.py:182-196) = roma_op_gemm with A = feats of image B
  * [H1*W1, C], W = feats of image A [H0*W0, C], alpha = 1/sqrt(C), batch = pairs: cv [B, H1*W1, H0*W0]. */

@@ -22,6 +22,7 @@
 #include "vit.h"
 #include "sampling.h"
 #include "essential.h"
+#include "model_refine.h"
 #include "pose_refine.h"
 #include "geometry.h"
 
@@ -567,6 +568,14 @@ int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, c
                         unsigned char* out_mask, int* out_info, void* workspace, long workspace_bytes, void* stream) {
   return refine_pose_launch(R, t, kpts_a, kpts_b, counts, valid, B, N, thr, max_steps, out_r, out_t, out_mask, out_info, workspace,
                             (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+// ---- homography / fundamental-matrix refinement (model_refine.hip)
+long roma_op_refine_model_workspace(int B, int N) { return (long)refine_model_workspace_bytes(B, N); }
+int roma_op_refine_model(int model, const double* M, const float* kpts_a, const float* kpts_b, const int* counts,
+                         const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_m, unsigned char* out_mask,
+                         int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream) {
+  return refine_model_launch(model, M, kpts_a, kpts_b, counts, valid, B, N, thr, max_steps, out_m, out_mask, out_info, out_cost,
+                             workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
 }
 // ---- Tiny RoMa matcher side (tiny.hip)
 int roma_op_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, void* stream) {

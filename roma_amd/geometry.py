@@ -3,7 +3,9 @@ OpenCV - cv2.findHomography(..., cv2.RANSAC) (benchmarks/hpatches_sequences_homo
 cv2.findFundamentalMat(..., cv2.FM_RANSAC) (demo/demo_fundamental.py) - batched over pairs, in HIP (csrc/geometry.hip).
 
 Plain RANSAC with OpenCV's adaptive iteration count, followed (refine=True) by up to three least-squares refits on the inliers
-(local optimisation), and no Levenberg-Marquardt polish.  The algorithm is restated in numpy float64 by tools/geometry_ref.py.
+(local optimisation).  The algorithm is restated in numpy float64 by tools/geometry_ref.py.  lm_steps > 0 (default 0) adds what
+OpenCV and PoseLib end with, a Levenberg-Marquardt fit of the geometric error over the rows inside the threshold
+(`refine_homography` / `refine_fundamental`, `roma_op_refine_model`, csrc/model_refine.hip; restated by tools/model_refine_ref.py).
 method="magsac" (`magsac`, `roma_op_magsac`) keeps the sampling and scores each model by the MAGSAC++ loss (Barath et al.,
 CVPR 2020, nu = 4) instead of its inlier count, then runs IRLS steps with the MAGSAC++ weights - what demo_fundamental asks
 OpenCV for with USAC_MAGSAC, as the paper defines it (not OpenCV's implementation); restated by tools/magsac_ref.py.
@@ -169,6 +171,79 @@ def _estimate(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, ref
     raise ValueError(f"roma_amd.geometry: method must be 'ransac' or 'magsac', got {method!r}")
 
 
+MODEL_MIN_ROWS = {HOMOGRAPHY: 4, FUNDAMENTAL: 7}  # csrc/model_refine.hip: rows below which nothing is fitted
+
+
+def _refine_model(model, M, kpts_A, kpts_B, threshold, max_steps, counts, valid, name):
+    """roma_op_refine_model on [B, N, 2] pixels: (M [B, 3, 3] float64, mask [B, N] bool, info [B, 4] int32, cost [B, 2] float64).
+    Nothing is launched for B == 0 or fewer rows than the model needs: every pair comes back untouched."""
+    a, b = _pair_batch(kpts_A, kpts_B)
+    B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
+    M = _pose_tensor(M, name, B, (3, 3), dev)
+    if not (threshold > 0) or int(max_steps) < 0:
+        raise ValueError("roma_amd.geometry: need threshold > 0, max_steps >= 0")
+    counts = _counts(counts, B, dev)
+    if valid is not None:
+        valid = torch.as_tensor(valid).to(device=dev).reshape(-1).to(torch.uint8).contiguous()
+        if valid.shape[0] != B:
+            raise ValueError(f"roma_amd.geometry: valid has {valid.shape[0]} entries for {B} pairs")
+    mask = torch.zeros((B, N), device=dev, dtype=torch.bool)
+    info = torch.zeros((B, 4), device=dev, dtype=torch.int32)
+    cost = torch.full((B, 2), float("nan"), device=dev, dtype=torch.float64)
+    if B == 0 or N < MODEL_MIN_ROWS[model]:
+        return M.clone(), mask, info, cost
+    out = torch.empty_like(M)
+    lib = _lib.load()
+    nws = int(lib.roma_op_refine_model_workspace(B, N))
+    ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
+    with torch.cuda.device(dev):
+        _lib.check(lib.roma_op_refine_model(int(model), _ptr(M), _ptr(a), _ptr(b), _ptr(counts), _ptr(valid), B, N, float(threshold),
+                                            int(max_steps), _ptr(out), _ptr(mask), _ptr(info), _ptr(cost), _ptr(ws), nws,
+                                            _stream(dev)))
+    return out, mask, info, cost
+
+
+def _refine_front(model, M, kpts_A, kpts_B, threshold, max_steps, counts, valid, name):
+    out = _refine_model(model, M, kpts_A, kpts_B, threshold, max_steps, counts, valid, name)
+    return tuple(o[0] for o in out) if isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2 else out
+
+
+def refine_homography(H, kpts_A, kpts_B, threshold, max_steps=25, counts=None, valid=None):
+    """Nonlinear refinement of a homography on the device (roma_op_refine_model, csrc/model_refine.hip): a Levenberg-Marquardt
+    fit of H to the forward reprojection error |H x_A - x_B| in image B under the truncated loss sum min(|e|^2, threshold^2) -
+    the cost cv2.findHomography(..., cv2.RANSAC) ends with; restated in numpy float64 by tools/model_refine_ref.py.  The rows
+    inside the threshold are re-evaluated with every cost (OpenCV freezes them to the RANSAC mask).  The fit runs in the
+    Hartley-normalised coordinates of the pair; the largest entry of the normalised start is held fixed.  At most max_steps
+    accepted steps; a fit that cannot move (fewer than 4 rows inside the threshold, a singular system) returns its input, so
+    the truncated cost never rises and a model is never lost.  threshold in pixels; inf means plain least squares.
+
+    H [3, 3] with kpts [N, 2] -> (H [3, 3] float64, mask [N] bool, info [4] int32, cost [2] float64);
+    H [B, 3, 3] with kpts [B, N, 2] -> (H [B, 3, 3], mask [B, N], info [B, 4], cost [B, 2]).  No host synchronisation in either
+    form.  H is scaled like find_homography's; mask: rows whose error is below threshold under the returned H;
+    info = (accepted steps, cost evaluations, active rows at the end, pair fitted); cost = truncated cost in px^2 at (start,
+    end), NaN where nothing was fitted.  valid [B] bool marks the pairs to fit; the others, and pairs of fewer than 4 rows,
+    come back untouched with an empty mask and info[3] = 0.  See `ransac` for counts."""
+    return _refine_front(HOMOGRAPHY, H, kpts_A, kpts_B, threshold, max_steps, counts, valid, "H")
+
+
+def refine_fundamental(F, kpts_A, kpts_B, threshold, max_steps=25, counts=None, valid=None):
+    """Nonlinear refinement of a fundamental matrix on the device (roma_op_refine_model): a Levenberg-Marquardt fit of F to the
+    Sampson distance in pixels under the truncated loss sum min(r^2, threshold^2) - the cost PoseLib's estimate_fundamental ends
+    with; restated by tools/model_refine_ref.py.  F = U diag(1, sigma, 0) V^T is updated on the rotations U, V and on sigma
+    (seven parameters), so it has rank 2 at every iterate; a start of full rank is projected first.  Needs 7 rows inside the
+    threshold.  Arguments and returns as `refine_homography`."""
+    return _refine_front(FUNDAMENTAL, F, kpts_A, kpts_B, threshold, max_steps, counts, valid, "F")
+
+
+def _polished(model, M, mask, ok, kpts_A, kpts_B, threshold, lm_steps, counts):
+    """the lm_steps > 0 tail of find_*: pairs without a model are passed as not valid and keep what they had"""
+    if int(lm_steps) < 0:
+        raise ValueError("roma_amd.geometry: lm_steps must not be negative")
+    if int(lm_steps) == 0:
+        return M, mask
+    return _refine_model(model, M, kpts_A, kpts_B, threshold, lm_steps, counts, ok, "model")[:2]
+
+
 def _front(kpts_A, outs, ok, none):
     """what the public functions return: for a batch outs + (ok,); for a single pair ([N, 2] kpts) the first entry of each of
     outs, or `none` when no model was found - the one host synchronisation of the single-pair forms (OpenCV returns None)"""
@@ -178,29 +253,37 @@ def _front(kpts_A, outs, ok, none):
 
 
 def find_homography(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.995, max_iters=2000, seed=None, refine=True,
-                    counts=None, method="ransac"):
+                    counts=None, method="ransac", lm_steps=0):
     """cv2.findHomography(kpts_A, kpts_B, cv2.RANSAC, ransac_reproj_threshold, maxIters=max_iters, confidence=confidence) on the
     device: 4-point DLT hypotheses (OpenCV's checkSubset), inliers |H x_A - x_B| < threshold in image B.
     method="magsac": the same sampling with MAGSAC++ scoring and IRLS local optimisation (`magsac`; refine=False: lo_iters=0).
+    lm_steps > 0: the model found, by either method, then goes through `refine_homography` (the call's threshold, at most
+    lm_steps accepted steps; pairs without a model are left alone) - the Levenberg-Marquardt fit OpenCV ends with - and mask
+    is the refinement's.  The default 0 leaves every output as it was before the keyword existed.
 
     kpts_A, kpts_B: [N, 2] -> (H [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
     [B, N, 2] -> (H [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
     M, mask, ok = _estimate(HOMOGRAPHY, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts,
                             method)
+    M, mask = _polished(HOMOGRAPHY, M, mask, ok, kpts_A, kpts_B, ransac_reproj_threshold, lm_steps, counts)
     return _front(kpts_A, (M, mask), ok, (None, None))
 
 
 def find_fundamental(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.99, max_iters=1000, seed=None, refine=True,
-                     counts=None, method="ransac"):
+                     counts=None, method="ransac", lm_steps=0):
     """cv2.findFundamentalMat(kpts_A, kpts_B, cv2.FM_RANSAC, ransac_reproj_threshold, confidence, max_iters) on the device:
     7-point hypotheses (up to 3 models each), inliers whose distances to both epipolar lines are below the threshold.
     method="magsac": the same sampling with MAGSAC++ scoring of the Sampson distance and IRLS local optimisation (`magsac`;
     refine=False: lo_iters=0) - what demo_fundamental's cv2.USAC_MAGSAC call asks for, as MAGSAC++ is defined in the paper.
+    lm_steps > 0: the model found, by either method, then goes through `refine_fundamental` (the call's threshold on the Sampson
+    distance, at most lm_steps accepted steps; pairs without a model are left alone) and mask is the refinement's.  The default
+    0 leaves every output as it was before the keyword existed.
 
     kpts_A, kpts_B: [N, 2] -> (F [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
     [B, N, 2] -> (F [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
     M, mask, ok = _estimate(FUNDAMENTAL, kpts_A, kpts_B, ransac_reproj_threshold, confidence, max_iters, seed, refine, counts,
                             method)
+    M, mask = _polished(FUNDAMENTAL, M, mask, ok, kpts_A, kpts_B, ransac_reproj_threshold, lm_steps, counts)
     return _front(kpts_A, (M, mask), ok, (None, None))
 
 

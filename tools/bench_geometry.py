@@ -10,9 +10,18 @@ with IRLS local optimisation (`magsac`, method="magsac").  Per leg one JSON line
 warm-up), model-point evaluations per second (the hypotheses the score kernel ran x models per hypothesis x points), rounds
 executed per pair, and the same work through tools/geometry_ref.py / tools/magsac_ref.py on the host (numpy f64, one pair after
 the other) - a CPU number, for scale only.
+--lm measures the Levenberg-Marquardt refinement (csrc/model_refine.hip) instead: the HPatches homography call (B = 8,
+N = 5 000, 0.5 px noise) and demo_fundamental's call (B = 8, N = 10 000, 0.1 px noise) at 0 % and 30 % outliers, the default
+call against the same call with lm_steps=10 in one process, timed alternately in rounds, medians over the rounds; one JSON
+line per configuration with the added time, refine_* alone and the fit's counters.  --parent-lib DIR (a directory holding another
+build of libroma_hip.so, e.g. the parent commit's) adds that build's default call to the same alternation, to show that the
+default path did not move.
 Usage: python tools/bench_geometry.py [--iters 20] [--no-cpu] [--method ransac|magsac|both]
+       python tools/bench_geometry.py --lm [--iters 20] [--rounds 7] [--parent-lib DIR]
 """
 import argparse
+import contextlib
+import ctypes
 import json
 import os
 import sys
@@ -29,7 +38,7 @@ import magsac_ref as mr  # noqa: E402
 from accuracy_harness import synthetic_relief_pair  # noqa: E402
 
 
-def relief_batch(B, N, outlier_frac, seed=0, h=480, w=640):
+def relief_batch(B, N, outlier_frac, seed=0, h=480, w=640, noise=0.0):
     a, b = np.zeros((B, N, 2)), np.zeros((B, N, 2))
     for i in range(B):
         d = synthetic_relief_pair(h, w, seed=seed + i)
@@ -41,6 +50,8 @@ def relief_batch(B, N, outlier_frac, seed=0, h=480, w=640):
         b[i] = np.stack([(m[sel, 2] + 1) * w / 2, (m[sel, 3] + 1) * h / 2], 1)
         out = rng.random(N) < outlier_frac
         b[i, out] = rng.uniform([0, 0], [w, h], (out.sum(), 2))
+        if noise:  # drawn last: the noise-free batches are what they were
+            b[i] += noise * rng.normal(size=(N, 2))
     return a, b
 
 
@@ -98,13 +109,109 @@ def run(name, model, a, b, thr, conf, max_iters, iters, cpu, method="ransac"):
     return res
 
 
+def _timed(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters, out
+
+
+def _other_build(directory):
+    """another build of libroma_hip.so, bound with the signatures it has"""
+    from roma_amd import _lib
+    lib = ctypes.CDLL(os.path.join(directory, "libroma_hip.so"))
+    for name, (res, args) in _lib.SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, args
+    lib.h16 = "bf16"
+    return lib
+
+
+@contextlib.contextmanager
+def _using(lib):
+    """roma_amd's calls go to `lib` inside the block (None: the in-tree build)"""
+    from roma_amd import _lib
+    mine = _lib.load()
+    if lib is not None:
+        _lib._libs["bf16"] = lib
+    try:
+        yield
+    finally:
+        _lib._libs["bf16"] = mine
+
+
+def _stats(ms):
+    return {"median": round(float(np.median(ms)), 4), "min": round(float(np.min(ms)), 4), "max": round(float(np.max(ms)), 4)}
+
+
+def run_lm(name, model, a, b, thr, conf, max_iters, iters, rounds, parent, lm_steps=10):
+    """default call, the same call with lm_steps, and the parent build's default call if given: timed alternately"""
+    from roma_amd.geometry import find_fundamental, find_homography, refine_fundamental, refine_homography
+    find, fit = (find_homography, refine_homography) if model == gr.HOMOGRAPHY else (find_fundamental, refine_fundamental)
+    da = torch.tensor(a, dtype=torch.float32, device="cuda:0")
+    db = torch.tensor(b, dtype=torch.float32, device="cuda:0")
+    seeds = torch.arange(len(a), dtype=torch.int64) + 1
+    plain = lambda: find(da, db, thr, conf, max_iters, seed=seeds)  # noqa: E731
+    fitted = lambda: find(da, db, thr, conf, max_iters, seed=seeds, lm_steps=lm_steps)  # noqa: E731
+    legs = {"this ms": (None, plain), f"this lm_steps={lm_steps} ms": (None, fitted)}
+    if parent is not None:
+        legs = {"parent ms": (parent, plain), **legs}
+    for lib, fn in legs.values():
+        with _using(lib):
+            for _ in range(3):
+                fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, (lib, fn) in legs.items():
+            with _using(lib):
+                ms[k].append(_timed(fn, iters)[0])
+    M, mask, ok = plain()
+    ms_fit, (M1, _, info, cost) = _timed(lambda: fit(M, da, db, thr, max_steps=lm_steps, valid=ok), iters)
+    if parent is not None:
+        with _using(parent):
+            same = all(torch.equal(x, y) for x, y in zip(plain(), (M, mask, ok)))
+    info, cost = info.cpu().numpy(), cost.cpu().numpy()
+    res = {"config": name, "B": int(a.shape[0]), "N": int(a.shape[1]), "threshold": thr, "lm_steps": lm_steps, "rounds": rounds,
+           "iters_per_round": iters, **{k: _stats(v) for k, v in ms.items()},
+           "added by lm ms": round(float(np.median(ms[f"this lm_steps={lm_steps} ms"]) - np.median(ms["this ms"])), 4),
+           "refine alone ms": round(ms_fit, 4), "steps_per_pair": info[:, 0].tolist(), "cost_evals_per_pair": info[:, 1].tolist(),
+           "active_rows_per_pair": info[:, 2].tolist(), "cost_start": cost[:, 0].round(3).tolist(), "cost_end": cost[:, 1].round(3).tolist()}
+    if parent is not None:
+        res["default outputs equal the parent's"] = bool(same)
+    print(json.dumps(res), flush=True)
+    return res
+
+
+def main_lm(args):
+    parent = _other_build(args.parent_lib) if args.parent_lib else None
+    B = 8
+    for frac in (0.0, 0.3):
+        a, b = homography_batch(B, 5000, frac)
+        run_lm(f"find_homography hpatches outliers={frac}", gr.HOMOGRAPHY, a, b, 3 * 864 / 480, 0.99999, 2000, args.iters, args.rounds,
+               parent)
+    for frac in (0.0, 0.3):
+        a, b = relief_batch(B, 10000, frac, noise=0.1)
+        run_lm(f"find_fundamental demo_fundamental outliers={frac}", gr.FUNDAMENTAL, a, b, 0.2, 0.999999, 10000, args.iters,
+               args.rounds, parent)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true", help="skip the host reference timing")
     ap.add_argument("--method", choices=("ransac", "magsac", "both"), default="both")
+    ap.add_argument("--lm", action="store_true", help="measure find_*(..., lm_steps=10) against the default call")
+    ap.add_argument("--rounds", type=int, default=7, help="--lm: alternating rounds per leg")
+    ap.add_argument("--parent-lib", default=None, help="--lm: directory of another build of libroma_hip.so to time next to this one")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_geometry.py measures the device path: it needs a GPU"
+    if args.lm:
+        return main_lm(args)
     methods = ("ransac", "magsac") if args.method == "both" else (args.method,)
     B = 8
     for frac in (0.0, 0.3):
