@@ -7,14 +7,9 @@
 //   coordinates x^ = (x - c) s, Hartley normalisation over the pair's finite rows (centroid to 0, mean distance to sqrt 2, the
 //               definition of the RANSAC pipeline; summed here in this kernel's own fixed order); the fit runs on
 //               M^ = T_b M T_a^-1 (H) or T_b^-T M T_a^-1 (F) scaled to unit Frobenius norm; residuals are in pixels
-//   cost        sum of |r|^2 over the active rows (|r|^2 < thr^2) + thr^2 (n - active); a non-finite residual is never active;
-//               thr^2 = inf: plain least squares over the finite rows, the second term is dropped
-//   iteration   the loop of pose_refine.hip, constants and order of decisions: H = J^T J, g = J^T r over the active rows;
-//               (H + lambda diag H) delta = -g by Cholesky; |delta| < MR_STEP_TOL stops; a trial is accepted if its cost is
-//               lower (lambda <- max(lambda / 10, MR_LAMBDA_MIN)), else lambda <- 10 lambda and the solve is repeated, at
-//               most MR_RETRIES times
-//   stop        max_steps accepted steps, a short step, MR_RETRIES failed retries, fewer than P::MIN_ROWS active rows, not
-//               positive definite.  The model so far is returned: the cost never rises, a model never turns into "not found".
+//
+// The loop - cost, iteration, stopping rules, the reduction and its fixed order - is lm_fit<P> of lm_fit.h, which this file
+// shares with pose_refine.hip.  Its policies here:
 //
 // HomographyFit (8 parameters, two residuals per row): p = H^ (x^, y^, 1), e = ((p_x / p_z - u^) / s_b, (p_y / p_z - v^) / s_b);
 //   the entry of the start with the largest magnitude (first maximum, row-major) is held fixed, the other eight are updated
@@ -25,29 +20,17 @@
 //   Every parameter's dF^ is a combination of u_i v_j^T, whose dl = u_i (v_j . x^_a), dk = v_j (u_i . x^_b): the Jacobian needs
 //   six dot products per row and no derivative matrices in registers.
 //
-// model_refine_kernel<P>: one workgroup of MR_THREADS per pair runs the normalisation and the whole loop in one launch.  Rows are
-// strided over the threads; every thread sums its rows in ascending order, a wave adds its lanes by an xor butterfly, the
-// waves' sums go through LDS and are added in wave order by every thread.  So each thread holds the same normal equations,
-// solves the same system in registers and takes the same branch; no atomics.  The order of every sum depends on MR_THREADS
-// alone: results are bit-identical from run to run, independent of B and of the pair's place in the batch.
-// MR_THREADS = 512 is two waves per SIMD and 256 VGPRs per thread.  The homography's 45 f64 accumulators take 90 of them in the
-// row loop and the 8 x 8 Cholesky factor 72 in the solve, so the waves' sums of H and g stay in LDS, where the exchange puts
-// them anyway, and the solve and its retries add them up from there: with the totals held in registers across the solve the
-// kernel spilled at 512 threads (27 VGPRs) and fitted only at 256, where a pass over the rows takes twice as long.
+// model_refine_kernel<P>: one workgroup of LM_THREADS per pair runs the normalisation (summed like the loop's passes: results are
+// bit-identical from run to run, independent of B and of the pair's place in the batch), lm_fit<P> and the de-normalisation.
 // model_refine_mask_kernel<P>: grid (point blocks, pair): mask = active under the final model.
 #include "model_refine.h"
 
 #include "geometry.h"
-#include "ransac.h"  // mat3, finite_row, align256, align_base; its fp-contract setting holds here as well
+#include "lm_fit.h"  // and through it ransac.h: mat3, finite_row, align256, align_base; its fp-contract setting holds here as well
 
 namespace roma {
 namespace {
 
-constexpr int MR_THREADS = 512, MR_WAVES = MR_THREADS / 64;
-constexpr double MR_LAMBDA0 = 1e-3, MR_LAMBDA_MIN = 1e-10;
-constexpr int MR_RETRIES = 10;            // retries of one step with a ten times larger lambda
-constexpr double MR_STEP_TOL = 1e-10;     // |delta| below which the fit has converged
-constexpr double MR_PIVOT_REL = 1e-14;    // Cholesky pivot / largest diagonal entry of H + lambda diag H
 constexpr int MR_SVD_SWEEPS = 20;
 constexpr double MR_SVD_TOL = 4 * DBL_EPSILON;
 
@@ -61,42 +44,23 @@ struct MrState {  // what the fit leaves for the mask kernel
   int n, valid;
 };
 
-struct MrPoint {
-  double x, y, u, v;
+// ------------------------------------------------------------------------------------------------------------ model policies
+// The policies of lm_fit.h's loop.  Beside what the loop asks for: init (the state of a unit-norm M^; false if it has none),
+// matrix (M^ of a state), matrix_aux (the Aux of an M^: the mask kernel's), left (the left factor of the normalisation or of
+// its inverse).
+struct NormalisedRows {  // what both have in common: the rows are read through the pair's Hartley normalisation
+  using Prep = MrNorm;
+  __device__ static LmPoint point(const MrNorm& q, float2 a, float2 b) {
+    LmPoint w;
+    w.x = (a.x - q.ca[0]) * q.sa;
+    w.y = (a.y - q.ca[1]) * q.sa;
+    w.u = (b.x - q.cb[0]) * q.sb;
+    w.v = (b.y - q.cb[1]) * q.sb;
+    return w;
+  }
 };
 
-__device__ __forceinline__ MrPoint mr_point(const MrNorm& q, float2 a, float2 b) {
-  MrPoint w;
-  w.x = (a.x - q.ca[0]) * q.sa;
-  w.y = (a.y - q.ca[1]) * q.sa;
-  w.u = (b.x - q.cb[0]) * q.sb;
-  w.v = (b.y - q.cb[1]) * q.sb;
-  return w;
-}
-
-// exp([w]x) = I + a K + b K^2 with h = th / 2, s = sin(h) / h: a = s cos(h), b = s^2 / 2 (pose_refine.hip)
-__device__ __forceinline__ void mr_rodrigues(double w0, double w1, double w2, double* M) {
-  const double th2 = (w0 * w0 + w1 * w1) + w2 * w2;
-  double a = 1.0, b = 0.5;
-  if (!(th2 < 1e-30)) {
-    const double h = 0.5 * sqrt(th2);
-    double sn, cs;
-    sincos(h, &sn, &cs);
-    const double sh = sn / h;
-    a = sh * cs;
-    b = 0.5 * (sh * sh);
-  }
-  const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
-  double K2[9];
-  mat3(K, K, K2);
-#pragma unroll
-  for (int k = 0; k < 9; ++k) M[k] = ((k % 4 == 0 ? 1.0 : 0.0) + a * K[k]) + b * K2[k];
-}
-
-// ------------------------------------------------------------------------------------------------------------ model policies
-// A policy supplies NP parameters, NR residuals per row, MIN_ROWS, State (the parametrised model), Aux (what a row evaluation
-// reads: M^ and the scales), Row (what the Jacobian reuses of the residual), init / aux / residual / jacobian / apply.
-struct HomographyFit {
+struct HomographyFit : NormalisedRows {
   static constexpr int NP = 8, NR = 2, MIN_ROWS = 4;
   struct State { double h[9]; int k0; };
   struct Aux { double m[9], isb; };
@@ -120,7 +84,7 @@ struct HomographyFit {
   }
   __device__ static void aux(const State& s, const MrNorm& q, Aux& ax) { matrix_aux(s.h, q, ax); }
 
-  __device__ static double residual(const Aux& ax, const MrPoint& w, Row& r, double (&e)[NR]) {
+  __device__ static double residual(const Aux& ax, const LmPoint& w, Row& r, double (&e)[NR]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) r.p[i] = (ax.m[3 * i] * w.x + ax.m[3 * i + 1] * w.y) + ax.m[3 * i + 2];
     e[0] = (r.p[0] / r.p[2] - w.u) * ax.isb;
@@ -128,7 +92,7 @@ struct HomographyFit {
     return e[0] * e[0] + e[1] * e[1];
   }
 
-  __device__ static void jacobian(const State& s, const Aux& ax, const MrPoint& w, const Row& r, const double (&e)[NR],
+  __device__ static void jacobian(const State& s, const Aux& ax, const LmPoint& w, const Row& r, const double (&e)[NR],
                                   double (&J)[NR][NP]) {
     const double iz = 1.0 / r.p[2];
     const double a = iz * ax.isb;
@@ -164,7 +128,7 @@ struct HomographyFit {
   }
 };
 
-struct FundamentalFit {
+struct FundamentalFit : NormalisedRows {
   static constexpr int NP = 7, NR = 1, MIN_ROWS = 7;
   struct State { double U[9], V[9], sg; };  // row-major
   struct Aux { double m[9], sa2, sb2; };
@@ -260,7 +224,7 @@ struct FundamentalFit {
     matrix_aux(m, q, ax);
   }
 
-  __device__ static double residual(const Aux& ax, const MrPoint& w, Row& r, double (&e)[NR]) {
+  __device__ static double residual(const Aux& ax, const LmPoint& w, Row& r, double (&e)[NR]) {
     const double* F = ax.m;
     const double l0 = (F[0] * w.x + F[1] * w.y) + F[2], l1 = (F[3] * w.x + F[4] * w.y) + F[5], l2 = (F[6] * w.x + F[7] * w.y) + F[8];
     r.l[0] = l0;
@@ -274,7 +238,7 @@ struct FundamentalFit {
     return e[0] * e[0];
   }
 
-  __device__ static void jacobian(const State& st, const Aux& ax, const MrPoint& w, const Row& r, const double (&e)[NR],
+  __device__ static void jacobian(const State& st, const Aux& ax, const LmPoint& w, const Row& r, const double (&e)[NR],
                                   double (&J)[NR][NP]) {
     const double inv_s = 1.0 / r.s, inv_den = 1.0 / r.den;
     const double* U = st.U;
@@ -301,9 +265,9 @@ struct FundamentalFit {
 
   __device__ static void apply(const State& s, const double (&d)[NP], State& o) {
     double E[9];
-    mr_rodrigues(d[0], d[1], d[2], E);
+    lm_rodrigues(d[0], d[1], d[2], E);
     mat3(s.U, E, o.U);
-    mr_rodrigues(d[3], d[4], d[5], E);
+    lm_rodrigues(d[3], d[4], d[5], E);
     mat3(s.V, E, o.V);
     o.sg = s.sg + d[6];
   }
@@ -316,69 +280,24 @@ struct FundamentalFit {
   }
 };
 
-// ------------------------------------------------------------------------------------------------------------ the loop
-// the per-wave sums of v[0 .. NV) and cnt into LDS: lanes by an xor butterfly, one row of sh per wave.  The totals are read
-// back by mr_total_of / mr_count, which add the waves in order - in every thread, so all threads hold the same bits.
-template <int NV>
-__device__ __forceinline__ void mr_exchange(double (&v)[NV], int cnt, double* sh, int* shc) {
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[k] = v[k] + __shfl_xor(v[k], off, 64);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();  // the previous exchange has been read
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) sh[wave * NV + k] = v[k];
-    shc[wave] = cnt;
-  }
-  __syncthreads();
-}
-
-template <int NV>
-__device__ __forceinline__ double mr_total_of(const double* sh, int k) {
-  double s = sh[k];
-#pragma unroll
-  for (int w = 1; w < MR_WAVES; ++w) s = s + sh[w * NV + k];
-  return s;
-}
-
-__device__ __forceinline__ int mr_count(const int* shc) {
-  int c = shc[0];
-#pragma unroll
-  for (int w = 1; w < MR_WAVES; ++w) c += shc[w];
-  return c;
-}
-
-// the workgroup's totals of v[0 .. NV) and cnt in every thread
-template <int NV>
-__device__ __forceinline__ void mr_reduce(double (&v)[NV], int& cnt, double* sh, int* shc) {
-  mr_exchange(v, cnt, sh, shc);
-#pragma unroll
-  for (int k = 0; k < NV; ++k) v[k] = mr_total_of<NV>(sh, k);
-  cnt = mr_count(shc);
-}
-
+// ------------------------------------------------------------------------------------------------------------ the kernels
 // Hartley normalisation of the pair over its finite rows; false if it is not defined
 __device__ __forceinline__ bool mr_normalise(const float2* ka, const float2* kb, int n, double* sh, int* shc, MrNorm& q) {
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   int cnt = 0;
-  for (int i = threadIdx.x; i < n; i += MR_THREADS) {
+  for (int i = threadIdx.x; i < n; i += LM_THREADS) {
     const float2 a = ka[i], b = kb[i];
     if (finite_row(a.x, a.y, b.x, b.y)) {
       s[0] = s[0] + a.x; s[1] = s[1] + a.y; s[2] = s[2] + b.x; s[3] = s[3] + b.y;
       ++cnt;
     }
   }
-  mr_reduce(s, cnt, sh, shc);
+  lm_reduce(s, cnt, sh, shc);
   const double c = (double)cnt;
   q.ca[0] = s[0] / c; q.ca[1] = s[1] / c; q.cb[0] = s[2] / c; q.cb[1] = s[3] / c;
   double d[2] = {0.0, 0.0};
   int cnt2 = 0;
-  for (int i = threadIdx.x; i < n; i += MR_THREADS) {
+  for (int i = threadIdx.x; i < n; i += LM_THREADS) {
     const float2 a = ka[i], b = kb[i];
     if (finite_row(a.x, a.y, b.x, b.y)) {
       const double ax = a.x - q.ca[0], ay = a.y - q.ca[1], bx = b.x - q.cb[0], by = b.y - q.cb[1];
@@ -386,143 +305,22 @@ __device__ __forceinline__ bool mr_normalise(const float2* ka, const float2* kb,
       d[1] = d[1] + sqrt(bx * bx + by * by);
     }
   }
-  mr_reduce(d, cnt2, sh, shc);
+  lm_reduce(d, cnt2, sh, shc);
   const double ma = d[0] / c, mb = d[1] / c;
   q.sa = M_SQRT2 / ma;
   q.sb = M_SQRT2 / mb;
   return cnt > 0 && ma > 0 && mb > 0 && isfinite(q.sa) && isfinite(q.sb);
 }
 
-__device__ __forceinline__ double mr_total(double sum, double thr2, int n, int cnt) {
-  return isfinite(thr2) ? sum + thr2 * (double)(n - cnt) : sum;
-}
-
-// truncated cost of the model behind ax and its active rows
 template <class P>
-__device__ __forceinline__ double mr_cost(const typename P::Aux& ax, const MrNorm& q, const float2* ka, const float2* kb, int n,
-                                          double thr2, double* sh, int* shc, int& nact) {
-  double s[1] = {0.0};
-  int cnt = 0;
-  for (int i = threadIdx.x; i < n; i += MR_THREADS) {
-    const MrPoint w = mr_point(q, ka[i], kb[i]);
-    typename P::Row r;
-    double e[P::NR];
-    const double r2 = P::residual(ax, w, r, e);
-    const bool act = r2 < thr2;  // false for NaN
-    s[0] = s[0] + (act ? r2 : 0.0);
-    cnt += act ? 1 : 0;
-  }
-  mr_reduce(s, cnt, sh, shc);
-  nact = cnt;
-  return mr_total(s[0], thr2, n, cnt);
-}
-
-// H (upper triangle, row-major), g and the truncated cost at st.  The waves' sums of H and g stay in shn for mr_solve, which
-// may run several times (retries) before the next call replaces them: the accumulators are live in the row loop only.
-template <class P, int NS>
-__device__ __forceinline__ double mr_normal(const typename P::State& st, const typename P::Aux& ax, const MrNorm& q, const float2* ka,
-                                            const float2* kb, int n, double thr2, double* shn, int* shc, int& nact) {
-  constexpr int NP = P::NP, NH = NP * (NP + 1) / 2;
-  double acc[NS];
-#pragma unroll
-  for (int k = 0; k < NS; ++k) acc[k] = 0.0;
-  int cnt = 0;
-  for (int i = threadIdx.x; i < n; i += MR_THREADS) {
-    const MrPoint w = mr_point(q, ka[i], kb[i]);
-    typename P::Row r;
-    double e[P::NR];
-    const double r2 = P::residual(ax, w, r, e);
-    if (r2 < thr2) {
-      double J[P::NR][NP];
-      P::jacobian(st, ax, w, r, e, J);
-#pragma unroll
-      for (int c = 0; c < P::NR; ++c) {
-        int k = 0;
-#pragma unroll
-        for (int i2 = 0; i2 < NP; ++i2)
-#pragma unroll
-          for (int j2 = i2; j2 < NP; ++j2) {
-            acc[k] = acc[k] + J[c][i2] * J[c][j2];
-            ++k;
-          }
-#pragma unroll
-        for (int i2 = 0; i2 < NP; ++i2) acc[NH + i2] = acc[NH + i2] + J[c][i2] * e[c];
-      }
-      acc[NH + NP] = acc[NH + NP] + r2;
-      ++cnt;
-    }
-  }
-  mr_exchange(acc, cnt, shn, shc);
-  nact = mr_count(shc);
-  return mr_total(mr_total_of<NS>(shn, NH + NP), thr2, n, nact);
-}
-
-// delta of (H + lam diag H) delta = -g by Cholesky; false when a pivot is not above MR_PIVOT_REL x the largest diagonal entry
-template <int NP, int NS>
-__device__ __forceinline__ bool mr_solve(const double* shn, double lam, double (&d)[NP]) {
-  constexpr int NH = NP * (NP + 1) / 2;
-  double A[NP][NP], L[NP][NP];
-  {
-    int k = 0;
-#pragma unroll
-    for (int i = 0; i < NP; ++i)
-#pragma unroll
-      for (int j = i; j < NP; ++j) {
-        A[i][j] = mr_total_of<NS>(shn, k);
-        A[j][i] = A[i][j];
-        ++k;
-      }
-  }
-  double big = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    A[i][i] = A[i][i] + lam * A[i][i];
-    big = fmax(big, A[i][i]);
-  }
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    double dj = A[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) dj = dj - L[j][k] * L[j][k];
-    ok = ok && dj > MR_PIVOT_REL * big;
-    L[j][j] = sqrt(dj);
-#pragma unroll
-    for (int i = j + 1; i < NP; ++i) {
-      double s = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
-      L[i][j] = s / L[j][j];
-    }
-  }
-  double y[NP];
-#pragma unroll
-  for (int i = 0; i < NP; ++i) {
-    double s = -mr_total_of<NS>(shn, NH + i);
-#pragma unroll
-    for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
-    y[i] = s / L[i][i];
-  }
-#pragma unroll
-  for (int i = NP - 1; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < NP; ++k) s = s - L[k][i] * d[k];
-    d[i] = s / L[i][i];
-  }
-  return ok;
-}
-
-template <class P>
-__global__ __launch_bounds__(MR_THREADS) void model_refine_kernel(const double* __restrict__ M_in, const float2* __restrict__ kpts_a,
+__global__ __launch_bounds__(LM_THREADS) void model_refine_kernel(const double* __restrict__ M_in, const float2* __restrict__ kpts_a,
                                                                   const float2* __restrict__ kpts_b, const int* __restrict__ counts,
                                                                   const unsigned char* __restrict__ valid, int N, double thr,
                                                                   int max_steps, double* __restrict__ out_M, int* __restrict__ out_info,
                                                                   double* __restrict__ out_cost, MrState* __restrict__ st) {
-  constexpr int NP = P::NP, NS = NP * (NP + 1) / 2 + NP + 1;
-  __shared__ double shn[MR_WAVES * NS];  // the waves' sums of the normal equations: kept across the retries of a step
-  __shared__ double sh[MR_WAVES * 4];    // every other exchange
-  __shared__ int shc[MR_WAVES];
+  __shared__ double shn[LM_WAVES * lm_sums(P::NP)];  // the waves' sums of the normal equations: kept across the retries of a step
+  __shared__ double sh[LM_WAVES * 4];    // every other exchange
+  __shared__ int shc[LM_WAVES];
   const int b = blockIdx.x;
   const int n = counts ? min(max(counts[b], 0), N) : N;
   const float2* ka = kpts_a + (long)b * N;
@@ -531,7 +329,6 @@ __global__ __launch_bounds__(MR_THREADS) void model_refine_kernel(const double* 
   bool ok = (!valid || valid[b]) && n >= P::MIN_ROWS;
   MrNorm q;
   typename P::State S;
-  typename P::Aux ax;
   double mn[9];
   if (ok) ok = mr_normalise(ka, kb, n, sh, shc, q);
   if (ok) {
@@ -554,49 +351,8 @@ __global__ __launch_bounds__(MR_THREADS) void model_refine_kernel(const double* 
     for (int k = 0; k < 9; ++k) mn[k] = mn[k] / f;
     ok = ok && P::init(mn, S);
   }
-  int steps = 0, evals = 0, nact = 0;
-  double cost0 = NAN, cur = NAN;
-  if (ok) {
-    const double thr2 = thr * thr;
-    double lam = MR_LAMBDA0;
-    P::aux(S, q, ax);
-    cur = mr_normal<P, NS>(S, ax, q, ka, kb, n, thr2, shn, shc, nact);
-    cost0 = cur;
-    evals = 1;
-    bool go = true;
-    while (go && steps < max_steps && nact >= P::MIN_ROWS) {
-      bool taken = false;
-      for (int tr = 0; tr <= MR_RETRIES && go && !taken; ++tr) {
-        double d[NP];
-        const bool pd = mr_solve<NP, NS>(shn, lam, d);
-        double len = 0.0;
-#pragma unroll
-        for (int k = 0; k < NP; ++k) len = len + d[k] * d[k];
-        if (!pd || sqrt(len) < MR_STEP_TOL) {
-          go = false;
-        } else {
-          typename P::State Sn;
-          typename P::Aux axn;
-          P::apply(S, d, Sn);
-          P::aux(Sn, q, axn);
-          int na;
-          const double c = mr_cost<P>(axn, q, ka, kb, n, thr2, sh, shc, na);
-          ++evals;
-          if (c < cur) {
-            S = Sn;
-            lam = fmax(lam / 10.0, MR_LAMBDA_MIN);
-            taken = true;
-          } else {
-            lam = lam * 10.0;
-          }
-        }
-      }
-      if (!taken) break;
-      ++steps;
-      P::aux(S, q, ax);
-      cur = mr_normal<P, NS>(S, ax, q, ka, kb, n, thr2, shn, shc, nact);
-    }
-  }
+  LmResult fit = {0, 0, 0, NAN, NAN};
+  if (ok) fit = lm_fit<P>(S, q, ka, kb, n, thr * thr, max_steps, shn, sh, shc);
   if (threadIdx.x == 0) {
     MrState& T = st[b];
     T.n = n;
@@ -607,29 +363,29 @@ __global__ __launch_bounds__(MR_THREADS) void model_refine_kernel(const double* 
     if (ok) {
       T.nrm = q;
       P::matrix(S, T.m);
-      if (steps) {  // the last lines of the RANSAC: de-normalise, [2, 2] = 1 unless it is below 1e-12 of the norm
+      if (fit.steps) {  // the last lines of the RANSAC: de-normalise, [2, 2] = 1 unless it is below 1e-12 of the norm
         const double ta[9] = {q.sa, 0, -q.sa * q.ca[0], 0, q.sa, -q.sa * q.ca[1], 0, 0, 1};
         double l[9], tmp[9];
         P::left(q, true, l);
         mat3(l, T.m, tmp);
         mat3(tmp, ta, out);
-        double f = 0.0;
+        double fro = 0.0;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) f = f + out[k] * out[k];
-        f = sqrt(f);
-        const double sc = fabs(out[8]) >= 1e-12 * f ? out[8] : f;
+        for (int k = 0; k < 9; ++k) fro = fro + out[k] * out[k];
+        fro = sqrt(fro);
+        const double sc = fabs(out[8]) >= 1e-12 * fro ? out[8] : fro;
 #pragma unroll
         for (int k = 0; k < 9; ++k) out[k] = out[k] / sc;
       }
     }
     // without an accepted step the input comes back untouched (read again: not kept in registers)
-    for (int k = 0; k < 9; ++k) out_M[(long)b * 9 + k] = steps ? out[k] : M_in[(long)b * 9 + k];
-    out_info[b * 4] = steps;
-    out_info[b * 4 + 1] = evals;
-    out_info[b * 4 + 2] = nact;
+    for (int k = 0; k < 9; ++k) out_M[(long)b * 9 + k] = fit.steps ? out[k] : M_in[(long)b * 9 + k];
+    out_info[b * 4] = fit.steps;
+    out_info[b * 4 + 1] = fit.evals;
+    out_info[b * 4 + 2] = fit.nact;
     out_info[b * 4 + 3] = ok ? 1 : 0;
-    out_cost[b * 2] = cost0;
-    out_cost[b * 2 + 1] = cur;
+    out_cost[b * 2] = fit.cost0;
+    out_cost[b * 2 + 1] = fit.cost;
   }
 }
 
@@ -645,7 +401,7 @@ __global__ __launch_bounds__(256) void model_refine_mask_kernel(const float2* __
   if (S.valid && i < S.n) {
     typename P::Aux ax;
     P::matrix_aux(S.m, S.nrm, ax);
-    const MrPoint w = mr_point(S.nrm, kpts_a[(long)b * N + i], kpts_b[(long)b * N + i]);
+    const LmPoint w = P::point(S.nrm, kpts_a[(long)b * N + i], kpts_b[(long)b * N + i]);
     typename P::Row r;
     double e[P::NR];
     in = P::residual(ax, w, r, e) < thr * thr;
@@ -657,7 +413,7 @@ template <class P>
 int refine_model_run(const double* M, const float2* ka, const float2* kb, const int* counts, const unsigned char* valid, int B, int N,
                      double thr, int max_steps, double* out_m, unsigned char* out_mask, int* out_info, double* out_cost, MrState* st,
                      hipStream_t s) {
-  hipLaunchKernelGGL(model_refine_kernel<P>, dim3(B), dim3(MR_THREADS), 0, s, M, ka, kb, counts, valid, N, thr, max_steps, out_m,
+  hipLaunchKernelGGL(model_refine_kernel<P>, dim3(B), dim3(LM_THREADS), 0, s, M, ka, kb, counts, valid, N, thr, max_steps, out_m,
                      out_info, out_cost, st);
   ROMA_LAUNCH_CHECK();
   if (N > 0) {

@@ -1,6 +1,7 @@
 """tools/pose_refine_ref.py (the oracle of the device pose refinement, roma_amd.refine_pose) on the relief scene, and the C ABI
 of roma_op_refine_pose (dlopen only).  No GPU."""
 import glob
+import math
 import os
 import re
 import sys
@@ -124,6 +125,22 @@ def test_degenerate_active_sets_return_the_input(frac, limit):
         o = pr.refine(Rs, ts, x0, x1, thr)
         assert np.array_equal(o["R"], Rs) and np.array_equal(o["t"], ts) and o["info"][0] == 0 and o["info"][3] == 1
         assert o["info"][1] == 1 and o["info"][2] == pr.cost(Rs, ts, x0, x1, thr)[1] and o["cost"] == o["cost0"]
+
+
+def test_a_threshold_whose_square_is_not_finite_is_least_squares_over_the_finite_rows():
+    """the loop's rule (lm_ref.truncated), which the pose shares with H and F: 1e200 is what the device call accepts, inf what
+    only the oracle does; every finite row is active, the thr^2 (n - active) term is dropped, and `cost` is the same sum"""
+    x0, x1, thr, R0, t0, truth = clean_scene(0.0)
+    x0 = x0.copy()
+    x0[[3, 700]] = np.nan
+    Rs, ts = starts(R0, t0, 0.01)[0]
+    fits = [pr.refine(Rs, ts, x0, x1, big) for big in (1e200, math.inf)]
+    for o, big in zip(fits, (1e200, math.inf)):
+        assert o["info"][0] >= 1 and o["info"][2:] == (len(x0) - 2, 1) and not o["mask"][[3, 700]].any()
+        assert math.isfinite(o["cost"]) and o["cost"] < o["cost0"]
+        assert pr.cost(o["R"], o["t"], x0, x1, big) == (o["cost"], len(x0) - 2)
+        assert pose_error(o["R"], o["t"], R0, t0) < 1e-3
+    assert np.array_equal(fits[0]["R"], fits[1]["R"]) and np.array_equal(fits[0]["t"], fits[1]["t"])
 
 
 def test_invalid_pairs_and_the_solver_rule():

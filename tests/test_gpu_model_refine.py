@@ -194,6 +194,45 @@ def test_ragged_counts_invalid_pairs_nan_rows_and_small_inputs(built_lib, model)
 
 
 @pytest.mark.parametrize("model", [H, F])
+def test_counts_around_a_wave_the_workgroup_and_the_minimum(built_lib, model):
+    """one batch whose counts leave threads and whole waves of the workgroup without rows, put one row past a wave (64) and
+    past the workgroup (512), and end at MIN_ROWS and one below it; exact data, a start 1e-4 off"""
+    M0, pa, pb, _, _ = scene(model, 0.0)
+    pa, pb = mr.as_f32(pa), mr.as_f32(pb)
+    Ms, thr, k = starts(model, M0)[0], CLEAN_THR[model], mr.MIN_ROWS[model]
+    n, counts = 1000, [513, 512, 511, 65, 64, 63, k, k - 1]
+    a = np.full((8, n, 2), np.nan)
+    b = np.full((8, n, 2), np.nan)
+    for i, c in enumerate(counts):
+        a[i, :c], b[i, :c] = pa[:c], pb[:c]
+    cd = torch.tensor(counts)
+    out = _refine(model, np.stack([Ms] * 8), a, b, thr, counts=cd)
+    again = _refine(model, np.stack([Ms] * 8), a, b, thr, counts=cd)
+    # the costs of the pair that is not fitted are NaN
+    assert all(torch.equal(x, y) for x, y in zip(out[:3], again[:3])) and torch.equal(out[3][:7], again[3][:7])
+    M, mask, info, cost = out
+    for i, c in enumerate(counts):
+        Mi, mi, ii, ci = _refine(model, Ms, pa[:c], pb[:c], thr)
+        assert torch.equal(Mi, M[i]) and torch.equal(mi, mask[i, :c]) and torch.equal(ii, info[i]), c
+        assert not bool(mask[i, c:].any())
+        Md, got = M[i].cpu().numpy(), info[i].cpu().tolist()
+        print(f"count {c}: info {got} cost {cost[i].cpu().tolist()}")
+        if c >= 63:
+            assert torch.equal(ci, cost[i])
+            o = mr.refine(model, Ms, pa[:c], pb[:c], thr)
+            assert o["info"][0] >= 1 and edge_rows(model, o["M"], pa[:c], pb[:c], thr) == 0
+            d = _unit_diff(Md, o["M"])
+            print(f"count {c}: diff {d:.3e} oracle {o['info']}")
+            assert d <= TOL, (c, d)
+            assert np.array_equal(mask[i, :c].cpu().numpy(), o["mask"]) and got[2:] == list(o["info"][2:]), (c, got, o["info"])
+        elif c == k:
+            assert torch.equal(ci, cost[i]) and got[3] == 1 and float(cost[i, 1]) <= float(cost[i, 0])
+            assert mr.pixel_cost(model, Md, pa[:c], pb[:c], thr)[0] <= mr.pixel_cost(model, Ms, pa[:c], pb[:c], thr)[0]
+        else:  # fewer rows than the model needs: untouched
+            assert np.array_equal(Md, Ms) and got == [0, 0, 0, 0] and not bool(mask[i].any()) and bool(torch.isnan(cost[i]).all())
+
+
+@pytest.mark.parametrize("model", [H, F])
 @pytest.mark.parametrize("method", ["ransac", "magsac"])
 def test_find_with_lm_steps_is_find_then_refine_and_the_default_is_unchanged(built_lib, model, method):
     """item 11"""

@@ -168,6 +168,41 @@ def test_batch_equals_single_pairs_ragged_counts_and_determinism(built_lib):
     assert estimate_pose(_dev(a[6, :4]), _dev(b[6, :4]), K, K, thr, refine=True) is None
 
 
+def test_counts_around_a_wave_the_workgroup_and_the_minimum(built_lib):
+    """one batch whose counts leave threads and whole waves of the workgroup without rows, put one row past a wave (64) and
+    past the workgroup (512), and end at MIN_ROWS and one below it; exact data, a start 0.01 degrees off"""
+    x0, x1, thr, R0, t0, truth = clean_scene(0.0)
+    Rs, ts = starts(R0, t0, 0.01)[0]
+    n, counts = 1000, [513, 512, 511, 65, 64, 63, pr.MIN_ROWS, pr.MIN_ROWS - 1]
+    a = np.full((8, n, 2), np.nan)
+    b = np.full((8, n, 2), np.nan)
+    for i, c in enumerate(counts):
+        a[i, :c], b[i, :c] = x0[:c], x1[:c]
+    cd = torch.tensor(counts)
+    out = _refine_normalised(np.stack([Rs] * 8), np.stack([ts] * 8), a, b, thr, counts=cd)
+    again = _refine_normalised(np.stack([Rs] * 8), np.stack([ts] * 8), a, b, thr, counts=cd)
+    assert all(torch.equal(x, y) for x, y in zip(out, again))
+    R, t, mask, info = out
+    for i, c in enumerate(counts):
+        Ri, ti, mi, ii = _refine_normalised(Rs, ts, x0[:c], x1[:c], thr)
+        assert torch.equal(Ri, R[i]) and torch.equal(ti, t[i]) and torch.equal(mi, mask[i, :c]) and torch.equal(ii, info[i]), c
+        assert not bool(mask[i, c:].any())
+        Rd, td, got = R[i].cpu().numpy(), t[i].cpu().numpy()[:, 0], info[i].cpu().tolist()
+        print(f"count {c}: info {got}")
+        if c >= 63:
+            o = pr.refine(Rs, ts, x0[:c], x1[:c], thr)
+            r2 = pr.residuals(o["R"], o["t"], x0[:c], x1[:c]) ** 2
+            assert o["info"][0] >= 1 and (np.abs(r2 - thr * thr) < 1e-9 * thr * thr).sum() == 0
+            dR, dt = float(np.linalg.norm(Rd - o["R"])), float(np.linalg.norm(td - o["t"]))
+            print(f"count {c}: |dR| {dR:.3e} |dt| {dt:.3e} oracle {o['info']}")
+            assert dR <= TOL and dt <= TOL, (c, dR, dt)
+            assert np.array_equal(mask[i, :c].cpu().numpy(), o["mask"]) and got[2:] == list(o["info"][2:]), (c, got, o["info"])
+        elif c == pr.MIN_ROWS:
+            assert got[3] == 1 and pr.cost(Rd, td, x0[:c], x1[:c], thr)[0] <= pr.cost(Rs, ts, x0[:c], x1[:c], thr)[0]
+        else:  # fewer rows than parameters: untouched
+            assert np.array_equal(Rd, Rs) and np.array_equal(td, ts) and got == [0, 0, 0, 0] and not bool(mask[i].any())
+
+
 def test_default_is_the_unrefined_path(built_lib):
     from roma_amd import estimate_pose, estimate_pose_uncalibrated
     K, T, pa, pb, thr, a, b, seeds = _noisy_batch(0.3, 0.5)

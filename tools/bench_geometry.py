@@ -14,8 +14,9 @@ the other) - a CPU number, for scale only.
 N = 5 000, 0.5 px noise) and demo_fundamental's call (B = 8, N = 10 000, 0.1 px noise) at 0 % and 30 % outliers, the default
 call against the same call with lm_steps=10 in one process, timed alternately in rounds, medians over the rounds; one JSON
 line per configuration with the added time, refine_* alone and the fit's counters.  --parent-lib DIR (a directory holding another
-build of libroma_hip.so, e.g. the parent commit's) adds that build's default call to the same alternation, to show that the
-default path did not move.
+build of libroma_hip.so, e.g. the parent commit's) adds that build's two calls to the same alternation, and compares the
+outputs build against build, bit for bit: the default call, refine_* on the bench batch and refine_* on a ragged batch
+(`ragged_batch`).
 Usage: python tools/bench_geometry.py [--iters 20] [--no-cpu] [--method ransac|magsac|both]
        python tools/bench_geometry.py --lm [--iters 20] [--rounds 7] [--parent-lib DIR]
 """
@@ -144,12 +145,43 @@ def _using(lib):
         _lib._libs["bf16"] = mine
 
 
+def same_bits(x, y):
+    """torch.equal of the bit patterns: a NaN equals itself"""
+    if x.is_floating_point():
+        x, y = x.view(torch.int64 if x.dtype == torch.float64 else torch.int32), y.view(torch.int64 if y.dtype == torch.float64 else torch.int32)
+    return bool(torch.equal(x, y))
+
+
+def outputs_equal(parent, call, names):
+    """{name: this build's output equals the parent build's}"""
+    mine = call()
+    with _using(parent):
+        theirs = call()
+    return {k: same_bits(x, y) for k, x, y in zip(names, mine, theirs)}
+
+
+def within_spread(this, parent):
+    """this build's median is at most the parent's plus the parent's own spread over its rounds"""
+    return bool(np.median(this) <= np.median(parent) + (np.max(parent) - np.min(parent)))
+
+
+def ragged_batch(a, b, min_rows, n=1000):
+    """the first n rows of pair 0 eight times, cut to the counts at which a workgroup's reduction can go wrong: threads and
+    whole waves without rows, one row past a wave or the workgroup, exactly min_rows, one below it: (a, b, counts)"""
+    counts = (n, 513, 512, 511, 65, 64, min_rows, min_rows - 1)
+    ra, rb = np.full((8, n, 2), np.nan), np.full((8, n, 2), np.nan)
+    for i, c in enumerate(counts):
+        ra[i, :c], rb[i, :c] = a[0, :c], b[0, :c]
+    dev = lambda x: torch.tensor(x, dtype=torch.float32, device="cuda:0")  # noqa: E731
+    return dev(ra), dev(rb), torch.tensor(counts, dtype=torch.int32, device="cuda:0")
+
+
 def _stats(ms):
     return {"median": round(float(np.median(ms)), 4), "min": round(float(np.min(ms)), 4), "max": round(float(np.max(ms)), 4)}
 
 
 def run_lm(name, model, a, b, thr, conf, max_iters, iters, rounds, parent, lm_steps=10):
-    """default call, the same call with lm_steps, and the parent build's default call if given: timed alternately"""
+    """default call, the same call with lm_steps, and the parent build's two calls if given: timed alternately"""
     from roma_amd.geometry import find_fundamental, find_homography, refine_fundamental, refine_homography
     find, fit = (find_homography, refine_homography) if model == gr.HOMOGRAPHY else (find_fundamental, refine_fundamental)
     da = torch.tensor(a, dtype=torch.float32, device="cuda:0")
@@ -159,7 +191,7 @@ def run_lm(name, model, a, b, thr, conf, max_iters, iters, rounds, parent, lm_st
     fitted = lambda: find(da, db, thr, conf, max_iters, seed=seeds, lm_steps=lm_steps)  # noqa: E731
     legs = {"this ms": (None, plain), f"this lm_steps={lm_steps} ms": (None, fitted)}
     if parent is not None:
-        legs = {"parent ms": (parent, plain), **legs}
+        legs = {"parent ms": (parent, plain), f"parent lm_steps={lm_steps} ms": (parent, fitted), **legs}
     for lib, fn in legs.values():
         with _using(lib):
             for _ in range(3):
@@ -175,6 +207,13 @@ def run_lm(name, model, a, b, thr, conf, max_iters, iters, rounds, parent, lm_st
     if parent is not None:
         with _using(parent):
             same = all(torch.equal(x, y) for x, y in zip(plain(), (M, mask, ok)))
+        names = ("M", "mask", "info", "cost")
+        refined = outputs_equal(parent, lambda: fit(M, da, db, thr, max_steps=lm_steps, valid=ok), names)
+        # every row of the ragged batch starts from pair 0's model at its full count
+        ra, rb, counts = ragged_batch(a, b, 4 if model == gr.HOMOGRAPHY else 7)
+        M0 = find(ra[0], rb[0], thr, conf, max_iters, seed=1)[0]
+        ragged = outputs_equal(parent, lambda: fit(M0.expand(8, 3, 3).contiguous(), ra, rb, thr, max_steps=lm_steps, counts=counts),
+                               names)
     info, cost = info.cpu().numpy(), cost.cpu().numpy()
     res = {"config": name, "B": int(a.shape[0]), "N": int(a.shape[1]), "threshold": thr, "lm_steps": lm_steps, "rounds": rounds,
            "iters_per_round": iters, **{k: _stats(v) for k, v in ms.items()},
@@ -183,6 +222,9 @@ def run_lm(name, model, a, b, thr, conf, max_iters, iters, rounds, parent, lm_st
            "active_rows_per_pair": info[:, 2].tolist(), "cost_start": cost[:, 0].round(3).tolist(), "cost_end": cost[:, 1].round(3).tolist()}
     if parent is not None:
         res["default outputs equal the parent's"] = bool(same)
+        res["refined outputs equal the parent's"] = refined
+        res["ragged refined outputs equal the parent's"] = ragged
+        res["lm within the parent's spread"] = within_spread(ms[f"this lm_steps={lm_steps} ms"], ms[f"parent lm_steps={lm_steps} ms"])
     print(json.dumps(res), flush=True)
     return res
 
@@ -207,7 +249,7 @@ def main():
     ap.add_argument("--method", choices=("ransac", "magsac", "both"), default="both")
     ap.add_argument("--lm", action="store_true", help="measure find_*(..., lm_steps=10) against the default call")
     ap.add_argument("--rounds", type=int, default=7, help="--lm: alternating rounds per leg")
-    ap.add_argument("--parent-lib", default=None, help="--lm: directory of another build of libroma_hip.so to time next to this one")
+    ap.add_argument("--parent-lib", default=None, help="--lm: directory of another build of libroma_hip.so to time next to this one and compare outputs with")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_geometry.py measures the device path: it needs a GPU"
     if args.lm:

@@ -8,8 +8,11 @@ hypothesis-point evaluations per second (hypotheses the score kernel ran x point
 tools/pose_geometry.estimate_pose on the same pairs, one after the other - a CPU number, for scale only.
 --refine adds, after each configuration's line, one line for estimate_pose(..., refine=True) (the Levenberg-Marquardt fit of
 csrc/pose_refine.hip after the RANSAC): ms per call, the added ms over the plain call timed next to it, steps and cost
-evaluations per pair.
-Usage: python tools/bench_pose.py [--iters 20] [--no-cpu] [--refine]
+evaluations per pair.  With --parent-lib DIR (a directory holding another build of libroma_hip.so, e.g. the parent commit's)
+that build's refined call and its refine_pose alone are timed in the same alternation (--rounds each, the medians), and the
+outputs of refine_pose are compared build against build, bit for bit, on the bench batch and on a ragged batch
+(bench_geometry.ragged_batch).
+Usage: python tools/bench_pose.py [--iters 20] [--no-cpu] [--refine [--rounds 7] [--parent-lib DIR]]
 """
 import argparse
 import json
@@ -24,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import pose_geometry as pg  # noqa: E402
-from bench_geometry import relief_batch  # noqa: E402
+from bench_geometry import _other_build, _stats, _using, outputs_equal, ragged_batch, relief_batch, within_spread  # noqa: E402
 from accuracy_harness import synthetic_relief_pair  # noqa: E402
 
 
@@ -73,8 +76,9 @@ def _timed(fn, iters):
     return e0.elapsed_time(e1) / iters, out
 
 
-def run_refined(name, a, b, K, iters):
-    """the refined leg: plain and refined calls timed alternately (three rounds each, the medians), and the fit's own counters"""
+def run_refined(name, a, b, K, iters, rounds, parent):
+    """the refined leg: the plain call, the refined call and refine_pose alone - and the parent build's refined call and
+    refine_pose alone if given - timed alternately in rounds (the medians), and the fit's own counters"""
     from roma_amd.geometry import estimate_pose, refine_pose
     thr = 0.5 / float(np.mean([K[0, 0], K[1, 1]]))
     da = torch.tensor(a, dtype=torch.float32, device="cuda:0")
@@ -82,21 +86,39 @@ def run_refined(name, a, b, K, iters):
     seeds = torch.arange(len(a), dtype=torch.int64) + 1
     plain = lambda: estimate_pose(da, db, K, K, thr, 0.99999, 1000, seed=seeds)  # noqa: E731
     fitted = lambda: estimate_pose(da, db, K, K, thr, 0.99999, 1000, seed=seeds, refine=True)  # noqa: E731
-    for _ in range(3):
-        plain()
-        fitted()
-    torch.cuda.synchronize()
-    ms_p, ms_r = [], []
-    for _ in range(3):
-        ms_p.append(_timed(plain, iters)[0])
-        ms_r.append(_timed(fitted, iters)[0])
     R, t, mask, ok = plain()
-    ms_fit, (_, _, _, info) = _timed(lambda: refine_pose(R, t, da, db, K, K, thr, valid=ok), iters)
-    info = info.cpu().numpy()
+    alone = lambda: refine_pose(R, t, da, db, K, K, thr, valid=ok)  # noqa: E731
+    legs = {"plain ms": (None, plain), "this refine=True ms": (None, fitted), "this refine_pose alone ms": (None, alone)}
+    if parent is not None:
+        legs = {"parent refine=True ms": (parent, fitted), "parent refine_pose alone ms": (parent, alone), **legs}
+    for lib, fn in legs.values():
+        with _using(lib):
+            for _ in range(3):
+                fn()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in legs}
+    for _ in range(rounds):
+        for k, (lib, fn) in legs.items():
+            with _using(lib):
+                ms[k].append(_timed(fn, iters)[0])
+    info = alone()[3].cpu().numpy()
     res = {"config": name + " refine=True", "B": int(a.shape[0]), "N": int(a.shape[1]), "threshold": thr, "max_steps": 25,
-           "ms_per_call": round(float(np.median(ms_r)), 4), "ms_per_plain_call": round(float(np.median(ms_p)), 4),
-           "added_ms": round(float(np.median(ms_r) - np.median(ms_p)), 4), "refine_pose_alone_ms": round(ms_fit, 4),
+           "ms_per_call": round(float(np.median(ms["this refine=True ms"])), 4), "ms_per_plain_call": round(float(np.median(ms["plain ms"])), 4),
+           "added_ms": round(float(np.median(ms["this refine=True ms"]) - np.median(ms["plain ms"])), 4),
+           "refine_pose_alone_ms": round(float(np.median(ms["this refine_pose alone ms"])), 4),
+           "rounds": rounds, "iters_per_round": iters, **{k: _stats(v) for k, v in ms.items()},
            "steps_per_pair": info[:, 0].tolist(), "cost_evals_per_pair": info[:, 1].tolist(), "active_rows_per_pair": info[:, 2].tolist()}
+    if parent is not None:
+        names = ("R", "t", "mask", "info")
+        res["refined outputs equal the parent's"] = outputs_equal(parent, alone, names)
+        # every row of the ragged batch starts from pair 0's pose at its full count
+        ra, rb, counts = ragged_batch(a, b, 5)
+        R0, t0, _ = estimate_pose(ra[0], rb[0], K, K, thr, 0.99999, 1000, seed=1)
+        res["ragged refined outputs equal the parent's"] = outputs_equal(
+            parent, lambda: refine_pose(R0.expand(8, 3, 3).contiguous(), t0.expand(8, 3, 1).contiguous(), ra, rb, K, K, thr, counts=counts),
+            names)
+        for leg in ("refine=True", "refine_pose alone"):
+            res[f"{leg} within the parent's spread"] = within_spread(ms[f"this {leg} ms"], ms[f"parent {leg} ms"])
     print(json.dumps(res), flush=True)
     return res
 
@@ -106,14 +128,17 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true", help="skip the host reference timing")
     ap.add_argument("--refine", action="store_true", help="add the estimate_pose(..., refine=True) leg")
+    ap.add_argument("--rounds", type=int, default=7, help="--refine: alternating rounds per leg")
+    ap.add_argument("--parent-lib", default=None, help="--refine: directory of another build of libroma_hip.so to time next to this one and compare outputs with")
     args = ap.parse_args()
+    parent = _other_build(args.parent_lib) if args.parent_lib else None
     assert torch.cuda.is_available(), "bench_pose.py measures the device path: it needs a GPU"
     K = synthetic_relief_pair(480, 640, seed=0)["K1"]
     for frac in (0.0, 0.3, 0.5):
         a, b = relief_batch(8, 5000, frac)
         run(f"estimate_pose megadepth outliers={frac}", a, b, K, args.iters, not args.no_cpu)
         if args.refine:
-            run_refined(f"estimate_pose megadepth outliers={frac}", a, b, K, args.iters)
+            run_refined(f"estimate_pose megadepth outliers={frac}", a, b, K, args.iters, args.rounds, parent)
 
 
 if __name__ == "__main__":

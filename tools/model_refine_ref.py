@@ -1,6 +1,6 @@
 """numpy float64 restatement of the device refinement of homographies and fundamental matrices (roma_amd/csrc/model_refine.hip,
 `roma_amd.refine_homography` / `refine_fundamental`, `find_*(..., lm_steps=k)`): the oracle of tests/test_gpu_model_refine.py, as
-tools/pose_refine_ref.py is for the pose refinement, whose loop (constants, order of decisions) this one shares.
+tools/pose_refine_ref.py is for the pose refinement; the loop of both is tools/lm_ref.py.
 
 A Levenberg-Marquardt fit of the model to the rows inside the threshold, under the hard-truncated loss: the reprojection error
 in image B for H (what cv2.findHomography(..., RANSAC) ends with) and the Sampson distance for F (what PoseLib's
@@ -9,15 +9,8 @@ estimate_fundamental ends with).  Neither library is a dependency or restated: t
 Common to both models (one pair; M [3, 3] in pixel coordinates, points [n, 2] pixels, thr in pixels):
   coordinates x^ = (x - c) s with (c_a, s_a, c_b, s_b) of geometry_ref.normalize over the finite rows; the fit runs on
               M^ = T_b M T_a^-1 (H) or T_b^-T M T_a^-1 (F) scaled to unit Frobenius norm; residuals are in pixels
-  cost        sum of |r|^2 over the active rows (|r|^2 < thr^2) + thr^2 (n - active); a non-finite residual is never active;
-              thr = inf is plain least squares over the finite rows (the second term is then dropped);
-              the active set is that of the model under evaluation, not the RANSAC mask
-  iteration   H = J^T J, g = J^T r over the active rows; (H + lambda diag H) delta = -g by Cholesky (`solve`: not positive
-              definite when a pivot is not above PIVOT_REL times the largest diagonal entry); |delta| < STEP_TOL stops; the
-              trial is accepted when its cost is strictly lower (lambda <- max(lambda / 10, LAMBDA_MIN)), else lambda <- 10 lambda
-              and the solve is repeated, at most RETRIES times
-  stop        max_steps accepted steps, a short step, RETRIES failed retries, fewer than MIN_ROWS active rows, not positive
-              definite: the model so far is returned, so the truncated cost never rises and a model never becomes "not found"
+  loop        cost, iteration and stopping rules are lm_ref.fit's, which tools/pose_refine_ref.py shares; thr = inf is plain
+              least squares over the finite rows; the active set is that of the model under evaluation, not the RANSAC mask
   output      the model de-normalised and scaled like geometry_ref.ransac's (the input itself when no step was accepted),
               mask = active under the final model, info = (accepted steps, cost evaluations, active rows at the end, pair
               fitted), cost = (start, final) truncated cost in px^2
@@ -44,7 +37,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import geometry_ref as gr  # noqa: E402
-from pose_refine_ref import LAMBDA0, LAMBDA_MIN, PIVOT_REL, RETRIES, STEP_TOL, rodrigues  # noqa: E402
+import lm_ref  # noqa: E402
+from lm_ref import LAMBDA0, LAMBDA_MIN, PIVOT_REL, RETRIES, STEP_TOL, active, solve, truncated  # noqa: E402,F401
+from pose_refine_ref import rodrigues  # noqa: E402
 
 HOMOGRAPHY, FUNDAMENTAL = gr.HOMOGRAPHY, gr.FUNDAMENTAL
 MIN_ROWS = {HOMOGRAPHY: 4, FUNDAMENTAL: 7}  # rows of a pair, and active rows of an iteration, below which nothing is fitted
@@ -98,8 +93,17 @@ class Rows:
         self.x, self.y, self.u, self.v, self.sa, self.sb = x, y, u, v, sa, sb
 
 
+class _Fit:
+    """what the two problems below share of lm_ref.fit's policy"""
+
+    @classmethod
+    def normal(cls, J, e, a):
+        Ja, ea = J[a].reshape(-1, cls.NPAR), e[a].reshape(-1)
+        return Ja.T @ Ja, Ja.T @ ea
+
+
 # ------------------------------------------------------------------------------------------------------------ homography
-class HomographyFit:
+class HomographyFit(_Fit):
     """state (h [9] row-major, k0 the fixed entry)"""
     MODEL, NPAR, NRES, MIN_ROWS = HOMOGRAPHY, 8, 2, 4
 
@@ -198,7 +202,7 @@ def outer(a, b):
     return np.array([[a[i] * b[j] for j in range(3)] for i in range(3)])
 
 
-class FundamentalFit:
+class FundamentalFit(_Fit):
     """state (U, V, sigma)"""
     MODEL, NPAR, NRES, MIN_ROWS = FUNDAMENTAL, 7, 1, 7
 
@@ -266,56 +270,7 @@ class FundamentalFit:
 FITS = {HOMOGRAPHY: HomographyFit, FUNDAMENTAL: FundamentalFit}
 
 
-# ------------------------------------------------------------------------------------------------------------ the loop
-def active(e, thr):
-    """(active rows, |e|^2 per row)"""
-    with np.errstate(all="ignore"):
-        r2 = (e * e).sum(axis=1) if e.shape[1] == 1 else e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]
-        return np.isfinite(r2) & (r2 < thr * thr), r2
-
-
-def truncated(e, thr):
-    """(truncated cost, active rows [n]); with thr^2 = inf (plain least squares) the rows that are not active - the non-finite
-    ones - are the same for every model and cost nothing"""
-    a, r2 = active(e, thr)
-    thr2 = thr * thr
-    return float(r2[a].sum() + (thr2 * (len(r2) - int(a.sum())) if math.isfinite(thr2) else 0.0)), a
-
-
-def solve(H, g, lam):
-    """delta of (H + lam diag H) delta = -g by Cholesky, or None when a pivot is not above PIVOT_REL x the largest diagonal"""
-    n = len(g)
-    A = np.array(H, dtype=np.float64)
-    A[np.arange(n), np.arange(n)] = np.diag(H) + lam * np.diag(H)
-    big = A.diagonal().max()
-    L = np.zeros((n, n))
-    for j in range(n):
-        d = A[j, j]
-        for k in range(j):
-            d = d - L[j, k] * L[j, k]
-        if not d > PIVOT_REL * big:
-            return None
-        L[j, j] = math.sqrt(d)
-        for i in range(j + 1, n):
-            s = A[i, j]
-            for k in range(j):
-                s = s - L[i, k] * L[j, k]
-            L[i, j] = s / L[j, j]
-    y = np.zeros(n)
-    for i in range(n):
-        s = -g[i]
-        for k in range(i):
-            s = s - L[i, k] * y[k]
-        y[i] = s / L[i, i]
-    d = np.zeros(n)
-    for i in range(n - 1, -1, -1):
-        s = y[i]
-        for k in range(i + 1, n):
-            s = s - L[k, i] * d[k]
-        d[i] = s / L[i, i]
-    return d
-
-
+# ------------------------------------------------------------------------------------------------------------ the pair
 def as_f32(p):
     """points rounded to f32, as the device reads them"""
     return np.asarray(p, dtype=np.float32).astype(np.float64)
@@ -360,31 +315,7 @@ def refine(model, M, pa, pb, thr, max_steps=25, valid=True):
     st = fit.init(Mn) if Mn is not None else None
     if st is None:
         return out
-    lam, steps, evals = LAMBDA0, 0, 1
-    e, J = fit.jacobian(st, w)
-    cur, a = truncated(e, thr)
-    cost0 = cur
-    while steps < max_steps and int(a.sum()) >= fit.MIN_ROWS:
-        Ja, ea = J[a].reshape(-1, fit.NPAR), e[a].reshape(-1)
-        H, g = Ja.T @ Ja, Ja.T @ ea
-        taken = stop = False
-        for _ in range(1 + RETRIES):
-            d = solve(H, g, lam)
-            if d is None or math.sqrt(float(d @ d)) < STEP_TOL:
-                stop = True
-                break
-            trial = fit.apply(st, d)
-            c, _ = truncated(fit.residuals(trial, w), thr)
-            evals += 1
-            if c < cur:
-                st, lam, taken = trial, max(lam / 10.0, LAMBDA_MIN), True
-                break
-            lam = lam * 10.0
-        if stop or not taken:
-            break
-        steps += 1
-        e, J = fit.jacobian(st, w)
-        cur, a = truncated(e, thr)
+    st, steps, evals, a, cost0, cur = lm_ref.fit(fit, st, w, thr, max_steps)
     out.update(M=denormalise(model, fit.matrix(st), *nrm) if steps else M, mask=a, info=(steps, evals, int(a.sum()), 1),
                cost0=cost0, cost=cur)
     return out

@@ -1,4 +1,4 @@
-"""numpy float64 restatement of the device relative-pose refinement (roma_amd/csrc/essential.hip `pose_refine_kernel`,
+"""numpy float64 restatement of the device relative-pose refinement (roma_amd/csrc/pose_refine.hip `pose_refine_kernel`,
 `roma_amd.refine_pose`, `estimate_pose(..., refine=True)`): the oracle of tests/test_gpu_pose_refine.py, as
 tools/essential_ref.py is for the RANSAC and recoverPose it follows.
 
@@ -9,15 +9,10 @@ is not a dependency and is not restated: the algorithm below is its own definiti
 State: rotation R, unit translation t, E = [t]x R, normalised points x0 = (x, y), x1 = (u, v).
   residual    p = R (x, y, 1), l = t x p (= E x0h), q = (u, v, 1) x t, k = R^T q (= E^T x1h),
               r = ((u l0 + v l1) + l2) / sqrt((l0^2 + l1^2) + (k0^2 + k1^2))
-  cost        sum of r^2 over the active rows (r^2 < thr^2) + thr^2 (n - active); a non-finite r is never active
   parameters  R <- exp([w]x) R (Rodrigues), t <- normalise(t + d0 b0 + d1 b1) with the tangent basis of `tangent_basis`
-  iteration   H = J^T J, g = J^T r over the active rows; (H + lambda diag H) delta = -g by Cholesky (`solve`: not positive
-              definite when a pivot is not above PIVOT_REL times the largest diagonal entry); |delta| < STEP_TOL stops; the
-              trial pose is accepted when its cost is lower (lambda <- max(lambda / 10, LAMBDA_MIN)), else lambda <- 10 lambda
-              and the solve is repeated, at most RETRIES times
-  stop        max_steps accepted steps, a short step, RETRIES failed retries, fewer than MIN_ROWS active rows (H = J^T J of
-              fewer rows than parameters is singular; an empty active set is the common case of a start outside the
-              threshold band), H + lambda diag H not positive definite: the pose so far is returned, so the truncated cost never rises and a pose never becomes "not found"
+  loop        cost, iteration and stopping rules are lm_ref.fit's, which tools/model_refine_ref.py shares; MIN_ROWS = 5; a
+              threshold whose square is not finite is plain least squares over the finite rows there (the device call
+              itself refuses thr = inf for the pose)
   mask        r^2 < thr^2 under the final pose and positive depth in both cameras (essential_ref.cheirality, distance DIST)
 The device sums H, g and the cost in its own fixed order and calls its own sin / cos / sqrt: the two agree to rounding.
 """
@@ -31,12 +26,9 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import essential_ref as er  # noqa: E402
+import lm_ref  # noqa: E402
+from lm_ref import LAMBDA0, LAMBDA_MIN, PIVOT_REL, RETRIES, STEP_TOL, solve  # noqa: E402,F401
 
-LAMBDA0 = 1e-3
-LAMBDA_MIN = 1e-10
-RETRIES = 10          # retries of one step with a ten times larger lambda
-STEP_TOL = 1e-10      # |delta| below which the fit has converged
-PIVOT_REL = 1e-14     # Cholesky pivot / largest diagonal entry of H + lambda diag H
 DIST = 1e9            # distance_thresh estimate_pose passes to recover_pose
 MIN_ROWS = 5          # rows of a pair, and active rows of an iteration, below which nothing is fitted
 
@@ -123,42 +115,8 @@ def active(r, thr):
 
 def cost(R, t, x0, x1, thr):
     """(truncated cost, active rows)"""
-    r = residuals(R, t, x0, x1)
-    a = active(r, thr)
-    return float((r[a] * r[a]).sum() + thr * thr * (len(r) - int(a.sum()))), int(a.sum())
-
-
-def solve(H, g, lam):
-    """delta of (H + lam diag H) delta = -g by Cholesky, or None when a pivot is not above PIVOT_REL x the largest diagonal"""
-    A = np.array(H, dtype=np.float64)
-    A[np.arange(5), np.arange(5)] = np.diag(H) + lam * np.diag(H)
-    big = A.diagonal().max()
-    L = np.zeros((5, 5))
-    for j in range(5):
-        d = A[j, j]
-        for k in range(j):
-            d = d - L[j, k] * L[j, k]
-        if not d > PIVOT_REL * big:
-            return None
-        L[j, j] = math.sqrt(d)
-        for i in range(j + 1, 5):
-            s = A[i, j]
-            for k in range(j):
-                s = s - L[i, k] * L[j, k]
-            L[i, j] = s / L[j, j]
-    y = np.zeros(5)
-    for i in range(5):
-        s = -g[i]
-        for k in range(i):
-            s = s - L[i, k] * y[k]
-        y[i] = s / L[i, i]
-    d = np.zeros(5)
-    for i in range(4, -1, -1):
-        s = y[i]
-        for k in range(i + 1, 5):
-            s = s - L[k, i] * d[k]
-        d[i] = s / L[i, i]
-    return d
+    c, a = lm_ref.truncated(residuals(R, t, x0, x1)[:, None], thr)
+    return c, int(a.sum())
 
 
 def apply(R, t, delta):
@@ -167,6 +125,28 @@ def apply(R, t, delta):
     t1 = (t + delta[3] * bas[0]) + delta[4] * bas[1]
     t1 = t1 / math.sqrt((t1[0] * t1[0] + t1[1] * t1[1]) + t1[2] * t1[2])
     return rodrigues(delta[:3]) @ R, t1
+
+
+class PoseFit:
+    """the problem as lm_ref.fit takes it: state (R, t), rows (x0, x1)"""
+    MIN_ROWS = MIN_ROWS
+
+    @staticmethod
+    def jacobian(st, w):
+        r, J = jacobian(st[0], st[1], w[0], w[1])
+        return r[:, None], J
+
+    @staticmethod
+    def normal(J, e, a):
+        return J[a].T @ J[a], J[a].T @ e[a, 0]
+
+    @staticmethod
+    def residuals(st, w):
+        return residuals(st[0], st[1], w[0], w[1])[:, None]
+
+    @staticmethod
+    def apply(st, d):
+        return apply(st[0], st[1], d)
 
 
 def refine(R, t, x0, x1, thr, max_steps=25, valid=True):
@@ -180,33 +160,7 @@ def refine(R, t, x0, x1, thr, max_steps=25, valid=True):
     out = dict(R=R, t=t, mask=np.zeros(n, dtype=bool), info=(0, 0, 0, int(ok)), cost0=math.nan, cost=math.nan)
     if not ok:
         return out
-    Rc, tc = R, t / tn
-    lam, steps, evals = LAMBDA0, 0, 1
-    r, J = jacobian(Rc, tc, x0, x1)
-    a = active(r, thr)
-    cur = float((r[a] * r[a]).sum() + thr * thr * (n - int(a.sum())))
-    cost0 = cur
-    while steps < max_steps and int(a.sum()) >= MIN_ROWS:  # fewer active rows than parameters: H is singular
-        H, g = J[a].T @ J[a], J[a].T @ r[a]
-        taken = stop = False
-        for _ in range(1 + RETRIES):
-            d = solve(H, g, lam)
-            if d is None or math.sqrt(float(d @ d)) < STEP_TOL:
-                stop = True
-                break
-            Rn, tn_ = apply(Rc, tc, d)
-            c, _ = cost(Rn, tn_, x0, x1, thr)
-            evals += 1
-            if c < cur:
-                Rc, tc, lam, taken = Rn, tn_, max(lam / 10.0, LAMBDA_MIN), True
-                break
-            lam = lam * 10.0
-        if stop or not taken:
-            break
-        steps += 1
-        r, J = jacobian(Rc, tc, x0, x1)
-        a = active(r, thr)
-        cur = float((r[a] * r[a]).sum() + thr * thr * (n - int(a.sum())))
+    (Rc, tc), steps, evals, a, cost0, cur = lm_ref.fit(PoseFit, (R, t / tn), (x0, x1), thr, max_steps)
     with np.errstate(all="ignore"):
         mask = a & er.cheirality(Rc, tc, x0, x1, DIST)
     # without an accepted step the input comes back untouched, whatever the norm of its t
