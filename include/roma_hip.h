@@ -349,6 +349,25 @@ int roma_op_essential(const float* kpts_a, const float* kpts_b, const int* count
                       const double* camera_matrix, int B, int N, float threshold, double prob, int max_iters, double* out_e,
                       unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes,
                       void* stream);
+/* roma_op_essential with MAGSAC++ scoring and local optimisation (Barath et al., CVPR 2020; nu = 4, k^2 = 13.2767), restated in
+ * tools/essential_magsac_ref.py.  Sampling, five-point solver, slots and adaptive iteration count are roma_op_essential's; a
+ * model's score is the sum over the pair's rows of the MAGSAC++ loss of its Sampson distance in normalised camera coordinates,
+ * (x_B^T E x_A)^2 / (|E x_A|_{1,2}^2 + |E^T x_B|_{1,2}^2), with tau = threshold / ((fx + fy) / 2) the largest residual that counts
+ * as an inlier; lower is better.  Then up to lo_iters (0 .. 64) IRLS steps: the MAGSAC++ weights of the current model, over the
+ * rows of positive weight (at least 8) the weighted eight-point system on Hartley-normalised coordinates, the eigenvectors of its
+ * four smallest eigenvalues as the basis of the five-point solver's cubic constraints (Nister's form for more than five points),
+ * the solution of the smallest score projected onto the essential manifold; a step is kept only if the score drops, so a model
+ * is never lost and lo_iters = 0 returns the winning five-point model untouched.  Inputs as for roma_op_essential.  Outputs, all
+ * DEVICE: E, ok as for roma_op_essential; mask u8 [B, N] (residual < tau under the returned E: roma_op_essential's inlier rule up
+ * to the rounding of one f32 division); info int32 [B, 7] = {rounds run, winning hypothesis, its root, inliers of the winning
+ * minimal model, final inliers, pair valid, LO steps accepted}; score f64 [B, 2] = {sum of the loss of the winning minimal
+ * model, final sum: that less the accepted LO steps' gains} (0 where no model).  No host synchronisation; bit-identical from run
+ * to run and independent of B.  workspace: device memory of roma_op_essential_magsac_workspace(B, N) bytes. */
+long roma_op_essential_magsac_workspace(int B, int N);
+int roma_op_essential_magsac(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                             const double* camera_matrix, int B, int N, float threshold, double prob, int max_iters, int lo_iters,
+                             double* out_e, unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score,
+                             void* workspace, long workspace_bytes, void* stream);
 /* The five-point solver alone: x0, x1 DEVICE f64 [S, 5, 2] (x1^T E x0 = 0) -> E DEVICE f64 [S, 10, 3, 3] (solutions in ascending
  * order of Nister's z, unused slots 0), n DEVICE int32 [S]. */
 int roma_op_essential_minimal(const double* x0, const double* x1, int S, double* out_e, int* out_n, void* stream);

@@ -96,6 +96,8 @@ SIGNATURES = {
     "roma_op_magsac": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_essential_workspace": (_l, [_i, _i]),
     "roma_op_essential": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "roma_op_essential_magsac_workspace": (_l, [_i, _i]),
+    "roma_op_essential_magsac": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_essential_minimal": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "roma_op_recover_pose_workspace": (_l, [_i, _i]),
     "roma_op_recover_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _l, _vp]),

@@ -551,6 +551,15 @@ int roma_op_essential(const float* kpts_a, const float* kpts_b, const int* count
   return essential_launch(kpts_a, kpts_b, counts, seeds, camera_matrix, B, N, threshold, prob, max_iters, out_e, out_mask, out_ok,
                           out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
 }
+long roma_op_essential_magsac_workspace(int B, int N) { return (long)essential_magsac_workspace_bytes(B, N); }
+int roma_op_essential_magsac(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                             const double* camera_matrix, int B, int N, float threshold, double prob, int max_iters, int lo_iters,
+                             double* out_e, unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score,
+                             void* workspace, long workspace_bytes, void* stream) {
+  return essential_magsac_launch(kpts_a, kpts_b, counts, seeds, camera_matrix, B, N, threshold, prob, max_iters, lo_iters, out_e,
+                                 out_mask, out_ok, out_info, out_score, workspace,
+                                 (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
 int roma_op_essential_minimal(const double* x0, const double* x1, int S_, double* out_e, int* out_n, void* stream) {
   return essential_minimal_launch(x0, x1, S_, out_e, out_n, S(stream));
 }

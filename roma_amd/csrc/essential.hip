@@ -8,6 +8,9 @@
 //   hypothesis  16 lanes per hypothesis: Nister's five-point solver in f64 (below), up to 10 slots.
 //   inlier      f32 Sampson test.
 //   finish      E as found, info of ESSENTIAL_INFO ints.  No refinement (OpenCV has none here).
+//   residual2   (MAGSAC++, magsac_run) f32 squared Sampson distance in normalised camera coordinates: inlier_e's quantities.
+//   wrefit      (MAGSAC++) one IRLS step: the weighted eight-point system over the rows of positive weight, its four smallest
+//               eigenvectors as the basis of the solver below, the solution of the smallest score (Essential::wrefit).
 //
 // The five-point solver (D. Nister, PAMI 2004): null space X, Y, Z, W of the 5 x 9 epipolar system (Gauss-Jordan, then modified
 // Gram-Schmidt: an orthonormal basis keeps the elimination below well conditioned), the ten cubic constraints det E = 0 and
@@ -52,6 +55,24 @@ __device__ __forceinline__ bool inlier_e(const float* m, float4 p, float t2) {
   const float kx = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
   const float ky = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
   return d * d < t2 * (fmaf(lx, lx, ly * ly) + fmaf(kx, kx, ky * ky));
+}
+
+// MAGSAC++ (magsac_run): the squared Sampson distance in normalised camera coordinates, d^2 / ((l_x^2 + l_y^2) + (k_x^2 + k_y^2)) -
+// the quantities inlier_e compares, so r^2 < thr^2 is its test up to the rounding of the division.  Split like the H and F
+// residuals of geometry.hip into terms linear in the model (d, l_x, l_y, k_x, k_y) and the residual formed from them.
+__device__ __forceinline__ void res_terms_e(const float* m, float4 p, float (&t)[5]) {
+  const float lx = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
+  const float ly = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
+  const float lz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
+  t[0] = fmaf(p.z, lx, fmaf(p.w, ly, lz));
+  t[1] = lx;
+  t[2] = ly;
+  t[3] = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
+  t[4] = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
+}
+
+__device__ __forceinline__ float r2_from_e(const float (&t)[5]) {
+  return t[0] * t[0] / (fmaf(t[1], t[1], t[2] * t[2]) + fmaf(t[3], t[3], t[4] * t[4]));
 }
 
 // ------------------------------------------------------------------------------------------------------------ five-point solver
@@ -266,6 +287,34 @@ __device__ __forceinline__ void refine_xyz(const double* basis, double& x, doubl
   }
 }
 
+// modified Gram-Schmidt of four vectors in the order X, Y, Z, W; lane 0 of the group stores the basis (entry k of E: the
+// coefficients of x, y, z, 1)
+__device__ __forceinline__ void store_basis(double (&v)[4][9], double* sm, int gl) {
+#pragma unroll
+  for (int f = 0; f < 4; ++f) {
+#pragma unroll
+    for (int g = 0; g < f; ++g) {
+      double d = 0;
+#pragma unroll
+      for (int k = 0; k < 9; ++k) d += v[f][k] * v[g][k];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) v[f][k] = v[f][k] - d * v[g][k];
+    }
+    double s = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) s += v[f][k] * v[f][k];
+    const double inv = 1.0 / sqrt(s);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[f][k] = v[f][k] * inv;
+    if (gl == 0) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) sm[LDS_BASIS + 4 * k + f] = v[f][k];
+    }
+  }
+}
+
+__device__ __forceinline__ void solve_e_basis(bool act, double* sm, int gl, double (&e)[9], int& rank, int& nsol);
+
 // One hypothesis on the G lanes of a group (gl = lane in the group); every lane of the workgroup must call it (barriers).
 // Returns this lane's model in e (valid: a real root whose E is finite), its rank among the group's valid models and their
 // number.  sm: the group's LDS_PER doubles.
@@ -283,31 +332,21 @@ __device__ __forceinline__ void solve_e_group(const double (&xa)[5], const doubl
     act = gauss_jordan(a) && act;
     double v[4][9];
 #pragma unroll
-    for (int f = 0; f < 4; ++f) {  // modified Gram-Schmidt in the order X, Y, Z, W
+    for (int f = 0; f < 4; ++f) {
 #pragma unroll
       for (int k = 0; k < 5; ++k) v[f][k] = -a[k][5 + f];
 #pragma unroll
       for (int k = 5; k < 9; ++k) v[f][k] = k == 5 + f ? 1.0 : 0.0;
-#pragma unroll
-      for (int g = 0; g < f; ++g) {
-        double d = 0;
-#pragma unroll
-        for (int k = 0; k < 9; ++k) d += v[f][k] * v[g][k];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) v[f][k] = v[f][k] - d * v[g][k];
-      }
-      double s = 0;
-#pragma unroll
-      for (int k = 0; k < 9; ++k) s += v[f][k] * v[f][k];
-      const double inv = 1.0 / sqrt(s);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) v[f][k] = v[f][k] * inv;
-      if (gl == 0) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) sm[LDS_BASIS + 4 * k + f] = v[f][k];  // entry k of E: (x, y, z, 1) coefficients
-      }
     }
+    store_basis(v, sm, gl);
   }
+  solve_e_basis(act, sm, gl, e, rank, nsol);
+}
+
+// The solver from the group's basis X, Y, Z, W in LDS on (store_basis; the barrier that publishes it is the first thing here):
+// the real E = x X + y Y + z Z + W that satisfy the cubic constraints.  A five-point sample's null space (solve_e_group), or
+// the least-squares null space of more rows (Essential::wrefit) - Nister's form for more than five points.
+__device__ __forceinline__ void solve_e_basis(bool act, double* sm, int gl, double (&e)[9], int& rank, int& nsol) {
   __syncthreads();
   // row gl of the 10 x 20 constraint matrix: 2 (E E^T E)_ij - tr(E E^T) E_ij for gl = 3 i + j < 9, det E for gl = 9
   double acc[20];
@@ -483,6 +522,57 @@ __device__ __forceinline__ void solve_e_group(const double (&xa)[5], const doubl
   __syncthreads();  // the group's LDS is reused by the caller's next hypothesis
 }
 
+// ------------------------------------------------------------------------------------------------------------ 3 x 3 SVD
+// A = U S V^T by one-sided Jacobi on the columns of A (A V = U S).  a[j]: column j of A on entry, of U S on return; v[j]: column
+// j of V (identity on entry); sg: the singular values, descending (columns of a and v sorted with them).  run = false skips
+// the sweeps (a matrix that is not finite).
+__device__ __forceinline__ void jacobi_svd3(double (&a)[3][3], double (&v)[3][3], double (&sg)[3], bool run) {
+  for (int sweep = 0; sweep < SVD_SWEEPS && run; ++sweep) {
+    bool rot = false;
+#pragma unroll
+    for (int pq = 0; pq < 3; ++pq) {
+      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+      double al = 0, be = 0, ga = 0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        al += a[p][k] * a[p][k];
+        be += a[q][k] * a[q][k];
+        ga += a[p][k] * a[q][k];
+      }
+      if (fabs(ga) > SVD_TOL * sqrt(al * be)) {
+        const double zz = (be - al) / (2 * ga);
+        const double tn = copysign(1.0, zz) / (fabs(zz) + sqrt(1 + zz * zz));
+        const double c = 1 / sqrt(1 + tn * tn), s = c * tn;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          const double ap = a[p][k], aq = a[q][k], vp = v[p][k], vq = v[q][k];
+          a[p][k] = c * ap - s * aq;
+          a[q][k] = s * ap + c * aq;
+          v[p][k] = c * vp - s * vq;
+          v[q][k] = s * vp + c * vq;
+        }
+        rot = true;
+      }
+    }
+    if (!rot) break;
+  }
+#pragma unroll
+  for (int j = 0; j < 3; ++j) sg[j] = sqrt(a[j][0] * a[j][0] + a[j][1] * a[j][1] + a[j][2] * a[j][2]);
+  // sort descending (columns of A and V together)
+#pragma unroll
+  for (int pass = 0; pass < 3; ++pass) {
+    const int p = pass == 1 ? 1 : 0, q = p + 1;
+    if (sg[q] > sg[p]) {
+      double t = sg[p]; sg[p] = sg[q]; sg[q] = t;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        t = a[p][k]; a[p][k] = a[q][k]; a[q][k] = t;
+        t = v[p][k]; v[p][k] = v[q][k]; v[q][k] = t;
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------ model policy
 struct Essential {
   struct Norm {
@@ -493,6 +583,7 @@ struct Essential {
     }
   };
   static constexpr int S = 5, SLOTS = MAXR, HYP_THREADS = 256, HYP_LANES = G, REFINE_ITERS = 0, INFO = ESSENTIAL_INFO;
+  static constexpr int MAG_INFO = ESSENTIAL_MAGSAC_INFO, NT = 5, REFIT_MIN = 8;  // MAGSAC++: info, residual terms, rows of a step
   static constexpr bool SCORE_EVERY_SLOT = false;  // 10 slots, a few of them used: score only those
 
   // every thread of the workgroup: the pair's camera; pts written for every row; one threshold (t2a == t2b)
@@ -532,6 +623,238 @@ struct Essential {
   }
 
   __device__ static bool inlier(const float* m, float4 p, float t2, float) { return inlier_e(m, p, t2); }
+
+  // ---- MAGSAC++ (magsac_run): residuals in normalised camera coordinates, so no scales and tau = thr_n of normalise
+  __device__ static void res_scales(const Norm&, float& sa2, float& sb2) { sa2 = sb2 = 1.f; }
+  __device__ static double mag_thr2(const Norm& nm, float thr) {
+    const double thr_n = (double)thr / ((nm.fx + nm.fy) * 0.5);
+    return thr_n * thr_n;
+  }
+  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) { res_terms_e(m, p, t); }
+  __device__ static float r2_from(const float (&t)[NT], float, float) { return r2_from_e(t); }
+  __device__ static float residual2(const float* m, float4 p, float, float) {
+    float t[NT];
+    res_terms_e(m, p, t);
+    return r2_from_e(t);
+  }
+
+  // One IRLS step of the local optimisation, every thread of the 256 (magsac_refit_kernel):
+  //   1. over the rows of positive MAGSAC++ weight under the current model (at least REFIT_MIN, else LO stops): Hartley
+  //      normalisation of both images, then the weighted eight-point normal equations sum w_i a_i a_i^T (f64, the reduction
+  //      tree of Hartley<>::fit);
+  //   2. wave 0: their eigenvectors by one-sided Jacobi; those of the four smallest eigenvalues, de-normalised (Tb^T F_n Ta),
+  //      span the least-squares null space;
+  //   3. the five-point solver on that basis (solve_e_basis; W the smallest eigenvector): the E of the span that satisfy the
+  //      cubic constraints.  The smallest eigenvector alone, projected onto the essential manifold, is the eight-point
+  //      algorithm - on scenes close to a plane it follows the noise (tools/essential_magsac_ref.py);
+  //   4. wave 0: the sum of rho of each solution (magsac_sums), the smallest one (lowest slot on ties) projected onto the
+  //      essential manifold (singular values ((s1 + s2) / 2, (s1 + s2) / 2, 0): exact where the solver's root was not), unit
+  //      norm, largest-magnitude entry positive -> P.cand.
+  // Every group of the workgroup runs step 3 on the same basis (the solver's barriers need every thread); group 0's is used.
+  __device__ static void wrefit(const float2* A, const float2* Bp, const float4* pts, PairState<Essential>& P, const MagState& S) {
+    __shared__ double sm[GPB * LDS_PER];
+    __shared__ double sh[256];
+    __shared__ double red[4][45];
+    __shared__ double Mx[9][9];
+    __shared__ double ev[4][9];
+    __shared__ double cd[MAXR][9];
+    __shared__ alignas(16) float cf[MAXR * 12];
+    __shared__ int ncand;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, n = P.n;
+    const bool run = !P.stop && P.best_h >= 0;
+    float curf[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) curf[k] = P.curf[k];
+    const double fx = P.nrm.fx, fy = P.nrm.fy, cx = P.nrm.cx, cy = P.nrm.cy;
+    const float vs = S.vs;
+    __syncthreads();  // the pair's flags are read; thread 0 may rewrite them from here on
+    if (!run) {
+      if (t == 0) { P.stop = 1; P.cand_ok = 0; }
+      return;
+    }
+    // 1. Hartley normalisation over the rows of positive weight (NaN rows have none)
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+    for (int i = t; i < n; i += 256) {
+      float w;
+      magsac_rho(residual2(curf, pts[i], 1.f, 1.f) * vs, w);
+      if (!(w > 0.f)) continue;
+      const float2 a = A[i], q = Bp[i];
+      s0 += (a.x - cx) / fx; s1 += (a.y - cy) / fy; s2 += (q.x - cx) / fx; s3 += (q.y - cy) / fy; s4 += 1;
+    }
+    const double cnt = block_sum(s4, sh);
+    const double cax = block_sum(s0, sh) / cnt, cay = block_sum(s1, sh) / cnt;
+    const double cbx = block_sum(s2, sh) / cnt, cby = block_sum(s3, sh) / cnt;
+    double da = 0, db = 0;
+    for (int i = t; i < n; i += 256) {
+      float w;
+      magsac_rho(residual2(curf, pts[i], 1.f, 1.f) * vs, w);
+      if (!(w > 0.f)) continue;
+      const float2 a = A[i], q = Bp[i];
+      const double ax = (a.x - cx) / fx - cax, ay = (a.y - cy) / fy - cay, bx = (q.x - cx) / fx - cbx, by = (q.y - cy) / fy - cby;
+      da += sqrt(ax * ax + ay * ay);
+      db += sqrt(bx * bx + by * by);
+    }
+    const double ma = block_sum(da, sh) / cnt, mb = block_sum(db, sh) / cnt;
+    const double sa = M_SQRT2 / ma, sb = M_SQRT2 / mb;
+    if (!(cnt >= REFIT_MIN && ma > 0 && mb > 0 && isfinite(sa) && isfinite(sb))) {  // uniform: block_sum's value
+      if (t == 0) { P.stop = 1; P.cand_ok = 0; }
+      return;
+    }
+    double acc[45];
+#pragma unroll
+    for (int e = 0; e < 45; ++e) acc[e] = 0;
+    for (int i = t; i < n; i += 256) {
+      float w;
+      magsac_rho(residual2(curf, pts[i], 1.f, 1.f) * vs, w);
+      if (!(w > 0.f)) continue;
+      const double wt = w;
+      const float2 a = A[i], q = Bp[i];
+      const double x = ((a.x - cx) / fx - cax) * sa, y = ((a.y - cy) / fy - cay) * sa;
+      const double u = ((q.x - cx) / fx - cbx) * sb, v = ((q.y - cy) / fy - cby) * sb;
+      const double r1[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1};
+      int e = 0;
+#pragma unroll
+      for (int p = 0; p < 9; ++p)
+#pragma unroll
+        for (int q2 = p; q2 < 9; ++q2, ++e) acc[e] += wt * (r1[p] * r1[q2]);
+    }
+#pragma unroll
+    for (int e = 0; e < 45; ++e) {
+      double s = acc[e];
+      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+      if (lane == 0) red[wave][e] = s;
+    }
+    __syncthreads();
+    if (t < 45) {
+      int p = 0, e = t;
+      while (e >= 9 - p) { e -= 9 - p; ++p; }
+      const int q2 = p + e;
+      const double s = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+      Mx[p][q2] = s;
+      Mx[q2][p] = s;
+    } else if (t < 45 + 36) {
+      ev[(t - 45) / 9][(t - 45) % 9] = 0.0;  // a system that is not finite ranks no eigenvector: a zero basis has no solution
+    }
+    __syncthreads();
+    // 2. the eigenvectors of the four smallest eigenvalues (ties: the lower lane first), de-normalised: ev[0 .. 3] = X, Y, Z, W
+    if (wave == 0) {
+      double col[9], vv[9];
+#pragma unroll
+      for (int k = 0; k < 9; ++k) {
+        col[k] = lane < 9 ? Mx[k][lane] : 0.0;
+        vv[k] = lane == k ? 1.0 : 0.0;
+      }
+      jacobi_sweeps<9, 10>(col, vv, lane);
+      const double lam = jacobi_eigenvalue<9>(col, lane);
+      int rk = 0;
+#pragma unroll
+      for (int j = 0; j < 9; ++j) {
+        const double lj = __shfl(lam, j);
+        rk += lj < lam || (lj == lam && j < lane) ? 1 : 0;
+      }
+      if (lane < 9 && rk < 4) {
+        const double ta[9] = {sa, 0, -sa * cax, 0, sa, -sa * cay, 0, 0, 1};
+        const double tbt[9] = {sb, 0, 0, 0, sb, 0, -sb * cbx, -sb * cby, 1};
+        double tmp[9], f[9];
+        mat3(tbt, vv, tmp);
+        mat3(tmp, ta, f);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) ev[3 - rk][k] = f[k];
+      }
+    }
+    __syncthreads();
+    // 3. the solver on the basis
+    double* smg = sm + (t / G) * LDS_PER;
+    const int gl = t % G;
+    {
+      double v[4][9];
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) v[f][k] = ev[f][k];
+      store_basis(v, smg, gl);
+    }
+    double e[9];
+    int rank, nsol;
+    solve_e_basis(true, smg, gl, e, rank, nsol);
+    if (t < G) {
+      if (rank >= 0) {
+        float mf[12];
+        to_f32(e, mf);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) cd[rank][k] = e[k];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) cf[12 * rank + k] = mf[k];
+      }
+      if (t == 0) ncand = nsol;
+    }
+    __syncthreads();
+    // 4. the solution of the smallest score
+    if (wave != 0) return;
+    const int nm = ncand;
+    if (nm == 0) {
+      if (lane == 0) { P.stop = 1; P.cand_ok = 0; }
+      return;
+    }
+    float sc[MAXR];
+    int ct[MAXR];
+    magsac_sums<Essential, MAXR>(cf, nm, pts, n, S, lane, sc, ct);
+    int bs = 0;
+    float bv = sc[0];
+#pragma unroll
+    for (int r = 1; r < MAXR; ++r)
+      if (r < nm && sc[r] < bv) { bv = sc[r]; bs = r; }
+    if (lane != 0) return;
+    double a[3][3], v[3][3], sg[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) {
+        a[j][i] = cd[bs][3 * i + j];
+        v[j][i] = i == j ? 1.0 : 0.0;
+      }
+    jacobi_svd3(a, v, sg, true);
+    const double sm2 = 0.5 * (sg[0] + sg[1]);
+    double m[9], fro = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        m[3 * i + k] = sm2 * ((a[0][i] / sg[0]) * v[0][k] + (a[1][i] / sg[1]) * v[1][k]);
+        fro += m[3 * i + k] * m[3 * i + k];
+      }
+    const double inv = 1.0 / sqrt(fro);
+    int big = 0;
+    bool ok = sg[1] > 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+      m[k] = m[k] * inv;
+      ok = ok && isfinite(m[k]);
+      if (fabs(m[k]) > fabs(m[big])) big = k;
+    }
+    double sgn = 1.0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k)
+      if (k == big && m[k] < 0) sgn = -1.0;
+    P.cand_ok = ok ? 1 : 0;
+    if (ok) {
+      for (int k = 0; k < 9; ++k) P.cand[k] = m[k] * sgn;
+      to_f32(P.cand, P.candf);
+    } else {
+      P.stop = 1;
+    }
+  }
+
+  // E as found or as optimised; info = {rounds, best_h, best_root, best_min, best, valid} (magsac_finish_kernel adds the LO steps)
+  __device__ static void mag_finish(const PairState<Essential>& P, bool good, double* out, int* info) {
+    for (int k = 0; k < 9; ++k) out[k] = good ? P.cur[k] : 0.0;
+    info[0] = P.rounds;
+    info[1] = P.best_h;
+    info[2] = P.best_root;
+    info[3] = P.best_min;
+    info[4] = P.best;
+    info[5] = P.valid;
+  }
 
   // E as found; info = {rounds, best_h, best_root, best, valid}
   __device__ static void finish(const PairState<Essential>& P, bool good, double* out, int* info) {
@@ -596,51 +919,8 @@ __global__ __launch_bounds__(64) void ess_decompose_kernel(const double* __restr
       fin = fin && isfinite(a[j][i]);
       v[j][i] = i == j ? 1.0 : 0.0;
     }
-  for (int sweep = 0; sweep < SVD_SWEEPS && fin; ++sweep) {
-    bool rot = false;
-#pragma unroll
-    for (int pq = 0; pq < 3; ++pq) {
-      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
-      double al = 0, be = 0, ga = 0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        al += a[p][k] * a[p][k];
-        be += a[q][k] * a[q][k];
-        ga += a[p][k] * a[q][k];
-      }
-      if (fabs(ga) > SVD_TOL * sqrt(al * be)) {
-        const double zz = (be - al) / (2 * ga);
-        const double tn = copysign(1.0, zz) / (fabs(zz) + sqrt(1 + zz * zz));
-        const double c = 1 / sqrt(1 + tn * tn), s = c * tn;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const double ap = a[p][k], aq = a[q][k], vp = v[p][k], vq = v[q][k];
-          a[p][k] = c * ap - s * aq;
-          a[q][k] = s * ap + c * aq;
-          v[p][k] = c * vp - s * vq;
-          v[q][k] = s * vp + c * vq;
-        }
-        rot = true;
-      }
-    }
-    if (!rot) break;
-  }
   double sg[3];
-#pragma unroll
-  for (int j = 0; j < 3; ++j) sg[j] = sqrt(a[j][0] * a[j][0] + a[j][1] * a[j][1] + a[j][2] * a[j][2]);
-  // sort descending (columns of A and V together)
-#pragma unroll
-  for (int pass = 0; pass < 3; ++pass) {
-    const int p = pass == 1 ? 1 : 0, q = p + 1;
-    if (sg[q] > sg[p]) {
-      double t = sg[p]; sg[p] = sg[q]; sg[q] = t;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        t = a[p][k]; a[p][k] = a[q][k]; a[q][k] = t;
-        t = v[p][k]; v[p][k] = v[q][k]; v[q][k] = t;
-      }
-    }
-  }
+  jacobi_svd3(a, v, sg, fin);
   double U[9], Vt[9];
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
@@ -779,6 +1059,21 @@ int essential_launch(const float* kpts_a, const float* kpts_b, const int* counts
     return -1;
   return ransac_run<Essential>(kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, false, out_e, out_mask, out_ok,
                                out_info, ws, s);
+}
+
+size_t essential_magsac_workspace_bytes(int B, int N) { return magsac_workspace_bytes<Essential>(B, N); }
+
+int essential_magsac_launch(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                            const double* K, int B, int N, float threshold, double prob, int max_iters, int lo_iters, double* out_e,
+                            unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score, void* ws,
+                            size_t ws_bytes, hipStream_t s) {
+  if (check_args("essential_magsac", "prob",
+                 kpts_a && kpts_b && seeds && out_e && out_mask && out_ok && out_info && out_score && ws, B, N, threshold, prob,
+                 max_iters, ws_bytes, essential_magsac_workspace_bytes(B, N)))
+    return -1;
+  ROMA_REQUIRE(lo_iters >= 0 && lo_iters <= ESSENTIAL_MAGSAC_MAX_LO, "essential_magsac: lo_iters must lie in [0, 64]");
+  return magsac_run<Essential>(kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, lo_iters, out_e, out_mask,
+                               out_ok, out_info, out_score, ws, s);
 }
 
 int essential_minimal_launch(const double* x0, const double* x1, int S, double* out_e, int* out_n, hipStream_t s) {

@@ -9,7 +9,7 @@
 //               space + cubic (up to 3 slots), f64.
 //   inlier      f32 reprojection error in image B (H); distances to both epipolar lines, each image with its own scale (F).
 //   refit       up to REFINE_ITERS times: 9 x 9 normal equations in f64 on the current inliers (fixed-order tree reduction),
-//               smallest eigenvector by one-sided Jacobi on one wave; rank 2 for F.
+//               smallest eigenvector by one-sided Jacobi on one wave (ransac.h: jacobi_min_vec); rank 2 for F.
 //   finish      de-normalised in f64 (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scaled so that [2, 2] = 1; info of RANSAC_INFO ints.
 //   residual2   (MAGSAC++, magsac_run) f32 squared pixel residuals: reprojection error in image B (H), Sampson distance (F).
 //   wrefit      (MAGSAC++) the refit's normal equations weighted by the MAGSAC++ weights of the current model (one IRLS step).
@@ -19,10 +19,8 @@
 namespace roma {
 namespace {
 
-constexpr int JACOBI_SWEEPS = 15;
 constexpr double COLLINEAR_EPS = 1e-4;  // |sin| of a triple's angle below which the triple counts as collinear
 constexpr double CUBIC_EPS = 1e-12;     // relative size below which a leading coefficient of the cubic is zero
-constexpr double JACOBI_TOL = 4 * DBL_EPSILON;
 
 // ------------------------------------------------------------------------------------------------------------ scoring (f32)
 // p = (xa, ya, xb, yb) normalised.  Multiplication forms of the reprojection / epipolar tests: no division, NaN never passes.
@@ -231,58 +229,6 @@ __device__ int solve_f(const double* xa, const double* ya, const double* xb, con
   return n;
 }
 
-// ---- refinement: smallest eigenvector of a symmetric PSD matrix by one-sided (Hestenes) Jacobi on one wave.  Lane j < NC
-// holds column j of M and of V; the P - 1 rounds of the circle method pair every column with every other once per sweep.
-template <int NC, int P>
-__device__ void jacobi_min_vec(double (&a)[NC], double (&v)[NC], int lane, double (&out)[NC]) {
-  for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
-    bool rot = false;
-    for (int r = 0; r < P - 1; ++r) {
-      int pt = lane;
-      if (lane < P) pt = lane == P - 1 ? r : lane == r ? P - 1 : ((2 * r - lane) % (P - 1) + (P - 1)) % (P - 1);
-      double pa[NC], pv[NC];
-#pragma unroll
-      for (int k = 0; k < NC; ++k) { pa[k] = __shfl(a[k], pt); pv[k] = __shfl(v[k], pt); }
-      const bool lo = lane < pt;
-      double al = 0, be = 0, ga = 0;
-#pragma unroll
-      for (int k = 0; k < NC; ++k) {
-        const double ap = lo ? a[k] : pa[k], aq = lo ? pa[k] : a[k];
-        al += ap * ap;
-        be += aq * aq;
-        ga += ap * aq;
-      }
-      if (pt != lane && fabs(ga) > JACOBI_TOL * sqrt(al * be)) {
-        const double z = (be - al) / (2 * ga);
-        const double tn = copysign(1.0, z) / (fabs(z) + sqrt(1 + z * z));
-        const double c = 1 / sqrt(1 + tn * tn), s = c * tn;
-#pragma unroll
-        for (int k = 0; k < NC; ++k) {
-          const double ap = lo ? a[k] : pa[k], aq = lo ? pa[k] : a[k];
-          const double vp = lo ? v[k] : pv[k], vq = lo ? pv[k] : v[k];
-          a[k] = lo ? c * ap - s * aq : s * ap + c * aq;
-          v[k] = lo ? c * vp - s * vq : s * vp + c * vq;
-        }
-        rot = true;
-      }
-    }
-    if (!__any(rot)) break;
-  }
-  // column norms of M V are the eigenvalues: the smallest one's column of V (lowest lane on ties)
-  double nrm = 0;
-#pragma unroll
-  for (int k = 0; k < NC; ++k) nrm += a[k] * a[k];
-  if (lane >= NC) nrm = INFINITY;
-  int bl = lane;
-  for (int off = 32; off > 0; off >>= 1) {
-    const double on = __shfl_xor(nrm, off);
-    const int ol = __shfl_xor(bl, off);
-    if (on < nrm || (on == nrm && ol < bl)) { nrm = on; bl = ol; }
-  }
-#pragma unroll
-  for (int k = 0; k < NC; ++k) out[k] = __shfl(v[k], bl);
-}
-
 // ------------------------------------------------------------------------------------------------------------ model policies
 // what H and F share: Hartley normalisation, one thread per hypothesis, the least-squares refit and the de-normalisation.
 // Model supplies MODEL, S, SLOTS, REFIT_MIN, inlier and solve.
@@ -295,10 +241,12 @@ struct Hartley {
       xb = (q.x - cb[0]) * sb; yb = (q.y - cb[1]) * sb;
     }
   };
-  static constexpr int HYP_THREADS = 64, HYP_LANES = 1, REFINE_ITERS = 3, INFO = RANSAC_INFO;
+  static constexpr int HYP_THREADS = 64, HYP_LANES = 1, REFINE_ITERS = 3, INFO = RANSAC_INFO, MAG_INFO = MAGSAC_INFO;
   // score all (at most 3) slots of a hypothesis, used or not: every model's coefficients then stay in registers across the
   // point loop, where a branch per slot reloads them (35 % slower for F); unused slots hold zeros and their counts are dropped
   static constexpr bool SCORE_EVERY_SLOT = true;
+
+  __device__ static double mag_thr2(const Norm&, float thr) { return (double)thr * thr; }  // residuals in pixels
 
   __device__ static void res_scales(const Norm& nm, float& sa2, float& sb2) {  // the scales of M::residual2
     sa2 = (float)(nm.sa * nm.sa);
@@ -490,6 +438,8 @@ struct Hartley {
     fit<true>(A, Bp, P, nullptr, pts, &S);
   }
 
+  __device__ static void mag_finish(const PairState<Model>& P, bool good, double* out, int* info) { finish(P, good, out, info); }
+
   // de-normalise (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scale; info = {rounds, best_h, best_root, best_min, best, valid}
   __device__ static void finish(const PairState<Model>& P, bool good, double* out, int* info) {
     const Norm& q = P.nrm;
@@ -588,10 +538,10 @@ int magsac_launch(int model, const float* kpts_a, const float* kpts_b, const int
     return -1;
   ROMA_REQUIRE(lo_iters >= 0 && lo_iters <= MAGSAC_MAX_LO, "magsac: lo_iters must lie in [0, 64]");
   return model == RANSAC_HOMOGRAPHY
-             ? magsac_run<Homography>(kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, lo_iters, out_model,
-                                      out_mask, out_ok, out_info, out_score, ws, s)
-             : magsac_run<Fundamental>(kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, lo_iters, out_model,
-                                       out_mask, out_ok, out_info, out_score, ws, s);
+             ? magsac_run<Homography>(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, lo_iters,
+                                      out_model, out_mask, out_ok, out_info, out_score, ws, s)
+             : magsac_run<Fundamental>(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, lo_iters,
+                                       out_model, out_mask, out_ok, out_info, out_score, ws, s);
 }
 
 }  // namespace roma

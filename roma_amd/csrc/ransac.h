@@ -15,7 +15,8 @@
 //      model), ransac_refit_kernel (M::refit: a least-squares candidate), ransac_accept_kernel (re-score; the candidate is kept
 //      if its inlier count is not lower, else refinement stops).
 //   4. ransac_mask_kernel + ransac_finish_kernel: final mask, ok flag, M::finish (model in pixel terms, info row).
-// magsac_run (below) is the same pipeline with MAGSAC++ scoring and IRLS local optimisation (tools/magsac_ref.py).
+// magsac_run (below) is the same pipeline with MAGSAC++ scoring and IRLS local optimisation (tools/magsac_ref.py for H and F,
+// tools/essential_magsac_ref.py for E).
 // Every flag and counter of the workspace is written with plain stores by one kernel and read by a later launch on the same
 // stream: no atomics and no hand-off inside a launch.  Results are bit-identical from run to run and independent of B.
 #pragma once
@@ -151,6 +152,73 @@ __device__ __forceinline__ void to_f32(const double* m, float* mf) {  // the 12-
   for (int k = 0; k < 9; ++k) mf[k] = (float)m[k];
 #pragma unroll
   for (int k = 9; k < 12; ++k) mf[k] = 0.f;
+}
+
+// ---- symmetric PSD eigenproblems by one-sided (Hestenes) Jacobi on one wave (the refits' 9 x 9 normal equations).  Lane j < NC
+// holds column j of M and of V; the P - 1 rounds of the circle method pair every column with every other once per sweep.
+// Afterwards the column norms of M V are the eigenvalues and the columns of V the eigenvectors.
+constexpr int JACOBI_SWEEPS = 15;
+constexpr double JACOBI_TOL = 4 * DBL_EPSILON;
+
+template <int NC, int P>
+__device__ __forceinline__ void jacobi_sweeps(double (&a)[NC], double (&v)[NC], int lane) {
+  for (int sweep = 0; sweep < JACOBI_SWEEPS; ++sweep) {
+    bool rot = false;
+    for (int r = 0; r < P - 1; ++r) {
+      int pt = lane;
+      if (lane < P) pt = lane == P - 1 ? r : lane == r ? P - 1 : ((2 * r - lane) % (P - 1) + (P - 1)) % (P - 1);
+      double pa[NC], pv[NC];
+#pragma unroll
+      for (int k = 0; k < NC; ++k) { pa[k] = __shfl(a[k], pt); pv[k] = __shfl(v[k], pt); }
+      const bool lo = lane < pt;
+      double al = 0, be = 0, ga = 0;
+#pragma unroll
+      for (int k = 0; k < NC; ++k) {
+        const double ap = lo ? a[k] : pa[k], aq = lo ? pa[k] : a[k];
+        al += ap * ap;
+        be += aq * aq;
+        ga += ap * aq;
+      }
+      if (pt != lane && fabs(ga) > JACOBI_TOL * sqrt(al * be)) {
+        const double z = (be - al) / (2 * ga);
+        const double tn = copysign(1.0, z) / (fabs(z) + sqrt(1 + z * z));
+        const double c = 1 / sqrt(1 + tn * tn), s = c * tn;
+#pragma unroll
+        for (int k = 0; k < NC; ++k) {
+          const double ap = lo ? a[k] : pa[k], aq = lo ? pa[k] : a[k];
+          const double vp = lo ? v[k] : pv[k], vq = lo ? pv[k] : v[k];
+          a[k] = lo ? c * ap - s * aq : s * ap + c * aq;
+          v[k] = lo ? c * vp - s * vq : s * vp + c * vq;
+        }
+        rot = true;
+      }
+    }
+    if (!__any(rot)) break;
+  }
+}
+
+// the eigenvalue of this lane's column (+inf for lanes that hold none)
+template <int NC>
+__device__ __forceinline__ double jacobi_eigenvalue(const double (&a)[NC], int lane) {
+  double nrm = 0;
+#pragma unroll
+  for (int k = 0; k < NC; ++k) nrm += a[k] * a[k];
+  return lane >= NC ? INFINITY : nrm;
+}
+
+// smallest eigenvector (lowest lane on ties), on every lane
+template <int NC, int P>
+__device__ void jacobi_min_vec(double (&a)[NC], double (&v)[NC], int lane, double (&out)[NC]) {
+  jacobi_sweeps<NC, P>(a, v, lane);
+  double nrm = jacobi_eigenvalue<NC>(a, lane);
+  int bl = lane;
+  for (int off = 32; off > 0; off >>= 1) {
+    const double on = __shfl_xor(nrm, off);
+    const int ol = __shfl_xor(bl, off);
+    if (on < nrm || (on == nrm && ol < bl)) { nrm = on; bl = ol; }
+  }
+#pragma unroll
+  for (int k = 0; k < NC; ++k) out[k] = __shfl(v[k], bl);
 }
 
 // ------------------------------------------------------------------------------------------------------------ state, workspace
@@ -468,14 +536,16 @@ int ransac_run(const float* kpts_a, const float* kpts_b, const int* counts, cons
 // ------------------------------------------------------------------------------------------------------------ MAGSAC++
 // The same pipeline with MAGSAC++ scoring (Barath et al., CVPR 2020; nu = 4; tools/magsac_ref.py restates it): a model's score
 // is the sum over the pair's rows of the loss rho(V), V = r^2 k^2 / (2 tau^2) with r the model's pixel residual (M::residual2)
-// and tau the threshold; lower is better.  Sampling rounds, hypotheses and slots are those above (ransac_norm_kernel and
-// ransac_hyp_kernel are shared); what changes:
+// and tau the threshold (M::mag_thr2: both in the model's own units - pixels for H and F, normalised camera coordinates for E);
+// lower is better.  Sampling rounds, hypotheses and slots are those above (ransac_norm_kernel and ransac_hyp_kernel are shared);
+// what changes:
 //   magsac_score_kernel  one wave per hypothesis: compensated f32 sum of rho per slot (lane partials over rows i = lane mod 64
 //                        ascending, then a fixed butterfly), and the count r < tau for the adaptive iteration count
 //   magsac_select_kernel arg-min (ties: lowest (h, slot)); the running best changes only on a strictly smaller score
 //   lo_iters times magsac_refit_kernel (M::wrefit: IRLS step, weights w(V) of the current model) and magsac_accept_kernel (the
 //   candidate is kept only if its score is strictly lower - the gain measured paired, on the same rows - else LO stops); then
-//   the mask r < tau and magsac_finish_kernel.
+//   the mask r < tau and magsac_finish_kernel (M::mag_finish: the model and the first M::MAG_INFO - 1 entries of the info row).
+// From the policy it needs residual2 / res_terms / r2_from / NT, res_scales, mag_thr2, wrefit, mag_finish, MAG_INFO.
 constexpr double MAGSAC_K2 = 13.276704135987625;      // 0.99 quantile of chi^2 with 4 DoF
 constexpr float MAGSAC_VK = 6.638352067993813f;       // k^2 / 2
 constexpr float MAGSAC_GK = 0.003611260617758621f;    // Gamma(3/2, V_k)
@@ -577,7 +647,7 @@ __device__ __forceinline__ void magsac_sums(const float* mf, int nm, const float
   for (int r = 0; r < SL; ++r) acc[r] = wave_total(acc[r], cmp[r]);
 }
 
-// one thread per pair: residual scales, V scale, threshold
+// one thread per pair: residual scales, V scale, threshold (M::mag_thr2: tau^2 in the units of M::residual2)
 template <class M>
 __global__ __launch_bounds__(64) void magsac_init_kernel(int B, float thr, const PairState<M>* __restrict__ st,
                                                          MagState* __restrict__ ms) {
@@ -585,7 +655,7 @@ __global__ __launch_bounds__(64) void magsac_init_kernel(int B, float thr, const
   if (b >= B) return;
   MagState& S = ms[b];
   M::res_scales(st[b].nrm, S.sa2, S.sb2);
-  const double t2 = (double)thr * thr;
+  const double t2 = M::mag_thr2(st[b].nrm, thr);
   S.vs = (float)(MAGSAC_K2 / (2 * t2));
   S.t2 = (float)t2;
   S.score = INFINITY;
@@ -743,7 +813,7 @@ __global__ __launch_bounds__(256) void magsac_mask_kernel(const float4* __restri
   mask[(long)b * N + i] = in ? 1 : 0;
 }
 
-// one thread per pair: ok flag, M::finish (model, the first M::INFO entries of the info row), LO steps, scores (the final sum
+// one thread per pair: ok flag, M::mag_finish (model, the first M::MAG_INFO - 1 entries of the info row), LO steps, scores (the final sum
 // of rho is the winning minimal model's less the gains of the accepted LO steps)
 template <class M>
 __global__ __launch_bounds__(64) void magsac_finish_kernel(int B, const PairState<M>* __restrict__ st, const MagState* __restrict__ ms,
@@ -754,8 +824,8 @@ __global__ __launch_bounds__(64) void magsac_finish_kernel(int B, const PairStat
   const PairState<M>& P = st[b];
   const MagState& S = ms[b];
   const bool good = P.valid && P.best > 0;
-  M::finish(P, good, out + (long)b * 9, info + (long)b * (M::INFO + 1));
-  info[(long)b * (M::INFO + 1) + M::INFO] = S.lo_steps;
+  M::mag_finish(P, good, out + (long)b * 9, info + (long)b * M::MAG_INFO);
+  info[(long)b * M::MAG_INFO + M::MAG_INFO - 1] = S.lo_steps;
   const bool found = P.best_h >= 0;
   score[2 * (long)b] = found ? (double)S.score_min : 0.0;
   score[2 * (long)b + 1] = found ? (double)S.score_min - S.gain : 0.0;
@@ -763,14 +833,15 @@ __global__ __launch_bounds__(64) void magsac_finish_kernel(int B, const PairStat
 }
 
 template <class M>
-int magsac_run(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B, int N, float thr,
+int magsac_run(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K, int B,
+               int N, float thr,
                double conf, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask, unsigned char* out_ok,
                int* out_info, double* out_score, void* ws, hipStream_t s) {
   const MagCarve<M> w = magsac_carve<M>(align_base<void*>(ws), B, N);
   const Carve<M>& c = w.c;
   const float2* ka = reinterpret_cast<const float2*>(kpts_a);
   const float2* kb = reinterpret_cast<const float2*>(kpts_b);
-  hipLaunchKernelGGL(ransac_norm_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, counts, nullptr, N, thr, max_iters, c.st, c.pts);
+  hipLaunchKernelGGL(ransac_norm_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, counts, K, N, thr, max_iters, c.st, c.pts);
   ROMA_LAUNCH_CHECK();
   hipLaunchKernelGGL(magsac_init_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, thr, c.st, w.ms);
   ROMA_LAUNCH_CHECK();

@@ -16,7 +16,9 @@ are scaled so that [2, 2] = 1 (unit Frobenius norm where |[2, 2]| < 1e-12 of it)
 The relative pose of the reference's pose benchmarks (romatch/utils/utils.py estimate_pose: cv2.findEssentialMat + cv2.recoverPose)
 runs on the device as well (`roma_op_essential` / `roma_op_recover_pose`, csrc/essential.hip): `find_essential`, `recover_pose`,
 `estimate_pose`, `estimate_pose_uncalibrated` and the five-point solver alone, `essential_minimal`.  Restated in numpy float64 by
-tools/essential_ref.py.  `refine_pose` (`roma_op_refine_pose`, csrc/pose_refine.hip) fits the recovered pose to its inliers by
+tools/essential_ref.py.  method="magsac" there (`essential_magsac`, `roma_op_essential_magsac`) scores the five-point models by the
+MAGSAC++ loss of their Sampson distance and optimises the winner over all the rows it weighs; restated by
+tools/essential_magsac_ref.py.  `refine_pose` (`roma_op_refine_pose`, csrc/pose_refine.hip) fits the recovered pose to its inliers by
 Levenberg-Marquardt on the truncated Sampson error, as the reference's PoseLib benchmark does; restated by tools/pose_refine_ref.py.
 """
 from __future__ import annotations
@@ -302,16 +304,57 @@ def essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max
                    (float(threshold), float(prob), int(max_iters)))
 
 
-def find_essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None):
+def essential_magsac(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, lo_iters=10,
+                     counts=None):
+    """`essential` with MAGSAC++ scoring and local optimisation (roma_op_essential_magsac; Barath et al., CVPR 2020, nu = 4, as
+    restated in tools/essential_magsac_ref.py), no host synchronisation.  The sampling of `essential` (same samples, five-point
+    models and adaptive iteration count), but each model is scored by the sum over the pair's rows of the MAGSAC++ loss of its
+    Sampson distance in normalised camera coordinates and the smallest score wins; then up to lo_iters IRLS steps - the
+    MAGSAC++ weights of the current model, the weighted eight-point system over the rows of positive weight (at least 8), the
+    five-point solver's cubic constraints on its four smallest eigenvectors - each kept only if the score drops.  threshold
+    (divided by (fx + fy) / 2 under a camera matrix) is the largest residual that counts as an inlier.  lo_iters=0 returns the
+    winning five-point model untouched.
+
+    Inputs as for `essential`.  Returns (E [B, 3, 3] float64 on the essential manifold, unit norm, largest-magnitude entry
+    positive; mask [B, N] bool (residual < threshold: `essential`'s inlier rule); ok [B] bool; info [B, 7] int32; score [B, 2]
+    float64) with info = (rounds run, winning hypothesis, its root, inliers of the winning minimal model, final inliers, pair
+    valid, LO steps accepted) and score = (loss of the winning minimal model, final loss)."""
+    a, b = _pair_batch(kpts_A, kpts_B)
+    if not (threshold > 0) or not (0 <= prob <= 1) or int(max_iters) <= 0:
+        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= prob <= 1, max_iters > 0")
+    if not (0 <= int(lo_iters) <= MAGSAC_MAX_LO):
+        raise ValueError(f"roma_amd.geometry: lo_iters must lie in [0, {MAGSAC_MAX_LO}]")
+    return _robust("essential_magsac", a, 5, 7, seed, counts,
+                   lambda counts, seeds: (a, b, counts, seeds, _cameras(camera_matrix, int(a.shape[0]), a.device)),
+                   (float(threshold), float(prob), int(max_iters), int(lo_iters)), nscore=2)
+
+
+def _check_method(method):
+    if method not in ("ransac", "magsac"):
+        raise ValueError(f"roma_amd.geometry: method must be 'ransac' or 'magsac', got {method!r}")
+
+
+def _essential(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, counts, method, lo_iters):
+    """(E, mask, ok) of `essential` (method "ransac") or `essential_magsac` (method "magsac")"""
+    _check_method(method)
+    if method == "ransac":
+        return essential(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, counts)[:3]
+    return essential_magsac(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, lo_iters, counts)[:3]
+
+
+def find_essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None,
+                   method="ransac", lo_iters=10):
     """cv2.findEssentialMat(kpts_A, kpts_B, camera_matrix, cv2.RANSAC, prob, threshold, max_iters) on the device: Nister's
     five-point hypotheses (up to 10 models each), inliers whose Sampson distance is below the threshold, no refinement.
+    method="magsac": the same sampling with MAGSAC++ scoring and up to lo_iters steps of local optimisation
+    (`essential_magsac`); lo_iters is not read otherwise.  The defaults leave every output as it was before the keywords existed.
     camera_matrix None means identity (the points are normalised already, as the reference calls it); a [3, 3] or [B, 3, 3]
     matrix normalises x_n = ((x - cx) / fx, (y - cy) / fy) and divides the threshold by (fx + fy) / 2, like OpenCV.  E relates
     the normalised points (x_B^T E x_A = 0), has unit Frobenius norm and its largest-magnitude entry positive.
 
     kpts_A, kpts_B: [N, 2] -> (E [3, 3] float64, mask [N] bool) or (None, None) when no model was found;
     [B, N, 2] -> (E [B, 3, 3], mask [B, N], ok [B]) with no host synchronisation.  See `ransac` for seed and counts."""
-    E, mask, ok, _ = essential(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, counts)
+    E, mask, ok = _essential(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, counts, method, lo_iters)
     return _front(kpts_A, (E, mask), ok, (None, None))
 
 
@@ -457,7 +500,8 @@ def _refined(R, t, good, ok, x0, x1, thr, counts):
     return R, t, torch.where(info[:, 3:4] > 0, mask, good)
 
 
-def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=1000, seed=None, counts=None, refine=False):
+def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=1000, seed=None, counts=None, refine=False,
+                  method="ransac"):
     """romatch/utils/utils.py:30-51 on the device: normalise with the inverse of K[:2, :2] and the principal point (f64), then
     find_essential (identity camera, threshold norm_thresh, prob conf) and recover_pose.
 
@@ -468,10 +512,15 @@ def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=100
 
     refine=True: the recovered pose, which is the winning five-point sample's, then goes through `refine_pose` (threshold
     norm_thresh, 25 steps; pairs without a pose are left alone) and mask is the refined one.  The default leaves every output
-    as it was before the keyword existed."""
+    as it was before the keyword existed.
+
+    method="magsac": E comes from `essential_magsac` (MAGSAC++ scoring, 10 steps of local optimisation over all the rows it
+    weighs) instead of `essential`; recover_pose and refine=True follow as above.  The default "ransac" leaves every output as
+    it was before the keyword existed."""
+    _check_method(method)
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
     x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
-    E, inl, ok, _ = essential(x0, x1, None, conf, norm_thresh, max_iters, seed, counts)
+    E, inl, ok = _essential(x0, x1, None, conf, norm_thresh, max_iters, seed, counts, method, 10)
     n, R, t, good = recover_pose(E, x0, x1, inl, None, 1e9, counts)
     ok = ok & (n > 0)
     if refine:
@@ -486,7 +535,7 @@ def _mean_focal(K0, K1):
 
 
 def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=10000, seed=None, counts=None,
-                               refine=False):
+                               refine=False, method="ransac"):
     """romatch/utils/utils.py:53-74 on the device: find_fundamental on the pixels (threshold norm_thresh in pixels, as the
     reference passes it; plain RANSAC + LO standing in for USAC_ACCURATE), E = K1^T F K0, then recover_pose on the normalised
     points.  Returns as estimate_pose.
@@ -494,10 +543,15 @@ def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, 
     refine=True: as in estimate_pose.  The refinement works on normalised points, so it gets norm_thresh divided by the mean of
     the four focal lengths (fx, fy of K0 and of K1; over all pairs where the matrices are [B, 3, 3]).  That mean is a host
     number: camera matrices given on the host (numpy, CPU tensors) cost nothing, matrices that live on the device are read back
-    once, which is the one host synchronisation of this option."""
+    once, which is the one host synchronisation of this option.
+
+    method="magsac": F comes from `magsac` (MAGSAC++ scoring and IRLS local optimisation, lo_iters 10) instead of `ransac` - the
+    USAC-style estimator the reference asks OpenCV for.  The default "ransac" leaves every output as it was before the keyword
+    existed."""
+    _check_method(method)
     focal = _mean_focal(K0, K1) if refine else None
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
-    F, inl, ok, _ = ransac(FUNDAMENTAL, a, b, norm_thresh, conf, max_iters, seed, True, counts)
+    F, inl, ok = _estimate(FUNDAMENTAL, a, b, norm_thresh, conf, max_iters, seed, True, counts, method)
     E = K1.transpose(1, 2) @ F @ K0
     x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
     n, R, t, good = recover_pose(E, x0, x1, inl, None, 1e9, counts)

@@ -214,9 +214,18 @@ def five_point(x0, x1):
     """Nister's five-point solver on samples [M, 5, 2]: (E [M, 10, 3, 3] unit norm, largest-magnitude entry positive, zeros
     beyond n; n [M]) in ascending order of z"""
     x0, x1 = np.asarray(x0, dtype=np.float64), np.asarray(x1, dtype=np.float64)
-    m = len(x0)
     with np.errstate(all="ignore"):
         basis, ok = null_basis(x0, x1)
+    return solve_basis(basis, ok)
+
+
+def solve_basis(basis, ok):
+    """the solver from a unit-norm basis X, Y, Z, W [M, 9, 4] on (five_point: a sample's null space; essential_magsac_ref: the
+    least-squares null space of more rows): the real E = x X + y Y + z Z + W that satisfy the cubic constraints, as five_point
+    returns them"""
+    m = len(basis)
+    ok = np.array(ok, dtype=bool)
+    with np.errstate(all="ignore"):
         red, ok2 = gauss_jordan10(constraints(basis))
         ok &= ok2
         bx, by, b1 = nister_rows(red)
