@@ -13,7 +13,7 @@ size_t essential_workspace_bytes(int B, int N);
 int essential_launch(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K,
                      int B, int N, float threshold, double prob, int max_iters, double* out_e, unsigned char* out_mask,
                      unsigned char* out_ok, int* out_info, void* ws, size_t ws_bytes, hipStream_t s);
-// The same sampling with MAGSAC++ scoring and local optimisation (ransac.h magsac_run, tools/essential_magsac_ref.py): a model's
+// The same sampling with MAGSAC++ scoring and local optimisation (ransac.h MagsacScoring, tools/essential_magsac_ref.py): a model's
 // score is the sum of the MAGSAC++ loss of its Sampson distance in normalised camera coordinates, then up to lo_iters (0 ..
 // ESSENTIAL_MAGSAC_MAX_LO) IRLS steps, each kept only if the score drops.  Inputs as for essential_launch.  info
 // [B, ESSENTIAL_MAGSAC_INFO] = {rounds, winning hypothesis, its root, inliers of the winning minimal model, final inliers, pair

@@ -6,11 +6,12 @@
 //   normalise   x_n = ((x - cx) / fx, (y - cy) / fy) in f64 (identity without a camera matrix), thr_n = thr / ((fx + fy) / 2).
 //               No Hartley normalisation: it would break the essential constraints.
 //   hypothesis  16 lanes per hypothesis: Nister's five-point solver in f64 (below), up to 10 slots.
-//   inlier      f32 Sampson test.
-//   finish      E as found, info of ESSENTIAL_INFO ints.  No refinement (OpenCV has none here).
-//   residual2   (MAGSAC++, magsac_run) f32 squared Sampson distance in normalised camera coordinates: inlier_e's quantities.
-//   wrefit      (MAGSAC++) one IRLS step: the weighted eight-point system over the rows of positive weight, its four smallest
+//   res_terms   the f32 scoring's terms linear in the model: the epipolar terms (ransac.h: epipolar_terms).
+//   inlier      (CountScoring) from them: the Sampson test.  No refinement (REFINE_ITERS = 0: OpenCV has none here).
+//   residual2   (MagsacScoring) from them: squared Sampson distance in normalised camera coordinates.
+//   wrefit      (MagsacScoring) one IRLS step: the weighted eight-point system over the rows of positive weight, its four smallest
 //               eigenvectors as the basis of the solver below, the solution of the smallest score (Essential::wrefit).
+//   model_out   E as found or as optimised.  Info rows of ESSENTIAL_INFO (no best_min) and ESSENTIAL_MAGSAC_INFO ints.
 //
 // The five-point solver (D. Nister, PAMI 2004): null space X, Y, Z, W of the 5 x 9 epipolar system (Gauss-Jordan, then modified
 // Gram-Schmidt: an orthonormal basis keeps the elimination below well conditioned), the ten cubic constraints det E = 0 and
@@ -44,36 +45,6 @@ constexpr double GN_REACH = 1e-2;         // relative length of a Gauss-Newton s
 constexpr double E_PIVOT_EPS = 1e-10;     // |pivot| of the 10 x 20 elimination (unit-norm null basis)
 constexpr int SVD_SWEEPS = 20;
 constexpr double SVD_TOL = 4 * DBL_EPSILON;
-
-// ------------------------------------------------------------------------------------------------------------ scoring (f32)
-// p = (x0, y0, x1, y1) normalised.  Sampson test in multiplication form: (x1^T E x0)^2 < thr^2 (|E x0|_{1,2}^2 + |E^T x1|_{1,2}^2)
-__device__ __forceinline__ bool inlier_e(const float* m, float4 p, float t2) {
-  const float lx = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
-  const float ly = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
-  const float lz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
-  const float d = fmaf(p.z, lx, fmaf(p.w, ly, lz));
-  const float kx = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
-  const float ky = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
-  return d * d < t2 * (fmaf(lx, lx, ly * ly) + fmaf(kx, kx, ky * ky));
-}
-
-// MAGSAC++ (magsac_run): the squared Sampson distance in normalised camera coordinates, d^2 / ((l_x^2 + l_y^2) + (k_x^2 + k_y^2)) -
-// the quantities inlier_e compares, so r^2 < thr^2 is its test up to the rounding of the division.  Split like the H and F
-// residuals of geometry.hip into terms linear in the model (d, l_x, l_y, k_x, k_y) and the residual formed from them.
-__device__ __forceinline__ void res_terms_e(const float* m, float4 p, float (&t)[5]) {
-  const float lx = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
-  const float ly = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
-  const float lz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
-  t[0] = fmaf(p.z, lx, fmaf(p.w, ly, lz));
-  t[1] = lx;
-  t[2] = ly;
-  t[3] = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
-  t[4] = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
-}
-
-__device__ __forceinline__ float r2_from_e(const float (&t)[5]) {
-  return t[0] * t[0] / (fmaf(t[1], t[1], t[2] * t[2]) + fmaf(t[3], t[3], t[4] * t[4]));
-}
 
 // ------------------------------------------------------------------------------------------------------------ five-point solver
 // Nister's column order of the cubic constraints: x^3 y^3 x^2y xy^2 x^2z x^2 y^2z y^2 xyz xy | xz^2 xz x yz^2 yz y z^3 z^2 z 1
@@ -574,7 +545,7 @@ __device__ __forceinline__ void jacobi_svd3(double (&a)[3][3], double (&v)[3][3]
 }
 
 // ------------------------------------------------------------------------------------------------------------ model policy
-struct Essential {
+struct Essential : Terms<Essential> {
   struct Norm {
     double fx, fy, cx, cy;  // x_n = (x - c) / f
     __device__ void apply(float2 a, float2 q, double& xa, double& ya, double& xb, double& yb) const {
@@ -622,26 +593,28 @@ struct Essential {
     if (gl == 0) sl.n[g] = nsol;
   }
 
-  __device__ static bool inlier(const float* m, float4 p, float t2, float) { return inlier_e(m, p, t2); }
+  // the f32 scoring on the epipolar terms (d, l_x, l_y, k_x, k_y) of p = (x0, y0, x1, y1) normalised.  Sampson test in
+  // multiplication form: (x1^T E x0)^2 < thr^2 (|E x0|_{1,2}^2 + |E^T x1|_{1,2}^2); MAGSAC++: the squared Sampson distance
+  // d^2 / ((l_x^2 + l_y^2) + (k_x^2 + k_y^2)) - the same quantities, so r^2 < thr^2 is that test up to the rounding of the division
+  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) { epipolar_terms(m, p, t); }
+  __device__ static bool inlier_from(const float (&t)[NT], float t2, float) {
+    return t[0] * t[0] < t2 * (fmaf(t[1], t[1], t[2] * t[2]) + fmaf(t[3], t[3], t[4] * t[4]));
+  }
+  __device__ static float r2_from(const float (&t)[NT], float, float) {
+    return t[0] * t[0] / (fmaf(t[1], t[1], t[2] * t[2]) + fmaf(t[3], t[3], t[4] * t[4]));
+  }
 
-  // ---- MAGSAC++ (magsac_run): residuals in normalised camera coordinates, so no scales and tau = thr_n of normalise
+  // ---- MAGSAC++ (MagsacScoring): residuals in normalised camera coordinates, so no scales and tau = thr_n of normalise
   __device__ static void res_scales(const Norm&, float& sa2, float& sb2) { sa2 = sb2 = 1.f; }
   __device__ static double mag_thr2(const Norm& nm, float thr) {
     const double thr_n = (double)thr / ((nm.fx + nm.fy) * 0.5);
     return thr_n * thr_n;
   }
-  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) { res_terms_e(m, p, t); }
-  __device__ static float r2_from(const float (&t)[NT], float, float) { return r2_from_e(t); }
-  __device__ static float residual2(const float* m, float4 p, float, float) {
-    float t[NT];
-    res_terms_e(m, p, t);
-    return r2_from_e(t);
-  }
 
-  // One IRLS step of the local optimisation, every thread of the 256 (magsac_refit_kernel):
+  // One IRLS step of the local optimisation, every thread of the 256 (ransac_refit_kernel):
   //   1. over the rows of positive MAGSAC++ weight under the current model (at least REFIT_MIN, else LO stops): Hartley
-  //      normalisation of both images, then the weighted eight-point normal equations sum w_i a_i a_i^T (f64, the reduction
-  //      tree of Hartley<>::fit);
+  //      normalisation of both images (hartley_moments), then the weighted eight-point normal equations sum w_i a_i a_i^T
+  //      (normal_equations: what Hartley<>::fit runs);
   //   2. wave 0: their eigenvectors by one-sided Jacobi; those of the four smallest eigenvalues, de-normalised (Tb^T F_n Ta),
   //      span the least-squares null space;
   //   3. the five-point solver on that basis (solve_e_basis; W the smallest eigenvector): the E of the span that satisfy the
@@ -654,7 +627,6 @@ struct Essential {
   __device__ static void wrefit(const float2* A, const float2* Bp, const float4* pts, PairState<Essential>& P, const MagState& S) {
     __shared__ double sm[GPB * LDS_PER];
     __shared__ double sh[256];
-    __shared__ double red[4][45];
     __shared__ double Mx[9][9];
     __shared__ double ev[4][9];
     __shared__ double cd[MAXR][9];
@@ -673,69 +645,37 @@ struct Essential {
       return;
     }
     // 1. Hartley normalisation over the rows of positive weight (NaN rows have none)
-    double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
-    for (int i = t; i < n; i += 256) {
-      float w;
+    const auto weight = [&](int i, float& w) {
       magsac_rho(residual2(curf, pts[i], 1.f, 1.f) * vs, w);
-      if (!(w > 0.f)) continue;
-      const float2 a = A[i], q = Bp[i];
-      s0 += (a.x - cx) / fx; s1 += (a.y - cy) / fy; s2 += (q.x - cx) / fx; s3 += (q.y - cy) / fy; s4 += 1;
-    }
-    const double cnt = block_sum(s4, sh);
-    const double cax = block_sum(s0, sh) / cnt, cay = block_sum(s1, sh) / cnt;
-    const double cbx = block_sum(s2, sh) / cnt, cby = block_sum(s3, sh) / cnt;
-    double da = 0, db = 0;
-    for (int i = t; i < n; i += 256) {
+      return w > 0.f;
+    };
+    const HartleyMoments hm = hartley_moments(n, [&](int i, double& ax, double& ay, double& bx, double& by) {
       float w;
-      magsac_rho(residual2(curf, pts[i], 1.f, 1.f) * vs, w);
-      if (!(w > 0.f)) continue;
+      if (!weight(i, w)) return false;
       const float2 a = A[i], q = Bp[i];
-      const double ax = (a.x - cx) / fx - cax, ay = (a.y - cy) / fy - cay, bx = (q.x - cx) / fx - cbx, by = (q.y - cy) / fy - cby;
-      da += sqrt(ax * ax + ay * ay);
-      db += sqrt(bx * bx + by * by);
-    }
-    const double ma = block_sum(da, sh) / cnt, mb = block_sum(db, sh) / cnt;
-    const double sa = M_SQRT2 / ma, sb = M_SQRT2 / mb;
-    if (!(cnt >= REFIT_MIN && ma > 0 && mb > 0 && isfinite(sa) && isfinite(sb))) {  // uniform: block_sum's value
+      ax = (a.x - cx) / fx; ay = (a.y - cy) / fy; bx = (q.x - cx) / fx; by = (q.y - cy) / fy;
+      return true;
+    }, sh);
+    if (!hm.ok(REFIT_MIN)) {  // uniform: block_sum's value
       if (t == 0) { P.stop = 1; P.cand_ok = 0; }
       return;
     }
-    double acc[45];
-#pragma unroll
-    for (int e = 0; e < 45; ++e) acc[e] = 0;
-    for (int i = t; i < n; i += 256) {
+    const double cax = hm.cax, cay = hm.cay, cbx = hm.cbx, cby = hm.cby, sa = hm.sa, sb = hm.sb;
+    if (t >= 45 && t < 45 + 36)
+      ev[(t - 45) / 9][(t - 45) % 9] = 0.0;  // a system that is not finite ranks no eigenvector: a zero basis has no solution
+    normal_equations<true, false>(n, [&](int i, double& wt) {
       float w;
-      magsac_rho(residual2(curf, pts[i], 1.f, 1.f) * vs, w);
-      if (!(w > 0.f)) continue;
-      const double wt = w;
+      const bool pos = weight(i, w);
+      wt = w;
+      return pos;
+    }, [&](int i, double (&r1)[9], double (&)[9]) {
       const float2 a = A[i], q = Bp[i];
       const double x = ((a.x - cx) / fx - cax) * sa, y = ((a.y - cy) / fy - cay) * sa;
       const double u = ((q.x - cx) / fx - cbx) * sb, v = ((q.y - cy) / fy - cby) * sb;
-      const double r1[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1};
-      int e = 0;
+      const double e1[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1};
 #pragma unroll
-      for (int p = 0; p < 9; ++p)
-#pragma unroll
-        for (int q2 = p; q2 < 9; ++q2, ++e) acc[e] += wt * (r1[p] * r1[q2]);
-    }
-#pragma unroll
-    for (int e = 0; e < 45; ++e) {
-      double s = acc[e];
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-      if (lane == 0) red[wave][e] = s;
-    }
-    __syncthreads();
-    if (t < 45) {
-      int p = 0, e = t;
-      while (e >= 9 - p) { e -= 9 - p; ++p; }
-      const int q2 = p + e;
-      const double s = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-      Mx[p][q2] = s;
-      Mx[q2][p] = s;
-    } else if (t < 45 + 36) {
-      ev[(t - 45) / 9][(t - 45) % 9] = 0.0;  // a system that is not finite ranks no eigenvector: a zero basis has no solution
-    }
-    __syncthreads();
+      for (int k = 0; k < 9; ++k) r1[k] = e1[k];
+    }, Mx);
     // 2. the eigenvectors of the four smallest eigenvalues (ties: the lower lane first), de-normalised: ev[0 .. 3] = X, Y, Z, W
     if (wave == 0) {
       double col[9], vv[9];
@@ -845,25 +785,9 @@ struct Essential {
     }
   }
 
-  // E as found or as optimised; info = {rounds, best_h, best_root, best_min, best, valid} (magsac_finish_kernel adds the LO steps)
-  __device__ static void mag_finish(const PairState<Essential>& P, bool good, double* out, int* info) {
+  // E as found or as optimised
+  __device__ static void model_out(const PairState<Essential>& P, bool good, double* out) {
     for (int k = 0; k < 9; ++k) out[k] = good ? P.cur[k] : 0.0;
-    info[0] = P.rounds;
-    info[1] = P.best_h;
-    info[2] = P.best_root;
-    info[3] = P.best_min;
-    info[4] = P.best;
-    info[5] = P.valid;
-  }
-
-  // E as found; info = {rounds, best_h, best_root, best, valid}
-  __device__ static void finish(const PairState<Essential>& P, bool good, double* out, int* info) {
-    for (int k = 0; k < 9; ++k) out[k] = good ? P.cur[k] : 0.0;
-    info[0] = P.rounds;
-    info[1] = P.best_h;
-    info[2] = P.best_root;
-    info[3] = P.best;
-    info[4] = P.valid;
   }
 };
 
@@ -1047,33 +971,40 @@ PoseCarve pose_carve(void* ws, int B, int N) {
   return c;
 }
 
+static_assert(MagsacScoring::MAX_STEPS == ESSENTIAL_MAGSAC_MAX_LO);
+
+// the check and launch behind essential_launch and essential_magsac_launch: `opt` is `lo_iters`, out_score NULL without scores
+template <class Sc>
+int e_launch(const char* op, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+             const double* K, int B, int N, float threshold, double prob, int max_iters, int opt, double* out_e,
+             unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score, void* ws, size_t ws_bytes,
+             hipStream_t s) {
+  if (check_args<Sc>(op, "prob", kpts_a && kpts_b && seeds && out_e && out_mask && out_ok && out_info && (out_score || !Sc::SCORES) && ws,
+                     B, N, threshold, prob, max_iters, opt, ws_bytes, workspace_bytes<Essential, Sc>(B, N)))
+    return -1;
+  return ransac_run<Essential, Sc>(kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, opt, out_e, out_mask, out_ok,
+                                   out_info, out_score, ws, s);
+}
+
 }  // namespace
 
-size_t essential_workspace_bytes(int B, int N) { return workspace_bytes<Essential>(B, N); }
+size_t essential_workspace_bytes(int B, int N) { return workspace_bytes<Essential, CountScoring>(B, N); }
 
 int essential_launch(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K,
                      int B, int N, float threshold, double prob, int max_iters, double* out_e, unsigned char* out_mask,
                      unsigned char* out_ok, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (check_args("essential", "prob", kpts_a && kpts_b && seeds && out_e && out_mask && out_ok && out_info && ws, B, N, threshold,
-                 prob, max_iters, ws_bytes, essential_workspace_bytes(B, N)))
-    return -1;
-  return ransac_run<Essential>(kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, false, out_e, out_mask, out_ok,
-                               out_info, ws, s);
+  return e_launch<CountScoring>("essential", kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, 0, out_e, out_mask,
+                                out_ok, out_info, nullptr, ws, ws_bytes, s);
 }
 
-size_t essential_magsac_workspace_bytes(int B, int N) { return magsac_workspace_bytes<Essential>(B, N); }
+size_t essential_magsac_workspace_bytes(int B, int N) { return workspace_bytes<Essential, MagsacScoring>(B, N); }
 
 int essential_magsac_launch(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
                             const double* K, int B, int N, float threshold, double prob, int max_iters, int lo_iters, double* out_e,
                             unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score, void* ws,
                             size_t ws_bytes, hipStream_t s) {
-  if (check_args("essential_magsac", "prob",
-                 kpts_a && kpts_b && seeds && out_e && out_mask && out_ok && out_info && out_score && ws, B, N, threshold, prob,
-                 max_iters, ws_bytes, essential_magsac_workspace_bytes(B, N)))
-    return -1;
-  ROMA_REQUIRE(lo_iters >= 0 && lo_iters <= ESSENTIAL_MAGSAC_MAX_LO, "essential_magsac: lo_iters must lie in [0, 64]");
-  return magsac_run<Essential>(kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, lo_iters, out_e, out_mask,
-                               out_ok, out_info, out_score, ws, s);
+  return e_launch<MagsacScoring>("essential_magsac", kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, lo_iters,
+                                 out_e, out_mask, out_ok, out_info, out_score, ws, ws_bytes, s);
 }
 
 int essential_minimal_launch(const double* x0, const double* x1, int S, double* out_e, int* out_n, hipStream_t s) {

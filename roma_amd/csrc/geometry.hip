@@ -7,12 +7,15 @@
 //               fixed-order reductions; thresholds thr * s per image.
 //   hypothesis  one thread per hypothesis: 4-point DLT as an 8 x 8 solve with OpenCV's checkSubset (1 slot), or 7-point null
 //               space + cubic (up to 3 slots), f64.
-//   inlier      f32 reprojection error in image B (H); distances to both epipolar lines, each image with its own scale (F).
-//   refit       up to REFINE_ITERS times: 9 x 9 normal equations in f64 on the current inliers (fixed-order tree reduction),
-//               smallest eigenvector by one-sided Jacobi on one wave (ransac.h: jacobi_min_vec); rank 2 for F.
-//   finish      de-normalised in f64 (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scaled so that [2, 2] = 1; info of RANSAC_INFO ints.
-//   residual2   (MAGSAC++, magsac_run) f32 squared pixel residuals: reprojection error in image B (H), Sampson distance (F).
-//   wrefit      (MAGSAC++) the refit's normal equations weighted by the MAGSAC++ weights of the current model (one IRLS step).
+//   res_terms   the f32 scoring's terms linear in the model: reprojection error in image B and p_z (H), the epipolar terms (F).
+//   inlier      (CountScoring) from them: reprojection error in image B (H); distances to both epipolar lines, each image with
+//               its own scale (F).
+//   residual2   (MagsacScoring) from them: squared pixel residuals - reprojection error in image B (H), Sampson distance (F).
+//   refit       (CountScoring) up to REFINE_ITERS times: 9 x 9 normal equations in f64 on the current inliers (ransac.h:
+//               normal_equations), smallest eigenvector by one-sided Jacobi on one wave (jacobi_min_vec); rank 2 for F.
+//   wrefit      (MagsacScoring) the same with the rows weighted by the MAGSAC++ weights of the current model (one IRLS step).
+//   model_out   de-normalised in f64 (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scaled so that [2, 2] = 1.  Info rows of RANSAC_INFO
+//               and MAGSAC_INFO ints.
 #include "geometry.h"
 #include "ransac.h"
 
@@ -21,62 +24,6 @@ namespace {
 
 constexpr double COLLINEAR_EPS = 1e-4;  // |sin| of a triple's angle below which the triple counts as collinear
 constexpr double CUBIC_EPS = 1e-12;     // relative size below which a leading coefficient of the cubic is zero
-
-// ------------------------------------------------------------------------------------------------------------ scoring (f32)
-// p = (xa, ya, xb, yb) normalised.  Multiplication forms of the reprojection / epipolar tests: no division, NaN never passes.
-__device__ __forceinline__ bool inlier_h(const float* m, float4 p, float t2a, float t2b) {
-  const float px = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
-  const float py = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
-  const float pz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
-  const float ex = fmaf(-p.z, pz, px), ey = fmaf(-p.w, pz, py);
-  return fmaf(ex, ex, ey * ey) < t2b * (pz * pz);
-}
-
-// OpenCV FM_RANSAC: max(d^2 / |F xa|_{1,2}^2, d^2 / |F^T xb|_{1,2}^2) < thr^2, each image with its own scale
-__device__ __forceinline__ bool inlier_f(const float* m, float4 p, float t2a, float t2b) {
-  const float lx = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
-  const float ly = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
-  const float lz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
-  const float d = fmaf(p.z, lx, fmaf(p.w, ly, lz));
-  const float kx = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
-  const float ky = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
-  const float d2 = d * d;
-  return d2 < t2b * fmaf(lx, lx, ly * ly) && d2 < t2a * fmaf(kx, kx, ky * ky);
-}
-
-// squared pixel residuals of the MAGSAC++ scoring from the normalised points; sa2, sb2 the squared scales x_n = (x - c) s.
-// Each is split into terms linear in the model (res_terms_*) and the squared residual formed from them (r2_from_*), so that
-// magsac_accept_kernel can evaluate a candidate as current + difference on the same rows.
-// H: forward reprojection error in image B, |e|^2 / (p_z^2 s_b^2) with the terms of inlier_h; terms (e_x, e_y, p_z).
-__device__ __forceinline__ void res_terms_h(const float* m, float4 p, float (&t)[3]) {
-  const float px = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
-  const float py = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
-  const float pz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
-  t[0] = fmaf(-p.z, pz, px);
-  t[1] = fmaf(-p.w, pz, py);
-  t[2] = pz;
-}
-
-__device__ __forceinline__ float r2_from_h(const float (&t)[3], float, float sb2) {
-  return fmaf(t[0], t[0], t[1] * t[1]) / (t[2] * t[2] * sb2);
-}
-
-// F: Sampson distance d^2 / (s_b^2 |F x_a|_{1,2}^2 + s_a^2 |F^T x_b|_{1,2}^2), exact in pixels (x_b^T F x_a = x_nb^T F_n x_na);
-// terms (d, l_x, l_y, k_x, k_y)
-__device__ __forceinline__ void res_terms_f(const float* m, float4 p, float (&t)[5]) {
-  const float lx = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
-  const float ly = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
-  const float lz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
-  t[0] = fmaf(p.z, lx, fmaf(p.w, ly, lz));
-  t[1] = lx;
-  t[2] = ly;
-  t[3] = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
-  t[4] = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
-}
-
-__device__ __forceinline__ float r2_from_f(const float (&t)[5], float sa2, float sb2) {
-  return t[0] * t[0] / fmaf(sb2, fmaf(t[1], t[1], t[2] * t[2]), sa2 * fmaf(t[3], t[3], t[4] * t[4]));
-}
 
 // ------------------------------------------------------------------------------------------------------------ f64 helpers
 __device__ __forceinline__ void unit_norm(double* m) {
@@ -231,9 +178,9 @@ __device__ int solve_f(const double* xa, const double* ya, const double* xb, con
 
 // ------------------------------------------------------------------------------------------------------------ model policies
 // what H and F share: Hartley normalisation, one thread per hypothesis, the least-squares refit and the de-normalisation.
-// Model supplies MODEL, S, SLOTS, REFIT_MIN, inlier and solve.
+// Model supplies MODEL, S, SLOTS, REFIT_MIN, NT, res_terms, inlier_from, r2_from and solve.
 template <class Model>
-struct Hartley {
+struct Hartley : Terms<Model> {
   struct Norm {
     double ca[2], cb[2], sa, sb;  // x_n = (x - c) * s
     __device__ void apply(float2 a, float2 q, double& xa, double& ya, double& xb, double& yb) const {
@@ -253,41 +200,27 @@ struct Hartley {
     sb2 = (float)(nm.sb * nm.sb);
   }
 
-  // every thread of the workgroup: the pair's normalisation; pts written only for a valid pair
+  // every thread of the workgroup: the pair's normalisation over its finite rows; pts written only for a valid pair
   __device__ static bool normalise(const float2* A, const float2* Bp, int n, const double*, float thr, double* sh, float4* pts,
                                    Norm& nm, float& t2a, float& t2b) {
-    const int t = threadIdx.x;
-    double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
-    for (int i = t; i < n; i += 256) {
+    const HartleyMoments m = hartley_moments(n, [&](int i, double& ax, double& ay, double& bx, double& by) {
       const float2 a = A[i], q = Bp[i];
-      if (finite_row(a.x, a.y, q.x, q.y)) { s0 += a.x; s1 += a.y; s2 += q.x; s3 += q.y; s4 += 1; }
-    }
-    const double cnt = block_sum(s4, sh);
-    const double cax = block_sum(s0, sh) / cnt, cay = block_sum(s1, sh) / cnt;
-    const double cbx = block_sum(s2, sh) / cnt, cby = block_sum(s3, sh) / cnt;
-    double da = 0, db = 0;
-    for (int i = t; i < n; i += 256) {
-      const float2 a = A[i], q = Bp[i];
-      if (finite_row(a.x, a.y, q.x, q.y)) {
-        const double ax = a.x - cax, ay = a.y - cay, bx = q.x - cbx, by = q.y - cby;
-        da += sqrt(ax * ax + ay * ay);
-        db += sqrt(bx * bx + by * by);
-      }
-    }
-    const double ma = block_sum(da, sh) / cnt, mb = block_sum(db, sh) / cnt;
-    const double sa = M_SQRT2 / ma, sb = M_SQRT2 / mb;
-    const bool valid = cnt >= Model::S && ma > 0 && mb > 0 && isfinite(sa) && isfinite(sb);
+      ax = a.x; ay = a.y; bx = q.x; by = q.y;
+      return finite_row(a.x, a.y, q.x, q.y);
+    }, sh);
+    const bool valid = m.ok(Model::S);
     if (valid) {
-      for (int i = t; i < n; i += 256) {
+      for (int i = threadIdx.x; i < n; i += 256) {
         const float2 a = A[i], q = Bp[i];
         float4 o = make_float4(NAN, NAN, NAN, NAN);
         if (finite_row(a.x, a.y, q.x, q.y))
-          o = make_float4((float)((a.x - cax) * sa), (float)((a.y - cay) * sa), (float)((q.x - cbx) * sb), (float)((q.y - cby) * sb));
+          o = make_float4((float)((a.x - m.cax) * m.sa), (float)((a.y - m.cay) * m.sa), (float)((q.x - m.cbx) * m.sb),
+                          (float)((q.y - m.cby) * m.sb));
         pts[i] = o;
       }
     }
-    nm.ca[0] = cax; nm.ca[1] = cay; nm.cb[0] = cbx; nm.cb[1] = cby; nm.sa = sa; nm.sb = sb;
-    const double ta = (double)thr * sa, tb = (double)thr * sb;
+    nm.ca[0] = m.cax; nm.ca[1] = m.cay; nm.cb[0] = m.cbx; nm.cb[1] = m.cby; nm.sa = m.sa; nm.sb = m.sb;
+    const double ta = (double)thr * m.sa, tb = (double)thr * m.sb;
     t2a = (float)(ta * ta);
     t2b = (float)(tb * tb);
     return valid;
@@ -315,7 +248,7 @@ struct Hartley {
   template <bool W>
   __device__ static void fit(const float2* A, const float2* Bp, PairState<Model>& P, const unsigned char* mask, const float4* pts,
                              const MagState* S) {
-    __shared__ double red[4][45];
+    constexpr bool H = Model::MODEL == RANSAC_HOMOGRAPHY;
     __shared__ double M[9][9];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     if (P.stop) return;
@@ -323,73 +256,33 @@ struct Hartley {
       if (t == 0) { P.stop = 1; P.cand_ok = 0; }
       return;
     }
-    double acc[45];
-#pragma unroll
-    for (int e = 0; e < 45; ++e) acc[e] = 0;
     const double cax = P.nrm.ca[0], cay = P.nrm.ca[1], cbx = P.nrm.cb[0], cby = P.nrm.cb[1], sa = P.nrm.sa, sb = P.nrm.sb;
-    int npos = 0;
-    for (int i = t; i < P.n; i += 256) {
-      double wt = 1;
+    const int rows = normal_equations<W, H>(P.n, [&](int i, double& wt) {
       if constexpr (W) {
         float w;
         magsac_rho(Model::residual2(P.curf, pts[i], S->sa2, S->sb2) * S->vs, w);
-        if (!(w > 0.f)) continue;
-        ++npos;
         wt = w;
+        return w > 0.f;
       } else {
-        if (!mask[i]) continue;
+        return mask[i] != 0;
       }
+    }, [&](int i, double (&r1)[9], double (&r2)[9]) {
       const float2 a = A[i], q = Bp[i];
       const double x = (a.x - cax) * sa, y = (a.y - cay) * sa, u = (q.x - cbx) * sb, v = (q.y - cby) * sb;
-      if (Model::MODEL == RANSAC_HOMOGRAPHY) {
-        const double r1[9] = {x, y, 1, 0, 0, 0, -u * x, -u * y, -u};
-        const double r2[9] = {0, 0, 0, x, y, 1, -v * x, -v * y, -v};
-        int e = 0;
+      if constexpr (H) {
+        const double h1[9] = {x, y, 1, 0, 0, 0, -u * x, -u * y, -u}, h2[9] = {0, 0, 0, x, y, 1, -v * x, -v * y, -v};
 #pragma unroll
-        for (int p = 0; p < 9; ++p)
-#pragma unroll
-          for (int q2 = p; q2 < 9; ++q2, ++e) {
-            if constexpr (W) acc[e] += wt * (r1[p] * r1[q2] + r2[p] * r2[q2]);
-            else acc[e] += r1[p] * r1[q2] + r2[p] * r2[q2];
-          }
+        for (int k = 0; k < 9; ++k) { r1[k] = h1[k]; r2[k] = h2[k]; }
       } else {
-        const double r1[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1};
-        int e = 0;
+        const double f1[9] = {u * x, u * y, u, v * x, v * y, v, x, y, 1};
 #pragma unroll
-        for (int p = 0; p < 9; ++p)
-#pragma unroll
-          for (int q2 = p; q2 < 9; ++q2, ++e) {
-            if constexpr (W) acc[e] += wt * (r1[p] * r1[q2]);
-            else acc[e] += r1[p] * r1[q2];
-          }
+        for (int k = 0; k < 9; ++k) r1[k] = f1[k];
       }
+    }, M);
+    if (W && rows < Model::REFIT_MIN) {  // rows of positive weight over the workgroup
+      if (t == 0) { P.stop = 1; P.cand_ok = 0; }
+      return;
     }
-    if constexpr (W) {  // rows of positive weight over the workgroup
-      __shared__ int cnt[4];
-      for (int off = 32; off > 0; off >>= 1) npos += __shfl_xor(npos, off);
-      if (lane == 0) cnt[wave] = npos;
-      __syncthreads();
-      if (((cnt[0] + cnt[1]) + cnt[2]) + cnt[3] < Model::REFIT_MIN) {
-        if (t == 0) { P.stop = 1; P.cand_ok = 0; }
-        return;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 45; ++e) {
-      double s = acc[e];
-      for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-      if (lane == 0) red[wave][e] = s;
-    }
-    __syncthreads();
-    if (t < 45) {
-      int p = 0, e = t;
-      while (e >= 9 - p) { e -= 9 - p; ++p; }
-      const int q2 = p + e;
-      const double s = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
-      M[p][q2] = s;
-      M[q2][p] = s;
-    }
-    __syncthreads();
     if (wave != 0) return;
     double col[9], vv[9], h[9];
 #pragma unroll
@@ -398,7 +291,7 @@ struct Hartley {
       vv[k] = lane == k ? 1.0 : 0.0;
     }
     jacobi_min_vec<9, 10>(col, vv, lane, h);
-    if (Model::MODEL == RANSAC_FUNDAMENTAL) {  // rank 2: F - (F v)(v^T), v the smallest right singular vector (eigenvector of F^T F)
+    if (!H) {  // rank 2: F - (F v)(v^T), v the smallest right singular vector (eigenvector of F^T F)
       double c3[3], v3[3], w3[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
@@ -438,10 +331,8 @@ struct Hartley {
     fit<true>(A, Bp, P, nullptr, pts, &S);
   }
 
-  __device__ static void mag_finish(const PairState<Model>& P, bool good, double* out, int* info) { finish(P, good, out, info); }
-
-  // de-normalise (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scale; info = {rounds, best_h, best_root, best_min, best, valid}
-  __device__ static void finish(const PairState<Model>& P, bool good, double* out, int* info) {
+  // de-normalise (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scale
+  __device__ static void model_out(const PairState<Model>& P, bool good, double* out) {
     const Norm& q = P.nrm;
     double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (good) {
@@ -463,25 +354,28 @@ struct Hartley {
       for (int k = 0; k < 9; ++k) m[k] = m[k] / sc;
     }
     for (int k = 0; k < 9; ++k) out[k] = m[k];
-    info[0] = P.rounds;
-    info[1] = P.best_h;
-    info[2] = P.best_root;
-    info[3] = P.best_min;
-    info[4] = P.best;
-    info[5] = P.valid;
   }
 };
 
+// The f32 scoring: p = (xa, ya, xb, yb) normalised; terms linear in the model (ransac.h: Terms), the count scoring's test on
+// them in multiplication form (no division, NaN never passes) and the MAGSAC++ squared pixel residual; sa2, sb2 the squared
+// scales x_n = (x - c) s.
 struct Homography : Hartley<Homography> {
-  static constexpr int MODEL = RANSAC_HOMOGRAPHY, S = 4, SLOTS = 1, REFIT_MIN = 4;
-  __device__ static bool inlier(const float* m, float4 p, float t2a, float t2b) { return inlier_h(m, p, t2a, t2b); }
-  static constexpr int NT = 3;  // residual terms linear in the model
-  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) { res_terms_h(m, p, t); }
-  __device__ static float r2_from(const float (&t)[NT], float sa2, float sb2) { return r2_from_h(t, sa2, sb2); }
-  __device__ static float residual2(const float* m, float4 p, float sa2, float sb2) {
-    float t[NT];
-    res_terms_h(m, p, t);
-    return r2_from_h(t, sa2, sb2);
+  static constexpr int MODEL = RANSAC_HOMOGRAPHY, S = 4, SLOTS = 1, REFIT_MIN = 4, NT = 3;
+  // forward reprojection error in image B, |e|^2 / (p_z^2 s_b^2); terms (e_x, e_y, p_z)
+  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) {
+    const float px = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
+    const float py = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
+    const float pz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
+    t[0] = fmaf(-p.z, pz, px);
+    t[1] = fmaf(-p.w, pz, py);
+    t[2] = pz;
+  }
+  __device__ static bool inlier_from(const float (&t)[NT], float, float t2b) {
+    return fmaf(t[0], t[0], t[1] * t[1]) < t2b * (t[2] * t[2]);
+  }
+  __device__ static float r2_from(const float (&t)[NT], float, float sb2) {
+    return fmaf(t[0], t[0], t[1] * t[1]) / (t[2] * t[2] * sb2);
   }
   __device__ static int solve(const double* xa, const double* ya, const double* xb, const double* yb, double (&m)[SLOTS][9]) {
     return solve_h(xa, ya, xb, yb, m);
@@ -489,59 +383,64 @@ struct Homography : Hartley<Homography> {
 };
 
 struct Fundamental : Hartley<Fundamental> {
-  static constexpr int MODEL = RANSAC_FUNDAMENTAL, S = 7, SLOTS = 3, REFIT_MIN = 8;
-  __device__ static bool inlier(const float* m, float4 p, float t2a, float t2b) { return inlier_f(m, p, t2a, t2b); }
-  static constexpr int NT = 5;
-  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) { res_terms_f(m, p, t); }
-  __device__ static float r2_from(const float (&t)[NT], float sa2, float sb2) { return r2_from_f(t, sa2, sb2); }
-  __device__ static float residual2(const float* m, float4 p, float sa2, float sb2) {
-    float t[NT];
-    res_terms_f(m, p, t);
-    return r2_from_f(t, sa2, sb2);
+  static constexpr int MODEL = RANSAC_FUNDAMENTAL, S = 7, SLOTS = 3, REFIT_MIN = 8, NT = 5;
+  // on the epipolar terms (d, l_x, l_y, k_x, k_y).  OpenCV FM_RANSAC: max(d^2 / |F xa|_{1,2}^2, d^2 / |F^T xb|_{1,2}^2) < thr^2,
+  // each image with its own scale; Sampson distance d^2 / (s_b^2 |F x_a|_{1,2}^2 + s_a^2 |F^T x_b|_{1,2}^2), exact in pixels
+  // (x_b^T F x_a = x_nb^T F_n x_na)
+  __device__ static void res_terms(const float* m, float4 p, float (&t)[NT]) { epipolar_terms(m, p, t); }
+  __device__ static bool inlier_from(const float (&t)[NT], float t2a, float t2b) {
+    const float d2 = t[0] * t[0];
+    return d2 < t2b * fmaf(t[1], t[1], t[2] * t[2]) && d2 < t2a * fmaf(t[3], t[3], t[4] * t[4]);
+  }
+  __device__ static float r2_from(const float (&t)[NT], float sa2, float sb2) {
+    return t[0] * t[0] / fmaf(sb2, fmaf(t[1], t[1], t[2] * t[2]), sa2 * fmaf(t[3], t[3], t[4] * t[4]));
   }
   __device__ static int solve(const double* xa, const double* ya, const double* xb, const double* yb, double (&m)[SLOTS][9]) {
     return solve_f(xa, ya, xb, yb, m);
   }
 };
 
+static_assert(MagsacScoring::MAX_STEPS == MAGSAC_MAX_LO);
+
+template <class Sc>
+size_t hf_workspace_bytes(int B, int N) {  // one size for both models (the roma_op_*_workspace calls take no model)
+  return std::max(workspace_bytes<Homography, Sc>(B, N), workspace_bytes<Fundamental, Sc>(B, N));
+}
+
+// the check and dispatch behind ransac_launch and magsac_launch: `opt` is `refine` or `lo_iters`, out_score NULL without scores
+template <class Sc>
+int hf_launch(const char* op, int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+              int B, int N, float threshold, double confidence, int max_iters, int opt, double* out_model, unsigned char* out_mask,
+              unsigned char* out_ok, int* out_info, double* out_score, void* ws, size_t ws_bytes, hipStream_t s) {
+  ROMA_REQUIRE(model == RANSAC_HOMOGRAPHY || model == RANSAC_FUNDAMENTAL,
+               std::string(op) + ": model must be 0 (homography) or 1 (fundamental)");
+  if (check_args<Sc>(op, "confidence",
+                     kpts_a && kpts_b && seeds && out_model && out_mask && out_ok && out_info && (out_score || !Sc::SCORES) && ws, B,
+                     N, threshold, confidence, max_iters, opt, ws_bytes, hf_workspace_bytes<Sc>(B, N)))
+    return -1;
+  const auto run = model == RANSAC_HOMOGRAPHY ? ransac_run<Homography, Sc> : ransac_run<Fundamental, Sc>;
+  return run(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, opt, out_model, out_mask, out_ok,
+             out_info, out_score, ws, s);
+}
+
 }  // namespace
 
-size_t ransac_workspace_bytes(int B, int N) {  // one size for both models (roma_op_ransac_workspace takes no model)
-  return std::max(workspace_bytes<Homography>(B, N), workspace_bytes<Fundamental>(B, N));
-}
+size_t ransac_workspace_bytes(int B, int N) { return hf_workspace_bytes<CountScoring>(B, N); }
 
 int ransac_launch(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
                   int N, float threshold, double confidence, int max_iters, int refine, double* out_model, unsigned char* out_mask,
                   unsigned char* out_ok, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
-  ROMA_REQUIRE(model == RANSAC_HOMOGRAPHY || model == RANSAC_FUNDAMENTAL, "ransac: model must be 0 (homography) or 1 (fundamental)");
-  if (check_args("ransac", "confidence", kpts_a && kpts_b && seeds && out_model && out_mask && out_ok && out_info && ws, B, N,
-                 threshold, confidence, max_iters, ws_bytes, ransac_workspace_bytes(B, N)))
-    return -1;
-  return model == RANSAC_HOMOGRAPHY
-             ? ransac_run<Homography>(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, refine,
-                                      out_model, out_mask, out_ok, out_info, ws, s)
-             : ransac_run<Fundamental>(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, refine,
-                                       out_model, out_mask, out_ok, out_info, ws, s);
+  return hf_launch<CountScoring>("ransac", model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, refine,
+                                 out_model, out_mask, out_ok, out_info, nullptr, ws, ws_bytes, s);
 }
 
-size_t magsac_workspace_bytes(int B, int N) {
-  return std::max(magsac_workspace_bytes<Homography>(B, N), magsac_workspace_bytes<Fundamental>(B, N));
-}
+size_t magsac_workspace_bytes(int B, int N) { return hf_workspace_bytes<MagsacScoring>(B, N); }
 
 int magsac_launch(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
                   int N, float threshold, double confidence, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask,
                   unsigned char* out_ok, int* out_info, double* out_score, void* ws, size_t ws_bytes, hipStream_t s) {
-  ROMA_REQUIRE(model == RANSAC_HOMOGRAPHY || model == RANSAC_FUNDAMENTAL, "magsac: model must be 0 (homography) or 1 (fundamental)");
-  if (check_args("magsac", "confidence",
-                 kpts_a && kpts_b && seeds && out_model && out_mask && out_ok && out_info && out_score && ws, B, N, threshold,
-                 confidence, max_iters, ws_bytes, magsac_workspace_bytes(B, N)))
-    return -1;
-  ROMA_REQUIRE(lo_iters >= 0 && lo_iters <= MAGSAC_MAX_LO, "magsac: lo_iters must lie in [0, 64]");
-  return model == RANSAC_HOMOGRAPHY
-             ? magsac_run<Homography>(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, lo_iters,
-                                      out_model, out_mask, out_ok, out_info, out_score, ws, s)
-             : magsac_run<Fundamental>(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, lo_iters,
-                                       out_model, out_mask, out_ok, out_info, out_score, ws, s);
+  return hf_launch<MagsacScoring>("magsac", model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, lo_iters,
+                                  out_model, out_mask, out_ok, out_info, out_score, ws, ws_bytes, s);
 }
 
 }  // namespace roma

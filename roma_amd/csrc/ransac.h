@@ -1,22 +1,25 @@
-// Batched RANSAC on the device: one pipeline for every model, templated on a model policy M (geometry.hip: homography and
-// fundamental matrix; essential.hip: essential matrix).  tools/geometry_ref.py restates it in numpy float64 (round_loop) and
-// is, with the models' own restatements, the oracle of the GPU tests.
+// Batched robust estimation on the device: one pipeline for every model and every scoring, templated on a model policy M
+// (geometry.hip: homography and fundamental matrix; essential.hip: essential matrix) and a scoring policy Sc (below:
+// CountScoring - RANSAC's inlier count; MagsacScoring - MAGSAC++).  tools/geometry_ref.py restates it in numpy float64
+// (round_loop) and is, with the models' and scorings' own restatements, the oracle of the GPU tests.
 //
 // Per pair b (counts[b] rows of kpts_a / kpts_b; later rows are never read):
 //   1. ransac_norm_kernel: M::normalise - the model's normalisation of both images, normalised f32 copies of the points
-//      (non-finite rows as NaN), squared thresholds in normalised units, whether the pair can be sampled.
+//      (non-finite rows as NaN), squared thresholds in normalised units, whether the pair can be sampled.  MagsacScoring only:
+//      magsac_init_kernel - residual scales, V scale and threshold of the pair.
 //   2. rounds of RANSAC_ROUND hypotheses, enqueued ceil(max_iters / ROUND) times, no host synchronisation:
 //      ransac_hyp_kernel    M::HYP_LANES lanes per hypothesis: sample (counter-based, from (seed_b, h) only), normalised in
 //                           f64 (M::Norm::apply), then M::hypothesis: the f64 minimal solver, up to M::SLOTS models
-//      ransac_score_kernel  one wave per hypothesis: its models' f32 inlier tests (M::inlier), popc(ballot) counts, -1 for
-//                           unused slots
-//      ransac_select_kernel per pair: arg-max (ties: lowest (h, slot)), OpenCV's adaptive iteration count, done flag.
-//   3. refinement (M::REFINE_ITERS > 0 and refine): up to REFINE_ITERS times ransac_mask_kernel (inliers of the current
-//      model), ransac_refit_kernel (M::refit: a least-squares candidate), ransac_accept_kernel (re-score; the candidate is kept
-//      if its inlier count is not lower, else refinement stops).
-//   4. ransac_mask_kernel + ransac_finish_kernel: final mask, ok flag, M::finish (model in pixel terms, info row).
-// magsac_run (below) is the same pipeline with MAGSAC++ scoring and IRLS local optimisation (tools/magsac_ref.py for H and F,
-// tools/essential_magsac_ref.py for E).
+//      ransac_score_kernel  one wave per hypothesis, Sc::score: its models' inlier counts (popc(ballot) of M::inlier, -1 for
+//                           unused slots), or their sums of rho (+inf for unused slots) and the counts r < tau
+//      ransac_select_kernel per pair: the best key (largest count / smallest sum; ties: lowest (h, slot); an earlier round keeps
+//                           a tie), OpenCV's adaptive iteration count from its inlier count, done flag.
+//   3. refinement, Sc::steps times (count: M::REFINE_ITERS if M has any and `refine`; MAGSAC++: lo_iters): count only
+//      ransac_mask_kernel (inliers of the current model); ransac_refit_kernel (Sc::refit: M::refit, a least-squares candidate on
+//      the mask, or M::wrefit, an IRLS step with the MAGSAC++ weights of the current model); ransac_accept_kernel (Sc::accept:
+//      the candidate is kept if its inlier count is not lower / its sum of rho strictly lower, else refinement stops).
+//   4. ransac_mask_kernel + ransac_finish_kernel: final mask (Sc::inlier), ok flag, M::model_out (model in pixel terms), info
+//      row (write_info, then Sc::finish: MAGSAC++ adds the LO steps and the two scores).
 // Every flag and counter of the workspace is written with plain stores by one kernel and read by a later launch on the same
 // stream: no atomics and no hand-off inside a launch.  Results are bit-identical from run to run and independent of B.
 #pragma once
@@ -266,18 +269,19 @@ T align_base(void* ws) {  // the caller's workspace need not be 256-aligned: eve
   return reinterpret_cast<T>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
 }
 
-template <class M>
+template <class M, class Sc>
 struct Carve {
   PairState<M>* st;
   float4* pts;
   Slots sl;
+  typename Sc::Ws w;            // what the scoring keeps next to them
   size_t bytes;
 };
 
-template <class M>
-Carve<M> carve(void* ws, int B, int N) {
+template <class M, class Sc>
+Carve<M, Sc> carve(void* ws, int B, int N) {
   constexpr int SL = M::SLOTS;
-  Carve<M> c;
+  Carve<M, Sc> c;
   char* p = static_cast<char*>(ws);
   size_t o = 0;
   c.st = reinterpret_cast<PairState<M>*>(p + o); o = align256(o + sizeof(PairState<M>) * B);
@@ -286,266 +290,154 @@ Carve<M> carve(void* ws, int B, int N) {
   c.sl.f = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * 12 * SL * (size_t)B * R);
   c.sl.n = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * (size_t)B * R);
   c.sl.cnt = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * SL * (size_t)B * R);
-  c.bytes = o + 256;
+  c.bytes = Sc::carve(c.w, p, o, (size_t)B * R * SL, B) + 256;
   return c;
 }
 
-template <class M>
-size_t workspace_bytes(int B, int N) { return B > 0 && N > 0 ? carve<M>(nullptr, B, N).bytes : 0; }
+template <class M, class Sc>
+size_t workspace_bytes(int B, int N) { return B > 0 && N > 0 ? carve<M, Sc>(nullptr, B, N).bytes : 0; }
 
-// ------------------------------------------------------------------------------------------------------------ kernels
-template <class M>
-__global__ __launch_bounds__(256) void ransac_norm_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
-                                                          const int* __restrict__ counts, const double* __restrict__ K, int N, float thr,
-                                                          int max_iters, PairState<M>* __restrict__ st, float4* __restrict__ pts) {
-  __shared__ double sh[256];
-  const int b = blockIdx.x;
-  const int n = counts ? min(max(counts[b], 0), N) : N;
-  typename M::Norm nrm;
-  float t2a, t2b;
-  const bool valid = M::normalise(ka + (long)b * N, kb + (long)b * N, n, K ? K + (long)b * 9 : nullptr, thr, sh,
-                                  pts + (long)b * N, nrm, t2a, t2b);
-  if (threadIdx.x == 0) {
-    PairState<M>& S = st[b];
-    S.nrm = nrm;
-    S.thr2a = t2a;
-    S.thr2b = t2b;
-    S.n = n;
-    S.valid = valid ? 1 : 0;
-    S.best = -1; S.best_h = -1; S.best_root = -1; S.best_min = -1;
-    S.needed = max_iters;
-    S.rounds = 0;
-    S.done = valid ? 0 : 1;
-    S.stop = 0;
-    S.cand_ok = 0;
-    for (int k = 0; k < 9; ++k) { S.cur[k] = 0; S.cand[k] = 0; }
-    for (int k = 0; k < 12; ++k) { S.curf[k] = 0; S.candf[k] = 0; }
+// ------------------------------------------------------------------------------------------------------------ shared by the models
+// The f32 scoring of a model is written once, as its residual terms linear in the model (Model::res_terms, NT of them): the
+// count scoring's inlier test (Model::inlier_from) and the MAGSAC++ squared residual (Model::r2_from) are both formed from them,
+// and the MAGSAC++ accept step evaluates a candidate as current + difference on the same terms.
+template <class Model>
+struct Terms {
+  __device__ static bool inlier(const float* m, float4 p, float t2a, float t2b) {
+    float t[Model::NT];
+    Model::res_terms(m, p, t);
+    return Model::inlier_from(t, t2a, t2b);
   }
+  __device__ static float residual2(const float* m, float4 p, float sa2, float sb2) {
+    float t[Model::NT];
+    Model::res_terms(m, p, t);
+    return Model::r2_from(t, sa2, sb2);
+  }
+};
+
+// the epipolar terms of F and E: (d, l_x, l_y, k_x, k_y) with d = x_b^T M x_a, l = M x_a, k = M^T x_b; p = (xa, ya, xb, yb)
+__device__ __forceinline__ void epipolar_terms(const float* m, float4 p, float (&t)[5]) {
+  const float lx = fmaf(m[0], p.x, fmaf(m[1], p.y, m[2]));
+  const float ly = fmaf(m[3], p.x, fmaf(m[4], p.y, m[5]));
+  const float lz = fmaf(m[6], p.x, fmaf(m[7], p.y, m[8]));
+  t[0] = fmaf(p.z, lx, fmaf(p.w, ly, lz));
+  t[1] = lx;
+  t[2] = ly;
+  t[3] = fmaf(m[0], p.z, fmaf(m[3], p.w, m[6]));
+  t[4] = fmaf(m[1], p.z, fmaf(m[4], p.w, m[7]));
 }
 
-// HYP_LANES lanes per (pair, hypothesis of the round), HYP_THREADS per workgroup; grid B * R * HYP_LANES / HYP_THREADS
+// the info row every model shares: {rounds, best_h, best_root, [best_min,] best, valid}; returns the entries written
 template <class M>
-__global__ __launch_bounds__(M::HYP_THREADS) void ransac_hyp_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
-                                                                    int N, const unsigned long long* __restrict__ seeds,
-                                                                    const PairState<M>* __restrict__ st, int round, Slots sl) {
-  constexpr int S = M::S, L = M::HYP_LANES;
-  static_assert(R % (M::HYP_THREADS / L) == 0, "a workgroup must not straddle two pairs");
-  const int g = blockIdx.x * (M::HYP_THREADS / L) + threadIdx.x / L, b = g / R;
-  const PairState<M>& P = st[b];
-  if (P.done) return;  // uniform over the workgroup: its hypotheses belong to one pair
-  const int h = round * R + g % R;
-  int idx[S];
-  bool act = draw_sample<S>(seeds[b], h, P.n, idx);
-  double xa[S], ya[S], xb[S], yb[S];
-#pragma unroll
-  for (int k = 0; k < S; ++k) {
-    const float2 a = act ? ka[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
-    const float2 q = act ? kb[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
-    act = act && finite_row(a.x, a.y, q.x, q.y);
-    P.nrm.apply(a, q, xa[k], ya[k], xb[k], yb[k]);
-  }
-  M::hypothesis(xa, ya, xb, yb, act, g, threadIdx.x % L, sl);
+__device__ __forceinline__ int write_info(const PairState<M>& P, int* info, bool with_min) {
+  int k = 0;
+  info[k++] = P.rounds;
+  info[k++] = P.best_h;
+  info[k++] = P.best_root;
+  if (with_min) info[k++] = P.best_min;
+  info[k++] = P.best;
+  info[k++] = P.valid;
+  return k;
 }
+constexpr int INFO_CORE = 5;    // the entries of write_info without best_min
 
-// one wave per (pair, hypothesis): the hypothesis' models (wave-uniform coefficients) against the pair's points
-template <class M>
-__global__ __launch_bounds__(256) void ransac_score_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
-                                                           Slots sl) {
-  constexpr int SL = M::SLOTS;
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = g / R;
-  const PairState<M>& P = st[b];
-  if (P.done) return;
-  const int nm = sl.n[g];
-  const float* mf = sl.f + (long)g * SL * 12;
-  const float4* Pp = pts + (long)b * N;
-  const int n = P.n;
-  const float t2a = P.thr2a, t2b = P.thr2b;
-  int c[SL];
-#pragma unroll
-  for (int r = 0; r < SL; ++r) c[r] = 0;
-  if (nm > 0) {
-    for (int i0 = 0; i0 < n; i0 += 64) {
-      const int i = i0 + lane;
-      const float4 p = i < n ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
-#pragma unroll
-      for (int r = 0; r < SL; ++r)
-        if (M::SCORE_EVERY_SLOT || r < nm) c[r] += __popcll(__ballot(M::inlier(mf + 12 * r, p, t2a, t2b)));
+// Hartley normalisation (centroid to 0, mean distance to sqrt 2) of both images over the rows that `row` selects, every thread
+// of the 256: row(i, ax, ay, bx, by) -> whether row i counts, and its coordinates.  f64 sums in a fixed order (block_sum).
+struct HartleyMoments {
+  double cnt, cax, cay, cbx, cby, ma, mb, sa, sb;  // rows, centroids, mean distances, scales x_n = (x - c) s
+  __device__ bool ok(int rows) const { return cnt >= rows && ma > 0 && mb > 0 && isfinite(sa) && isfinite(sb); }
+};
+
+template <class Row>
+__device__ __forceinline__ HartleyMoments hartley_moments(int n, Row row, double* sh) {
+  const int t = threadIdx.x;
+  HartleyMoments m;
+  double s0 = 0, s1 = 0, s2 = 0, s3 = 0, s4 = 0;
+  for (int i = t; i < n; i += 256) {
+    double ax, ay, bx, by;
+    if (row(i, ax, ay, bx, by)) { s0 += ax; s1 += ay; s2 += bx; s3 += by; s4 += 1; }
+  }
+  m.cnt = block_sum(s4, sh);
+  m.cax = block_sum(s0, sh) / m.cnt;
+  m.cay = block_sum(s1, sh) / m.cnt;
+  m.cbx = block_sum(s2, sh) / m.cnt;
+  m.cby = block_sum(s3, sh) / m.cnt;
+  double da = 0, db = 0;
+  for (int i = t; i < n; i += 256) {
+    double ax, ay, bx, by;
+    if (row(i, ax, ay, bx, by)) {
+      ax = ax - m.cax; ay = ay - m.cay; bx = bx - m.cbx; by = by - m.cby;
+      da += sqrt(ax * ax + ay * ay);
+      db += sqrt(bx * bx + by * by);
     }
   }
-  if (lane == 0) {
-    int* o = sl.cnt + (long)g * SL;
-#pragma unroll
-    for (int r = 0; r < SL; ++r) o[r] = r < nm ? c[r] : -1;
-  }
+  m.ma = block_sum(da, sh) / m.cnt;
+  m.mb = block_sum(db, sh) / m.cnt;
+  m.sa = M_SQRT2 / m.ma;
+  m.sb = M_SQRT2 / m.mb;
+  return m;
 }
 
-// one workgroup per pair: best (count, lowest slot) of the round, running best, adaptive iteration count, done flag
-template <class M>
-__global__ __launch_bounds__(256) void ransac_select_kernel(PairState<M>* __restrict__ st, int round, double conf, int max_iters,
-                                                            Slots sl) {
-  constexpr int SL = M::SLOTS;
-  __shared__ int sc[256], si[256];
-  const int b = blockIdx.x, t = threadIdx.x;
-  PairState<M>& P = st[b];
-  if (P.done) return;
-  const int* cnt = sl.cnt + (long)b * R * SL;
-  int bc = -1, bi = 0x7fffffff;
-  for (int k = t; k < R * SL; k += 256) {
-    const int c = cnt[k];
-    if (c > bc) { bc = c; bi = k; }  // k ascends: ties keep the lower slot
+// The refits' 9 x 9 normal equations, every thread of the 256: sum over the rows i < n that `sel` selects of w a a^T (TWO: of
+// w (a a^T + a2 a2^T), the homography's two rows per point); sel(i, w) -> whether row i counts, and its weight (read only if W);
+// row(i, a, a2) -> its row(s), called for selected rows only (on its own, so that the constants of a row reach the products).
+// Per thread in ascending i, then over the wave by a fixed butterfly, over the four waves in order, and symmetrised into Mx;
+// returns the number of rows selected.  Mx is published (the barrier is the last thing here).
+template <bool W, bool TWO, class Sel, class Row>
+__device__ __forceinline__ int normal_equations(int n, Sel sel, Row row, double (&Mx)[9][9]) {
+  __shared__ double red[4][45];
+  __shared__ int cnt[4];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  double acc[45];
+#pragma unroll
+  for (int e = 0; e < 45; ++e) acc[e] = 0;
+  int rows = 0;
+  for (int i = t; i < n; i += 256) {
+    double wt = 1;
+    if (!sel(i, wt)) continue;
+    ++rows;
+    double a[9], a2[9];
+    row(i, a, a2);
+    int e = 0;
+#pragma unroll
+    for (int p = 0; p < 9; ++p)
+#pragma unroll
+      for (int q = p; q < 9; ++q, ++e) {
+        if constexpr (TWO) {
+          if constexpr (W) acc[e] += wt * (a[p] * a[q] + a2[p] * a2[q]);
+          else acc[e] += a[p] * a[q] + a2[p] * a2[q];
+        } else {
+          if constexpr (W) acc[e] += wt * (a[p] * a[q]);
+          else acc[e] += a[p] * a[q];
+        }
+      }
   }
-  sc[t] = bc;
-  si[t] = bi;
+  for (int off = 32; off > 0; off >>= 1) rows += __shfl_xor(rows, off);
+  if (lane == 0) cnt[wave] = rows;
+#pragma unroll
+  for (int e = 0; e < 45; ++e) {
+    double s = acc[e];
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (lane == 0) red[wave][e] = s;
+  }
   __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      const int c = sc[t + w], i = si[t + w];
-      if (c > sc[t] || (c == sc[t] && i < si[t])) { sc[t] = c; si[t] = i; }
-    }
-    __syncthreads();
+  if (t < 45) {
+    int p = 0, e = t;
+    while (e >= 9 - p) { e -= 9 - p; ++p; }
+    const int q = p + e;
+    const double s = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
+    Mx[p][q] = s;
+    Mx[q][p] = s;
   }
-  if (t == 0) {
-    const int c = sc[0], k = si[0];
-    if (c > P.best) {  // strictly: an earlier round's model keeps a tie
-      P.best = c;
-      P.best_min = c;
-      P.best_h = round * R + k / SL;
-      P.best_root = k % SL;
-      const double* m = sl.d + ((long)b * R * SL + k) * 9;
-      for (int q = 0; q < 9; ++q) P.cur[q] = m[q];
-      to_f32(P.cur, P.curf);
-      P.needed = update_num_iters(conf, (double)c / P.n, M::S, max_iters);
-    }
-    P.rounds = round + 1;
-    const long drawn = (long)(round + 1) * R;
-    P.done = drawn >= (long)min(max_iters, P.needed) ? 1 : 0;
-  }
+  rows = ((cnt[0] + cnt[1]) + cnt[2]) + cnt[3];
+  __syncthreads();
+  return rows;
 }
 
-// mask[b, i] = inlier of the current model (rows beyond counts[b], and pairs without a model: 0); grid (ceil(N / 256), B)
-template <class M>
-__global__ __launch_bounds__(256) void ransac_mask_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
-                                                          unsigned char* __restrict__ mask) {
-  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  const PairState<M>& P = st[b];
-  bool in = false;
-  if (P.best > 0 && i < P.n) in = M::inlier(P.curf, pts[(long)b * N + i], P.thr2a, P.thr2b);
-  mask[(long)b * N + i] = in ? 1 : 0;
-}
-
-// one workgroup per pair: a least-squares candidate from the current mask (M::refit)
-template <class M>
-__global__ __launch_bounds__(256) void ransac_refit_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb, int N,
-                                                           PairState<M>* __restrict__ st, const unsigned char* __restrict__ mask) {
-  const long o = (long)blockIdx.x * N;
-  M::refit(ka + o, kb + o, st[blockIdx.x], mask + o);
-}
-
-// one wave per pair: re-score the candidate; keep it if its count is not lower, else stop refining
-template <class M>
-__global__ __launch_bounds__(64) void ransac_accept_kernel(const float4* __restrict__ pts, int N, PairState<M>* __restrict__ st) {
-  const int b = blockIdx.x, lane = threadIdx.x;
-  PairState<M>& P = st[b];
-  if (P.stop || !P.cand_ok) return;
-  const float4* Pp = pts + (long)b * N;
-  const int n = P.n;
-  const float t2a = P.thr2a, t2b = P.thr2b;
-  int c = 0;
-  for (int i0 = 0; i0 < n; i0 += 64) {
-    const int i = i0 + lane;
-    const float4 p = i < n ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
-    c += __popcll(__ballot(M::inlier(P.candf, p, t2a, t2b)));
-  }
-  if (lane == 0) {
-    if (c >= P.best) {
-      P.best = c;
-      for (int k = 0; k < 9; ++k) P.cur[k] = P.cand[k];
-      for (int k = 0; k < 12; ++k) P.curf[k] = P.candf[k];
-    } else {
-      P.stop = 1;
-    }
-    P.cand_ok = 0;
-  }
-}
-
-// one thread per pair: ok flag, M::finish (model, info row)
-template <class M>
-__global__ __launch_bounds__(64) void ransac_finish_kernel(int B, const PairState<M>* __restrict__ st, double* __restrict__ out,
-                                                           unsigned char* __restrict__ ok, int* __restrict__ info) {
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  const PairState<M>& P = st[b];
-  const bool good = P.valid && P.best > 0;
-  M::finish(P, good, out + (long)b * 9, info + (long)b * M::INFO);
-  ok[b] = good ? 1 : 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------ host
-// the argument checks of every RANSAC entry point: `op` prefixes each message, `conf` names the confidence argument
-int check_args(const char* op, const char* conf, bool pointers, int B, int N, float threshold, double confidence, int max_iters,
-               size_t ws_bytes, size_t ws_need) {
-  const std::string o(op);
-  ROMA_REQUIRE(pointers, o + ": null pointer");
-  ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), o + ": need 0 < B <= 65536, 0 < N, B * N < 2^31");
-  ROMA_REQUIRE(max_iters > 0, o + ": max_iters must be positive");
-  ROMA_REQUIRE(threshold > 0 && isfinite(threshold), o + ": threshold must be positive and finite");
-  ROMA_REQUIRE(confidence >= 0 && confidence <= 1, o + ": " + conf + " must lie in [0, 1]");
-  ROMA_REQUIRE(ws_bytes >= ws_need, o + ": workspace too small (roma_op_" + o + "_workspace)");
-  return 0;
-}
-
-// the launch sequence of the pipeline above; K: [B, 3, 3] f64 camera matrices or NULL, read by M::normalise only
-template <class M>
-int ransac_run(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K, int B,
-               int N, float thr, double conf, int max_iters, bool refine, double* out_model, unsigned char* out_mask,
-               unsigned char* out_ok, int* out_info, void* ws, hipStream_t s) {
-  const Carve<M> c = carve<M>(align_base<void*>(ws), B, N);
-  const float2* ka = reinterpret_cast<const float2*>(kpts_a);
-  const float2* kb = reinterpret_cast<const float2*>(kpts_b);
-  hipLaunchKernelGGL(ransac_norm_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, counts, K, N, thr, max_iters, c.st, c.pts);
-  ROMA_LAUNCH_CHECK();
-  const int rounds = (max_iters + R - 1) / R;
-  for (int r = 0; r < rounds; ++r) {
-    hipLaunchKernelGGL(ransac_hyp_kernel<M>, dim3(B * R * M::HYP_LANES / M::HYP_THREADS), dim3(M::HYP_THREADS), 0, s, ka, kb, N,
-                       seeds, c.st, r, c.sl);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ransac_score_kernel<M>, dim3(B * R / 4), dim3(256), 0, s, c.pts, N, c.st, c.sl);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ransac_select_kernel<M>, dim3(B), dim3(256), 0, s, c.st, r, conf, max_iters, c.sl);
-    ROMA_LAUNCH_CHECK();
-  }
-  const dim3 mgrid((N + 255) / 256, B);
-  if constexpr (M::REFINE_ITERS > 0) {
-    for (int it = 0; refine && it < M::REFINE_ITERS; ++it) {
-      hipLaunchKernelGGL(ransac_mask_kernel<M>, mgrid, dim3(256), 0, s, c.pts, N, c.st, out_mask);
-      ROMA_LAUNCH_CHECK();
-      hipLaunchKernelGGL(ransac_refit_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, N, c.st, out_mask);
-      ROMA_LAUNCH_CHECK();
-      hipLaunchKernelGGL(ransac_accept_kernel<M>, dim3(B), dim3(64), 0, s, c.pts, N, c.st);
-      ROMA_LAUNCH_CHECK();
-    }
-  }
-  hipLaunchKernelGGL(ransac_mask_kernel<M>, mgrid, dim3(256), 0, s, c.pts, N, c.st, out_mask);
-  ROMA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ransac_finish_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, out_model, out_ok, out_info);
-  ROMA_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------------------------ MAGSAC++
-// The same pipeline with MAGSAC++ scoring (Barath et al., CVPR 2020; nu = 4; tools/magsac_ref.py restates it): a model's score
-// is the sum over the pair's rows of the loss rho(V), V = r^2 k^2 / (2 tau^2) with r the model's pixel residual (M::residual2)
-// and tau the threshold (M::mag_thr2: both in the model's own units - pixels for H and F, normalised camera coordinates for E);
-// lower is better.  Sampling rounds, hypotheses and slots are those above (ransac_norm_kernel and ransac_hyp_kernel are shared);
-// what changes:
-//   magsac_score_kernel  one wave per hypothesis: compensated f32 sum of rho per slot (lane partials over rows i = lane mod 64
-//                        ascending, then a fixed butterfly), and the count r < tau for the adaptive iteration count
-//   magsac_select_kernel arg-min (ties: lowest (h, slot)); the running best changes only on a strictly smaller score
-//   lo_iters times magsac_refit_kernel (M::wrefit: IRLS step, weights w(V) of the current model) and magsac_accept_kernel (the
-//   candidate is kept only if its score is strictly lower - the gain measured paired, on the same rows - else LO stops); then
-//   the mask r < tau and magsac_finish_kernel (M::mag_finish: the model and the first M::MAG_INFO - 1 entries of the info row).
-// From the policy it needs residual2 / res_terms / r2_from / NT, res_scales, mag_thr2, wrefit, mag_finish, MAG_INFO.
+// ------------------------------------------------------------------------------------------------------------ MAGSAC++ arithmetic
+// MAGSAC++ (Barath et al., CVPR 2020; nu = 4; tools/magsac_ref.py restates it): a model's score is the sum over the pair's rows
+// of the loss rho(V), V = r^2 k^2 / (2 tau^2) with r the model's residual (M::residual2) and tau the threshold (M::mag_thr2:
+// both in the model's own units - pixels for H and F, normalised camera coordinates for E); lower is better.
 constexpr double MAGSAC_K2 = 13.276704135987625;      // 0.99 quantile of chi^2 with 4 DoF
 constexpr float MAGSAC_VK = 6.638352067993813f;       // k^2 / 2
 constexpr float MAGSAC_GK = 0.003611260617758621f;    // Gamma(3/2, V_k)
@@ -574,31 +466,8 @@ struct MagState {               // per pair, next to PairState
   float score;                  // sum of rho of the running best of the sampling rounds (+inf: none yet)
   float score_min;              // sum of rho of the winning minimal model
   int lo_steps;                 // LO steps accepted
-  double gain;                  // what the accepted LO steps lowered the sum of rho by (magsac_accept_kernel)
+  double gain;                  // what the accepted LO steps lowered the sum of rho by (MagsacScoring::accept)
 };
-
-template <class M>
-struct MagCarve {
-  Carve<M> c;                   // the RANSAC carve: pair states, points, slots (cnt: inlier counts per slot)
-  MagState* ms;
-  float* sc;                    // sum of rho per slot, +inf if unused [B * R * SLOTS]
-  size_t bytes;
-};
-
-template <class M>
-MagCarve<M> magsac_carve(void* ws, int B, int N) {
-  MagCarve<M> m;
-  m.c = carve<M>(ws, B, N);
-  char* p = static_cast<char*>(ws);
-  size_t o = m.c.bytes - 256;
-  m.ms = reinterpret_cast<MagState*>(p + o); o = align256(o + sizeof(MagState) * B);
-  m.sc = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * M::SLOTS * (size_t)B * R);
-  m.bytes = o + 256;
-  return m;
-}
-
-template <class M>
-size_t magsac_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? magsac_carve<M>(nullptr, B, N).bytes : 0; }
 
 // s + x with its rounding error added to the compensation c (Knuth's TwoSum: exact, whatever the order of s and x)
 __device__ __forceinline__ void two_sum(float& s, float& c, float x) {
@@ -647,81 +516,332 @@ __device__ __forceinline__ void magsac_sums(const float* mf, int nm, const float
   for (int r = 0; r < SL; ++r) acc[r] = wave_total(acc[r], cmp[r]);
 }
 
-// one thread per pair: residual scales, V scale, threshold (M::mag_thr2: tau^2 in the units of M::residual2)
+// lane 0 of the accept wave: the candidate (c inliers) becomes the current model, or refinement stops
+template <class M>
+__device__ __forceinline__ void settle(PairState<M>& P, bool keep, int c) {
+  if (keep) {
+    P.best = c;
+    for (int k = 0; k < 9; ++k) P.cur[k] = P.cand[k];
+    for (int k = 0; k < 12; ++k) P.curf[k] = P.candf[k];
+  } else {
+    P.stop = 1;
+  }
+  P.cand_ok = 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------ scoring policies
+// What a scoring supplies to the pipeline below: Ws (what it keeps in the workspace next to the pair states) and carve; Key,
+// worst, better, keys, running and record (the arg-best of the select kernel); score (what one wave computes for one hypothesis,
+// and stores per slot); inlier (the mask); refit and accept (one refinement step), REFITS, steps and MASK_BEFORE_REFIT (whether
+// and how often the host enqueues it, from the entry point's `refine` / `lo_iters`); INFO, INFO_MIN and finish (its info row);
+// INIT (a launch that fills Ws) and SCORES (the entry point has an out_score).
+
+// Inlier counts: larger is better; refinement is a least-squares refit on the current inliers, kept while the count does not drop.
+struct CountScoring {
+  using Key = int;
+  struct Ws {};                 // nothing: the keys are Slots::cnt, the running best PairState::best
+  static constexpr bool INIT = false, MASK_BEFORE_REFIT = true, SCORES = false;
+  static constexpr int MAX_STEPS = 0;  // `refine` is a flag
+  template <class M> static constexpr int INFO = M::INFO;
+  template <class M> static constexpr bool INFO_MIN = M::INFO > INFO_CORE;
+  template <class M> static constexpr bool REFITS = M::REFINE_ITERS > 0;
+  template <class M> static int steps(int refine) { return refine ? M::REFINE_ITERS : 0; }
+  static size_t carve(Ws&, char*, size_t o, size_t, int) { return o; }
+
+  __device__ static Key worst() { return -1; }
+  __device__ static bool better(Key a, Key b) { return a > b; }
+  __device__ static const Key* keys(const Ws&, const Slots& sl) { return sl.cnt; }
+  template <class M> __device__ static Key running(const PairState<M>& P, const Ws&, int) { return P.best; }
+  __device__ static void record(const Ws&, int, Key) {}
+
+  // the models' f32 inlier tests (M::inlier), popc(ballot) counts, -1 for unused slots
+  template <class M>
+  __device__ static void score(const float* mf, int nm, const float4* __restrict__ Pp, const PairState<M>& P, const Ws&, int,
+                               int lane, long g, const Slots& sl) {
+    constexpr int SL = M::SLOTS;
+    const int n = P.n;
+    const float t2a = P.thr2a, t2b = P.thr2b;
+    int c[SL];
+#pragma unroll
+    for (int r = 0; r < SL; ++r) c[r] = 0;
+    if (nm > 0) {
+      for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        const float4 p = i < n ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
+#pragma unroll
+        for (int r = 0; r < SL; ++r)
+          if (M::SCORE_EVERY_SLOT || r < nm) c[r] += __popcll(__ballot(M::inlier(mf + 12 * r, p, t2a, t2b)));
+      }
+    }
+    if (lane == 0) {
+      int* o = sl.cnt + g * SL;
+#pragma unroll
+      for (int r = 0; r < SL; ++r) o[r] = r < nm ? c[r] : -1;
+    }
+  }
+
+  template <class M>
+  __device__ static bool inlier(const PairState<M>& P, const Ws&, int, float4 p) { return M::inlier(P.curf, p, P.thr2a, P.thr2b); }
+
+  template <class M>
+  __device__ static void refit(const float2* A, const float2* Bp, const float4*, PairState<M>& P, const Ws&, int,
+                               const unsigned char* mask) {
+    M::refit(A, Bp, P, mask);
+  }
+
+  // re-score the candidate; keep it if its count is not lower, else stop refining
+  template <class M>
+  __device__ static void accept(const float4* __restrict__ Pp, PairState<M>& P, const Ws&, int, int lane) {
+    const int n = P.n;
+    const float t2a = P.thr2a, t2b = P.thr2b;
+    int c = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+      const int i = i0 + lane;
+      const float4 p = i < n ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
+      c += __popcll(__ballot(M::inlier(P.candf, p, t2a, t2b)));
+    }
+    if (lane == 0) settle(P, c >= P.best, c);
+  }
+
+  template <class M>
+  __device__ static void finish(const PairState<M>&, const Ws&, int, int*, double*) {}
+};
+
+// MAGSAC++: the key is the sum of rho, smaller is better, the inlier count r < tau carried along for the adaptive iteration
+// count; refinement is IRLS local optimisation (M::wrefit), a step kept only if it lowers the sum of rho.  From the model it
+// needs residual2 / res_terms / r2_from / NT, res_scales, mag_thr2, wrefit, MAG_INFO.
+struct MagsacScoring {
+  using Key = float;
+  struct Ws {
+    MagState* ms;               // [B]
+    float* sc;                  // sum of rho per slot, +inf if unused [B * R * SLOTS]
+  };
+  static constexpr bool INIT = true, MASK_BEFORE_REFIT = false, SCORES = true;
+  static constexpr int MAX_STEPS = 64;  // lo_iters of the entry points (MAGSAC_MAX_LO, ESSENTIAL_MAGSAC_MAX_LO)
+  template <class M> static constexpr int INFO = M::MAG_INFO;
+  template <class M> static constexpr bool INFO_MIN = true;
+  template <class M> static constexpr bool REFITS = true;
+  template <class M> static int steps(int lo_iters) { return lo_iters; }
+  static size_t carve(Ws& w, char* p, size_t o, size_t slots, int B) {
+    w.ms = reinterpret_cast<MagState*>(p + o); o = align256(o + sizeof(MagState) * B);
+    w.sc = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * slots);
+    return o;
+  }
+
+  __device__ static Key worst() { return INFINITY; }
+  __device__ static bool better(Key a, Key b) { return a < b; }
+  __device__ static const Key* keys(const Ws& w, const Slots&) { return w.sc; }
+  template <class M> __device__ static Key running(const PairState<M>&, const Ws& w, int b) { return w.ms[b].score; }
+  __device__ static void record(const Ws& w, int b, Key v) {
+    w.ms[b].score = v;
+    w.ms[b].score_min = v;
+  }
+
+  // one thread per pair (magsac_init_kernel): residual scales, V scale, threshold (M::mag_thr2: tau^2 in the units of M::residual2)
+  template <class M>
+  __device__ static void init(const PairState<M>& P, float thr, MagState& S) {
+    M::res_scales(P.nrm, S.sa2, S.sb2);
+    const double t2 = M::mag_thr2(P.nrm, thr);
+    S.vs = (float)(MAGSAC_K2 / (2 * t2));
+    S.t2 = (float)t2;
+    S.score = INFINITY;
+    S.score_min = INFINITY;
+    S.lo_steps = 0;
+    S.gain = 0.0;
+  }
+
+  // compensated f32 sum of rho per slot (lane partials over rows i = lane mod 64 ascending, then a fixed butterfly), and the
+  // count r < tau
+  template <class M>
+  __device__ static void score(const float* mf, int nm, const float4* __restrict__ Pp, const PairState<M>& P, const Ws& w, int b,
+                               int lane, long g, const Slots& sl) {
+    constexpr int SL = M::SLOTS;
+    float acc[SL];
+    int c[SL];
+#pragma unroll
+    for (int r = 0; r < SL; ++r) { acc[r] = 0.f; c[r] = 0; }
+    if (nm > 0) magsac_sums<M, SL>(mf, nm, Pp, P.n, w.ms[b], lane, acc, c);
+    if (lane == 0) {
+#pragma unroll
+      for (int r = 0; r < SL; ++r) {
+        w.sc[g * SL + r] = r < nm ? acc[r] : INFINITY;
+        sl.cnt[g * SL + r] = r < nm ? c[r] : -1;
+      }
+    }
+  }
+
+  template <class M>
+  __device__ static bool inlier(const PairState<M>& P, const Ws& w, int b, float4 p) {  // r < tau
+    const MagState& S = w.ms[b];
+    return M::residual2(P.curf, p, S.sa2, S.sb2) < S.t2;
+  }
+
+  template <class M>
+  __device__ static void refit(const float2* A, const float2* Bp, const float4* pts, PairState<M>& P, const Ws& w, int b,
+                               const unsigned char*) {
+    M::wrefit(A, Bp, pts, P, w.ms[b]);
+  }
+
+  // keep the candidate if its sum of rho is strictly lower than the current model's, else stop.  The gain sum(rho_cur - rho_cand)
+  // is measured on the same rows in one pass, the candidate's residual terms as the current model's plus those of the f32
+  // difference (cand - cur): rounding the two models to f32 separately moves each sum by far more than a late IRLS step gains (an
+  // inlier's residual is a small difference of O(1) normalised terms), and paired this way the shared part of that error
+  // cancels.  The inlier count is the candidate's own (what the mask kernel evaluates).
+  template <class M>
+  __device__ static void accept(const float4* __restrict__ Pp, PairState<M>& P, const Ws& w, int b, int lane) {
+    constexpr int NT = M::NT;
+    MagState& S = w.ms[b];
+    float dm[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) dm[k] = (float)(P.cand[k] - P.cur[k]);
+    const int n = P.n;
+    const float sa2 = S.sa2, sb2 = S.sb2, vs = S.vs, t2 = S.t2;
+    float g = 0.f, gc = 0.f;
+    int c = 0;
+    for (int i0 = 0; i0 < n; i0 += 64) {
+      const int i = i0 + lane;
+      const bool row = i < n;
+      const float4 p = row ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
+      float tu[NT], td[NT], tc[NT];
+      M::res_terms(P.curf, p, tu);
+      M::res_terms(dm, p, td);
+#pragma unroll
+      for (int k = 0; k < NT; ++k) tc[k] = tu[k] + td[k];
+      float wt;
+      const float ru = magsac_rho(M::r2_from(tu, sa2, sb2) * vs, wt);
+      const float rc = magsac_rho(M::r2_from(tc, sa2, sb2) * vs, wt);
+      two_sum(g, gc, row ? ru - rc : 0.f);
+      c += __popcll(__ballot(M::residual2(P.candf, p, sa2, sb2) < t2));
+    }
+    g = wave_total(g, gc);
+    if (lane == 0) {
+      if (g > 0.f) {
+        S.gain = S.gain + (double)g;
+        S.lo_steps = S.lo_steps + 1;
+      }
+      settle(P, g > 0.f, c);
+    }
+  }
+
+  // LO steps after the shared info entries; scores (the final sum of rho is the winning minimal model's less the gains of the
+  // accepted LO steps)
+  template <class M>
+  __device__ static void finish(const PairState<M>& P, const Ws& w, int b, int* info, double* score) {
+    const MagState& S = w.ms[b];
+    info[0] = S.lo_steps;
+    const bool found = P.best_h >= 0;
+    score[2 * (long)b] = found ? (double)S.score_min : 0.0;
+    score[2 * (long)b + 1] = found ? (double)S.score_min - S.gain : 0.0;
+  }
+};
+
+// ------------------------------------------------------------------------------------------------------------ kernels
+template <class M>
+__global__ __launch_bounds__(256) void ransac_norm_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
+                                                          const int* __restrict__ counts, const double* __restrict__ K, int N, float thr,
+                                                          int max_iters, PairState<M>* __restrict__ st, float4* __restrict__ pts) {
+  __shared__ double sh[256];
+  const int b = blockIdx.x;
+  const int n = counts ? min(max(counts[b], 0), N) : N;
+  typename M::Norm nrm;
+  float t2a, t2b;
+  const bool valid = M::normalise(ka + (long)b * N, kb + (long)b * N, n, K ? K + (long)b * 9 : nullptr, thr, sh,
+                                  pts + (long)b * N, nrm, t2a, t2b);
+  if (threadIdx.x == 0) {
+    PairState<M>& S = st[b];
+    S.nrm = nrm;
+    S.thr2a = t2a;
+    S.thr2b = t2b;
+    S.n = n;
+    S.valid = valid ? 1 : 0;
+    S.best = -1; S.best_h = -1; S.best_root = -1; S.best_min = -1;
+    S.needed = max_iters;
+    S.rounds = 0;
+    S.done = valid ? 0 : 1;
+    S.stop = 0;
+    S.cand_ok = 0;
+    for (int k = 0; k < 9; ++k) { S.cur[k] = 0; S.cand[k] = 0; }
+    for (int k = 0; k < 12; ++k) { S.curf[k] = 0; S.candf[k] = 0; }
+  }
+}
+
+// one thread per pair: the MAGSAC++ state of the pair (MagsacScoring::init)
 template <class M>
 __global__ __launch_bounds__(64) void magsac_init_kernel(int B, float thr, const PairState<M>* __restrict__ st,
                                                          MagState* __restrict__ ms) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
-  MagState& S = ms[b];
-  M::res_scales(st[b].nrm, S.sa2, S.sb2);
-  const double t2 = M::mag_thr2(st[b].nrm, thr);
-  S.vs = (float)(MAGSAC_K2 / (2 * t2));
-  S.t2 = (float)t2;
-  S.score = INFINITY;
-  S.score_min = INFINITY;
-  S.lo_steps = 0;
-  S.gain = 0.0;
+  MagsacScoring::init<M>(st[b], thr, ms[b]);
 }
 
-// one wave per (pair, hypothesis)
+// HYP_LANES lanes per (pair, hypothesis of the round), HYP_THREADS per workgroup; grid B * R * HYP_LANES / HYP_THREADS
 template <class M>
-__global__ __launch_bounds__(256) void magsac_score_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
-                                                           const MagState* __restrict__ ms, Slots sl, float* __restrict__ sc) {
-  constexpr int SL = M::SLOTS;
+__global__ __launch_bounds__(M::HYP_THREADS) void ransac_hyp_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
+                                                                    int N, const unsigned long long* __restrict__ seeds,
+                                                                    const PairState<M>* __restrict__ st, int round, Slots sl) {
+  constexpr int S = M::S, L = M::HYP_LANES;
+  static_assert(R % (M::HYP_THREADS / L) == 0, "a workgroup must not straddle two pairs");
+  const int g = blockIdx.x * (M::HYP_THREADS / L) + threadIdx.x / L, b = g / R;
+  const PairState<M>& P = st[b];
+  if (P.done) return;  // uniform over the workgroup: its hypotheses belong to one pair
+  const int h = round * R + g % R;
+  int idx[S];
+  bool act = draw_sample<S>(seeds[b], h, P.n, idx);
+  double xa[S], ya[S], xb[S], yb[S];
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    const float2 a = act ? ka[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
+    const float2 q = act ? kb[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
+    act = act && finite_row(a.x, a.y, q.x, q.y);
+    P.nrm.apply(a, q, xa[k], ya[k], xb[k], yb[k]);
+  }
+  M::hypothesis(xa, ya, xb, yb, act, g, threadIdx.x % L, sl);
+}
+
+// one wave per (pair, hypothesis): the hypothesis' models (wave-uniform coefficients) against the pair's points (Sc::score)
+template <class M, class Sc>
+__global__ __launch_bounds__(256) void ransac_score_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
+                                                           typename Sc::Ws w, Slots sl) {
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = g / R;
   const PairState<M>& P = st[b];
   if (P.done) return;
-  const int nm = sl.n[g];
-  float acc[SL];
-  int c[SL];
-#pragma unroll
-  for (int r = 0; r < SL; ++r) { acc[r] = 0.f; c[r] = 0; }
-  if (nm > 0) magsac_sums<M, SL>(sl.f + (long)g * SL * 12, nm, pts + (long)b * N, P.n, ms[b], lane, acc, c);
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < SL; ++r) {
-      sc[(long)g * SL + r] = r < nm ? acc[r] : INFINITY;
-      sl.cnt[(long)g * SL + r] = r < nm ? c[r] : -1;
-    }
-  }
+  Sc::template score<M>(sl.f + (long)g * M::SLOTS * 12, sl.n[g], pts + (long)b * N, P, w, b, lane, g, sl);
 }
 
-// one workgroup per pair: smallest score of the round (lowest slot on ties), running best, adaptive iteration count, done flag
-template <class M>
-__global__ __launch_bounds__(256) void magsac_select_kernel(PairState<M>* __restrict__ st, MagState* __restrict__ ms, int round,
-                                                            double conf, int max_iters, Slots sl, const float* __restrict__ sc) {
+// one workgroup per pair: best key of the round (ties: lowest (h, slot)), running best, adaptive iteration count, done flag
+template <class M, class Sc>
+__global__ __launch_bounds__(256) void ransac_select_kernel(PairState<M>* __restrict__ st, typename Sc::Ws w, int round, double conf,
+                                                            int max_iters, Slots sl) {
+  using Key = typename Sc::Key;
   constexpr int SL = M::SLOTS;
-  __shared__ float ss[256];
+  __shared__ Key sk[256];
   __shared__ int si[256];
   const int b = blockIdx.x, t = threadIdx.x;
   PairState<M>& P = st[b];
   if (P.done) return;
-  const float* s = sc + (long)b * R * SL;
-  float bs = INFINITY;
+  const Key* key = Sc::keys(w, sl) + (long)b * R * SL;
+  Key bk = Sc::worst();
   int bi = 0x7fffffff;
   for (int k = t; k < R * SL; k += 256) {
-    const float v = s[k];
-    if (v < bs) { bs = v; bi = k; }  // k ascends: ties keep the lower slot
+    const Key v = key[k];
+    if (Sc::better(v, bk)) { bk = v; bi = k; }  // k ascends: ties keep the lower slot
   }
-  ss[t] = bs;
+  sk[t] = bk;
   si[t] = bi;
   __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (t < w) {
-      const float v = ss[t + w];
-      const int i = si[t + w];
-      if (v < ss[t] || (v == ss[t] && i < si[t])) { ss[t] = v; si[t] = i; }
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) {
+      const Key v = sk[t + s];
+      const int i = si[t + s];
+      if (Sc::better(v, sk[t]) || (v == sk[t] && i < si[t])) { sk[t] = v; si[t] = i; }
     }
     __syncthreads();
   }
   if (t == 0) {
-    MagState& S = ms[b];
-    const float v = ss[0];
+    const Key v = sk[0];
     const int k = si[0];
-    if (v < S.score) {  // strictly: an earlier round's model keeps a tie
-      S.score = v;
-      S.score_min = v;
+    if (Sc::better(v, Sc::template running<M>(P, w, b))) {  // strictly: an earlier round's model keeps a tie
+      Sc::record(w, b, v);
       const int c = sl.cnt[(long)b * R * SL + k];
       P.best = c;
       P.best_min = c;
@@ -738,132 +858,112 @@ __global__ __launch_bounds__(256) void magsac_select_kernel(PairState<M>* __rest
   }
 }
 
-// one workgroup per pair: an IRLS candidate from the MAGSAC++ weights of the current model (M::wrefit)
-template <class M>
-__global__ __launch_bounds__(256) void magsac_refit_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
-                                                           const float4* __restrict__ pts, int N, PairState<M>* __restrict__ st,
-                                                           const MagState* __restrict__ ms) {
-  const long o = (long)blockIdx.x * N;
-  M::wrefit(ka + o, kb + o, pts + o, st[blockIdx.x], ms[blockIdx.x]);
-}
-
-// one wave per pair: keep the candidate if its sum of rho is strictly lower than the current model's, else stop.  The gain
-// sum(rho_cur - rho_cand) is measured on the same rows in one pass, the candidate's residual terms as the current model's
-// plus those of the f32 difference (cand - cur): rounding the two models to f32 separately moves each sum by far more than a
-// late IRLS step gains (an inlier's residual is a small difference of O(1) normalised terms), and paired this way the shared
-// part of that error cancels.  The inlier count is the candidate's own (what the mask kernel evaluates).
-template <class M>
-__global__ __launch_bounds__(64) void magsac_accept_kernel(const float4* __restrict__ pts, int N, PairState<M>* __restrict__ st,
-                                                           MagState* __restrict__ ms) {
-  constexpr int NT = M::NT;
-  const int b = blockIdx.x, lane = threadIdx.x;
-  PairState<M>& P = st[b];
-  if (P.stop || !P.cand_ok) return;
-  MagState& S = ms[b];
-  float dm[9];
-#pragma unroll
-  for (int k = 0; k < 9; ++k) dm[k] = (float)(P.cand[k] - P.cur[k]);
-  const float4* Pp = pts + (long)b * N;
-  const int n = P.n;
-  const float sa2 = S.sa2, sb2 = S.sb2, vs = S.vs, t2 = S.t2;
-  float g = 0.f, gc = 0.f;
-  int c = 0;
-  for (int i0 = 0; i0 < n; i0 += 64) {
-    const int i = i0 + lane;
-    const bool row = i < n;
-    const float4 p = row ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
-    float tu[NT], td[NT], tc[NT];
-    M::res_terms(P.curf, p, tu);
-    M::res_terms(dm, p, td);
-#pragma unroll
-    for (int k = 0; k < NT; ++k) tc[k] = tu[k] + td[k];
-    float w;
-    const float ru = magsac_rho(M::r2_from(tu, sa2, sb2) * vs, w);
-    const float rc = magsac_rho(M::r2_from(tc, sa2, sb2) * vs, w);
-    two_sum(g, gc, row ? ru - rc : 0.f);
-    c += __popcll(__ballot(M::residual2(P.candf, p, sa2, sb2) < t2));
-  }
-  g = wave_total(g, gc);
-  if (lane == 0) {
-    if (g > 0.f) {
-      S.gain = S.gain + (double)g;
-      S.lo_steps = S.lo_steps + 1;
-      P.best = c;
-      for (int k = 0; k < 9; ++k) P.cur[k] = P.cand[k];
-      for (int k = 0; k < 12; ++k) P.curf[k] = P.candf[k];
-    } else {
-      P.stop = 1;
-    }
-    P.cand_ok = 0;
-  }
-}
-
-// mask[b, i] = r < tau under the current model (rows beyond counts[b], and pairs without inliers: 0); grid (ceil(N / 256), B)
-template <class M>
-__global__ __launch_bounds__(256) void magsac_mask_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
-                                                          const MagState* __restrict__ ms, unsigned char* __restrict__ mask) {
+// mask[b, i] = inlier of the current model (Sc::inlier; rows beyond counts[b], and pairs without a model: 0); grid (ceil(N / 256), B)
+template <class M, class Sc>
+__global__ __launch_bounds__(256) void ransac_mask_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
+                                                          typename Sc::Ws w, unsigned char* __restrict__ mask) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   const PairState<M>& P = st[b];
   bool in = false;
-  if (P.best > 0 && i < P.n) {
-    const MagState& S = ms[b];
-    in = M::residual2(P.curf, pts[(long)b * N + i], S.sa2, S.sb2) < S.t2;
-  }
+  if (P.best > 0 && i < P.n) in = Sc::template inlier<M>(P, w, b, pts[(long)b * N + i]);
   mask[(long)b * N + i] = in ? 1 : 0;
 }
 
-// one thread per pair: ok flag, M::mag_finish (model, the first M::MAG_INFO - 1 entries of the info row), LO steps, scores (the final sum
-// of rho is the winning minimal model's less the gains of the accepted LO steps)
-template <class M>
-__global__ __launch_bounds__(64) void magsac_finish_kernel(int B, const PairState<M>* __restrict__ st, const MagState* __restrict__ ms,
+// one workgroup per pair: a candidate from the current model (Sc::refit: M::refit on the mask, or M::wrefit)
+template <class M, class Sc>
+__global__ __launch_bounds__(256) void ransac_refit_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
+                                                           const float4* __restrict__ pts, int N, PairState<M>* __restrict__ st,
+                                                           typename Sc::Ws w, const unsigned char* __restrict__ mask) {
+  const int b = blockIdx.x;
+  const long o = (long)b * N;
+  Sc::template refit<M>(ka + o, kb + o, pts + o, st[b], w, b, mask + o);
+}
+
+// one wave per pair: re-score the candidate and keep it or stop (Sc::accept)
+template <class M, class Sc>
+__global__ __launch_bounds__(64) void ransac_accept_kernel(const float4* __restrict__ pts, int N, PairState<M>* __restrict__ st,
+                                                           typename Sc::Ws w) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  PairState<M>& P = st[b];
+  if (P.stop || !P.cand_ok) return;
+  Sc::template accept<M>(pts + (long)b * N, P, w, b, lane);
+}
+
+// one thread per pair: ok flag, M::model_out (model in pixel terms), the info row (write_info, then Sc::finish), Sc's scores
+template <class M, class Sc>
+__global__ __launch_bounds__(64) void ransac_finish_kernel(int B, const PairState<M>* __restrict__ st, typename Sc::Ws w,
                                                            double* __restrict__ out, unsigned char* __restrict__ ok,
                                                            int* __restrict__ info, double* __restrict__ score) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   const PairState<M>& P = st[b];
-  const MagState& S = ms[b];
   const bool good = P.valid && P.best > 0;
-  M::mag_finish(P, good, out + (long)b * 9, info + (long)b * M::MAG_INFO);
-  info[(long)b * M::MAG_INFO + M::MAG_INFO - 1] = S.lo_steps;
-  const bool found = P.best_h >= 0;
-  score[2 * (long)b] = found ? (double)S.score_min : 0.0;
-  score[2 * (long)b + 1] = found ? (double)S.score_min - S.gain : 0.0;
+  M::model_out(P, good, out + (long)b * 9);
+  int* row = info + (long)b * Sc::template INFO<M>;
+  Sc::template finish<M>(P, w, b, row + write_info(P, row, Sc::template INFO_MIN<M>), score);
   ok[b] = good ? 1 : 0;
 }
 
-template <class M>
-int magsac_run(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K, int B,
-               int N, float thr,
-               double conf, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask, unsigned char* out_ok,
-               int* out_info, double* out_score, void* ws, hipStream_t s) {
-  const MagCarve<M> w = magsac_carve<M>(align_base<void*>(ws), B, N);
-  const Carve<M>& c = w.c;
+// ------------------------------------------------------------------------------------------------------------ host
+// the argument checks of every entry point: `op` prefixes each message, `conf` names the confidence argument, `opt` is `refine`
+// or `lo_iters` (Sc::MAX_STEPS bounds the latter)
+template <class Sc>
+int check_args(const char* op, const char* conf, bool pointers, int B, int N, float threshold, double confidence, int max_iters,
+               int opt, size_t ws_bytes, size_t ws_need) {
+  const std::string o(op);
+  ROMA_REQUIRE(pointers, o + ": null pointer");
+  ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), o + ": need 0 < B <= 65536, 0 < N, B * N < 2^31");
+  ROMA_REQUIRE(max_iters > 0, o + ": max_iters must be positive");
+  ROMA_REQUIRE(threshold > 0 && isfinite(threshold), o + ": threshold must be positive and finite");
+  ROMA_REQUIRE(confidence >= 0 && confidence <= 1, o + ": " + conf + " must lie in [0, 1]");
+  ROMA_REQUIRE(ws_bytes >= ws_need, o + ": workspace too small (roma_op_" + o + "_workspace)");
+  if constexpr (Sc::MAX_STEPS > 0)
+    ROMA_REQUIRE(opt >= 0 && opt <= Sc::MAX_STEPS, o + ": lo_iters must lie in [0, " + std::to_string(Sc::MAX_STEPS) + "]");
+  return 0;
+}
+
+// the launch sequence of the pipeline; K: [B, 3, 3] f64 camera matrices or NULL, read by M::normalise only; opt: the entry
+// point's `refine` or `lo_iters` (Sc::steps); out_score: NULL for a scoring without scores
+template <class M, class Sc>
+int ransac_run(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K, int B,
+               int N, float thr, double conf, int max_iters, int opt, double* out_model, unsigned char* out_mask,
+               unsigned char* out_ok, int* out_info, double* out_score, void* ws, hipStream_t s) {
+  const Carve<M, Sc> c = carve<M, Sc>(align_base<void*>(ws), B, N);
   const float2* ka = reinterpret_cast<const float2*>(kpts_a);
   const float2* kb = reinterpret_cast<const float2*>(kpts_b);
   hipLaunchKernelGGL(ransac_norm_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, counts, K, N, thr, max_iters, c.st, c.pts);
   ROMA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(magsac_init_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, thr, c.st, w.ms);
-  ROMA_LAUNCH_CHECK();
+  if constexpr (Sc::INIT) {
+    hipLaunchKernelGGL(magsac_init_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, thr, c.st, c.w.ms);
+    ROMA_LAUNCH_CHECK();
+  }
   const int rounds = (max_iters + R - 1) / R;
   for (int r = 0; r < rounds; ++r) {
     hipLaunchKernelGGL(ransac_hyp_kernel<M>, dim3(B * R * M::HYP_LANES / M::HYP_THREADS), dim3(M::HYP_THREADS), 0, s, ka, kb, N,
                        seeds, c.st, r, c.sl);
     ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(magsac_score_kernel<M>, dim3(B * R / 4), dim3(256), 0, s, c.pts, N, c.st, w.ms, c.sl, w.sc);
+    hipLaunchKernelGGL((ransac_score_kernel<M, Sc>), dim3(B * R / 4), dim3(256), 0, s, c.pts, N, c.st, c.w, c.sl);
     ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(magsac_select_kernel<M>, dim3(B), dim3(256), 0, s, c.st, w.ms, r, conf, max_iters, c.sl, w.sc);
-    ROMA_LAUNCH_CHECK();
-  }
-  for (int it = 0; it < lo_iters; ++it) {
-    hipLaunchKernelGGL(magsac_refit_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, c.pts, N, c.st, w.ms);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(magsac_accept_kernel<M>, dim3(B), dim3(64), 0, s, c.pts, N, c.st, w.ms);
+    hipLaunchKernelGGL((ransac_select_kernel<M, Sc>), dim3(B), dim3(256), 0, s, c.st, c.w, r, conf, max_iters, c.sl);
     ROMA_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(magsac_mask_kernel<M>, dim3((N + 255) / 256, B), dim3(256), 0, s, c.pts, N, c.st, w.ms, out_mask);
+  const dim3 mgrid((N + 255) / 256, B);
+  if constexpr (Sc::template REFITS<M>) {
+    for (int it = 0, n = Sc::template steps<M>(opt); it < n; ++it) {
+      if (Sc::MASK_BEFORE_REFIT) {
+        hipLaunchKernelGGL((ransac_mask_kernel<M, Sc>), mgrid, dim3(256), 0, s, c.pts, N, c.st, c.w, out_mask);
+        ROMA_LAUNCH_CHECK();
+      }
+      hipLaunchKernelGGL((ransac_refit_kernel<M, Sc>), dim3(B), dim3(256), 0, s, ka, kb, c.pts, N, c.st, c.w, out_mask);
+      ROMA_LAUNCH_CHECK();
+      hipLaunchKernelGGL((ransac_accept_kernel<M, Sc>), dim3(B), dim3(64), 0, s, c.pts, N, c.st, c.w);
+      ROMA_LAUNCH_CHECK();
+    }
+  }
+  hipLaunchKernelGGL((ransac_mask_kernel<M, Sc>), mgrid, dim3(256), 0, s, c.pts, N, c.st, c.w, out_mask);
   ROMA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(magsac_finish_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, w.ms, out_model, out_ok, out_info,
+  hipLaunchKernelGGL((ransac_finish_kernel<M, Sc>), dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, c.w, out_model, out_ok, out_info,
                      out_score);
   ROMA_LAUNCH_CHECK();
   return 0;

@@ -96,11 +96,40 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
-def _robust(op, a, s, ninfo, seed, counts, head, tail, nscore=0):
-    """what ransac(), magsac() and essential() share after their own checks: zeroed outputs (M [B, 3, 3] float64, mask [B, N]
-    bool, ok [B] bool, info [B, ninfo] int32, and score [B, nscore] float64 if nscore), counts and seeds on the device, then
-    roma_op_<op>(*head(counts, seeds), B, N, *tail, outputs, workspace, stream) with the tensors of head passed as pointers.
-    Nothing is launched for B == 0 or N < s, where no pair can hold a minimal sample."""
+def _single(kpts):
+    """the single-pair form of the public functions: [N, 2] keypoints"""
+    return isinstance(kpts, torch.Tensor) and kpts.dim() == 2
+
+
+def _valid(valid, B, dev):
+    if valid is None:
+        return None
+    valid = torch.as_tensor(valid).to(device=dev).reshape(-1).to(torch.uint8).contiguous()
+    if valid.shape[0] != B:
+        raise ValueError(f"roma_amd.geometry: valid has {valid.shape[0]} entries for {B} pairs")
+    return valid
+
+
+MAGSAC_MAX_LO = 64  # csrc/geometry.h, csrc/essential.h
+# roma_op_<op>: (info columns, score columns, what the confidence argument is called)
+ROBUST_OPS = {"ransac": (6, 0, "confidence"), "magsac": (7, 2, "confidence"), "essential": (5, 0, "prob"),
+              "essential_magsac": (7, 2, "prob")}
+
+
+def _robust(op, kpts_A, kpts_B, threshold, confidence, max_iters, seed, counts, option=None, model=None, camera_matrix=None):
+    """ransac(), magsac(), essential() and essential_magsac(): the argument checks, zeroed outputs (M [B, 3, 3] float64, mask
+    [B, N] bool, ok [B] bool, info int32, and score float64 where the op has one: ROBUST_OPS), counts and seeds on the device,
+    then roma_op_<op>.  model: HOMOGRAPHY or FUNDAMENTAL, None for the essential matrix (which takes camera_matrix); option: the
+    op's `refine` or `lo_iters`, None where it has neither.  Nothing is launched for B == 0 or fewer columns than a minimal
+    sample, where no pair can hold one."""
+    ninfo, nscore, conf_name = ROBUST_OPS[op]
+    a, b = _pair_batch(kpts_A, kpts_B)
+    if model is not None and model not in SAMPLE_SIZE:
+        raise ValueError(f"roma_amd.geometry: unknown model {model}")
+    if not (threshold > 0) or not (0 <= confidence <= 1) or int(max_iters) <= 0:
+        raise ValueError(f"roma_amd.geometry: need threshold > 0, 0 <= {conf_name} <= 1, max_iters > 0")
+    if nscore and not (0 <= int(option) <= MAGSAC_MAX_LO):
+        raise ValueError(f"roma_amd.geometry: lo_iters must lie in [0, {MAGSAC_MAX_LO}]")
     B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
     outs = (torch.zeros((B, 3, 3), device=dev, dtype=torch.float64), torch.zeros((B, N), device=dev, dtype=torch.bool),
             torch.zeros((B,), device=dev, dtype=torch.bool), torch.zeros((B, ninfo), device=dev, dtype=torch.int32))
@@ -109,9 +138,11 @@ def _robust(op, a, s, ninfo, seed, counts, head, tail, nscore=0):
     if B == 0:
         return outs
     counts, seeds = _counts(counts, B, dev), _seeds(seed, B, dev)
-    front = head(counts, seeds)  # holds its tensors until the launch is enqueued
-    if N < s:
+    # the tensors live until the launch is enqueued
+    front = (a, b, counts, seeds, _cameras(camera_matrix, B, dev)) if model is None else (int(model), a, b, counts, seeds)
+    if N < (5 if model is None else SAMPLE_SIZE[model]):
         return outs
+    tail = (float(threshold), float(confidence), int(max_iters)) + (() if option is None else (int(option),))
     lib = _lib.load()
     nws = int(getattr(lib, f"roma_op_{op}_workspace")(B, N))
     ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
@@ -127,17 +158,7 @@ def ransac(model: int, kpts_A: torch.Tensor, kpts_B: torch.Tensor, threshold: fl
     (rows at or beyond counts[b] are never read); seed an int (every pair), a [B] tensor (one per pair) or None (drawn from
     torch's CPU generator).  Returns (M [B, 3, 3] float64, mask [B, N] bool, ok [B] bool, info [B, 6] int32) with
     info = (rounds run, winning hypothesis, its root, its inlier count, final inlier count, pair valid)."""
-    a, b = _pair_batch(kpts_A, kpts_B)
-    if model not in SAMPLE_SIZE:
-        raise ValueError(f"roma_amd.geometry: unknown model {model}")
-    if not (threshold > 0) or not (0 <= confidence <= 1) or int(max_iters) <= 0:
-        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= confidence <= 1, max_iters > 0")
-    return _robust("ransac", a, SAMPLE_SIZE[model], 6, seed, counts,
-                   lambda counts, seeds: (int(model), a, b, counts, seeds),
-                   (float(threshold), float(confidence), int(max_iters), 1 if refine else 0))
-
-
-MAGSAC_MAX_LO = 64  # csrc/geometry.h
+    return _robust("ransac", kpts_A, kpts_B, threshold, confidence, max_iters, seed, counts, 1 if refine else 0, model=model)
 
 
 def magsac(model: int, kpts_A: torch.Tensor, kpts_B: torch.Tensor, threshold: float, confidence: float, max_iters: int,
@@ -152,62 +173,59 @@ def magsac(model: int, kpts_A: torch.Tensor, kpts_B: torch.Tensor, threshold: fl
     Inputs as for `ransac`.  Returns (M [B, 3, 3] float64, mask [B, N] bool (residual < threshold), ok [B] bool,
     info [B, 7] int32, score [B, 2] float64) with info = (rounds run, winning hypothesis, its root, inliers of the winning minimal
     model, final inliers, pair valid, LO steps accepted) and score = (loss of the winning minimal model, final loss: that less the gains of the accepted LO steps)."""
-    a, b = _pair_batch(kpts_A, kpts_B)
-    if model not in SAMPLE_SIZE:
-        raise ValueError(f"roma_amd.geometry: unknown model {model}")
-    if not (threshold > 0) or not (0 <= confidence <= 1) or int(max_iters) <= 0:
-        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= confidence <= 1, max_iters > 0")
-    if not (0 <= int(lo_iters) <= MAGSAC_MAX_LO):
-        raise ValueError(f"roma_amd.geometry: lo_iters must lie in [0, {MAGSAC_MAX_LO}]")
-    return _robust("magsac", a, SAMPLE_SIZE[model], 7, seed, counts,
-                   lambda counts, seeds: (int(model), a, b, counts, seeds),
-                   (float(threshold), float(confidence), int(max_iters), int(lo_iters)), nscore=2)
+    return _robust("magsac", kpts_A, kpts_B, threshold, confidence, max_iters, seed, counts, lo_iters, model=model)
+
+
+def _method(method, plain=None, scored=None):
+    """`plain` for method "ransac", `scored` for method "magsac"; any other method is an error"""
+    if method not in ("ransac", "magsac"):
+        raise ValueError(f"roma_amd.geometry: method must be 'ransac' or 'magsac', got {method!r}")
+    return plain if method == "ransac" else scored
 
 
 def _estimate(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, refine, counts, method):
     """(M, mask, ok) of `ransac` (method "ransac") or `magsac` (method "magsac"; refine=False means lo_iters=0)"""
-    if method == "ransac":
-        return ransac(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, refine, counts)[:3]
-    if method == "magsac":
-        return magsac(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, 10 if refine else 0, counts)[:3]
-    raise ValueError(f"roma_amd.geometry: method must be 'ransac' or 'magsac', got {method!r}")
+    fn = _method(method, ransac, magsac)
+    return fn(model, kpts_A, kpts_B, threshold, confidence, max_iters, seed, refine if fn is ransac else 10 if refine else 0, counts)[:3]
 
 
 MODEL_MIN_ROWS = {HOMOGRAPHY: 4, FUNDAMENTAL: 7}  # csrc/model_refine.hip: rows below which nothing is fitted
 
 
-def _refine_model(model, M, kpts_A, kpts_B, threshold, max_steps, counts, valid, name):
-    """roma_op_refine_model on [B, N, 2] pixels: (M [B, 3, 3] float64, mask [B, N] bool, info [B, 4] int32, cost [B, 2] float64).
-    Nothing is launched for B == 0 or fewer rows than the model needs: every pair comes back untouched."""
-    a, b = _pair_batch(kpts_A, kpts_B)
+def _refine(op, head, start, a, b, threshold, max_steps, counts, valid, min_rows, need, cost=False):
+    """roma_op_refine_<op>(*head, *start, ...) on the pair batch a, b [B, N, 2]: (*fitted, mask [B, N] bool, info [B, 4] int32)
+    and, if cost, cost [B, 2] float64.  start: the [B, r, c] float64 tensors to fit.  Nothing is launched for B == 0 or fewer
+    than min_rows columns: every pair comes back untouched."""
     B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
-    M = _pose_tensor(M, name, B, (3, 3), dev)
     if not (threshold > 0) or int(max_steps) < 0:
-        raise ValueError("roma_amd.geometry: need threshold > 0, max_steps >= 0")
-    counts = _counts(counts, B, dev)
-    if valid is not None:
-        valid = torch.as_tensor(valid).to(device=dev).reshape(-1).to(torch.uint8).contiguous()
-        if valid.shape[0] != B:
-            raise ValueError(f"roma_amd.geometry: valid has {valid.shape[0]} entries for {B} pairs")
+        raise ValueError(f"roma_amd.geometry: need {need} > 0, max_steps >= 0")
+    counts, valid = _counts(counts, B, dev), _valid(valid, B, dev)
     mask = torch.zeros((B, N), device=dev, dtype=torch.bool)
     info = torch.zeros((B, 4), device=dev, dtype=torch.int32)
-    cost = torch.full((B, 2), float("nan"), device=dev, dtype=torch.float64)
-    if B == 0 or N < MODEL_MIN_ROWS[model]:
-        return M.clone(), mask, info, cost
-    out = torch.empty_like(M)
+    extra = (torch.full((B, 2), float("nan"), device=dev, dtype=torch.float64),) if cost else ()
+    if B == 0 or N < min_rows:
+        return (*(x.clone() for x in start), mask, info, *extra)
+    out = tuple(torch.empty_like(x) for x in start)
     lib = _lib.load()
-    nws = int(lib.roma_op_refine_model_workspace(B, N))
+    nws = int(getattr(lib, f"roma_op_refine_{op}_workspace")(B, N))
     ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
     with torch.cuda.device(dev):
-        _lib.check(lib.roma_op_refine_model(int(model), _ptr(M), _ptr(a), _ptr(b), _ptr(counts), _ptr(valid), B, N, float(threshold),
-                                            int(max_steps), _ptr(out), _ptr(mask), _ptr(info), _ptr(cost), _ptr(ws), nws,
-                                            _stream(dev)))
-    return out, mask, info, cost
+        _lib.check(getattr(lib, f"roma_op_refine_{op}")(*head, *map(_ptr, start), _ptr(a), _ptr(b), _ptr(counts), _ptr(valid), B, N,
+                                                        float(threshold), int(max_steps), *map(_ptr, out), _ptr(mask), _ptr(info),
+                                                        *map(_ptr, extra), _ptr(ws), nws, _stream(dev)))
+    return (*out, mask, info, *extra)
+
+
+def _refine_model(model, M, kpts_A, kpts_B, threshold, max_steps, counts, valid, name):
+    """roma_op_refine_model on [B, N, 2] pixels: (M [B, 3, 3] float64, mask [B, N] bool, info [B, 4] int32, cost [B, 2] float64)"""
+    a, b = _pair_batch(kpts_A, kpts_B)
+    M = _pose_tensor(M, name, int(a.shape[0]), (3, 3), a.device)
+    return _refine("model", (int(model),), (M,), a, b, threshold, max_steps, counts, valid, MODEL_MIN_ROWS[model], "threshold", True)
 
 
 def _refine_front(model, M, kpts_A, kpts_B, threshold, max_steps, counts, valid, name):
     out = _refine_model(model, M, kpts_A, kpts_B, threshold, max_steps, counts, valid, name)
-    return tuple(o[0] for o in out) if isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2 else out
+    return tuple(o[0] for o in out) if _single(kpts_A) else out
 
 
 def refine_homography(H, kpts_A, kpts_B, threshold, max_steps=25, counts=None, valid=None):
@@ -249,7 +267,7 @@ def _polished(model, M, mask, ok, kpts_A, kpts_B, threshold, lm_steps, counts):
 def _front(kpts_A, outs, ok, none):
     """what the public functions return: for a batch outs + (ok,); for a single pair ([N, 2] kpts) the first entry of each of
     outs, or `none` when no model was found - the one host synchronisation of the single-pair forms (OpenCV returns None)"""
-    if not (isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2):
+    if not _single(kpts_A):
         return (*outs, ok)
     return tuple(o[0] for o in outs) if bool(ok[0]) else none
 
@@ -296,12 +314,7 @@ ESSENTIAL_MAX_ROOTS = 10  # solutions of one five-point sample (csrc/essential.h
 def essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None):
     """Batched cv2.findEssentialMat, no host synchronisation.  Returns (E [B, 3, 3] float64, mask [B, N] bool, ok [B] bool,
     info [B, 5] int32) with info = (rounds run, winning hypothesis, its root, inlier count, pair valid)."""
-    a, b = _pair_batch(kpts_A, kpts_B)
-    if not (threshold > 0) or not (0 <= prob <= 1) or int(max_iters) <= 0:
-        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= prob <= 1, max_iters > 0")
-    return _robust("essential", a, 5, 5, seed, counts,
-                   lambda counts, seeds: (a, b, counts, seeds, _cameras(camera_matrix, int(a.shape[0]), a.device)),
-                   (float(threshold), float(prob), int(max_iters)))
+    return _robust("essential", kpts_A, kpts_B, threshold, prob, max_iters, seed, counts, camera_matrix=camera_matrix)
 
 
 def essential_magsac(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, lo_iters=10,
@@ -319,27 +332,13 @@ def essential_magsac(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1
     positive; mask [B, N] bool (residual < threshold: `essential`'s inlier rule); ok [B] bool; info [B, 7] int32; score [B, 2]
     float64) with info = (rounds run, winning hypothesis, its root, inliers of the winning minimal model, final inliers, pair
     valid, LO steps accepted) and score = (loss of the winning minimal model, final loss)."""
-    a, b = _pair_batch(kpts_A, kpts_B)
-    if not (threshold > 0) or not (0 <= prob <= 1) or int(max_iters) <= 0:
-        raise ValueError("roma_amd.geometry: need threshold > 0, 0 <= prob <= 1, max_iters > 0")
-    if not (0 <= int(lo_iters) <= MAGSAC_MAX_LO):
-        raise ValueError(f"roma_amd.geometry: lo_iters must lie in [0, {MAGSAC_MAX_LO}]")
-    return _robust("essential_magsac", a, 5, 7, seed, counts,
-                   lambda counts, seeds: (a, b, counts, seeds, _cameras(camera_matrix, int(a.shape[0]), a.device)),
-                   (float(threshold), float(prob), int(max_iters), int(lo_iters)), nscore=2)
-
-
-def _check_method(method):
-    if method not in ("ransac", "magsac"):
-        raise ValueError(f"roma_amd.geometry: method must be 'ransac' or 'magsac', got {method!r}")
+    return _robust("essential_magsac", kpts_A, kpts_B, threshold, prob, max_iters, seed, counts, lo_iters, camera_matrix=camera_matrix)
 
 
 def _essential(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, counts, method, lo_iters):
     """(E, mask, ok) of `essential` (method "ransac") or `essential_magsac` (method "magsac")"""
-    _check_method(method)
-    if method == "ransac":
-        return essential(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, counts)[:3]
-    return essential_magsac(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, lo_iters, counts)[:3]
+    fn = _method(method, essential, essential_magsac)
+    return fn(kpts_A, kpts_B, camera_matrix, prob, threshold, max_iters, seed, *(() if fn is essential else (lo_iters,)), counts)[:3]
 
 
 def find_essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None,
@@ -366,7 +365,6 @@ def recover_pose(E, kpts_A, kpts_B, mask=None, camera_matrix=None, distance_thre
 
     E [3, 3] with kpts [N, 2] -> (n_good int, R [3, 3] float64, t [3, 1] float64, mask_good [N] bool);
     E [B, 3, 3] with kpts [B, N, 2] -> (n_good [B] int32, R [B, 3, 3], t [B, 3, 1], mask_good [B, N]), no synchronisation."""
-    single = isinstance(kpts_A, torch.Tensor) and kpts_A.dim() == 2
     a, b = _pair_batch(kpts_A, kpts_B)
     B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
     if not isinstance(E, torch.Tensor) or not E.is_cuda:
@@ -391,7 +389,7 @@ def recover_pose(E, kpts_A, kpts_B, mask=None, camera_matrix=None, distance_thre
             _lib.check(lib.roma_op_recover_pose(_ptr(E), _ptr(a), _ptr(b), _ptr(mask), _ptr(counts), _ptr(K), B, N,
                                                 float(distance_thresh), _ptr(n_good), _ptr(R), _ptr(t), _ptr(good), _ptr(ws), nws,
                                                 _stream(dev)))
-    if single:
+    if _single(kpts_A):
         return int(n_good[0]), R[0], t[0], good[0]
     return n_good, R, t, good
 
@@ -447,30 +445,11 @@ def _pose_tensor(x, name, B, shape, dev):
 
 def _refine_normalised(R, t, x0, x1, thr, max_steps, counts, valid):
     """roma_op_refine_pose on normalised points [B, N, 2] (read as f32): (R [B, 3, 3], t [B, 3, 1], mask [B, N] bool,
-    info [B, 4] int32).  Nothing is launched for B == 0 or N < 5: every pair comes back untouched."""
+    info [B, 4] int32)"""
     a, b = _pair_batch(x0, x1)
-    B, N, dev = int(a.shape[0]), int(a.shape[1]), a.device
-    R, t = _pose_tensor(R, "R", B, (3, 3), dev), _pose_tensor(t, "t", B, (3, 1), dev)
-    if not (thr > 0) or int(max_steps) < 0:
-        raise ValueError("roma_amd.geometry: need norm_thresh > 0, max_steps >= 0")
-    counts = _counts(counts, B, dev)
-    if valid is not None:
-        valid = torch.as_tensor(valid).to(device=dev).reshape(-1).to(torch.uint8).contiguous()
-        if valid.shape[0] != B:
-            raise ValueError(f"roma_amd.geometry: valid has {valid.shape[0]} entries for {B} pairs")
-    mask = torch.zeros((B, N), device=dev, dtype=torch.bool)
-    info = torch.zeros((B, 4), device=dev, dtype=torch.int32)
-    if B == 0 or N < 5:
-        return R.clone(), t.clone(), mask, info
-    out_R, out_t = torch.empty_like(R), torch.empty_like(t)
-    lib = _lib.load()
-    nws = int(lib.roma_op_refine_pose_workspace(B, N))
-    ws = torch.empty((nws,), device=dev, dtype=torch.uint8)
-    with torch.cuda.device(dev):
-        _lib.check(lib.roma_op_refine_pose(_ptr(R), _ptr(t), _ptr(a), _ptr(b), _ptr(counts), _ptr(valid), B, N, float(thr),
-                                           int(max_steps), _ptr(out_R), _ptr(out_t), _ptr(mask), _ptr(info), _ptr(ws), nws,
-                                           _stream(dev)))
-    return out_R, out_t, mask, info
+    B, dev = int(a.shape[0]), a.device
+    start = (_pose_tensor(R, "R", B, (3, 3), dev), _pose_tensor(t, "t", B, (3, 1), dev))
+    return _refine("pose", (), start, a, b, thr, max_steps, counts, valid, 5, "norm_thresh")
 
 
 def refine_pose(R, t, kpts0, kpts1, K0, K1, norm_thresh, max_steps=25, counts=None, valid=None):
@@ -487,11 +466,10 @@ def refine_pose(R, t, kpts0, kpts1, K0, K1, norm_thresh, max_steps=25, counts=No
     depth is positive in both cameras (the triangulation of recover_pose); info = (accepted steps, cost evaluations, active
     rows at the end, pair fitted).  valid [B] bool marks the pairs to fit; the others, and pairs of fewer than 5 rows, come
     back untouched with an empty mask and info[3] = 0.  See `ransac` for counts."""
-    single = isinstance(kpts0, torch.Tensor) and kpts0.dim() == 2
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
     x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
     out = _refine_normalised(R, t, x0, x1, norm_thresh, max_steps, counts, valid)
-    return tuple(o[0] for o in out) if single else out
+    return tuple(o[0] for o in out) if _single(kpts0) else out
 
 
 def _refined(R, t, good, ok, x0, x1, thr, counts):
@@ -517,7 +495,7 @@ def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=100
     method="magsac": E comes from `essential_magsac` (MAGSAC++ scoring, 10 steps of local optimisation over all the rows it
     weighs) instead of `essential`; recover_pose and refine=True follow as above.  The default "ransac" leaves every output as
     it was before the keyword existed."""
-    _check_method(method)
+    _method(method)
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
     x0, x1 = _normalise_pose_points(a, K0), _normalise_pose_points(b, K1)
     E, inl, ok = _essential(x0, x1, None, conf, norm_thresh, max_iters, seed, counts, method, 10)
@@ -548,7 +526,7 @@ def estimate_pose_uncalibrated(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, 
     method="magsac": F comes from `magsac` (MAGSAC++ scoring and IRLS local optimisation, lo_iters 10) instead of `ransac` - the
     USAC-style estimator the reference asks OpenCV for.  The default "ransac" leaves every output as it was before the keyword
     existed."""
-    _check_method(method)
+    _method(method)
     focal = _mean_focal(K0, K1) if refine else None
     a, b, K0, K1, counts = _pose_inputs(kpts0, kpts1, K0, K1, counts)
     F, inl, ok = _estimate(FUNDAMENTAL, a, b, norm_thresh, conf, max_iters, seed, True, counts, method)

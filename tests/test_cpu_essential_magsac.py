@@ -174,10 +174,16 @@ def test_essential_magsac_kernels_have_no_spills_and_no_scratch(build):
     if not glob.glob(obj):
         pytest.skip(f"{build}/essential.o not built")
     import kernel_resources
-    ks = [k for k in kernel_resources.kernels(obj) if "magsac_" in k["name"]]
-    names = sorted(re.search(r"(magsac_\w+)<", k["name"]).group(1) for k in ks)
-    assert names == ["magsac_accept_kernel", "magsac_finish_kernel", "magsac_init_kernel", "magsac_mask_kernel",
-                     "magsac_refit_kernel", "magsac_score_kernel", "magsac_select_kernel"], names
+    ks = [k for k in kernel_resources.kernels(obj) if "Essential" in k["name"]]
+    names = sorted(re.sub(r"(roma::)?\(anonymous namespace\)::", "", k["name"]) for k in ks)
+    # every kernel of the shared pipeline (ransac.h) instantiated on Essential, under both scorings
+    assert names == ["magsac_init_kernel<Essential>", "ransac_accept_kernel<Essential, MagsacScoring>",
+                     "ransac_finish_kernel<Essential, CountScoring>", "ransac_finish_kernel<Essential, MagsacScoring>",
+                     "ransac_hyp_kernel<Essential>", "ransac_mask_kernel<Essential, CountScoring>",
+                     "ransac_mask_kernel<Essential, MagsacScoring>", "ransac_norm_kernel<Essential>",
+                     "ransac_refit_kernel<Essential, MagsacScoring>", "ransac_score_kernel<Essential, CountScoring>",
+                     "ransac_score_kernel<Essential, MagsacScoring>", "ransac_select_kernel<Essential, CountScoring>",
+                     "ransac_select_kernel<Essential, MagsacScoring>"], names
     for k in ks:
         assert "Essential" in k["name"]
         assert k["spill"] == 0 and k["sgpr_spill"] == 0 and k["scratch"] == 0, k

@@ -66,12 +66,12 @@ def _score_bound(x0, x1, thr, ms):
     return S, float((w * 2 * Vf * REL_R).sum() + len(x0) * 2.0 ** -22 * S.sum())
 
 
-def _check_against_oracle(x0, x1, thr, seed, out, T=None):
+def _check_against_oracle(x0, x1, thr, seed, out, T=None, prob=PROB, max_iters=1000):
     """the agreement statement for one pair: out = the device's five outputs of that pair as numpy arrays.  Returns the measured
     (device to f64 oracle pose distance, the oracle's own f32-vs-f64 pose distance, the f64 oracle's pose error against T)"""
     E, mask, ok, info, score = out
-    ref = em.magsac(x0, x1, thr, PROB, 1000, seed)
-    ref32 = em.magsac(x0, x1, thr, PROB, 1000, seed, f32=True)
+    ref = em.magsac(x0, x1, thr, prob, max_iters, seed)
+    ref32 = em.magsac(x0, x1, thr, prob, max_iters, seed, f32=True)
     assert bool(ok) and ref["ok"] and ref32["ok"]
     sens = _pose_distance(ref["E"], ref["mask"], ref32["E"], ref32["mask"], x0, x1)
     dist = _pose_distance(ref["E"], ref["mask"], E, mask, x0, x1)

@@ -16,13 +16,16 @@ call against the same call with lm_steps=10 in one process, timed alternately in
 line per configuration with the added time, refine_* alone and the fit's counters.  --parent-lib DIR (a directory holding another
 build of libroma_hip.so, e.g. the parent commit's) adds that build's two calls to the same alternation, and compares the
 outputs build against build, bit for bit: the default call, refine_* on the bench batch and refine_* on a ragged batch
-(`ragged_batch`).
-Usage: python tools/bench_geometry.py [--iters 20] [--no-cpu] [--method ransac|magsac|both]
+(`ragged_batch`).  Without --lm, --parent-lib adds one line per configuration (`against_parent`): every output of `ransac` and
+`magsac` on the bench batch and on the ragged batch of the pipeline (`pipeline_counts`) build against build, and both builds
+timed alternately over --rounds.
+Usage: python tools/bench_geometry.py [--iters 20] [--no-cpu] [--method ransac|magsac|both] [--rounds 7] [--parent-lib DIR]
        python tools/bench_geometry.py --lm [--iters 20] [--rounds 7] [--parent-lib DIR]
 """
 import argparse
 import contextlib
 import ctypes
+import itertools
 import json
 import os
 import sys
@@ -165,15 +168,57 @@ def within_spread(this, parent):
     return bool(np.median(this) <= np.median(parent) + (np.max(parent) - np.min(parent)))
 
 
-def ragged_batch(a, b, min_rows, n=1000):
+def ragged_batch(a, b, min_rows, n=1000, counts=None):
     """the first n rows of pair 0 eight times, cut to the counts at which a workgroup's reduction can go wrong: threads and
     whole waves without rows, one row past a wave or the workgroup, exactly min_rows, one below it: (a, b, counts)"""
-    counts = (n, 513, 512, 511, 65, 64, min_rows, min_rows - 1)
+    counts = counts or (n, 513, 512, 511, 65, 64, min_rows, min_rows - 1)
     ra, rb = np.full((8, n, 2), np.nan), np.full((8, n, 2), np.nan)
     for i, c in enumerate(counts):
         ra[i, :c], rb[i, :c] = a[0, :c], b[0, :c]
     dev = lambda x: torch.tensor(x, dtype=torch.float32, device="cuda:0")  # noqa: E731
     return dev(ra), dev(rb), torch.tensor(counts, dtype=torch.int32, device="cuda:0")
+
+
+def pipeline_counts(s):
+    """rows per pair around the 64-row stride of the score and accept waves and the 256-row stride of the normalise, refit and
+    mask workgroups of csrc/ransac.h, the sample size s and one below it"""
+    return (513, 257, 256, 65, 64, 63, s, s - 1)
+
+
+def against_parent(parent, calls, iters, rounds):
+    """calls {name: fn -> tensors}.  Per call: whether every output of this build equals the parent build's bit for bit, and
+    (rounds > 0) both builds timed alternately, `iters` calls per round: {name: {...}}"""
+    res = {}
+    for name, fn in calls.items():
+        r = {"outputs equal the parent's": all(outputs_equal(parent, fn, itertools.count()).values())}
+        ms = {"parent": [], "this": []}
+        for _ in range(rounds):
+            for k, lib in (("parent", parent), ("this", None)):
+                with _using(lib):
+                    ms[k].append(_timed(fn, iters)[0])
+        if rounds:
+            r.update({"this ms": _stats(ms["this"]), "parent ms": _stats(ms["parent"]),
+                      "within the parent's spread": within_spread(ms["this"], ms["parent"])})
+        res[name] = r
+    return res
+
+
+def compare_plain(name, model, a, b, thr, conf, max_iters, iters, rounds, parent):
+    from roma_amd.geometry import magsac, ransac
+    da = torch.tensor(a, dtype=torch.float32, device="cuda:0")
+    db = torch.tensor(b, dtype=torch.float32, device="cuda:0")
+    seeds = torch.arange(len(a), dtype=torch.int64) + 1
+    s = 4 if model == gr.HOMOGRAPHY else 7
+    ra, rb, counts = ragged_batch(a, b, s, counts=pipeline_counts(s))
+    calls = {}
+    for fn in (ransac, magsac):
+        calls[fn.__name__] = lambda fn=fn: fn(model, da, db, thr, conf, max_iters, seed=seeds)
+        calls[fn.__name__ + " ragged"] = lambda fn=fn: fn(model, ra, rb, thr, conf, 600, seed=seeds, counts=counts)
+        calls[fn.__name__ + " ragged confidence=1"] = lambda fn=fn: fn(model, ra, rb, thr, 1.0, 600, seed=seeds, counts=counts)
+    res = {"config": name + " against the parent build", "rounds": rounds, "iters_per_round": iters,
+           **against_parent(parent, calls, iters, rounds)}
+    print(json.dumps(res), flush=True)
+    return res
 
 
 def _stats(ms):
@@ -248,23 +293,24 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the host reference timing")
     ap.add_argument("--method", choices=("ransac", "magsac", "both"), default="both")
     ap.add_argument("--lm", action="store_true", help="measure find_*(..., lm_steps=10) against the default call")
-    ap.add_argument("--rounds", type=int, default=7, help="--lm: alternating rounds per leg")
-    ap.add_argument("--parent-lib", default=None, help="--lm: directory of another build of libroma_hip.so to time next to this one and compare outputs with")
+    ap.add_argument("--rounds", type=int, default=7, help="--lm, --parent-lib: alternating rounds per leg")
+    ap.add_argument("--parent-lib", default=None, help="directory of another build of libroma_hip.so to time next to this one and compare outputs with")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_geometry.py measures the device path: it needs a GPU"
     if args.lm:
         return main_lm(args)
     methods = ("ransac", "magsac") if args.method == "both" else (args.method,)
+    parent = _other_build(args.parent_lib) if args.parent_lib else None
     B = 8
-    for frac in (0.0, 0.3):
-        a, b = relief_batch(B, 10000, frac)
+    configs = [(f"find_fundamental demo_fundamental outliers={frac}", gr.FUNDAMENTAL, *relief_batch(B, 10000, frac), 0.2, 0.999999,
+                10000) for frac in (0.0, 0.3)]
+    configs.append(("find_homography hpatches outliers=0.3", gr.HOMOGRAPHY, *homography_batch(B, 5000, 0.3), 3 * 864 / 480, 0.99999,
+                    2000))
+    for cfg in configs:
         for m in methods:
-            run(f"find_fundamental demo_fundamental outliers={frac}", gr.FUNDAMENTAL, a, b, 0.2, 0.999999, 10000, args.iters,
-                not args.no_cpu, m)
-    a, b = homography_batch(B, 5000, 0.3)
-    for m in methods:
-        run("find_homography hpatches outliers=0.3", gr.HOMOGRAPHY, a, b, 3 * 864 / 480, 0.99999, 2000, args.iters, not args.no_cpu,
-            m)
+            run(*cfg, args.iters, not args.no_cpu, m)
+        if parent is not None:
+            compare_plain(*cfg, args.iters, args.rounds, parent)
 
 
 if __name__ == "__main__":

@@ -11,8 +11,10 @@ csrc/pose_refine.hip after the RANSAC): ms per call, the added ms over the plain
 evaluations per pair.  With --parent-lib DIR (a directory holding another build of libroma_hip.so, e.g. the parent commit's)
 that build's refined call and its refine_pose alone are timed in the same alternation (--rounds each, the medians), and the
 outputs of refine_pose are compared build against build, bit for bit, on the bench batch and on a ragged batch
-(bench_geometry.ragged_batch).
-Usage: python tools/bench_pose.py [--iters 20] [--no-cpu] [--refine [--rounds 7] [--parent-lib DIR]]
+(bench_geometry.ragged_batch).  Without --refine, --parent-lib adds one line per configuration (bench_geometry.against_parent):
+every output of `essential`, of estimate_pose with and without refine, and of estimate_pose_uncalibrated for both methods with
+and without refine, on the bench batch and on the pipeline's ragged batch, build against build, both timed alternately.
+Usage: python tools/bench_pose.py [--iters 20] [--no-cpu] [--rounds 7] [--parent-lib DIR] [--refine]
 """
 import argparse
 import json
@@ -27,7 +29,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import pose_geometry as pg  # noqa: E402
-from bench_geometry import _other_build, _stats, _using, outputs_equal, ragged_batch, relief_batch, within_spread  # noqa: E402
+from bench_geometry import (pipeline_counts, _other_build, _stats, _using, against_parent, outputs_equal, ragged_batch,  # noqa: E402
+                            relief_batch, within_spread)
 from accuracy_harness import synthetic_relief_pair  # noqa: E402
 
 
@@ -64,6 +67,28 @@ def run(name, a, b, K, iters, cpu):
         res["cpu_numpy_pose_geometry_ms_per_call"] = round((time.perf_counter() - t0) * 1e3, 1)
     print(json.dumps(res), flush=True)
     return res
+
+
+def pose_calls(a, b, K, method, fns=("essential", "estimate_pose", "estimate_pose_uncalibrated")):
+    """{name: call} of the relative-pose entry points for `method` on the bench batch and on the pipeline's ragged batch"""
+    from roma_amd import geometry as g
+    thr = 0.5 / float(np.mean([K[0, 0], K[1, 1]]))
+    da = torch.tensor(a, dtype=torch.float32, device="cuda:0")
+    db = torch.tensor(b, dtype=torch.float32, device="cuda:0")
+    seeds = torch.arange(len(a), dtype=torch.int64) + 1
+    ra, rb, counts = ragged_batch(a, b, 5, counts=pipeline_counts(5))
+    ess = g.essential if method == "ransac" else g.essential_magsac
+    calls = {}
+    for tag, x, y, kw in (("", da, db, {}), (" ragged", ra, rb, {"counts": counts})):
+        if "essential" in fns:
+            calls[ess.__name__ + tag] = lambda x=x, y=y, kw=kw: ess(x, y, K, 0.99999, 0.5, 1000 if not tag else 600, seed=seeds, **kw)
+        for refine in (False, True):
+            for fn, t, iters in ((g.estimate_pose, thr, 1000), (g.estimate_pose_uncalibrated, 0.5, 10000)):
+                if fn.__name__ in fns:
+                    calls[f"{fn.__name__} {method}{' refine=True' if refine else ''}{tag}"] = (
+                        lambda fn=fn, t=t, iters=iters, refine=refine, x=x, y=y, kw=kw:
+                        fn(x, y, K, K, t, 0.99999, iters if not tag else 600, seed=seeds, refine=refine, method=method, **kw))
+    return calls
 
 
 def _timed(fn, iters):
@@ -128,8 +153,8 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--no-cpu", action="store_true", help="skip the host reference timing")
     ap.add_argument("--refine", action="store_true", help="add the estimate_pose(..., refine=True) leg")
-    ap.add_argument("--rounds", type=int, default=7, help="--refine: alternating rounds per leg")
-    ap.add_argument("--parent-lib", default=None, help="--refine: directory of another build of libroma_hip.so to time next to this one and compare outputs with")
+    ap.add_argument("--rounds", type=int, default=7, help="--refine, --parent-lib: alternating rounds per leg")
+    ap.add_argument("--parent-lib", default=None, help="directory of another build of libroma_hip.so to time next to this one and compare outputs with")
     args = ap.parse_args()
     parent = _other_build(args.parent_lib) if args.parent_lib else None
     assert torch.cuda.is_available(), "bench_pose.py measures the device path: it needs a GPU"
@@ -139,6 +164,10 @@ def main():
         run(f"estimate_pose megadepth outliers={frac}", a, b, K, args.iters, not args.no_cpu)
         if args.refine:
             run_refined(f"estimate_pose megadepth outliers={frac}", a, b, K, args.iters, args.rounds, parent)
+        elif parent is not None:
+            calls = {**pose_calls(a, b, K, "ransac"), **pose_calls(a, b, K, "magsac", ("estimate_pose_uncalibrated",))}
+            print(json.dumps({"config": f"estimate_pose megadepth outliers={frac} against the parent build", "rounds": args.rounds,
+                              "iters_per_round": args.iters, **against_parent(parent, calls, args.iters, args.rounds)}), flush=True)
 
 
 if __name__ == "__main__":

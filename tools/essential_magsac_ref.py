@@ -50,15 +50,6 @@ def residual2(E, xa, xb, f32=False):
     return r2_from(mr.res_terms(mr.FUNDAMENTAL, E, xa, xb, f32), f32)
 
 
-def lo_gain(cur, cand, xa, xb, vs, f32=False):
-    """sum(rho_cur - rho_cand) over the rows, measured paired as the device does (magsac_ref.lo_gain)"""
-    r, _ = mr._ops(f32)
-    tu = mr.res_terms(mr.FUNDAMENTAL, cur[None], xa, xb, f32)
-    tc = r(tu + mr.res_terms(mr.FUNDAMENTAL, (cand - cur)[None], xa, xb, f32))
-    with np.errstate(invalid="ignore"):
-        return float((mr.loss(r2_from(tu, f32) * vs)[0] - mr.loss(r2_from(tc, f32) * vs)[0]).sum())
-
-
 def project(F):
     """the closest essential matrix in the Frobenius norm: singular values ((s1 + s2) / 2, (s1 + s2) / 2, 0); then unit norm and
     the sign rule of five_point (largest-magnitude entry positive, the first one on ties)"""
@@ -172,48 +163,9 @@ def magsac(pa, pb, thr, prob, max_iters, seed, K=None, lo_iters=LO_ITERS, f32=Fa
     xa, xb, fin, t2 = _pair(pa, pb, thr, K)
     if n < 5 or fin.sum() < 5 or not (t2 > 0 and math.isfinite(t2)):
         return out
-    vs = mr.K2 / (2 * t2)
-    slots = er.MAX_ROOTS
-
-    def score(Ms):
-        r2 = residual2(Ms, xa, xb, f32)
-        with np.errstate(invalid="ignore"):
-            return mr.loss(r2 * vs)[0].sum(axis=1), (r2 < t2).sum(axis=1)
-
-    best_score, cur, best_h, best_root, best, needed, rounds = math.inf, None, -1, -1, -1, max_iters, 0
-    for rd in range((max_iters + gr.ROUND - 1) // gr.ROUND):
-        models, nm = _round_models(xa, xb, fin, seed, rd)
-        sc, ct = score(models.reshape(-1, 3, 3))
-        sc = np.where((np.arange(slots)[None, :] < nm[:, None]).reshape(-1), sc, np.inf)
-        k = int(np.argmin(sc))  # first minimum: lowest (h, slot)
-        if sc[k] < best_score:
-            best_score, best_h, best_root, best = float(sc[k]), rd * gr.ROUND + k // slots, k % slots, int(ct[k])
-            cur = models.reshape(-1, 3, 3)[k].copy()
-            needed = gr.update_num_iters(prob, best / n, 5, max_iters)
-        rounds = rd + 1
-        if rounds * gr.ROUND >= min(max_iters, needed):
-            break
-    out.update(rounds=rounds, best_h=best_h, best_root=best_root, best_min=best)
-    if cur is None:
-        return out
-    score_min, gains, lo_steps = best_score, 0.0, 0
-    for _ in range(lo_iters):
-        with np.errstate(invalid="ignore"):
-            w = np.maximum(mr.loss(residual2(cur[None], xa, xb, f32)[0] * vs)[1], 0.0)
-        cand = weighted_refit(xa, xb, w, lambda Es: score(Es)[0])
-        if cand is None:
-            break
-        gain = lo_gain(cur, cand, xa, xb, vs, f32)
-        if not gain > 0:
-            break
-        cur, gains, best, lo_steps = cand, gains + gain, int(score(cand[None])[1][0]), lo_steps + 1
-    out.update(best=best, score_min=score_min, score=score_min - gains, lo_steps=lo_steps)
-    if best <= 0:
-        return out
-    with np.errstate(invalid="ignore"):
-        mask = residual2(cur[None], xa, xb, f32)[0] < t2
-    out.update(E=cur, mask=mask, ok=True)
-    return out
+    return mr.run(out, "E", n, 5, er.MAX_ROOTS, fin, seed, prob, max_iters, lo_iters, t2,
+                  lambda idx: er.five_point(xa[idx], xb[idx]), lambda Ms: mr.res_terms(mr.FUNDAMENTAL, Ms, xa, xb, f32),
+                  lambda t: r2_from(t, f32), lambda w, score: weighted_refit(xa, xb, w, score), lambda cur: cur, f32)
 
 
 def estimate_pose(kpts0, kpts1, K0, K1, norm_thresh, conf=0.99999, max_iters=1000, seed=0, lo_iters=LO_ITERS, f32=False):

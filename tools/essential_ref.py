@@ -313,9 +313,9 @@ def ransac(pa, pb, thr, prob, max_iters, seed, K=None):
     with np.errstate(invalid="ignore"):
         xa, xb = _normalise(pa, K), _normalise(pb, K)
     t2 = thr_n * thr_n
-    best, cur, best_h, best_root, rounds = gr.round_loop(n, 5, MAX_ROOTS, fin, seed, prob, max_iters,
-                                                         lambda idx: five_point(xa[idx], xb[idx]),
-                                                         lambda M: inliers(M, xa, xb, t2).sum(axis=1))
+    _, best, cur, best_h, best_root, rounds = gr.round_loop(n, 5, MAX_ROOTS, fin, seed, prob, max_iters,
+                                                            lambda idx: five_point(xa[idx], xb[idx]),
+                                                            lambda M: (inliers(M, xa, xb, t2).sum(axis=1),) * 2)
     out.update(rounds=rounds, best_h=best_h, best_root=best_root)
     if best <= 0:
         return out

@@ -231,13 +231,16 @@ def update_num_iters(conf, w, s, max_iters):
     return int(math.ceil(num / denom))
 
 
-def round_loop(n, s, slots, fin, seed, conf, max_iters, solve, count):
-    """the sampling rounds of one pair, as every model runs them (csrc/ransac.h): ROUND hypotheses per round drawn by
+def round_loop(n, s, slots, fin, seed, conf, max_iters, solve, key, smaller=False):
+    """the sampling rounds of one pair, as every model and scoring runs them (csrc/ransac.h): ROUND hypotheses per round drawn by
     draw_samples; solve(idx [k, s]) -> (models [k, slots, 3, 3], number of models [k]) on the samples that were drawn and hold
-    finite rows only; count(models [K, 3, 3]) -> inlier counts [K], -1 for unused slots; the largest count (ties: lowest
-    (h, slot)) replaces the current model if it is strictly larger; OpenCV's adaptive iteration count; stop once ROUND * rounds
-    reaches it or max_iters.  Returns (best count, current model or None, best_h, best_root, rounds)."""
-    best, cur, best_h, best_root, needed, rounds = -1, None, -1, -1, max_iters, 0
+    finite rows only; key(models [K, 3, 3]) -> (keys [K], inlier counts [K]): the inlier count itself, larger is better, or
+    (smaller) a score, smaller is better, with the count carried along; the best key of the used slots (ties: lowest (h, slot))
+    replaces the current model if it is strictly better; OpenCV's adaptive iteration count from the winner's inlier count;
+    stop once ROUND * rounds reaches it or max_iters.
+    Returns (best key, its inlier count, current model or None, best_h, best_root, rounds)."""
+    worst = math.inf if smaller else -1
+    best_key, best, cur, best_h, best_root, needed, rounds = worst, -1, None, -1, -1, max_iters, 0
     for r in range((max_iters + ROUND - 1) // ROUND):
         hs = np.arange(r * ROUND, (r + 1) * ROUND)
         idx, drawn = draw_samples(seed, hs, n, s)
@@ -248,17 +251,17 @@ def round_loop(n, s, slots, fin, seed, conf, max_iters, solve, count):
         sel = np.nonzero(ok)[0]
         if len(sel):
             models[sel], nm[sel] = solve(idx[sel])
-        counts = count(models.reshape(-1, 3, 3)).reshape(ROUND, slots)
-        counts = np.where(np.arange(slots)[None, :] < nm[:, None], counts, -1).reshape(-1)
-        k = int(np.argmax(counts))
-        if counts[k] > best:
-            best, best_h, best_root = int(counts[k]), r * ROUND + k // slots, k % slots
+        keys, counts = key(models.reshape(-1, 3, 3))
+        keys = np.where((np.arange(slots)[None, :] < nm[:, None]).reshape(-1), keys, worst)
+        k = int(np.argmin(keys) if smaller else np.argmax(keys))  # the first one: lowest (h, slot)
+        if keys[k] < best_key if smaller else keys[k] > best_key:
+            best_key, best, best_h, best_root = keys[k].item(), int(counts[k]), r * ROUND + k // slots, k % slots
             cur = models.reshape(-1, 3, 3)[k].copy()
             needed = update_num_iters(conf, best / n, s, max_iters)
         rounds = r + 1
         if rounds * ROUND >= min(max_iters, needed):
             break
-    return best, cur, best_h, best_root, rounds
+    return best_key, best, cur, best_h, best_root, rounds
 
 
 def refit(model, xa, xb):
@@ -276,6 +279,18 @@ def refit(model, xa, xb):
         U, S, Vt = np.linalg.svd(h)
         h = U @ np.diag([S[0], S[1], 0.0]) @ Vt
     return h / np.linalg.norm(h)
+
+
+def denormalise(model, cur, ca, sa, cb, sb):
+    """the pixel model of a normalised one (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scaled so that [2, 2] = 1"""
+    Ta = np.array([[sa, 0, -sa * ca[0]], [0, sa, -sa * ca[1]], [0, 0, 1]])
+    if model == HOMOGRAPHY:
+        L = np.array([[1 / sb, 0, cb[0]], [0, 1 / sb, cb[1]], [0, 0, 1]])
+    else:
+        L = np.array([[sb, 0, 0], [0, sb, 0], [-sb * cb[0], -sb * cb[1], 1]])
+    M = L @ cur @ Ta
+    fro = np.linalg.norm(M)
+    return M / (M[2, 2] if abs(M[2, 2]) >= 1e-12 * fro else fro)
 
 
 def ransac(model, pa, pb, thr, conf, max_iters, seed, refine=True):
@@ -299,8 +314,8 @@ def ransac(model, pa, pb, thr, conf, max_iters, seed, refine=True):
             return H[:, None], ok.astype(np.int64)
         return solve_f(xa[idx], xb[idx])
 
-    best, cur, best_h, best_root, rounds = round_loop(n, s, SLOTS[model], fin, seed, conf, max_iters, solve,
-                                                      lambda M: inliers(model, M, xa, xb, t2a, t2b).sum(axis=1))
+    _, best, cur, best_h, best_root, rounds = round_loop(n, s, SLOTS[model], fin, seed, conf, max_iters, solve,
+                                                         lambda M: (inliers(model, M, xa, xb, t2a, t2b).sum(axis=1),) * 2)
     out.update(rounds=rounds, best_h=best_h, best_root=best_root, best_min=best)
     if best <= 0:
         return out
@@ -315,14 +330,7 @@ def ransac(model, pa, pb, thr, conf, max_iters, seed, refine=True):
                 break
             best, cur = c, cand
     mask = inliers(model, cur[None], xa, xb, t2a, t2b)[0]
-    Ta = np.array([[sa, 0, -sa * ca[0]], [0, sa, -sa * ca[1]], [0, 0, 1]])
-    if model == HOMOGRAPHY:
-        L = np.array([[1 / sb, 0, cb[0]], [0, 1 / sb, cb[1]], [0, 0, 1]])
-    else:
-        L = np.array([[sb, 0, 0], [0, sb, 0], [-sb * cb[0], -sb * cb[1], 1]])
-    M = L @ cur @ Ta
-    fro = np.linalg.norm(M)
-    M = M / (M[2, 2] if abs(M[2, 2]) >= 1e-12 * fro else fro)
+    M = denormalise(model, cur, ca, sa, cb, sb)
     out.update(M=M, mask=mask, ok=True, best=best)
     return out
 

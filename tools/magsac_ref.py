@@ -122,14 +122,15 @@ def residual2(model, M, xa, xb, sa, sb, f32=False):
     return r2_from(model, res_terms(model, M, xa, xb, f32), sa, sb, f32)
 
 
-def lo_gain(model, cur, cand, xa, xb, sa, sb, vs, f32=False):
+def lo_gain(terms, r2_of, cur, cand, vs, f32=False):
     """sum(rho_cur - rho_cand) over the rows, measured paired as the device does: the candidate's residual terms are the current
-    model's plus those of the difference (cand - cur), so the error both share cancels"""
+    model's plus those of the difference (cand - cur), so the error both share cancels.  terms(M [1, 3, 3]) -> the residual
+    terms, r2_of(terms) -> the squared residuals"""
     r, _ = _ops(f32)
-    tu = res_terms(model, cur[None], xa, xb, f32)
-    tc = r(tu + res_terms(model, (cand - cur)[None], xa, xb, f32))
+    tu = terms(cur[None])
+    tc = r(tu + terms((cand - cur)[None]))
     with np.errstate(invalid="ignore"):
-        return float((loss(r2_from(model, tu, sa, sb, f32) * vs)[0] - loss(r2_from(model, tc, sa, sb, f32) * vs)[0]).sum())
+        return float((loss(r2_of(tu) * vs)[0] - loss(r2_of(tc) * vs)[0]).sum())
 
 
 def weighted_refit(model, xa, xb, w):
@@ -180,12 +181,52 @@ def scores(model, pa, pb, thr, Ms, f32=False):
     return rho.sum(axis=1), rho, w, V
 
 
+def run(out, name, n, s, slots, fin, seed, conf, max_iters, lo_iters, t2, solve, terms, r2_of, refit, finish, f32=False):
+    """what the MAGSAC++ oracles (`magsac` here, essential_magsac_ref.magsac) share once the pair is normalised: the sampling
+    rounds (geometry_ref.round_loop on the smallest sum of rho), the LO loop with its paired gain, the result dict.  t2: squared
+    threshold in the units of the residual; solve: round_loop's; terms(Ms [K, 3, 3]) -> residual terms and r2_of(terms) ->
+    squared residuals [K, n]; refit(w [n], score) -> an IRLS candidate or None (score(Ms) -> sums of rho); finish(cur) -> the
+    model returned as out[name].  Fills and returns out."""
+    vs = K2 / (2 * t2)
+
+    def residual2(Ms):
+        return r2_of(terms(Ms))
+
+    def score(Ms):
+        r2 = residual2(Ms)
+        with np.errstate(invalid="ignore"):
+            return loss(r2 * vs)[0].sum(axis=1), (r2 < t2).sum(axis=1)
+
+    score_min, best, cur, best_h, best_root, rounds = gr.round_loop(n, s, slots, fin, seed, conf, max_iters, solve, score, smaller=True)
+    out.update(rounds=rounds, best_h=best_h, best_root=best_root, best_min=best)
+    if cur is None:
+        return out
+    gains, lo_steps = 0.0, 0
+    for _ in range(lo_iters):
+        with np.errstate(invalid="ignore"):
+            w = np.maximum(loss(residual2(cur[None])[0] * vs)[1], 0.0)
+        cand = refit(w, lambda Ms: score(Ms)[0])
+        if cand is None:
+            break
+        gain = lo_gain(terms, r2_of, cur, cand, vs, f32)
+        if not gain > 0:
+            break
+        cur, gains, best, lo_steps = cand, gains + gain, int(score(cand[None])[1][0]), lo_steps + 1
+    out.update(best=best, score_min=score_min, score=score_min - gains, lo_steps=lo_steps)
+    if best <= 0:
+        return out
+    with np.errstate(invalid="ignore"):
+        mask = residual2(cur[None])[0] < t2
+    out.update({name: finish(cur)}, mask=mask, ok=True)
+    return out
+
+
 def magsac(model, pa, pb, thr, conf, max_iters, seed, lo_iters=LO_ITERS, f32=False):
     """One pair.  pa, pb [n, 2] pixels (rows of the pair only).  Returns a dict with geometry_ref.ransac's fields (M [3, 3] or
     zeros, mask [n], ok, rounds, best_h, best_root, best_min = inliers of the winning minimal model, best = final inliers) plus
     score_min (sum of rho of the winning minimal model), score (final sum of rho: score_min less the LO gains; both 0 where no model) and lo_steps."""
     pa, pb = np.asarray(pa, dtype=np.float64), np.asarray(pb, dtype=np.float64)
-    n, s, slots = len(pa), gr.SAMPLE[model], gr.SLOTS[model]
+    n, s = len(pa), gr.SAMPLE[model]
     out = dict(M=np.zeros((3, 3)), mask=np.zeros(n, dtype=bool), ok=False, rounds=0, best_h=-1, best_root=-1, best_min=-1,
                best=-1, score_min=0.0, score=0.0, lo_steps=0)
     if n < s:
@@ -195,67 +236,19 @@ def magsac(model, pa, pb, thr, conf, max_iters, seed, lo_iters=LO_ITERS, f32=Fal
         return out
     with np.errstate(invalid="ignore"):
         xa, xb = (pa - ca) * sa, (pb - cb) * sb
-    thr2 = float(thr) ** 2
-    vs = K2 / (2 * thr2)
 
-    def score(Ms):
-        r2 = residual2(model, Ms, xa, xb, sa, sb, f32)
-        with np.errstate(invalid="ignore"):
-            return loss(r2 * vs)[0].sum(axis=1), (r2 < thr2).sum(axis=1)
+    def solve(idx):
+        if model == HOMOGRAPHY:
+            H, ok = gr.solve_h(xa[idx], xb[idx])
+            return H[:, None], ok.astype(np.int64)
+        return gr.solve_f(xa[idx], xb[idx])
 
-    best_score, cur, best_h, best_root, best, needed, rounds = math.inf, None, -1, -1, -1, max_iters, 0
-    for rd in range((max_iters + gr.ROUND - 1) // gr.ROUND):
-        idx, drawn = gr.draw_samples(seed, np.arange(rd * gr.ROUND, (rd + 1) * gr.ROUND), n, s)
-        idx = np.where(drawn[:, None], idx, 0)
-        ok = drawn & fin[idx].all(axis=1)
-        models = np.zeros((gr.ROUND, slots, 3, 3))
-        nm = np.zeros(gr.ROUND, dtype=np.int64)
-        sel = np.nonzero(ok)[0]
-        if len(sel):
-            if model == HOMOGRAPHY:
-                H, hok = gr.solve_h(xa[idx[sel]], xb[idx[sel]])
-                models[sel], nm[sel] = H[:, None], hok.astype(np.int64)
-            else:
-                models[sel], nm[sel] = gr.solve_f(xa[idx[sel]], xb[idx[sel]])
-        sc, ct = score(models.reshape(-1, 3, 3))
-        sc = np.where((np.arange(slots)[None, :] < nm[:, None]).reshape(-1), sc, np.inf)
-        k = int(np.argmin(sc))  # first minimum: lowest (h, slot)
-        if sc[k] < best_score:
-            best_score, best_h, best_root, best = float(sc[k]), rd * gr.ROUND + k // slots, k % slots, int(ct[k])
-            cur = models.reshape(-1, 3, 3)[k].copy()
-            needed = gr.update_num_iters(conf, best / n, s, max_iters)
-        rounds = rd + 1
-        if rounds * gr.ROUND >= min(max_iters, needed):
-            break
-    out.update(rounds=rounds, best_h=best_h, best_root=best_root, best_min=best)
-    if cur is None:
-        return out
-    score_min, gains, lo_steps = best_score, 0.0, 0
-    for _ in range(lo_iters):
-        r2 = residual2(model, cur[None], xa, xb, sa, sb, f32)[0]
-        with np.errstate(invalid="ignore"):
-            w = np.maximum(loss(r2 * vs)[1], 0.0)
+    def refit(w, score):
         if int((w > 0).sum()) < gr.REFIT_MIN[model]:
-            break
+            return None
         cand = weighted_refit(model, xa, xb, w)
-        if not np.isfinite(cand).all():
-            break
-        gain = lo_gain(model, cur, cand, xa, xb, sa, sb, vs, f32)
-        if not gain > 0:
-            break
-        cur, gains, best, lo_steps = cand, gains + gain, int(score(cand[None])[1][0]), lo_steps + 1
-    out.update(best=best, score_min=score_min, score=score_min - gains, lo_steps=lo_steps)
-    if best <= 0:
-        return out
-    with np.errstate(invalid="ignore"):
-        mask = residual2(model, cur[None], xa, xb, sa, sb, f32)[0] < thr2
-    Ta = np.array([[sa, 0, -sa * ca[0]], [0, sa, -sa * ca[1]], [0, 0, 1]])
-    if model == HOMOGRAPHY:
-        L = np.array([[1 / sb, 0, cb[0]], [0, 1 / sb, cb[1]], [0, 0, 1]])
-    else:
-        L = np.array([[sb, 0, 0], [0, sb, 0], [-sb * cb[0], -sb * cb[1], 1]])
-    M = L @ cur @ Ta
-    fro = np.linalg.norm(M)
-    M = M / (M[2, 2] if abs(M[2, 2]) >= 1e-12 * fro else fro)
-    out.update(M=M, mask=mask, ok=True)
-    return out
+        return cand if np.isfinite(cand).all() else None
+
+    return run(out, "M", n, s, gr.SLOTS[model], fin, seed, conf, max_iters, lo_iters, float(thr) ** 2, solve,
+               lambda Ms: res_terms(model, Ms, xa, xb, f32), lambda t: r2_from(model, t, sa, sb, f32), refit,
+               lambda cur: gr.denormalise(model, cur, ca, sa, cb, sb), f32)
