@@ -162,28 +162,18 @@ long roma_debug_trace(roma_handle_t h, int slot, unsigned long long* sums_host, 
 int roma_destroy(roma_handle_t h);
 /* Per-launch HIP-event timing of the dominant kernels (bench.py roofline pass). roma_profile_report writes a JSON
  * object {kernel: {calls,total_ms,work,unit}} (work = algorithmic FLOPs or bytes); returns bytes needed when buf==NULL. */
-/* process-wide kernel-selection switches for A/B measurements and tests (not needed for normal use): "gemm8p" 1 / 0 =
- * route the large bf16 GEMMs to the 8-phase kernel or keep them on the one-barrier-per-slab kernel (-1 = environment
- * ROMA_GEMM8P, default on); "gemm_dbg" = experiment bits of the GEMM kernels (-1 = environment ROMA_GEMM_DBG);
- * "lc_mode" = local correlation: 0 tiled LDS form with a per-tile gather work list (default), 1 every tile on the gather
- * list, 2 the per-pixel kernel of round 1 (-1 = environment ROMA_LC_MODE); "conv64" = bit mask of the
- * weight-stationary VGG front-end kernels; "attn_xcd" 1 / 0 = attention work items in per-XCD bands; "attn_exp2" 1 / 0 = tools
- * only: force the 2^x softmax of the 16-bit attention kernel on / off (it assumes q pre-scaled by log2 e); "dw_ring" 0 / 1 / 2 = depthwise 5x5: register-prefetch
- * kernel / wave-private ring kernel for launches >= 64 M elements (default) / ring kernel for every shape it takes;
- * "rb24w" 1 / 0 = C = 24 fused block: wave-private kernel (default) / two-barrier workgroup kernel; "rb144_1b" 1 / 0 = C = 144
- * fused block: one barrier per row (default) / two; "gemm8p_sched" 1 / 0 = K-loop schedule of the 8-phase GEMM: k-half
- * phases (default) / quadrant phases (bit-identical results); "rb_wide" 1 / 0 = the C = 576 ConvRefiner block as ONE fused kernel
- * (measured slower: off) / as dwconv5x5 + 1x1 GEMM (default; ROMA_RB_WIDE=1 enables the fused kernel); "ws1x1" 1 / 0 = the N = K = 576 refiner 1x1 on the
- * weight-stationary kernel (default) / on the 256 x 192 tile kernel (bit-identical results); "gp_col" 1 / 0 = the GP's blocked
- * Cholesky solve left-looking, one launch per block column (default) / the right-looking chain of three launches per column
- * (results agree to f32 rounding); "gp_col_leader" 1 / 0 = inside a column launch one leader workgroup per image factorises
- * the diagonal block and hands its inverse to the row-block workgroups (default) / every workgroup factorises its own copy
- * (bit-identical results; also the time-out path of the hand-off); "gemm8p_maxwg" n = measurement only: cap the persistent grid
- * of the 8-phase GEMM at n workgroups (tools/bench_gemm_burst.py; -1 = one per CU); "gemm8p_walk" g = tile rows per group of its
- * walk through an XCD's band of output tiles (1 = row-major; -1 = row-major below 24 tile columns, 8 from there on; same values in
- * any order: tools/bench_gemm_walk.py).  Every alternative computes the same values (the stencil / block
- * kernels bit for bit); -1 restores the default (or the environment variable of the same name in upper case, ROMA_...). */
+/* process-wide kernel-selection switches for A/B measurements and tests (not needed for normal use).  The one list of keys,
+ * environment variables, defaults and meanings is the table in roma_amd/csrc/tuning.hip, printed in INTEGRATION.md section 2
+ * and by roma_tuning_describe.  A value below the key's lowest override value (-1 for every key) clears the override: the
+ * environment variable of the row, else its default, holds again.  Every alternative computes the same values - the stencil /
+ * block kernels, "gemm8p_sched", "ws1x1", "conv_patch" and "gp_col_leader" (also the time-out path of its hand-off) bit for bit,
+ * "gp_col" to f32 rounding, "gemm8p_walk" and "gemm8p_maxwg" change only the order and number of workgroups - except that
+ * "attn_exp2" assumes q pre-scaled by log2 e and the "gemm_dbg" experiment bits produce wrong outputs by design. */
 int roma_tuning(const char* key, int value);
+/* The switch table as a JSON array, one object per row in table order: {"key": str | null, "env": str | null, "default": n,
+ * "override": n | null, "value": n, "tools_only_env": bool, "doc": str}; "value" is what a launch would see now.  Size query
+ * as roma_profile_report (buf == NULL: bytes needed).  Touches no device; each library describes its own table. */
+long roma_tuning_describe(char* buf, long nbytes);
 /* measuring tool (tools/bench_gemm_ablation.py): after a GEMM launched with the "gemm_dbg" trace bit (32768), copies the
  * phase time stamps [workgroup < 16][wave group][K tile < 256][phase] (low 32 bits of s_memtime at each phase's first
  * barrier release) to the host; returns the number of bytes written. */

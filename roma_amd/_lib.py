@@ -57,6 +57,7 @@ SIGNATURES = {
     "roma_debug_inject": (_i, [_vp, C.c_char_p, _vp, _l]),
     "roma_destroy": (_i, [_vp]),
     "roma_tuning": (_i, [C.c_char_p, _i]),
+    "roma_tuning_describe": (_l, [C.c_char_p, _l]),
     "roma_debug_gemm_trace": (_l, [_vp, _l]),
     "roma_vit_forward": (_i, [_vp, _vp]),
     "roma_op_convert_from_bf16": (_i, [_vp, _vp, _l, _vp]),

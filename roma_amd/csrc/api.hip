@@ -19,6 +19,7 @@
 #include "kde.h"
 #include "keypoints.h"
 #include "tiny.h"
+#include "tuning.h"
 #include "vit.h"
 #include "sampling.h"
 #include "essential.h"
@@ -240,31 +241,15 @@ int roma_tuning(const char* key, int value) {
         set_error(std::string("roma_tuning: the bfloat16 sibling library refused key ") + key);
         return rc;
       }
-  const std::string k(key);
-  if (k == "gemm8p") g_gemm_tuning[0] = value;
-  else if (k == "gemm_dbg") g_gemm_tuning[1] = value;
-  else if (k == "gemm8p_walk") g_gemm8p_walk = value;
-  else if (k == "gemm8p_sched") g_gemm8p_sched = value;
-  else if (k == "gemm8p_maxwg") g_gemm8p_maxwg = value;
-  else if (k == "ws1x1") g_ws1x1_mode = value;
-  else if (k == "lc_mode") g_lc_mode = value;
-  else if (k == "lc_bin") g_lc_bin = value;
-  else if (k == "conv64") g_conv64_mode = value;
-  else if (k == "conv_patch") g_conv_patch = value;
-  else if (k == "attn_xcd") g_attn_xcd_map = value;
-  else if (k == "attn_exp2") g_attn_exp2 = value;
-  else if (k == "rb24w") g_rb24_wave = value;
-  else if (k == "rb144_1b") g_rb144_1b = value;
-  else if (k == "rb_wide") g_rb_wide = value;
-  else if (k == "dw_ring") g_dw_ring = value;
-  else if (k == "gp_col") g_gp_col = value;
-  else if (k == "pool_proj") g_pool_proj = value;
-  else if (k == "gp_col_leader") g_gp_col_leader = value;
-  else {
-    set_error("roma_tuning: unknown key " + k);
-    return ROMA_ERR_ARG;
-  }
-  return 0;
+  return tuning_set(key, value);
+}
+
+long roma_tuning_describe(char* buf, long nbytes) {
+  const std::string js = tuning_describe();
+  if (!buf) return (long)js.size() + 1;
+  if (nbytes < (long)js.size() + 1) return ROMA_ERR_ARG;
+  memcpy(buf, js.c_str(), js.size() + 1);
+  return (long)js.size() + 1;
 }
 
 int roma_vit_forward(const roma_vit_args_t* a, void* stream) {

@@ -9,6 +9,7 @@
 // order inside a k-step is a free permutation as long as V^T is read with the same one),
 // so P never leaves registers and the running max / rescale factor is one scalar per lane.
 #include "attention.h"
+#include "tuning.h"
 
 #include <stdlib.h>
 #include <type_traits>
@@ -398,18 +399,14 @@ __global__ __launch_bounds__(256, HD == 64 ? 3 : 2) void attn_h16_v2_kernel(cons
 }
 #undef ROMA_ATTN_STAGE
 
-int g_attn_exp2 = -1;     // roma_tuning("attn_exp2", v): tools only - force the 2^x softmax (q pre-scaled by log2 e) on / off; -1 = as the caller says
-int g_attn_xcd_map = -1;  // roma_tuning("attn_xcd", v): 1 = per-XCD bands of (b, head) (default), 0 = plain order, -1 = env ROMA_ATTN_XCD
-
 int attention_launch(const AttnArgs& a_in, hipStream_t stream) {
   AttnArgs a = a_in;
   ROMA_REQUIRE(a.hd == 64 || a.hd == 128, "attention: head dim must be 64 or 128");
   ROMA_REQUIRE(a.npad % 128 == 0 && a.npad >= a.N, "attention: Npad must be a multiple of 128 and >= N");
   ROMA_REQUIRE(a.ldo % 4 == 0, "attention: ldo must be a multiple of 4");
-  if (g_attn_exp2 >= 0) a.exp2_domain = g_attn_exp2 ? 1 : 0;  // tools/attn_determinism.py (never set on the product path)
+  if (tuning(SW_ATTN_EXP2) >= 0) a.exp2_domain = tuning(SW_ATTN_EXP2) ? 1 : 0;  // tools/attn_determinism.py (never set on the product path)
   const long nwork = (long)((a.N + 127) / 128) * a.heads * a.B;
-  static const int map_env = getenv("ROMA_ATTN_XCD") ? atoi(getenv("ROMA_ATTN_XCD")) : 1;
-  a.xcd_map = g_attn_xcd_map >= 0 ? g_attn_xcd_map : map_env;
+  a.xcd_map = tuning(SW_ATTN_XCD);  // 1 = per-XCD bands of (b, head), 0 = plain order
   ROMA_REQUIRE(nwork > 0 && nwork < (1l << 30), "attention: bad problem size");
   dim3 grid((unsigned)(a.xcd_map ? 8 * ((nwork + 7) / 8) : nwork));
   char pname[64];

@@ -30,6 +30,7 @@
 // to rounding, not bit for bit (tests/test_gpu_ops.py::test_cholesky_solve*).
 #include "chol_diag.h"
 #include "elementwise.h"
+#include "tuning.h"
 
 namespace roma {
 
@@ -232,8 +233,6 @@ __global__ __launch_bounds__(256) void chol_col_restore_kernel(float* __restrict
   for (int idx = tid; idx < 64 * 64; idx += 256) dst[(long)(idx >> 6) * ld + (idx & 63)] = tile[(idx & 63) * 65 + (idx >> 6)];
 }
 
-int g_gp_col_leader = -1;  // roma_tuning("gp_col_leader", v): 1 = leader + followers (default), 0 = every workgroup factorises its own copy
-
 // Block column k of the augmented system: A [batch][(n + d) x n] (ld = n), LT [batch][n x n].  `epoch`: any value that differs
 // between consecutive solves on the same buffers (cholesky_solve_t counts its calls).
 int chol_col_launch(float* A, long ld, long strideA, float* LT, long strideLT, int n, int d, float* Linv, float* LinvT, int k,
@@ -241,8 +240,7 @@ int chol_col_launch(float* A, long ld, long strideA, float* LT, long strideLT, i
   ROMA_REQUIRE(n % 64 == 0 && d % 64 == 0 && d >= 64 && ld % 4 == 0 && LT, "chol_col: n, d multiples of 64, d >= 64, ld of 4, LT");
   const int nrb = (n + d) / 64 - (k + 1);
   ROMA_REQUIRE(nrb >= 1 && k < nblk, "chol_col: no row block below the column");
-  static const int leader_env = getenv("ROMA_GP_COL_LEADER") ? atoi(getenv("ROMA_GP_COL_LEADER")) : 1;
-  const int use_leader = g_gp_col_leader >= 0 ? g_gp_col_leader : leader_env;
+  const int use_leader = tuning(SW_GP_COL_LEADER);  // 1 = leader + followers, 0 = every workgroup factorises its own copy
   const int gx = nrb + ((use_leader && k > 0) ? 1 : 0);
   hipLaunchKernelGGL(chol_col_kernel, dim3((unsigned)gx, (unsigned)batch), dim3(256), 0, s, A, ld, strideA, LT, strideLT, n, Linv,
                      LinvT, k, nblk, epoch & 0xffffffu, use_leader);

@@ -27,12 +27,11 @@
 #include <algorithm>
 
 #include "gemm_device.h"
+#include "tuning.h"
 
 namespace roma {
 
 static __device__ __attribute__((aligned(256))) unsigned int g_c64_dump[256];  // where lanes right of the image store
-
-int g_conv64_mode = -1;
 
 #define C64_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 
@@ -609,8 +608,7 @@ int conv3x3_c3_bf16_launch(const float* img, const void* w, const float* bias, v
 
 // 0 = launched, 1 = not this kernel's problem
 int conv64_try_launch(const GemmArgs& a, hipStream_t stream) {
-  static const int use_env = getenv("ROMA_CONV64") ? atoi(getenv("ROMA_CONV64")) : 7;
-  const int use = g_conv64_mode >= 0 ? g_conv64_mode : use_env;  // bit 0: Cin = 64 kernels, bit 1: the Cin = 128 kernel
+  const int use = tuning(SW_CONV64);  // bit 0: Cin = 64 kernels, bit 1: the Cin = 128 kernel
   const bool c128 = a.conv_c == 128;
   if (!(use & (c128 ? 2 : 1))) return 1;
   if ((a.conv_c != 64 && !c128) || a.in_dt != DT_BF16 || a.out_dt != DT_BF16 || a.act != ACT_RELU || !a.bias) return 1;
@@ -624,7 +622,7 @@ int conv64_try_launch(const GemmArgs& a, hipStream_t stream) {
   const int B = (int)(a.M / hw);
   const int TW = (!c128 && a.N == 64) ? 128 : 64;
   const int slots = c128 ? 256 : 512;  // persistent workgroups: one (8 waves) or two (4 waves) per CU
-  static const int sy_env = getenv("ROMA_CONV64_SY") ? atoi(getenv("ROMA_CONV64_SY")) : 0;
+  const int sy_env = tuning(SW_CONV64_SY);
   const int nxt = (W + TW - 1) / TW;
   // strip height: the persistent workgroups take the strips round-robin, so the launch lasts rounds x (SY + ~3 rows of ring
   // prologue); pick the split of H that minimises it (432 rows, 112 columns of strips: 9 strips of 48 rows fill 1.97 rounds

@@ -8,6 +8,5 @@ namespace roma {
 // ReLU, Cin in {128 .. 512} % 64 == 0, Cout % 256 == 0).  0 = launched, 1 = not this kernel's problem, < 0 = error.
 bool conv_patch_supported(const GemmArgs& a);
 int conv_patch_try_launch(const GemmArgs& a, hipStream_t stream);
-extern int g_conv_patch;  // roma_tuning("conv_patch")
 
 }  // namespace roma

@@ -31,12 +31,11 @@
 #include <algorithm>
 
 #include "gemm_device.h"
+#include "tuning.h"
 
 namespace roma {
 
 static __device__ __attribute__((aligned(256))) unsigned int g_cp_zero[64];  // source of every out-of-image DMA chunk
-
-int g_conv_patch = -1;  // roma_tuning("conv_patch", v): 1 = this kernel for slab-major VGG layers (default), 0 = gemm8p, -1 = env ROMA_CONV_PATCH
 
 struct ConvPatchArgs {
   const bf16_t* in;    // [B, H, W, Cin]
@@ -368,8 +367,7 @@ bool conv_patch_supported(const GemmArgs& a) {
 
 // 0 = launched, 1 = not this kernel's problem, < 0 = error
 int conv_patch_try_launch(const GemmArgs& g, hipStream_t stream) {
-  static const int use_env = getenv("ROMA_CONV_PATCH") ? atoi(getenv("ROMA_CONV_PATCH")) : 1;
-  if (!(g_conv_patch >= 0 ? g_conv_patch : use_env)) return 1;
+  if (!tuning(SW_CONV_PATCH)) return 1;  // 1 = this kernel for slab-major VGG layers, 0 = gemm8p
   if (!conv_patch_supported(g)) return 1;
   const int H = g.conv_h, W = g.conv_w;
   const long hw = (long)H * W;

@@ -28,6 +28,7 @@
 #include <algorithm>
 
 #include "elementwise.h"
+#include "tuning.h"
 #include "gemm.h"  // DT_*
 
 namespace roma {
@@ -246,13 +247,12 @@ __global__ __launch_bounds__(256, 2) void dwconv5x5_ring_kernel(const bf16_t* __
   ROMA_DWR_WAIT_VM(0);  // trailing zero-page DMAs must not outlive the workgroup's LDS allocation
 }
 
-int g_dw_ring = -1;  // roma_tuning("dw_ring", v): 1 = this kernel for the large launches it is faster on (default), 2 = for every shape it takes, 0 = dwconv5x5_kernel, -1 = env ROMA_DW_RING
-
 // 0 = launched, 1 = not this kernel's problem, < 0 = error
 int dwconv5x5_ring_try_launch(const void* in, void* out, const float* w, const float* bias, int B, int H, int W, int Cp, int dt,
                               hipStream_t s) {
-  static const int env = getenv("ROMA_DW_RING") ? atoi(getenv("ROMA_DW_RING")) : 1;
-  if (!(g_dw_ring >= 0 ? g_dw_ring : env)) return 1;
+  // 1 = this kernel for the large launches it is faster on, 2 = for every shape it takes, 0 = dwconv5x5_kernel
+  const int dw_ring = tuning(SW_DW_RING);
+  if (!dw_ring) return 1;
   if (dt != DT_BF16 || Cp % 64 != 0 || Cp < 256 || H < 1 || W < 1) return 1;
   if ((long)H * W * Cp * 2 >= (1l << 31)) return 1;  // 32-bit byte offsets inside an image (buffer descriptor per image; 0x80000000 = outside)
   if ((reinterpret_cast<uintptr_t>(in) & 15) != 0 || (reinterpret_cast<uintptr_t>(out) & 7) != 0) return 1;
@@ -268,7 +268,7 @@ int dwconv5x5_ring_try_launch(const void* in, void* out, const float* w, const f
     // (Rounds 3-6 capped a strip at 48 rows; without the cap the five wide shapes are 2.5 % faster in sum - 16 x 108^2 x 1152
     // 231 -> 216 us, 8 x 216^2 x 576 235 -> 224 - and none slower beyond noise: profiles/r06_v41_dwconv_strip_height.log.
     // ROMA_DWR_MAXSY: A/B.)
-    static const int max_sy = getenv("ROMA_DWR_MAXSY") ? std::max(6, atoi(getenv("ROMA_DWR_MAXSY"))) : (1 << 20);
+    const int max_sy = std::max(6, (int)tuning(SW_DWR_MAXSY));
     for (int ns = (H + max_sy - 1) / max_sy; ns <= std::max(1, H / 6); ++ns) {
       const int sy = (H + ns - 1) / ns;
       const long nt = per_strip * ((H + sy - 1) / sy);
@@ -286,8 +286,8 @@ int dwconv5x5_ring_try_launch(const void* in, void* out, const float* w, const f
   // sub-batch stream): 40^2 x 1408: 53.9 / 48.6 and 34.9 / 32.6 us; 70^2 x 1152: 118 / 142 and 62.7 / 59.0; 140^2 x 576:
   // 205 / 224 and 86.8 / 109; 108^2 x 1152: 220 / 258 and 112 / 137; 216^2 x 576: 407 / 463 and 204 / 240.  The crossover
   // sits between 45 M and 90 M elements.  ROMA_DW_RING=2 forces this kernel (tests, A/B).
-  static const long min_elems = getenv("ROMA_DW_RING_MINELEMS") ? atol(getenv("ROMA_DW_RING_MINELEMS")) : (64l << 20);
-  if ((g_dw_ring >= 0 ? g_dw_ring : env) != 2 && (long)B * H * W * Cp < min_elems) return 1;
+  const long min_elems = tuning(SW_DW_RING_MINELEMS);
+  if (dw_ring != 2 && (long)B * H * W * Cp < min_elems) return 1;
   ProfScope ps("dwconv5x5_kernel<" ROMA_H16_NAME ">", 2.0 * (double)B * H * W * Cp * 2.0, "byte", s);
   const long nwg = (ntasks + 3) / 4;
   hipLaunchKernelGGL(dwconv5x5_ring_kernel, dim3((unsigned)(((nwg + 7) / 8) * 8)), dim3(256), 0, s, (const bf16_t*)in,

@@ -59,7 +59,6 @@ int chol_diag_launch(float* A, long ld, long strideA, float* Linv, float* LinvT,
 // chol_col_restore_launch copies them into A (behind the last column).
 int chol_col_launch(float* A, long ld, long strideA, float* LT, long strideLT, int n, int d, float* Linv, float* LinvT, int k,
                     int nblk, int batch, unsigned epoch, hipStream_t s);
-extern int g_gp_col_leader;  // roma_tuning("gp_col_leader"): leader / follower hand-off inside a column launch on / off
 int chol_col_restore_launch(float* A, long ld, long strideA, const float* LT, long strideLT, int n, int batch, hipStream_t s);
 
 // pad the trailing (npad - n) diagonal of a Gram matrix with identity and zero its off-diagonals
@@ -87,12 +86,9 @@ int refiner_input_launch(const RefinerInputArgs& a, hipStream_t s);
 int dwconv5x5_launch(const void* in, void* out, const float* w, const float* bias, int B, int H, int W, int Cp,
                      int dt, hipStream_t s);
 // wide 16-bit problems (Cp % 64 == 0, Cp >= 256): the wave-private LDS-DMA ring form (dwconv_ring.hip), bit-identical to the
-// kernel above.  0 = launched, 1 = not its problem, < 0 = error.  g_dw_ring: roma_tuning("dw_ring") A/B switch.
+// kernel above.  0 = launched, 1 = not its problem, < 0 = error.  roma_tuning("dw_ring"): A/B switch.
 int dwconv5x5_ring_try_launch(const void* in, void* out, const float* w, const float* bias, int B, int H, int W, int Cp, int dt,
                               hipStream_t s);
-extern int g_dw_ring;
-extern int g_pool_proj;  // model.hip: roma_tuning("pool_proj")
-extern int g_gp_col;  // model.hip: roma_tuning("gp_col") - left-looking block-column Cholesky (chol_col.hip) on / off
 
 // out_conv (C->3, f32) fused with the flow / certainty update (matcher.py:177-178, 496-506)
 int refiner_out_launch(const void* d, long ldd, int dt, const float* w /*[3][Cp]*/, const float* b /*[3]*/,

@@ -3,6 +3,7 @@
 // one wave64 per row for row reductions, f32 math everywhere.
 #include <algorithm>
 #include "elementwise.h"
+#include "tuning.h"
 #include "chol_diag.h"
 #include <stdio.h>
 
@@ -865,7 +866,7 @@ int refiner_input_launch(const RefinerInputArgs& a, hipStream_t s) {
   {
     const int cv = a.dt == DT_F32 ? 4 : 8;
     const bool aligned = ((reinterpret_cast<uintptr_t>(a.feat) | reinterpret_cast<uintptr_t>(a.d)) & 15) == 0;
-    static const bool vec_off = getenv("ROMA_RI_VEC") && atoi(getenv("ROMA_RI_VEC")) == 0;  // A/B debugging only
+    const bool vec_off = tuning(SW_RI_VEC) == 0;  // A/B debugging only
     if (!vec_off && aligned && a.C % cv == 0 && a.ldf % cv == 0 && a.ldd % cv == 0) {
       int lpp = 1;
       while (lpp < 64 && lpp * cv < a.C) lpp *= 2;
@@ -1277,7 +1278,7 @@ int refiner_apply_delta_launch(const float* delta, float* flow, float* cert, lon
 int refiner_out_launch(const void* d, long ldd, int dt, const float* w, const float* b, float* flow, float* cert,
                        long M, int Cp, float sx, float sy, hipStream_t s) {
   ROMA_REQUIRE(Cp % 4 == 0 && ldd % 4 == 0, "refiner_out: channel padding must be a multiple of 4");
-  static const int row_env = getenv("ROMA_OUT_ROW") ? atoi(getenv("ROMA_OUT_ROW")) : 1;
+  const int row_env = tuning(SW_OUT_ROW);
   if (row_env && dt == DT_BF16 && Cp == 24 && ldd % 8 == 0 && (reinterpret_cast<uintptr_t>(d) & 15) == 0 &&
       (reinterpret_cast<uintptr_t>(flow) & 7) == 0) {
     constexpr int ROWS = 8;
@@ -1296,7 +1297,7 @@ int refiner_out_launch(const void* d, long ldd, int dt, const float* w, const fl
       // second piece has 2 / 8 / 16 active lanes of 16 / 64 / 64): take the power of two that fills the pieces best with
       // at most 5 per lane (18 = 4 x 5 - 2, 72 = 16 x 5 - 8, 144 = 32 x 5 - 16: 90 %), which also shortens the shuffle
       // reduction.  The f32 mode keeps its split (bit-for-bit history of the parity runs).
-      static const int lpr_env = getenv("ROMA_OUT_LPR") ? atoi(getenv("ROMA_OUT_LPR")) : 1;
+      const int lpr_env = tuning(SW_OUT_LPR);
       if (dt == DT_BF16 && lpr_env) {
         int best_l = lpr;
         double best_e = (double)chunks / ((double)lpr * ((chunks + lpr - 1) / lpr));
@@ -1315,7 +1316,7 @@ int refiner_out_launch(const void* d, long ldd, int dt, const float* w, const fl
       if (nk <= 6) {
         // 8 row groups per wave.  (With the weight prologue as guarded scalar loads 32 groups were 1.5 x faster than 8; with the
         // 16-byte prologue 8 and 16 are equal and 32 loses on the sub-batch sizes - profiles/r06_v39_*.  ROMA_OUT_ROWS_IT: A/B, even.)
-        static const int rows_it_env = getenv("ROMA_OUT_ROWS_IT") ? atoi(getenv("ROMA_OUT_ROWS_IT")) : 0;
+        const int rows_it_env = tuning(SW_OUT_ROWS_IT);
         const int rows_it = rows_it_env >= 2 ? rows_it_env & ~1 : 8;
         const long rows_per_block = 4l * (64 / lpr) * rows_it;
         dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block));

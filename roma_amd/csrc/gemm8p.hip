@@ -51,15 +51,13 @@
 
 #include "conv_patch.h"
 #include "gemm_device.h"
+#include "tuning.h"
 
 namespace roma {
 
 // zero source for out-of-range rows of the dense form: the per-k-tile byte offset (k * 128) is added to EVERY lane's
 // pointer, so the zero "row" must be as long as the longest K row (K <= 32704 bf16)
 static __device__ __attribute__((aligned(256))) unsigned int g_zero_rows[16384];
-
-int g_gemm8p_maxwg = -1;  // roma_tuning("gemm8p_maxwg"): see launch8p_s
-int g_gemm_tuning[2] = {-1, -1};  // [0] gemm8p on / off, [1] dbg bits; -1 = environment (roma_tuning, tests / A-B runs)
 
 enum { E8_NONE = 0, E8_RELU = 1, E8_GELU = 2, E8_RESBF16 = 3, E8_QKV = 4 };
 
@@ -515,7 +513,8 @@ static int launch8p_s(const GemmArgs& a, hipStream_t stream, const char* epi_nam
   const size_t lds = (size_t)2 * (BM + BN) * ROWB + 8 * 4096;  // 160 KiB: one persistent workgroup per CU
   // roma_tuning("gemm8p_maxwg", n): tools only - cap the persistent grid (a multiple of 8) to measure what a tile's epilogue
   // costs when fewer workgroups store at the same time (tools/bench_gemm_burst.py)
-  const long cap = g_gemm8p_maxwg >= 8 ? (g_gemm8p_maxwg / 8) * 8 : 256;
+  const long maxwg = tuning(SW_GEMM8P_MAXWG);
+  const long cap = maxwg >= 8 ? (maxwg / 8) * 8 : 256;
   const long gx = std::min<long>(((nblk + 7) / 8) * 8, std::min<long>(cap, 256));
   char pname[96];
   snprintf(pname, sizeof pname, "gemm8p_kernel<" ROMA_H16_NAME ",%s,%s,%s>", sizeof(TOUT) == 4 ? "f32" : ROMA_H16_NAME, CONV ? "conv3x3" : "dense", epi_name);
@@ -535,10 +534,8 @@ static int launch8p_s(const GemmArgs& a, hipStream_t stream, const char* epi_nam
 
 // schedule selection: roma_tuning("gemm8p_sched", v) (-1 = environment ROMA_GEMM8P_SCHED, default 1 = k-half phases; 0 =
 // quadrant phases); dbg bit 65536 flips it for one launch (A/B inside one process)
-int g_gemm8p_sched = -1;
 static int gemm8p_sched_of(const GemmArgs& a) {
-  static const int sched_env = getenv("ROMA_GEMM8P_SCHED") ? atoi(getenv("ROMA_GEMM8P_SCHED")) : 1;
-  const int base = g_gemm8p_sched >= 0 ? g_gemm8p_sched : sched_env;
+  const int base = tuning(SW_GEMM8P_SCHED);
   return (base ? 1 : 0) ^ ((a.dbg & 65536) ? 1 : 0);
 }
 template <typename TOUT, bool CONV, int EPI>
@@ -562,13 +559,13 @@ int gemm8p_trace_read(unsigned* host, long n) {
 // gemm_launch's own normalisation (qkv_pad / m_alg already applied).
 int conv64_try_launch(const GemmArgs& a, hipStream_t stream);  // conv64.hip (weight-stationary 3x3, Cin = 64)
 
-int g_gemm8p_walk = -1;  // roma_tuning("gemm8p_walk", n): tile rows per walk group (1 = row major); -1 = the dispatcher's choice
 int gemm8p_try_launch(const GemmArgs& a_in, hipStream_t stream) {
   GemmArgs a = a_in;
   // Row-major inside the band for every shape of the model (NT <= 16: measured neutral, profiles/r06_v33_gemm_walk.log); problems
   // with 24 or more tile columns walk groups of 8 tile rows (8192^3: 1 309 -> 1 397 TFLOP/s - with one tile row per XCD round the
   // 33 operand panels of a K step do not stay in the 4 MB L2)
-  a.walk_gm = g_gemm8p_walk >= 1 ? g_gemm8p_walk : ((a.N + 255) / 256 >= 24 ? 8 : 1);
+  const int walk = tuning(SW_GEMM8P_WALK);  // roma_tuning("gemm8p_walk", n): tile rows per walk group (1 = row major)
+  a.walk_gm = walk >= 1 ? walk : ((a.N + 255) / 256 >= 24 ? 8 : 1);
   if (a.conv_c > 0 && a.conv_korder == 1) {  // slab-major VGG layers: the patch-resident kernel (conv_patch.hip, round 6)
     const int rc = conv_patch_try_launch(a, stream);
     if (rc <= 0) return rc;
@@ -577,8 +574,7 @@ int gemm8p_try_launch(const GemmArgs& a_in, hipStream_t stream) {
     const int rc = conv64_try_launch(a, stream);
     if (rc <= 0) return rc;
   }
-  static const int use_env = getenv("ROMA_GEMM8P") ? atoi(getenv("ROMA_GEMM8P")) : 1;
-  const int use = g_gemm_tuning[0] >= 0 ? g_gemm_tuning[0] : use_env;
+  const int use = tuning(SW_GEMM8P);
   if (!use) return 1;
   if ((long)a.M * 1 >= (1L << 31) - 512) return 1;
   if (a.in_dt != DT_BF16 || a.batch != 1 || a.batch2 != 1 || a.lower_only || a.alpha != 1.0f) return 1;
@@ -592,7 +588,7 @@ int gemm8p_try_launch(const GemmArgs& a_in, hipStream_t stream) {
   // shapes gemm.hip would run on 256 x 256 tiles; for a single pair (M = 3 202 token rows, BASELINE config 2) the wide
   // launches (qkv, fc1: N >= 2048, 150-210 tiles of 256 x 256) are still better off on this kernel's pipelined loop with
   // part of the CUs idle than on gemm.hip's 128 x 128 loop at one wave per SIMD (ROMA_GEMM8P_MINM: A/B)
-  static const long minm_env = getenv("ROMA_GEMM8P_MINM") ? atol(getenv("ROMA_GEMM8P_MINM")) : 2048;
+  const long minm_env = tuning(SW_GEMM8P_MINM);
   const bool big_m = (long)a.M >= 8192 || ((long)a.M >= minm_env && a.N >= 2048 && !conv);
   if (!big_m) return 1;
   bool tile256 = false;

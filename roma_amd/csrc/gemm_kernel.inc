@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "gemm_device.h"
+#include "tuning.h"
 
 namespace roma {
 
@@ -543,7 +544,7 @@ static int launch_shape(const GemmArgs& a, hipStream_t stream) {
     // posterior mean K_xy alpha (M = 1600, N = 512, K = 1600 per image: 14 tiles of 256 x 256) ran on 56 of 256 CUs per
     // sub-batch stream, 345 us (profiles/r05_final_bench_bf16_2stream_kernel_trace.csv.gz); 128 x 128 tiles give 52 per image.
     // Same k order per output element: bit-identical results.  ROMA_GEMM_F32_FILL=0 switches the rule off (A/B).
-    static const bool fill_env = !(getenv("ROMA_GEMM_F32_FILL") && atoi(getenv("ROMA_GEMM_F32_FILL")) == 0);
+    const bool fill_env = tuning(SW_GEMM_F32_FILL) != 0;
     const long tiles256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256) * a.batch * a.batch2;
     if (fill_env && big_m && a.N >= 384 && !a.lower_only && tiles256 < 192) return launch_cfg<TIN, TOUT, 2, 2, 2, 2, CONV>(a, stream);  // 128 x 128
   }
@@ -565,7 +566,7 @@ static int launch_shape(const GemmArgs& a, hipStream_t stream) {
   // 48 CUs idle and ONE wave per SIMD on the rest, so every DMA / LDS / MFMA latency is exposed (370 TFLOP/s,
   // profiles/r02_final_bench_coarse.json).  128 x 64 tiles double the workgroups; three fit a CU (48 KiB of LDS each), so
   // all of them are resident at once and a CU interleaves the waves of 1-2 tiles.  ROMA_GEMM_SMALLM=0 switches it off (A/B).
-  static const bool smallm_env = !(getenv("ROMA_GEMM_SMALLM") && atoi(getenv("ROMA_GEMM_SMALLM")) == 0);
+  const bool smallm_env = tuning(SW_GEMM_SMALLM) != 0;
   const long tiles128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) * a.batch * a.batch2;
   if (smallm_env && !a.lower_only && tiles128 < 320) return launch_cfg<TIN, TOUT, 4, 1, 1, 2, CONV>(a, stream);  // 128 x 64
   return launch_cfg<TIN, TOUT, 2, 2, 2, 2, CONV>(a, stream);                      // 128 x 128

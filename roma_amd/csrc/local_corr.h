@@ -31,8 +31,6 @@ struct LocalCorrArgs {
   // set by the launcher: bin geometry and the offsets (in ints) of the bin tables / the sorted query list inside ws
   int bin_ts = 0, bin_nx = 0, bin_ny = 0, ws_bins = 0, ws_qlist = 0;
 };
-extern int g_lc_mode;  // roma_tuning("lc_mode")
-extern int g_lc_bin;   // roma_tuning("lc_bin"): 1 = incoherent tiles through the bin-sorted LIST form (default), 0 = per-query gathers
 
 // ints of device scratch local_corr_window_launch needs for this problem (window form, tiled radii 2 / 3 / 7; 0 otherwise)
 long local_corr_ws_ints(int B, int H, int W, int radius);

@@ -14,6 +14,7 @@
 // split the channels in interleaved 16-byte chunks, so one wave load instruction touches
 // (2r+2) fully used 64..128-byte segments.  f0 is staged once per wave in LDS as f32.
 #include "local_corr.h"
+#include "tuning.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -746,10 +747,6 @@ static int check_common(const LocalCorrArgs& a, int ce) {
   return 0;
 }
 
-int g_lc_mode = -1;  // roma_tuning("lc_mode"): -1 / 0 = tiled (MFMA all-pairs for 16-bit features) + work list (default), 1 = every tile to the gather list, 2 = per-pixel launch (the form every other radius uses)
-
-int g_lc_bin = -1;
-
 // bin edge: the largest TS with (TS + P - 1)^2 <= the smallest stage any build of the tile kernel has for this radius (the
 // 16-bit MFMA form's 320 slots for r <= 3) - one geometry for every precision keeps local_corr_ws_ints independent of it
 static int lc_bin_ts(int radius) {
@@ -777,8 +774,8 @@ static int launch_tiled(const LocalCorrArgs& a0, hipStream_t stream) {
   const long nbins = (long)a.B * a.bin_nx * a.bin_ny;
   a.ws_bins = 4 + 2 * tiles;
   a.ws_qlist = a.ws_bins + 3 * (int)nbins;
-  static const int bin_env = getenv("ROMA_LC_BIN") ? atoi(getenv("ROMA_LC_BIN")) : 1;
-  const bool binned = (g_lc_bin >= 0 ? g_lc_bin : bin_env) != 0 && (long)a.B * a.H * a.W < (1l << 31) &&
+  // lc_bin: 1 = incoherent tiles through the bin-sorted LIST form, 0 = per-query gathers
+  const bool binned = tuning(SW_LC_BIN) != 0 && (long)a.B * a.H * a.W < (1l << 31) &&
                       (a.bin_ts + P - 1) * (a.bin_ts + P - 1) <= LcGeom<R, MFMA>::PXMAX;
   const size_t need = (size_t)local_corr_ws_ints(a.B, a.H, a.W, R) * sizeof(int);
   bool own_ws = false;
@@ -788,7 +785,7 @@ static int launch_tiled(const LocalCorrArgs& a0, hipStream_t stream) {
   } else {
     ROMA_REQUIRE((size_t)a.ws_bytes >= need, "local_corr(window): work-list scratch too small");
   }
-  a.force_gather = g_lc_mode == 1 ? 1 : 0;
+  a.force_gather = tuning_override(SW_LC_MODE) == 1 ? 1 : 0;  // (the key alone: ROMA_LC_MODE=1 keeps the work list)
   ROMA_CHECK_HIP(hipMemsetAsync(a.ws, 0, 4 * sizeof(int), stream));
   const size_t lds_tile = (size_t)LcGeom<R, MFMA>::STAGE + 5 * 64 * 4 + 32;
   a.pxmax = LcGeom<R, MFMA>::PXMAX;  // what the classifier calls a coherent tile: its rectangle fits this kernel's stage
@@ -849,8 +846,9 @@ static int launch_window_r(const LocalCorrArgs& a, hipStream_t stream) {
   char pname[64];
   snprintf(pname, sizeof pname, "local_corr_window_kernel<%d,%s>", R, a.in_dt == DT_F32 ? "f32" : ROMA_H16_NAME);
   ProfScope ps(pname, (double)total * (2.0 * a.C * es_in + 8.0 + (2.0 * R + 1) * (2.0 * R + 1) * es_out), "byte", stream);
-  static const int env_mode = getenv("ROMA_LC_MODE") ? atoi(getenv("ROMA_LC_MODE")) : 0;
-  const int mode = g_lc_mode >= 0 ? g_lc_mode : env_mode;
+  // lc_mode: 0 = tiled (MFMA all-pairs for 16-bit features) + work list, 1 = every tile to the gather list, 2 = per-pixel
+  // launch (the form every other radius uses)
+  const int mode = tuning(SW_LC_MODE);
   const int cc = a.in_dt == DT_F32 ? 32 : 64;  // channels per 128-byte chunk of the tiled form
   // the tiled form is instantiated for the radii RoMa uses (roma_models.py:103-139: 7, 3, 2); other radii keep the
   // per-pixel kernel

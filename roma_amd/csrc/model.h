@@ -2,8 +2,6 @@
 // workspace (bump arena, planned by a dry run - no allocation inside roma_match) and the
 // kernel schedule of RegressionMatcher.match() (romatch/models/matcher.py:779-934).
 #pragma once
-#include <stdlib.h>
-
 #include <map>
 #include <mutex>
 #include <string>
@@ -11,6 +9,7 @@
 
 #include "../../include/roma_hip.h"
 #include "common.h"
+#include "tuning.h"
 
 namespace roma {
 
@@ -103,7 +102,7 @@ class Model {
   // The last ConvRefiner block's 1x1 convolution and out_conv are composed into ONE C -> 3 map at pack time (option
   // "compose_out_conv", default 1): 1/9 of the refiners' 1x1 GEMM work and one pass over the block output disappear; the
   // result differs from the two-step evaluation only by rounding (the 16-bit modes no longer round the dropped intermediate)
-  bool compose_out_conv = !(getenv("ROMA_COMPOSE_OUT") && atoi(getenv("ROMA_COMPOSE_OUT")) == 0);  // env: A/B runs
+  bool compose_out_conv = tuning(SW_COMPOSE_OUT) != 0;  // env: A/B runs
   // VGG layers with Cout >= 256 in the 16-bit modes: weight rows in slab-major K order (gemm.h, GemmArgs::conv_korder) - the nine
   // taps of a 64-channel slab back to back, an L2-sized working set per workgroup.  Measured in round 5: L2-miss traffic of the
   // conv GEMM 477 -> 143 MB raw FETCH_SIZE per launch, and the kernel 1.6 % SLOWER (9.31 against 9.15 ms per step, three
@@ -112,8 +111,8 @@ class Model {
   // are packed; it changes only the summation order of the K loop).
   // Round 6: ON by default - it is the K order of the patch-resident kernel (conv_patch.hip), which keeps the activation patch of a
   // slab in LDS across the nine taps.  ROMA_CONV_KORDER=0 (or ROMA_CONV_PATCH=0) restores tap-major rows on the implicit GEMM.
-  bool vgg_slab_major = !(getenv("ROMA_CONV_KORDER") && atoi(getenv("ROMA_CONV_KORDER")) == 0) &&
-                        !(getenv("ROMA_CONV_PATCH") && atoi(getenv("ROMA_CONV_PATCH")) == 0);
+  // (The environment half of conv_patch alone: roma_tuning("conv_patch", v) switches kernels, never the weight layout.)
+  bool vgg_slab_major = tuning(SW_CONV_KORDER) != 0 && tuning_env(SW_CONV_PATCH) != 0;
   int vgg_korder[12] = {0};
   bool fuse_refiner_blocks = true;  // bf16 mode: fused dw5x5+1x1 kernel at the narrow scales (option "fuse_refiner_blocks")
   // bf16 mode: DINOv2's residual stream in bf16, like the reference's bf16 backbone (encoders.py: dinov2 weights and

@@ -598,13 +598,13 @@ int Model::ensure_side_streams(int n) {
 
 // diagnostics (tools/repro_mixed.py): ROMA_DEBUG_DUAL_SLOT = k keeps the sub-batch stream split on in debug mode and lets only
 // sub-batch k capture its stages (the capture table is per handle, not per stream)
-static const int g_dbg_dual_slot = getenv("ROMA_DEBUG_DUAL_SLOT") ? atoi(getenv("ROMA_DEBUG_DUAL_SLOT")) : -1;
+static int dbg_dual_slot() { return tuning(SW_DEBUG_DUAL_SLOT); }
 
 int Model::dbg_save(const char* name, const void* p, size_t bytes, hipStream_t st) {
   if (!debug) return 0;
-  if (g_dbg_dual_slot >= 0) {  // only the stages named in ROMA_DEBUG_ONLY (comma separated), only for the chosen sub-batch
+  if (dbg_dual_slot() >= 0) {  // only the stages named in ROMA_DEBUG_ONLY (comma separated), only for the chosen sub-batch
     static const std::string only = std::string(",") + (getenv("ROMA_DEBUG_ONLY") ? getenv("ROMA_DEBUG_ONLY") : "") + ",";
-    if (dbg_cur_slot != g_dbg_dual_slot || only.find(std::string(",") + name + ",") == std::string::npos) return 0;
+    if (dbg_cur_slot != dbg_dual_slot() || only.find(std::string(",") + name + ",") == std::string::npos) return 0;
   }
   auto it = dbg.find(name);
   if (it == dbg.end() || it->second.second != bytes) {
@@ -646,9 +646,9 @@ int Model::forward(int B, const float* ima, const float* imb, const roma_forward
 
 int Model::match_streams(int B, const float* ima, const float* imb, const float* ima_hr, const float* imb_hr, float* warp,
                          float* cert, hipStream_t st) {
-  static const int env_streams = getenv("ROMA_STREAMS") ? atoi(getenv("ROMA_STREAMS")) : 0;
-  static const bool serial_env = getenv("ROMA_STREAMS_SERIAL") && atoi(getenv("ROMA_STREAMS_SERIAL")) != 0;
-  const int ns = (debug && g_dbg_dual_slot < 0) ? 1 : std::min(std::min(env_streams > 0 ? env_streams : n_streams, (int)MAX_STREAMS), B);
+  const int env_streams = tuning(SW_STREAMS);
+  const bool serial_env = tuning(SW_STREAMS_SERIAL) != 0;
+  const int ns = (debug && dbg_dual_slot() < 0) ? 1 : std::min(std::min(env_streams > 0 ? env_streams : n_streams, (int)MAX_STREAMS), B);
   if (ns <= 1) return match_impl(B, ima, imb, ima_hr, imb_hr, warp, cert, st, false, arena, persist);
   if (int rc = ensure_side_streams(ns)) return rc;
   // fork: the side streams start after everything already queued on the caller's stream (inputs); join at the end
@@ -693,21 +693,18 @@ int Model::match_streams(int B, const float* ima, const float* imb, const float*
 // GEMM of step k simply run over mrem + d rows and the 2 * nblk - 1 launches of the forward loop disappear from the GP's
 // launch-latency-bound chain (~0.75 ms of 10 .. 25 us launches at n = 1600); same operations on every element in the same
 // order, so the result is bit-identical to the separate loop.
-int g_pool_proj = -1;  // roma_tuning("pool_proj", v): 1 = max-pool + proj head of strides 1 / 2 in one pass (default), 0 = separate kernels, -1 = env ROMA_POOL_PROJ
-int g_gp_col = -1;  // roma_tuning("gp_col", v): 1 = left-looking block-column kernel (default), 0 = right-looking chain, -1 = env ROMA_GP_COL
 int cholesky_solve_t(float* A, float* Rt, float* LT, float* Linv, float* LinvT, int n, int d, int batch, hipStream_t st,
                      long strideA, long strideR) {
   ROMA_REQUIRE(n % 64 == 0 && n > 0 && d % 4 == 0, "cholesky_solve: n must be a multiple of 64, d of 4");
   const int nblk = n / 64;
   const long sA = strideA > 0 ? strideA : (long)n * n, sR = strideR > 0 ? strideR : (long)d * n, sL = (long)nblk * 4096;
   const long sLT = (long)n * n;  // LT is always dense
-  static const bool aug_env = !(getenv("ROMA_GP_AUG") && atoi(getenv("ROMA_GP_AUG")) == 0);  // A/B: 0 = always the separate forward loop
+  const bool aug_env = tuning(SW_GP_AUG) != 0;  // A/B: 0 = always the separate forward loop
   const bool aug = aug_env && Rt == A + (long)n * n && (batch == 1 || (sA == sR && sA >= (long)(n + d) * n));
   const int extra = aug ? d : 0;
   // Round 6: the augmented system left-looking, ONE launch per block column (chol_col.hip) instead of chol_diag + panel +
   // trailing update; L^T is written by the same launches.  roma_tuning("gp_col", 0) / ROMA_GP_COL=0: the right-looking chain.
-  static const bool col_env = !(getenv("ROMA_GP_COL") && atoi(getenv("ROMA_GP_COL")) == 0);
-  const bool col = aug && (g_gp_col >= 0 ? g_gp_col != 0 : col_env) && d >= 64 && d % 64 == 0;
+  const bool col = aug && tuning(SW_GP_COL) != 0 && d >= 64 && d % 64 == 0;
   static std::atomic<unsigned> solve_epoch{0};  // tags the in-launch hand-off flags of this solve (chol_col.hip)
   const unsigned epoch = col ? ++solve_epoch : 0u;
   for (int k = 0; k < nblk && col; ++k)
@@ -755,7 +752,7 @@ int cholesky_solve_t(float* A, float* Rt, float* LT, float* Linv, float* LinvT, 
     u.M = d; u.N = mrem; u.K = 64; u.batch = batch;
     if (int rc = gemm_launch(u, st)) return rc;
   }
-  static const bool bwd_env = !(getenv("ROMA_GP_BWD2") && atoi(getenv("ROMA_GP_BWD2")) == 0);  // A/B: 0 = two launches per backward step
+  const bool bwd_env = tuning(SW_GP_BWD2) != 0;  // A/B: 0 = two launches per backward step
   if (bwd_env && nblk > 1) {
     // Backward substitution with ONE launch per step.  X_k = R_k Linv_kk and R_j -= X_k L[k,j] (j < k) re-associate to
     // R_j -= R_k (Linv_kk L[k,j]): the products M_k = Linv_kk L[k, :k] do not depend on the right-hand sides, so they are formed
@@ -966,14 +963,13 @@ int Model::match_impl(int B, const float* ima, const float* imb, const float* im
     for (int l = 0; l < 4; ++l) feat[l] = AL((size_t)nimg * fh[l] * fw_[l] * fc[l], esz);
     // Round 6 (pool_proj.hip): at strides 1 and 2 the max-pool and the proj head of the level read the un-pooled map in ONE
     // pass (16-bit modes); the projected maps are then ready when the decoder reaches those scales.  pf_pre[l]: stride 2^l.
-    static const bool pp_env = !(getenv("ROMA_POOL_PROJ") && atoi(getenv("ROMA_POOL_PROJ")) == 0);
     void* pf_pre[2] = {nullptr, nullptr};
     const int pp_si[2] = {4, 3};  // index of stride 1 / 2 in SCALES
     bool pp_on[2];
     for (int l = 0; l < 2; ++l) {
       const RefinerW& rr = ref[pp_si[l]];
       const int ldf_l = (int)round_up(rr.Cf, 8);
-      pp_on[l] = (g_pool_proj >= 0 ? g_pool_proj != 0 : pp_env) && fh[l] >= 2 && fw_[l] >= 2 &&
+      pp_on[l] = tuning(SW_POOL_PROJ) != 0 && fh[l] >= 2 && fw_[l] >= 2 &&
                  pool_proj_supported(fc[l], rr.Cf, ldf_l, act_dt) && proj[pp_si[l]].b != nullptr;
       if (pp_on[l] || dry) pf_pre[l] = AL((size_t)nimg * fh[l] * fw_[l] * ldf_l, esz);  // (planned whatever the switch says now)
       if (!pp_on[l] && !dry) pf_pre[l] = nullptr;
@@ -982,9 +978,8 @@ int Model::match_impl(int B, const float* ima, const float* imb, const float* im
       const size_t enc_mark = arena.mark();
       void* t0 = AL((size_t)nimg * H * W * 64, esz);
       void* t1 = AL((size_t)nimg * (H / 2) * (W / 2) * 64, esz);
-      static const int c64_env = getenv("ROMA_CONV64") ? atoi(getenv("ROMA_CONV64")) : 7;
       void* col1 = AL((size_t)nimg * H * W * 32, esz);  // (planned whichever form runs: the switch may change between calls)
-      if (act_dt == DT_BF16 && ((g_conv64_mode >= 0 ? g_conv64_mode : c64_env) & 4) && (long)3 * H * W < (1l << 23)) {  // (its packed tap offsets)
+      if (act_dt == DT_BF16 && (tuning(SW_CONV64) & 4) && (long)3 * H * W < (1l << 23)) {  // (its packed tap offsets)
         // first layer (Cin = 3), bf16: fused kernel straight from the f32 image (conv64.hip)
         RUN(conv3x3_c3_bf16_launch(imA, vgg[0].w, vgg[0].b, t0, B, H, W, st));
         RUN(conv3x3_c3_bf16_launch(imB, vgg[0].w, vgg[0].b, off(t0, (long)B * H * W * 64), B, H, W, st));
@@ -1057,7 +1052,7 @@ int Model::match_impl(int B, const float* ima, const float* imb, const float* im
       void* col = AL((size_t)nimg * T * patch.ldw, esz);
       float* pt = (float*)AL((size_t)nimg * T * 1024, 4);
       float* x = (float*)AL((size_t)rows_d * 1024, 4);
-      static const bool res_f32_env = getenv("ROMA_VIT_RES_F32") && atoi(getenv("ROMA_VIT_RES_F32")) != 0;
+      const bool res_f32_env = tuning(SW_VIT_RES_F32) != 0;
       void* xs = nullptr;
       if (act_dt == DT_BF16) xs = AL((size_t)rows_d * 1024, 2);  // 16-bit residual stream: always planned, the option may flip later
       void* feat_vit = feat[4];
@@ -1209,9 +1204,9 @@ int Model::match_impl(int B, const float* ima, const float* imb, const float* im
         }
         if (debug && !dry) {
           const std::string nm = std::string("p") + (up ? "2" : "1") + "_din" + SCALES[si];
-          if ((size_t)M * r.Cp * esz <= ((size_t)(g_dbg_dual_slot >= 0 ? 512 : 64) << 20))
+          if ((size_t)M * r.Cp * esz <= ((size_t)(dbg_dual_slot() >= 0 ? 512 : 64) << 20))
             if (int rc = dbg_save(nm.c_str(), d0, (size_t)M * r.Cp * esz, st)) return rc;
-          if (g_dbg_dual_slot >= 0 && ins == 1)
+          if (dbg_dual_slot() >= 0 && ins == 1)
             if (int rc = dbg_save((std::string("p") + (up ? "2" : "1") + "_flowin1").c_str(), flow, (size_t)M * 2 * 4, st)) return rc;
         }
         void *dcur = d0, *dalt = d1;

@@ -26,7 +26,4 @@ int refiner_block_final_launch(const void* in, float* delta, const float* dw_w, 
 bool refiner_block_wide_supported(int Cp, int dt);
 int refiner_block_wide_try_launch(const void* in, void* out, const float* dw_w, const float* dw_b, const void* pw, long ldpw,
                                   const float* pw_b, int B, int H, int W, int Cp, int dt, hipStream_t s, bool force = false);
-extern int g_rb_wide;
-extern int g_rb24_wave;
-extern int g_rb144_1b;
 }  // namespace roma

@@ -13,6 +13,7 @@
 //     16-channel remainder block comes from LDS.  C = 24: the single (padded) 32-channel block comes from LDS.
 // The in-flight prefetch of the next input row spans the MFMA phase, which is what hides the HBM latency.
 #include "refiner_block.h"
+#include "tuning.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -438,7 +439,6 @@ __global__ __launch_bounds__(256, 2) void refiner_block144_1b_kernel(const bf16_
 //  0.541 vs 0.504 ms at 16x216x216x576, 0.299 vs 0.266 ms at 16x108x108x1152 - slower than the register-prefetch
 //  kernel in elementwise.hip.  The depthwise phase is bound by its 200 v_pk_fma_f32 + 25 LDS weight reads per row,
 //  not by load latency; the ring only pays off here, where it also frees the registers the 1x1 weights need.)
-int g_rb144_1b = -1;  // roma_tuning("rb144_1b", v): 1 = refiner_block144_1b_kernel (default), 0 = refiner_block_kernel<144>, -1 = env ROMA_RB144_1B
 bool refiner_block_supported(int Cp, int dt) { return dt == DT_BF16 && (Cp == 24 || Cp == 144); }
 
 template <int CP>
@@ -449,7 +449,7 @@ static int launch_cp(const void* in, void* out, const float* dw_w, const float* 
   const int nxg = (W + Cf::PX - 1) / Cf::PX;
   // strip height: SY + 4 input rows are read per strip (and ~2 more rows' worth of pipeline fill), and the 512 resident
   // workgroups take the strips in rounds - pick the split of H that minimises rounds x (SY + 6).  ROMA_RB_SY overrides.
-  static const int sy_env = getenv("ROMA_RB_SY") ? atoi(getenv("ROMA_RB_SY")) : 0;
+  const int sy_env = tuning(SW_RB_SY);
   int SY = sy_env;
   if (SY <= 0) {
     long best = -1;
@@ -468,14 +468,13 @@ static int launch_cp(const void* in, void* out, const float* dw_w, const float* 
   const int nblocks = (int)nb;
   dim3 grid((unsigned)(((nblocks + 7) / 8) * 8));
 #ifdef ROMA_TOOLS_BUILD
-  static const int dbg = getenv("ROMA_RB_DBG") ? atoi(getenv("ROMA_RB_DBG")) : 0;  // tuning ablations only
+  const int dbg = tuning(SW_RB_DBG);  // tuning ablations only
   if (dbg & 16) {
     int nb_cu = -1;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_cu, refiner_block_kernel<CP>, 256, 0);
     fprintf(stderr, "refiner_block<%d>: %d workgroups/CU, grid %d\n", CP, nb_cu, nblocks);
   }
-  static const int env1b = getenv("ROMA_RB144_1B") ? atoi(getenv("ROMA_RB144_1B")) : 1;
-  if (!delta && (CP == 24 || !(g_rb144_1b >= 0 ? g_rb144_1b : env1b) || dbg)) {
+  if (!delta && (CP == 24 || !tuning(SW_RB144_1B) || dbg)) {  // 1 = refiner_block144_1b_kernel, 0 = refiner_block_kernel<144>
     hipLaunchKernelGGL(refiner_block_kernel<CP>, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, dw_w, dw_b,
                        (const bf16_t*)pw, ldpw, pw_b, B, H, W, SY, nxg, nblocks, dbg);
     ROMA_LAUNCH_CHECK();
@@ -483,7 +482,7 @@ static int launch_cp(const void* in, void* out, const float* dw_w, const float* 
   }
 #else
   ROMA_REQUIRE(CP == 144, "refiner_block: C = 24 runs on the wave-private kernel only (it declined these tensors: 16-byte aligned bf16 in / out / weights are required)");
-  ROMA_REQUIRE(g_rb144_1b != 0, "refiner_block: the two-barrier A/B kernel is not part of this build (make TOOLS=1)");
+  ROMA_REQUIRE(tuning(SW_RB144_1B) != 0, "refiner_block: the two-barrier A/B kernel is not part of this build (make TOOLS=1)");
 #endif
   if (delta)
     hipLaunchKernelGGL(refiner_block144_1b_kernel<true>, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)nullptr, dw_w, dw_b,

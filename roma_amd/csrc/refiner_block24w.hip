@@ -27,6 +27,7 @@
 
 #include "gemm.h"  // DT_*
 #include "refiner_block.h"
+#include "tuning.h"
 
 namespace roma {
 
@@ -357,14 +358,11 @@ __global__ __launch_bounds__(256, 2) void refiner_block24_wave_kernel(const bf16
   ROMA_RBW_WAIT_VM(0);  // trailing zero-page DMAs must not outlive the workgroup's LDS allocation
 }
 
-int g_rb24_wave = -1;  // roma_tuning("rb24w", v): 1 = this kernel for C = 24 (default), 0 = refiner_block_kernel<24>, -1 = env ROMA_RB24W
-
 // 0 = launched, 1 = not this kernel's problem, < 0 = error
 int refiner_block24_wave_try_launch(const void* in, void* out, const float* dw_w, const float* dw_b, const void* pw, long ldpw,
                                     const float* pw_b, int B, int H, int W, int dt, hipStream_t s, float* delta) {
-  static const int env = getenv("ROMA_RB24W") ? atoi(getenv("ROMA_RB24W")) : 1;
 #ifdef ROMA_TOOLS_BUILD
-  if (!(g_rb24_wave >= 0 ? g_rb24_wave : env)) return 1;  // A/B: the two-barrier workgroup kernel (refiner_block_2b.inc)
+  if (!tuning(SW_RB24W)) return 1;  // A/B: the two-barrier workgroup kernel (refiner_block_2b.inc)
 #endif
   if (dt != DT_BF16 || H < 1 || W < 1 || (long)H * W * RBW_C * 2 >= (1l << 31)) return 1;  // (32-bit offsets inside an image)
   if ((reinterpret_cast<uintptr_t>(in) & 15) != 0 || (reinterpret_cast<uintptr_t>(delta ? (void*)delta : out) & 15) != 0) return 1;

@@ -32,6 +32,7 @@
 // v_pk_fma_f32 + ~330 other VALU per wave.  v0 (round 5, visit 2) ran the two phases back to back with all waves in lock-step:
 // bit-identical to the two-kernel path but 1 372 vs 996 us at 16 x 216 x 216; v2 below de-phases two wave groups.
 #include "refiner_block.h"
+#include "tuning.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -373,15 +374,12 @@ __global__ __launch_bounds__(512, 2) void refiner_block_wide_kernel(const bf16_t
   }
 }
 
-int g_rb_wide = -1;  // roma_tuning("rb_wide", v): 1 = this kernel for C = 576, 0 = dwconv5x5 + 1x1 GEMM (default: the fused kernel measured slower), 2 / 3 = this kernel with the scalar / packed stencil, -1 = env ROMA_RB_WIDE
-
 bool refiner_block_wide_supported(int Cp, int dt) { return dt == DT_BF16 && Cp == RW_C; }
 
 // 0 = launched, 1 = not taken (the caller runs dwconv5x5 + GEMM), < 0 = error
 int refiner_block_wide_try_launch(const void* in, void* out, const float* dw_w, const float* dw_b, const void* pw, long ldpw,
                                   const float* pw_b, int B, int H, int W, int Cp, int dt, hipStream_t s, bool force) {
-  static const int env = getenv("ROMA_RB_WIDE") ? atoi(getenv("ROMA_RB_WIDE")) : 0;  // measured slower than dwconv5x5 + ws1x1 (1 306 vs 978 us): off
-  if (!force && !(g_rb_wide >= 0 ? g_rb_wide : env)) return 1;
+  if (!force && !tuning(SW_RB_WIDE)) return 1;  // measured slower than dwconv5x5 + ws1x1 (1 306 vs 978 us): off by default
   if (!refiner_block_wide_supported(Cp, dt) || H < 1 || W < 1 || B < 1) return 1;
   if ((long)H * W * Cp * 2 >= (1l << 32)) return 1;  // 32-bit byte offsets inside an image
   if ((reinterpret_cast<uintptr_t>(in) & 15) != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) return 1;
@@ -395,13 +393,12 @@ int refiner_block_wide_try_launch(const void* in, void* out, const float* dw_w, 
   ROMA_REQUIRE(ntiles < (1l << 30), "refiner_block_wide: grid too large");
   // algorithmic work of the block: the 1x1's FLOPs (the stencil's 50 FLOP per element ride along)
   ProfScope ps("refiner_block_wide_kernel<576>", 2.0 * (double)B * H * W * (double)Cp * Cp, "flop", s);
-#ifdef ROMA_TOOLS_BUILD  // ablations (tools/bench_refiner_wide.py): 1 no stencil, 2 no MFMA, 4 no DMA after the prologue, 8 no tap reads, 16 no epilogue
-  static const int dbg = getenv("ROMA_RBW_DBG") ? atoi(getenv("ROMA_RBW_DBG")) : 0;
-#else  // the shipped libraries never take ablation bits from the environment (they produce wrong outputs by design)
-  constexpr int dbg = 0;
-#endif
-  static const int pk_env = getenv("ROMA_RB_WIDE_PK") ? atoi(getenv("ROMA_RB_WIDE_PK")) : 1;
-  const int mode = g_rb_wide >= 2 ? g_rb_wide : 0;  // roma_tuning("rb_wide", 2 / 3): force the scalar / packed stencil (A/B)
+  // ablations (tools/bench_refiner_wide.py): 1 no stencil, 2 no MFMA, 4 no DMA after the prologue, 8 no tap reads, 16 no epilogue.
+  // The shipped libraries never take these bits from the environment (they produce wrong outputs by design): a tools-only row.
+  const int dbg = tuning(SW_RBW_DBG);
+  const int pk_env = tuning(SW_RB_WIDE_PK);
+  const int rb_wide = tuning_override(SW_RB_WIDE);  // (the key alone: ROMA_RB_WIDE=2 / 3 only switches the kernel on)
+  const int mode = rb_wide >= 2 ? rb_wide : 0;  // roma_tuning("rb_wide", 2 / 3): force the scalar / packed stencil (A/B)
   const bool pk = mode == 3 ? true : (mode == 2 ? false : pk_env != 0);
   static bool attr_set[64] = {false};
   int dev = 0;

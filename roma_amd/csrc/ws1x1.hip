@@ -42,10 +42,9 @@
 #include <algorithm>
 
 #include "gemm_device.h"
+#include "tuning.h"
 
 namespace roma {
-
-int g_ws1x1_mode = -1;  // roma_tuning("ws1x1", v): 1 = this kernel for the C = 576 refiner GEMMs (default), 0 = gemm6p; -1 = env ROMA_WS1X1
 
 #define WS_WAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
@@ -200,10 +199,7 @@ __global__ __launch_bounds__(384, 2) void ws1x1_kernel(const bf16_t* __restrict_
 #undef WS_ISSUE_PIECE
 }
 
-static int ws_mode() {
-  static const int env = getenv("ROMA_WS1X1") ? atoi(getenv("ROMA_WS1X1")) : 1;
-  return g_ws1x1_mode >= 0 ? g_ws1x1_mode : env;
-}
+static int ws_mode() { return tuning(SW_WS1X1); }  // 1 = this kernel for the C = 576 refiner GEMMs, 0 = gemm6p
 
 template <int ACT>
 static int launch_ws(const GemmArgs& a, hipStream_t stream) {
