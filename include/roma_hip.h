@@ -295,6 +295,37 @@ int roma_op_mutual_nn_fill(const float* a, long na, const float* b, long nb, con
 long roma_op_multinomial_workspace(long n, long k);
 int roma_op_multinomial(const float* weights, long n, long k, unsigned long long seed, long long* out_indices, void* workspace,
                         long workspace_bytes, void* stream);
+/* RegressionMatcher.sample (matcher.py:598-629) applied to each of B pairs separately, in one enqueue of a fixed number of
+ * launches (24 in the balanced modes, 12 otherwise, whatever B is) with no host read.  matches [B, n, 4] and certainty [B, n] are
+ * f32; pair b draws from seeds[b].  threshold != 0 (the "threshold" sample modes): a certainty above `thresh` counts as 1, in
+ * the weights and in out_certainty.  With k = min(4 num, n) if balanced != 0 (the "balanced" modes), min(num, n) otherwise, and
+ * m = min(num, k), per pair:
+ *   first draw: k of the n rows without replacement, weight = the (thresholded) certainty, by roma_op_multinomial's exponential
+ *     race on seed seeds[b] (row i: u from mix64 of (seed, i), key = min(-log(u) / w, 3e38), +inf for w <= 0; the k smallest keys,
+ *     in ascending (key, index) order = draw order).  Entries that share the k-th key are taken by ascending index, so a pair
+ *     with fewer than k positive weights is completed by its LOWEST zero-weight rows, behind every real row.
+ *   balanced == 0: the first draw is the result (k = m).
+ *   balanced != 0: density[j] = sum over the k drawn rows of exp(-|x_j - x_i|^2 / (2 0.1^2)) as roma_op_kde(half_inputs = 1)
+ *     evaluates it (coordinates rounded to fp16, f32 sum), summed in a fixed order that depends on k alone;
+ *     p[j] = 1 / (density[j] + 1), 1e-7 where density[j] < 10, and - the one extension of the reference - 0 for a drawn row whose
+ *     certainty is not positive (a filler row).  Second draw: m of the k rows with weight p, the same race over j = 0 .. k - 1
+ *     on seed seeds[b] ^ 0x5851f42d4c957f2d, again in draw order, filler rows last.
+ * out_matches [B, m, 4] and out_certainty [B, m] are the drawn rows and their (thresholded) certainties.  Nullable outputs:
+ * out_counts [B] = min(m, positive weights of the pair), the number of leading rows that are real matches (the `counts` of
+ * roma_op_ransac and its neighbours); out_idx [B, m] the drawn rows' indices into the pair's n rows; out_first_idx [B, k] the
+ * first draw's; out_density [B, k] the density of the first draw's rows (balanced modes only, otherwise not written).
+ * Every output is a function of the pair's inputs and its seed alone: bit-identical from run to run, for every B and for every
+ * position of the pair in the batch (ties are broken by index, the density adds its partial sums in a fixed order, no float is
+ * added atomically).  The stream of random numbers is not torch's: parity with the reference is distributional.
+ * k > 65536 (num > 16384 in the balanced modes) is refused: the order of larger samples (roma_op_multinomial's bitonic
+ * network) is not batched.  Also refused, before anything is enqueued: null required pointers, n >= 2^31, B > 65535, a
+ * workspace below roma_op_sample_matches_workspace(B, n, num, balanced) bytes (0 for B <= 0, n <= 0 or num <= 0, where the call
+ * does nothing), matches / out_matches / workspace not 16-byte aligned.  Restated in numpy float64 by tools/sample_ref.py. */
+long roma_op_sample_matches_workspace(int B, long n, long num, int balanced);
+int roma_op_sample_matches(const float* matches, const float* certainty, const unsigned long long* seeds, int B, long n, long num,
+                           int threshold, float thresh, int balanced, float* out_matches, float* out_certainty, int* out_counts,
+                           long long* out_idx, long long* out_first_idx, float* out_density, void* workspace, long workspace_bytes,
+                           void* stream);
 /* Batched RANSAC - the robust estimation the reference's demos run on sample() output through OpenCV:
  * cv2.findHomography(A, B, RANSAC) (model 0: 4-point DLT, one-sided reprojection error in image B) and
  * cv2.findFundamentalMat(A, B, FM_RANSAC) (model 1: 7-point solver, up to 3 models per sample, max of the two point-to-epipolar-line

@@ -7,12 +7,12 @@ fundamental / essential-matrix estimation, relative pose).  Everything numerical
 from .matcher import RegressionMatcher, roma_indoor, roma_model, roma_outdoor  # noqa: F401
 from .local_correlation import local_corr, local_correlation  # noqa: F401
 from .kde import kde  # noqa: F401
-from .sampling import multinomial  # noqa: F401
+from .sampling import multinomial, sample_matches  # noqa: F401
 from .geometry import (essential_magsac, essential_minimal, estimate_pose, estimate_pose_uncalibrated, find_essential,  # noqa: F401
                        find_fundamental, find_homography, magsac, recover_pose, refine_fundamental, refine_homography, refine_pose)
 from .tiny import TinyRoMa, tiny_roma_v1_outdoor  # noqa: F401
 
 __all__ = ["RegressionMatcher", "roma_model", "roma_outdoor", "roma_indoor", "local_corr", "local_correlation", "kde",
-           "multinomial", "find_homography", "find_fundamental", "find_essential", "recover_pose", "refine_pose", "estimate_pose",
+           "multinomial", "sample_matches", "find_homography", "find_fundamental", "find_essential", "recover_pose", "refine_pose", "estimate_pose",
            "refine_homography", "refine_fundamental", "estimate_pose_uncalibrated", "essential_minimal", "magsac", "essential_magsac",
            "TinyRoMa", "tiny_roma_v1_outdoor"]

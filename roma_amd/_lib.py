@@ -91,6 +91,8 @@ SIGNATURES = {
     "roma_op_visualize_warp": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "roma_op_multinomial_workspace": (_l, [_l, _l]),
     "roma_op_multinomial": (_i, [_vp, _l, _l, C.c_ulonglong, _vp, _vp, _l, _vp]),
+    "roma_op_sample_matches_workspace": (_l, [_i, _l, _l, _i]),
+    "roma_op_sample_matches": (_i, [_vp, _vp, _vp, _i, _l, _l, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_ransac_workspace": (_l, [_i, _i]),
     "roma_op_ransac": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_magsac_workspace": (_l, [_i, _i]),

@@ -22,6 +22,7 @@
 #include "tuning.h"
 #include "vit.h"
 #include "sampling.h"
+#include "sample_batched.h"
 #include "essential.h"
 #include "model_refine.h"
 #include "pose_refine.h"
@@ -511,6 +512,18 @@ long roma_op_multinomial_workspace(long n, long k) { return (long)multinomial_wo
 int roma_op_multinomial(const float* weights, long n, long k, unsigned long long seed, long long* out_indices, void* workspace,
                         long workspace_bytes, void* stream) {
   return multinomial_launch(weights, n, k, seed, out_indices, workspace, (size_t)workspace_bytes, S(stream));
+}
+// ---- RegressionMatcher.sample for a batch of pairs (sample_batched.hip)
+long roma_op_sample_matches_workspace(int B, long n, long num, int balanced) {
+  return (long)sample_matches_workspace_bytes(B, n, num, balanced);
+}
+int roma_op_sample_matches(const float* matches, const float* certainty, const unsigned long long* seeds, int B, long n, long num,
+                           int threshold, float thresh, int balanced, float* out_matches, float* out_certainty, int* out_counts,
+                           long long* out_idx, long long* out_first_idx, float* out_density, void* workspace, long workspace_bytes,
+                           void* stream) {
+  return sample_matches_launch(matches, certainty, seeds, B, n, num, threshold, thresh, balanced, out_matches, out_certainty, out_counts,
+                               out_idx, out_first_idx, out_density, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0),
+                               S(stream));
 }
 // ---- batched RANSAC (geometry.hip)
 long roma_op_ransac_workspace(int B, int N) { return (long)ransac_workspace_bytes(B, N); }

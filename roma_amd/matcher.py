@@ -457,6 +457,20 @@ class RegressionMatcher:
         balanced_samples = multinomial(p, min(num, len(good_certainty)))
         return good_matches[balanced_samples], good_certainty[balanced_samples]
 
+    def sample_batched(self, matches, certainty, num=10000, seed=None, **kw):
+        """`sample` for every pair of a batch in one enqueue, reproducible from `seed` (`roma_amd.sample_matches` with this
+        matcher's `sample_mode` and `sample_thresh`; see there for shapes, `return_counts`, `return_indices`).  The output feeds
+        the batched geometry directly:
+
+            warp, certainty = model.match(im_A, im_B)                                # [B, H, W, 4], [B, H, W]
+            m, c, counts = model.sample_batched(warp, certainty, num=5000, seed=0, return_counts=True)
+            kpts_A, kpts_B = model.to_pixel_coordinates(m, H_A, W_A, H_B, W_B)      # elementwise: [B, 5000, 2] each
+            R, t, mask, ok = roma_amd.estimate_pose(kpts_A, kpts_B, K_A, K_B, norm_thresh, counts=counts)
+        """
+        from .sampling import sample_matches
+        return sample_matches(matches, certainty, num=num, sample_mode=self.sample_mode, sample_thresh=self.sample_thresh,
+                              seed=seed, **kw)
+
     # ------------------------------------------------------------------ keypoint matching (matcher.py:732-773)
     def match_keypoints(self, x_A, x_B, warp, certainty, return_tuple=True, return_inds=False, max_dist=0.005, cert_th=0):
         """Mutual-nearest-neighbour matching of detector keypoints through the dense warp.
