@@ -440,6 +440,59 @@ long roma_op_refine_model_workspace(int B, int N);
 int roma_op_refine_model(int model, const double* M, const float* kpts_a, const float* kpts_b, const int* counts,
                          const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_m, unsigned char* out_mask,
                          int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream);
+/* Triangulation under a known relative pose: the depth of every match and its 3-D point - what follows roma_op_recover_pose /
+ * roma_op_refine_pose when the user wants a depth map or a point cloud from a dense warp (or from sample() output).  Restated
+ * operation by operation in numpy float64 by tools/triangulate_ref.py; evaluated in float64 with fp contraction off.
+ * The error model is one-sided, as a dense matcher's is: the pixel on the grid of the REFERENCE image is exact, the predicted
+ * coordinate in the OTHER image carries the error, so the point lies on the reference pixel's ray at the depth whose projection
+ * into the other image is closest to the prediction.  Reference pixel (u, v) with camera K_r, observation (u', v') with camera
+ * K_o, (R, t) mapping reference-frame points to the other frame, cameras applied by fx, fy, cx, cy only:
+ *   x = ((u - cx_r) / fx_r, (v - cy_r) / fy_r, 1), r = R x, A = K_o r (image of the ray's point at infinity), Bv = K_o t (epipole);
+ *   l = A x Bv (epipolar line), n2 = l0^2 + l1^2, s = l0 u' + l1 v' + l2; signed residual d = s / sqrt(n2) in pixels of the other
+ *   image; foot point p = (u', v') - s (l0, l1) / n2;
+ *   a = (p_x A2 - A0, p_y A2 - A1), b = (Bv0 - p_x Bv2, Bv1 - p_y Bv2), z_ref = a.b / a.a, X = z_ref x, z_other = z_ref r2 + t2;
+ *   xh = ((p_x - cx_o) / fx_o, (p_y - cy_o) / fy_o, 1), parallax = atan2(|r x xh|, r . xh) in degrees.
+ * matches DEVICE f32 [B, n, 4], 16-byte aligned: columns 0:2 in image A, 2:4 in image B; coords 0: pixels, 1: normalised [-1, 1]
+ * with pixel = (x + 1) * W / 2 of the image sizes W_a, H_a, W_b, H_b (not read for coords 0).  sym_w 0: every point is
+ * A-reference (columns 0:2 exact, K_r = K_a, K_o = K_b, pose (R, t)).  sym_w = W: the rows are those of a symmetric warp on an
+ * [H, 2W] grid, n a multiple of 2W, and point i is B-reference when i mod 2W >= W: columns 2:4 are the exact grid of image B,
+ * the roles of the cameras swap and the pose is (R^T, -R^T t), formed in the kernel; its X is in camera B's frame.
+ * certainty DEVICE f32 [B, n] or NULL; counts DEVICE int32 [B] or NULL (n); valid DEVICE u8 [B] or NULL (every pair); R DEVICE
+ * f64 [B, 3, 3], t DEVICE f64 [B, 3] (A to B); K_a, K_b DEVICE f64 [B, 3, 3] or NULL (identity).
+ * Outputs, all DEVICE: points f32 [B, n, 3] in the reference camera's frame (points[..., 2] is the depth map); nullable
+ * depth_other, reproj (signed), parallax (degrees) f32 [B, n]; flags u8 [B, n], a point is valid when its byte is 0:
+ *    1 skipped: the row lies at or beyond counts[b], or valid[b] == 0 (inputs of such rows are never read);
+ *    2 degenerate: a non-finite coordinate, pose or camera entry (fx, fy, cx, cy), or not n2 > 0 (the reference pixel is at the
+ *      epipole, or t = 0);
+ *    4 cheirality: not 0 < z_ref < max_depth or not 0 < z_other < max_depth (NaN and a.a = 0 fail by this wording);
+ *    8 not |d| <= max_reproj;   16 not parallax >= min_parallax;   32 certainty given and not certainty >= min_certainty.
+ * A row with bit 1 or 2 carries no other bit and its float outputs are NaN; every other row gets all of its bits and its computed
+ * values.  Nullable stats int32 [B, 2, 8] = {rows considered, valid rows, degenerate, cheirality, reproj, parallax, certainty,
+ * 0} for the A-reference and the B-reference rows (second row zero when sym_w = 0): integer atomics, cleared on the stream by
+ * the same call.  One launch (plus the clear) for the whole batch, no workspace, no host read; bit-identical from run to run and
+ * independent of B and of the order of the pairs.  Refused before anything is enqueued: a null required pointer, B < 0 or
+ * B > 65535, n < 0, B * n >= 2^31, matches not 16-byte aligned, sym_w < 0 or n not a multiple of 2 sym_w, coords = 1 with a
+ * size that is not positive, a negative threshold.  B = 0 or n = 0 returns 0 and launches nothing. */
+int roma_op_triangulate(const float* matches, const float* certainty, const int* counts, const unsigned char* valid, const double* R,
+                        const double* t, const double* K_a, const double* K_b, int B, long n, int coords, int W_a, int H_a, int W_b,
+                        int H_b, int sym_w, double max_depth, double max_reproj, double min_parallax, double min_certainty,
+                        float* out_points, float* out_depth_other, float* out_reproj, float* out_parallax, unsigned char* out_flags,
+                        int* out_stats, void* stream);
+/* Depth consistency of the two halves of a symmetric warp, which triangulate the same surface from both sides - the rule of the
+ * reference's warp_kpts (romatch/utils/utils.py: relative_depth_error_threshold) with triangulated depth in place of sensor
+ * depth.  points, flags: the outputs of a roma_op_triangulate call with sym_w = W on an [H, 2W] grid.  For a valid point with
+ * position X in its own frame: X' = R X + t (A half) or R^T (X - t) (B half); p = (fx X'_x / X'_z + cx, fy X'_y / X'_z + cy) with
+ * the other camera; the other half's grid position by the align_corners=False rule, gx = p_x / W_other * W - 0.5,
+ * gy = p_y / H_other * H - 0.5, x0 = floor(gx), y0 = floor(gy); the point has support only if 0 <= x0, x0 + 1 <= W - 1, 0 <= y0,
+ * y0 + 1 <= H - 1 and its four neighbours in the other half are valid (stricter than zero padding, on purpose); v = the bilinear
+ * interpolation of their z_ref (f32 depths, f64 arithmetic: (d00 (1 - fx) + d01 fx) (1 - fy) + (d10 (1 - fx) + d11 fx) fy);
+ * err = |v - X'_z| / v.  consistent DEVICE u8 [B, H, 2W]: 1 err < rel_thresh, 0 otherwise, 2 no support or the point itself is not
+ * valid; nullable err DEVICE f32 [B, H, 2W], NaN where there is no support.  R, t, K_a, K_b as for roma_op_triangulate.  One
+ * launch, no workspace, no host read.  Refused before anything is enqueued: a null required pointer, B < 0 or B > 65535, negative
+ * H or W, B * H * 2W >= 2^31, an image size that is not positive, a negative rel_thresh.  B, H or W = 0 launches nothing. */
+int roma_op_depth_consistency(const float* points, const unsigned char* flags, const double* R, const double* t, const double* K_a,
+                              const double* K_b, int W_a, int H_a, int W_b, int H_b, int B, int H, int W, double rel_thresh,
+                              unsigned char* out_consistent, float* out_err, void* stream);
 /* ---- Tiny RoMa (romatch/models/tiny.py), matcher side; the XFeat backbone is the caller's (model_zoo/__init__.py:24-27).
  * All tensors f32, channels-last unless noted.  corr_volume (tiny.py:182-196) = roma_op_gemm with A = feats of image B
  * [H1*W1, C], W = feats of image A [H0*W0, C], alpha = 1/sqrt(C), batch = pairs: cv [B, H1*W1, H0*W0]. */

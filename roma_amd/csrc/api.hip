@@ -27,6 +27,7 @@
 #include "model_refine.h"
 #include "pose_refine.h"
 #include "geometry.h"
+#include "triangulate.h"
 
 namespace roma {
 static thread_local std::string g_err;
@@ -583,6 +584,22 @@ int roma_op_refine_model(int model, const double* M, const float* kpts_a, const 
                          int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream) {
   return refine_model_launch(model, M, kpts_a, kpts_b, counts, valid, B, N, thr, max_steps, out_m, out_mask, out_info, out_cost,
                              workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+// ---- triangulation and depth consistency (triangulate.hip)
+int roma_op_triangulate(const float* matches, const float* certainty, const int* counts, const unsigned char* valid, const double* R,
+                        const double* t, const double* K_a, const double* K_b, int B, long n, int coords, int W_a, int H_a, int W_b,
+                        int H_b, int sym_w, double max_depth, double max_reproj, double min_parallax, double min_certainty,
+                        float* out_points, float* out_depth_other, float* out_reproj, float* out_parallax, unsigned char* out_flags,
+                        int* out_stats, void* stream) {
+  return triangulate_launch(matches, certainty, counts, valid, R, t, K_a, K_b, B, n, coords, W_a, H_a, W_b, H_b, sym_w, max_depth,
+                            max_reproj, min_parallax, min_certainty, out_points, out_depth_other, out_reproj, out_parallax, out_flags,
+                            out_stats, S(stream));
+}
+int roma_op_depth_consistency(const float* points, const unsigned char* flags, const double* R, const double* t, const double* K_a,
+                              const double* K_b, int W_a, int H_a, int W_b, int H_b, int B, int H, int W, double rel_thresh,
+                              unsigned char* out_consistent, float* out_err, void* stream) {
+  return depth_consistency_launch(points, flags, R, t, K_a, K_b, W_a, H_a, W_b, H_b, B, H, W, rel_thresh, out_consistent, out_err,
+                                  S(stream));
 }
 // ---- Tiny RoMa matcher side (tiny.hip)
 int roma_op_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, void* stream) {

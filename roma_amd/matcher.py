@@ -471,6 +471,18 @@ class RegressionMatcher:
         return sample_matches(matches, certainty, num=num, sample_mode=self.sample_mode, sample_thresh=self.sample_thresh,
                               seed=seed, **kw)
 
+    def triangulate_warp(self, warp, certainty, R, t, K_A, K_B, H_A, W_A, H_B=None, W_B=None, **kw):
+        """Depth maps and point clouds of this matcher's warp under a relative pose (`roma_amd.triangulate_warp` with this
+        matcher's `symmetric`; see there for the arguments and what is returned) - the link after the pose:
+
+            R, t, mask, ok = roma_amd.estimate_pose(kpts_A, kpts_B, K_A, K_B, norm_thresh, counts=counts)
+            tri = model.triangulate_warp(warp, certainty, R, t, K_A, K_B, H_A, W_A, H_B, W_B, valid=ok, consistency=True)
+            depth_A, keep_A = tri.depth_A, tri.valid_A & (tri.consistent_A == 1)
+        """
+        from .triangulation import triangulate_warp
+        kw.setdefault("symmetric", bool(self.symmetric))
+        return triangulate_warp(warp, certainty, R, t, K_A, K_B, H_A, W_A, H_B, W_B, **kw)
+
     # ------------------------------------------------------------------ keypoint matching (matcher.py:732-773)
     def match_keypoints(self, x_A, x_B, warp, certainty, return_tuple=True, return_inds=False, max_dist=0.005, cert_th=0):
         """Mutual-nearest-neighbour matching of detector keypoints through the dense warp.
