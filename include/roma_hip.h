@@ -193,6 +193,13 @@ int roma_op_local_corr(const void* feature0, const void* feature1, const float* 
  * result (1/sqrt(C) when feature0 is not pre-scaled); out row stride ldo >= K. */
 int roma_op_local_corr_window(const void* feature0, const void* feature1, const float* warp, void* out, int B, int H,
                               int W, int C, int radius, float scale, long ldo, int dt_in, int dt_out, void* stream);
+/* The same operator on caller-owned device scratch (the plain entry allocates stream-ordered scratch per call): ws holds at
+ * least roma_op_local_corr_window_workspace(B, H, W, radius) bytes - 0 for the radii that need none: ws may then be
+ * NULL - and needs no initialisation: the call writes every word it reads. */
+long roma_op_local_corr_window_workspace(int B, int H, int W, int radius);
+int roma_op_local_corr_window_ws(const void* feature0, const void* feature1, const float* warp, void* out, int B, int H,
+                                 int W, int C, int radius, float scale, long ldo, int dt_in, int dt_out, void* ws,
+                                 long ws_bytes, void* stream);
 
 /* C[M,N] = act(A[M,K] W[N,K]^T + bias) * scale + res   (batched with element strides; any pointer may be NULL) */
 int roma_op_gemm(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, int batch,

@@ -337,6 +337,27 @@ int roma_op_local_corr_window(const void* feature0, const void* feature1, const 
   return local_corr_window_launch(a, S(stream));
 }
 
+long roma_op_local_corr_window_workspace(int B, int H, int W, int radius) {
+  if (B <= 0 || H <= 0 || W <= 0) return 0;
+  return local_corr_ws_ints(B, H, W, radius) * (long)sizeof(int);
+}
+
+int roma_op_local_corr_window_ws(const void* feature0, const void* feature1, const float* warp, void* out, int B, int H,
+                                 int W, int C, int radius, float scale, long ldo, int dt_in, int dt_out, void* ws,
+                                 long ws_bytes, void* stream) {
+  LocalCorrArgs a;
+  a.f0 = feature0; a.f1 = feature1; a.warp = warp; a.out = out; a.B = B; a.H = H; a.W = W; a.C = C; a.radius = radius;
+  a.ld0 = C; a.ld1 = C; a.ldo = ldo; a.nimg = B; a.f1_shift = 0; a.scale = scale; a.in_dt = DT(dt_in); a.out_dt = DT(dt_out);
+  a.ws = static_cast<int*>(ws); a.ws_bytes = ws_bytes;
+  ROMA_REQUIRE(ldo >= (2 * radius + 1) * (2 * radius + 1), "local_corr_window: ldo < K");
+  if (roma_op_local_corr_window_workspace(B, H, W, radius) == 0) {  // a radius that needs no scratch: ws may be NULL
+    a.ws = nullptr; a.ws_bytes = 0;
+  } else {
+    ROMA_REQUIRE(ws && (reinterpret_cast<uintptr_t>(ws) & 3) == 0, "local_corr_window_ws: ws must be a 4-byte aligned device pointer");
+  }
+  return local_corr_window_launch(a, S(stream));
+}
+
 int roma_op_gemm(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, int batch,
                  long sA, long sW, long sC, const float* bias, const float* scale, const float* res, long ldr, int act,
                  float alpha, int dt_in, int dt_out, void* stream) {

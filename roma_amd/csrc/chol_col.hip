@@ -21,6 +21,8 @@
 //     factorisation - no hand-off at all.  Alone 2.62 -> 2.14 ms per solve, but with both sub-batch streams inside the chain
 //     (the benchmark's regime) 3.0 -> 3.4 ms: 512 workgroups x 4 waves of redundant f32 MFMA work, two per CU.  That form is
 //     what column 0 still runs (its T is A[S, S] itself - nothing to recompute) and what the time-out path falls back to.
+//   * look-ahead: the leader's own k-slab product sat in front of every factorisation; all but its last slab is now formed one
+//     launch earlier by an extra workgroup (see the kernel) - same operands, same order, bit-identical results.
 // Inside a workgroup (4 waves): 32 x 32 tiles on v_mfma_f32_32x32x2_f32 (exact f32), operands straight from L2 into
 // registers (lane (i, kk) holds row i, columns 32 kk + [0, 32) of a 64-deep slab: both operands use the same k pairing, so
 // no LDS staging and no barrier in the K loop), slabs double buffered; the product with Linv^T takes its operands from LDS;
@@ -30,7 +32,6 @@
 // to rounding, not bit for bit (tests/test_gpu_ops.py::test_cholesky_solve*).
 #include "chol_diag.h"
 #include "elementwise.h"
-#include "tuning.h"
 
 namespace roma {
 
@@ -50,24 +51,23 @@ __device__ __forceinline__ f32x16 cc_mfma(const CFrag& a, const CFrag& b, f32x16
     for (int u = 0; u < 4; ++u) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.v[q][u], b.v[q][u], acc, 0, 0, 0);
   return acc;
 }
-// one 32 x 32 tile of  sum_{t < k} X[rows pa][slab t] . Y[rows pb][slab t]^T ;  pa / pb: this lane's row, column 32 kk
-__device__ __forceinline__ f32x16 cc_tile_product(const float* pa, const float* pb, int k) {
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+// one 32 x 32 tile of  acc + sum_{t0 <= t < t1} X[rows pa][slab t] . Y[rows pb][slab t]^T ;  pa / pb: this lane's row, column
+// 32 kk.  The slabs enter the accumulator in ascending order whatever t0 is: a sum cut at a slab boundary and resumed from the
+// stored accumulator gives the bits of the uncut one (the look-ahead below).
+__device__ __forceinline__ f32x16 cc_tile_product(const float* pa, const float* pb, int t0, int t1, f32x16 acc) {
   CFrag a0, b0, a1, b1;
-  if (k > 0) {
-    cc_load(a0, pa);
-    cc_load(b0, pb);
+  if (t0 < t1) {
+    cc_load(a0, pa + 64 * t0);
+    cc_load(b0, pb + 64 * t0);
   }
-  for (int t = 0; t < k; t += 2) {
-    if (t + 1 < k) {
+  for (int t = t0; t < t1; t += 2) {
+    if (t + 1 < t1) {
       cc_load(a1, pa + 64 * (t + 1));
       cc_load(b1, pb + 64 * (t + 1));
     }
     acc = cc_mfma(a0, b0, acc);
-    if (t + 1 < k) {
-      if (t + 2 < k) {
+    if (t + 1 < t1) {
+      if (t + 2 < t1) {
         cc_load(a0, pa + 64 * (t + 2));
         cc_load(b0, pb + 64 * (t + 2));
       }
@@ -76,6 +76,16 @@ __device__ __forceinline__ f32x16 cc_tile_product(const float* pa, const float* 
   }
   return acc;
 }
+__device__ __forceinline__ f32x16 cc_zero() {
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+  return acc;
+}
+
+// look-ahead flags of a launch (chol_col_launch)
+constexpr int CC_LA_PARK = 1;     // the last workgroup of every image parks the leader's accumulators of column k + 1
+constexpr int CC_LA_CONSUME = 2;  // the leader starts from the accumulators the previous launch parked
 
 constexpr int CC_POLLS = 2000;  // x (relaxed L2 load + s_sleep 8): ~0.5 ms before a follower gives up on its leader
 
@@ -84,7 +94,7 @@ constexpr int CC_POLLS = 2000;  // x (relaxed L2 load + s_sleep 8): ~0.5 ms befo
 __global__ __launch_bounds__(256, 2) void chol_col_kernel(float* __restrict__ A, long ld, long strideA, float* __restrict__ LTm,
                                                           long strideLT, int n, float* __restrict__ Linv,
                                                           float* __restrict__ LinvT, int k, int nblk, unsigned epoch,
-                                                          int use_leader) {
+                                                          int use_leader, int lookahead) {
   constexpr int S = CHOL_S;
   __shared__ __attribute__((aligned(16))) float L[64 * S];
   __shared__ __attribute__((aligned(16))) float LT[64 * S];
@@ -115,11 +125,28 @@ __global__ __launch_bounds__(256, 2) void chol_col_kernel(float* __restrict__ A,
   }
   const int ti = wave >> 1, tj = wave & 1;  // this wave's 32 x 32 tile of a 64 x 64 product
 
+  // ---- look-ahead: the leader's product is on the critical path of its column (k dependent slabs in front of the
+  // factorisation, everybody else polling), yet all of it but the last slab is known one launch earlier.  So the last
+  // workgroup of an image in the launch of column k forms  sum_{t < k} L[S', t] L[S', t]^T  for S' = the rows of column k + 1 -
+  // slabs written by the launches before this one - and parks the four raw accumulator tiles in block k + 1 of the image's
+  // Linv table: 4096 floats that nothing reads until the leader of the next launch has taken them and overwrites them with
+  // the inverse.  The hand-off is stream order between two launches: no flag, no wait.
+  if ((lookahead & CC_LA_PARK) && blockIdx.x == gridDim.x - 1) {
+    const long S1 = S0 + 64;
+    const float* pa = Ai + (S1 + 32 * ti + l31) * ld + 32 * kk;
+    const float* pb = Ai + (S1 + 32 * tj + l31) * ld + 32 * kk;
+    const f32x16 acc = cc_tile_product(pa, pb, 0, k, cc_zero());
+    float* park = Li + 4096 + wave * 1024 + lane;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) park[64 * r] = acc[r];
+    return;
+  }
+
   // ---- followers (and the redundant form): P = A[R, S] - sum_t L[R, t] L[S, t]^T, one tile per wave -> LDS
   if (!leader) {
     const float* pa = Ai + (R0 + 32 * ti + l31) * ld + 32 * kk;
     const float* pb = Ai + (S0 + 32 * tj + l31) * ld + 32 * kk;
-    const f32x16 acc = cc_tile_product(pa, pb, k);
+    const f32x16 acc = cc_tile_product(pa, pb, 0, k, cc_zero());
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = 32 * ti + (r & 3) + 8 * (r >> 2) + 4 * kk, col = 32 * tj + l31;
@@ -155,7 +182,17 @@ __global__ __launch_bounds__(256, 2) void chol_col_kernel(float* __restrict__ A,
   if (!have_inverse) {
     const float* pa = Ai + (S0 + 32 * ti + l31) * ld + 32 * kk;
     const float* pb = Ai + (S0 + 32 * tj + l31) * ld + 32 * kk;
-    const f32x16 acc = cc_tile_product(pa, pb, k);
+    // the leader resumes from what the previous launch parked and runs the last slab only; the redundant and time-out forms
+    // keep the whole product
+    int t0 = 0;
+    f32x16 acc = cc_zero();
+    if (leader && (lookahead & CC_LA_CONSUME)) {
+      const float* park = Li + wave * 1024 + lane;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = park[64 * r];
+      t0 = k - 1;
+    }
+    acc = cc_tile_product(pa, pb, t0, k, acc);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = 32 * ti + (r & 3) + 8 * (r >> 2) + 4 * kk, col = 32 * tj + l31;
@@ -234,16 +271,20 @@ __global__ __launch_bounds__(256) void chol_col_restore_kernel(float* __restrict
 }
 
 // Block column k of the augmented system: A [batch][(n + d) x n] (ld = n), LT [batch][n x n].  `epoch`: any value that differs
-// between consecutive solves on the same buffers (cholesky_solve_t counts its calls).
+// between consecutive solves on the same buffers (cholesky_solve_t counts its calls).  `use_leader`: the value of the
+// gp_col_leader switch, read ONCE per solve by the caller - launch k consumes what launch k - 1 parked, so the columns of a
+// chain must agree on it: 1 = leader + followers, the leader's product one launch ahead; 2 = leader + followers, the leader
+// forms its whole product; 0 = every workgroup factorises its own copy.
 int chol_col_launch(float* A, long ld, long strideA, float* LT, long strideLT, int n, int d, float* Linv, float* LinvT, int k,
-                    int nblk, int batch, unsigned epoch, hipStream_t s) {
+                    int nblk, int batch, unsigned epoch, int use_leader, hipStream_t s) {
   ROMA_REQUIRE(n % 64 == 0 && d % 64 == 0 && d >= 64 && ld % 4 == 0 && LT, "chol_col: n, d multiples of 64, d >= 64, ld of 4, LT");
   const int nrb = (n + d) / 64 - (k + 1);
   ROMA_REQUIRE(nrb >= 1 && k < nblk, "chol_col: no row block below the column");
-  const int use_leader = tuning(SW_GP_COL_LEADER);  // 1 = leader + followers, 0 = every workgroup factorises its own copy
-  const int gx = nrb + ((use_leader && k > 0) ? 1 : 0);
+  // column k consumes what launch k - 1 parked (k >= 2: column 1 has the one slab launch 0 writes); launch k parks for k + 1
+  const int lookahead = use_leader != 1 ? 0 : (k >= 2 ? CC_LA_CONSUME : 0) | (k >= 1 && k + 1 < nblk ? CC_LA_PARK : 0);
+  const int gx = nrb + ((use_leader && k > 0) ? 1 : 0) + ((lookahead & CC_LA_PARK) ? 1 : 0);
   hipLaunchKernelGGL(chol_col_kernel, dim3((unsigned)gx, (unsigned)batch), dim3(256), 0, s, A, ld, strideA, LT, strideLT, n, Linv,
-                     LinvT, k, nblk, epoch & 0xffffffu, use_leader);
+                     LinvT, k, nblk, epoch & 0xffffffu, use_leader, lookahead);
   ROMA_LAUNCH_CHECK();
   return 0;
 }

@@ -56,9 +56,10 @@ int chol_diag_launch(float* A, long ld, long strideA, float* Linv, float* LinvT,
 // Round 6 (chol_col.hip): block column k of the left-looking factorisation of the augmented system A [batch][(n + d) x n]
 // (ld floats per row): L[R, S_k] for every row block R below the diagonal block incl. the d right-hand-side rows, the inverse
 // tables of block k, LT[S_k, R] = L[R, S_k]^T.  The factor's diagonal blocks travel in LT's diagonal blocks until
-// chol_col_restore_launch copies them into A (behind the last column).
+// chol_col_restore_launch copies them into A (behind the last column).  use_leader: the gp_col_leader switch, one value for
+// all columns of a solve.
 int chol_col_launch(float* A, long ld, long strideA, float* LT, long strideLT, int n, int d, float* Linv, float* LinvT, int k,
-                    int nblk, int batch, unsigned epoch, hipStream_t s);
+                    int nblk, int batch, unsigned epoch, int use_leader, hipStream_t s);
 int chol_col_restore_launch(float* A, long ld, long strideA, const float* LT, long strideLT, int n, int batch, hipStream_t s);
 
 // pad the trailing (npad - n) diagonal of a Gram matrix with identity and zero its off-diagonals

@@ -23,13 +23,18 @@ struct LocalCorrArgs {
   // window form: device scratch for the tile work list, (2 * tiles + 4) ints with tiles = B * ceil(H/8) * ceil(W/8); nullptr =
   // allocate stream-ordered scratch for the call.  force_gather is set by the launcher (tuning switch).
   // Round 6: the queries of incoherent tiles are sorted into bins of f1 (local_corr.hip, LIST form of the tile kernel); the scratch
-  // then also holds the bin counters and the sorted query list: local_corr_ws_ints(B, H, W, radius) ints in all.
+  // then also holds the bin counters, the sorted query list, a class per tile and the band histograms of the sort:
+  // local_corr_ws_ints(B, H, W, radius) ints in all.
   int* ws = nullptr;
   long ws_bytes = 0;
   int force_gather = 0;
   int pxmax = 0;               // set by the launcher: largest rectangle (pixels) the tile kernel's LDS stage holds
   // set by the launcher: bin geometry and the offsets (in ints) of the bin tables / the sorted query list inside ws
   int bin_ts = 0, bin_nx = 0, bin_ny = 0, ws_bins = 0, ws_qlist = 0;
+  // set by the launcher, LDS counting sort of the incoherent queries: bands of tile rows per image (0 = the device-atomic
+  // sort) and the offsets of the tile classes [tiles] and the band histograms [B][bands][bins per image] inside ws
+  int sort_bands = 0;
+  long ws_tclass = 0, ws_hist = 0;
 };
 
 // ints of device scratch local_corr_window_launch needs for this problem (window form, tiled radii 2 / 3 / 7; 0 otherwise)

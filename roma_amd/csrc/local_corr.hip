@@ -584,6 +584,8 @@ __global__ __launch_bounds__(64) void local_corr_classify_kernel(const LocalCorr
   if (valid) {
     if (coherent) a.ws[4 + tiles + basec + __popcll(mc & below)] = tile;
     else a.ws[4 + baseg + __popcll(mg & below)] = tile;
+    // the LDS sort walks the image in tile order (local_corr_sort_kernel): it wants the class of a tile, not the list
+    if (a.sort_bands) a.ws[a.ws_tclass + tile] = coherent ? 1 : 0;
   }
 }
 
@@ -596,14 +598,18 @@ __global__ __launch_bounds__(64) void local_corr_classify_kernel(const LocalCorr
 // one bin);  ws + ws_qlist: items x 64 global pixel indices, -1 = padding (memset by the launcher).
 // The order of the queries inside a bin depends on the atomics' arrival order; the RESULT of a query does not (its dot
 // products are evaluated per (slot, query) with a fixed channel order whatever the item looks like).
-template <int R> __device__ __forceinline__ int lc_bin_of(const LocalCorrArgs& a, long pix, int b) {
+// bin of a query inside its image, from its warp (wx, wy)
+template <int R> __device__ __forceinline__ int lc_bin_in_image(const LocalCorrArgs& a, float wx, float wy) {
   constexpr int P = 2 * R + 2;
   int x0, y0;
   float fx, fy;
-  unnormalize_floor(a.warp[pix * 2 + 0], a.W, x0, fx);
-  unnormalize_floor(a.warp[pix * 2 + 1], a.H, y0, fy);
+  unnormalize_floor(wx, a.W, x0, fx);
+  unnormalize_floor(wy, a.H, y0, fy);
   const int ox = min(max(x0 - R, -P), a.W), oy = min(max(y0 - R, -P), a.H);
-  return (b * a.bin_ny + (oy + P) / a.bin_ts) * a.bin_nx + (ox + P) / a.bin_ts;
+  return ((oy + P) / a.bin_ts) * a.bin_nx + (ox + P) / a.bin_ts;
+}
+template <int R> __device__ __forceinline__ int lc_bin_of(const LocalCorrArgs& a, long pix, int b) {
+  return b * a.bin_ny * a.bin_nx + lc_bin_in_image<R>(a, a.warp[pix * 2 + 0], a.warp[pix * 2 + 1]);
 }
 
 // grid: one 64-thread workgroup per gather-list tile (the launch covers every tile of the call; surplus workgroups exit)
@@ -633,16 +639,122 @@ __global__ __launch_bounds__(64) void local_corr_bin_kernel(const LocalCorrArgs 
   }
 }
 
-// one workgroup: items per bin = ceil(count / 64), exclusive scan -> first item of every bin, total -> ws[2]
+// ---------------------------------------------------------------------------------------------------------------
+// The same sort without device-scope atomics (lc_bin = 1; the kernels above are lc_bin = 2 and the fallback).  The two
+// passes above issue one device-scope atomic per query on counters spread over a few thousand words - 750 K atomics in
+// 110 + 93 us at r = 2, 16 x 216^2, i.e. ~7 / ns whatever the occupancy (profiles/r06_v40_lc_bin_4waves_rejected.log) - and
+// need the bin table and the whole item list memset in front.  The bins of one image are few (<= 361 at the model's shapes),
+// so the counters fit LDS:
+//   count  grid (band, image): a workgroup owns a band of tile rows of one image, walks its tiles in tile order (a class flag
+//          per tile, written by the classifier; coherent tiles cost that one read), counts its queries per bin with LDS
+//          atomics and writes hist[image][band][bin] with plain stores - every entry, zeros included;
+//   scan   the one-workgroup scan below sums the bands of every bin first: count and first item of every bin, ws[2];
+//   place  same grid: the LDS counters start at the first slot of (bin, band) - 64 x the bin's first item + the counts of the
+//          earlier bands - and every query takes the next slot of its bin.  Band 0 also writes the -1 padding behind each
+//          bin's last query, so every slot of items [0, ws[2]) is written exactly once and nothing needs a memset.
+// No workgroup waits for another one of its launch; stream order between the three launches is the only ordering.  The order
+// of the queries inside (bin, band) depends on the LDS atomics' arrival order, the results do not (see above).
+constexpr int LC_SORT_MAXBINS = 1024;  // LDS counters of a workgroup = bins per image the sort takes
+constexpr int LC_SORT_MAXBANDS = 16;   // the band counts of a bin are read as one unrolled batch of loads
+constexpr int LC_SORT_NTHR = 1024;
+constexpr int LC_SORT_U = 4;           // tiles in flight per wave: class reads, then warp reads, then LDS atomics
+// bands per image: ~128 workgroups per launch at the model's batch, at least two tile rows per band (a workgroup's fixed cost
+// is one pass over the image's bin table)
+static inline int lc_sort_bands(int B, int tiles_y) {
+  return std::max(1, std::min(std::min((128 + B - 1) / B, LC_SORT_MAXBANDS), (tiles_y + 1) / 2));
+}
+
+template <int R, bool PLACE>
+__global__ __launch_bounds__(LC_SORT_NTHR) void local_corr_sort_kernel(const LocalCorrArgs a) {
+  __shared__ int tbl[LC_SORT_MAXBINS];
+  if (a.ws[0] == 0) return;  // no incoherent tile in this call (workgroup-uniform): the scan leaves ws[2] = 0
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int NW = LC_SORT_NTHR / 64;
+  const int g = blockIdx.x, G = gridDim.x, b = blockIdx.y;
+  const int tiles_x = (a.W + LC_TQ - 1) / LC_TQ, tiles_y = (a.H + LC_TQ - 1) / LC_TQ;
+  const int tpi = tiles_x * tiles_y;
+  const int nb = a.bin_nx * a.bin_ny, nbins = a.B * nb;
+  const long HW = (long)a.H * a.W;
+  int* hist = a.ws + a.ws_hist + (long)b * G * nb;  // [band][bin] of this image
+  int* ql = a.ws + a.ws_qlist;
+  const int* cnt = a.ws + a.ws_bins + (long)b * nb;
+  for (int i = tid; i < nb; i += LC_SORT_NTHR) {
+    int start = 0;
+    if constexpr (PLACE) {
+      // first slot of (bin, band): the bin's first item, then the queries the earlier bands put into the bin
+      const int first = cnt[nbins + i];
+#pragma unroll
+      for (int q = 0; q < LC_SORT_MAXBANDS; ++q) start += q < g ? hist[q * nb + i] : 0;
+      start += first * 64;
+      if (g == 0) {  // band 0 also pads the bin: slots [count, 64 * items) behind its first slot
+        const int c = cnt[i];
+        for (int s = c; s < ((c + 63) & ~63); ++s) ql[(long)first * 64 + s] = -1;
+      }
+    }
+    tbl[i] = start;
+  }
+  __syncthreads();
+  const int* tclass = a.ws + a.ws_tclass + (long)b * tpi;
+  const float2* warp = reinterpret_cast<const float2*>(a.warp) + (long)b * HW;
+  const int t1 = ((g + 1) * tiles_y / G) * tiles_x;  // tiles [t0, t1) of the image: the band's tile rows
+  for (int tb = (g * tiles_y / G) * tiles_x + wave; tb < t1; tb += NW * LC_SORT_U) {
+    int qp[LC_SORT_U];  // this lane's query of tile tb + NW u as a pixel of the image, -1: none
+    float2 wv[LC_SORT_U];
+#pragma unroll
+    for (int u = 0; u < LC_SORT_U; ++u) {
+      const int t = tb + NW * u;
+      const bool incoherent = t < t1 && tclass[min(t, t1 - 1)] == 0;
+      const int ty = t / tiles_x, tx = t - ty * tiles_x;
+      const int gy = ty * LC_TQ + (lane >> 3), gx = tx * LC_TQ + (lane & 7);
+      qp[u] = (incoherent && gy < a.H && gx < a.W) ? gy * a.W + gx : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < LC_SORT_U; ++u) wv[u] = warp[max(qp[u], 0)];
+#pragma unroll
+    for (int u = 0; u < LC_SORT_U; ++u) {
+      if (qp[u] >= 0) {
+        const int slot = atomicAdd(&tbl[lc_bin_in_image<R>(a, wv[u].x, wv[u].y)], 1);
+        if constexpr (PLACE) ql[slot] = (int)((long)b * HW + qp[u]);
+      }
+    }
+  }
+  if constexpr (!PLACE) {
+    __syncthreads();
+    for (int i = tid; i < nb; i += LC_SORT_NTHR) hist[g * nb + i] = tbl[i];
+  }
+}
+
+// one workgroup: items per bin = ceil(count / 64), exclusive scan -> first item of every bin, total -> ws[2].  After the LDS
+// sort's count launch (sort_bands > 0) the count of a bin is the sum of its band histograms.
 __global__ __launch_bounds__(1024) void local_corr_bin_scan_kernel(const LocalCorrArgs a) {
   __shared__ int part[1024];
-  const int nbins = a.B * a.bin_nx * a.bin_ny;
+  const int nb = a.bin_nx * a.bin_ny, nbins = a.B * nb;
+  const int G = a.sort_bands;
+  if (G > 0 && a.ws[0] == 0) return;  // nothing was counted; ws[2] = 0 from the launcher's memset of the header
   int* cnt = a.ws + a.ws_bins;
   const int tid = threadIdx.x;
   const int per = (nbins + 1023) / 1024;
   const int i0 = tid * per, i1 = min(i0 + per, nbins);
   int sum = 0;
-  for (int i = i0; i < i1; ++i) sum += (cnt[i] + 63) >> 6;
+  if (G > 0) {
+    // this kernel is one dependent L2 round trip after the other: two bins per trip, all band counts of both in flight at once
+    const auto band_sum = [&](int i) {
+      const int* h = a.ws + a.ws_hist + (long)(i / nb) * G * nb + i % nb;
+      int c = 0;
+#pragma unroll
+      for (int q = 0; q < LC_SORT_MAXBANDS; ++q) c += q < G ? h[(long)q * nb] : 0;
+      return c;
+    };
+    for (int i = i0; i < i1; i += 2) {
+      const int c0 = band_sum(i), c1 = i + 1 < i1 ? band_sum(i + 1) : 0;
+      cnt[i] = c0;
+      if (i + 1 < i1) cnt[i + 1] = c1;
+      sum += ((c0 + 63) >> 6) + ((c1 + 63) >> 6);
+    }
+  } else {
+    for (int i = i0; i < i1; ++i) sum += (cnt[i] + 63) >> 6;
+  }
   part[tid] = sum;
   __syncthreads();
   for (int off = 1; off < 1024; off <<= 1) {  // Hillis-Steele inclusive scan of the 1024 partial sums
@@ -652,9 +764,12 @@ __global__ __launch_bounds__(1024) void local_corr_bin_scan_kernel(const LocalCo
     __syncthreads();
   }
   int run = part[tid] - sum;
-  for (int i = i0; i < i1; ++i) {
+  for (int i = i0; i < i1; i += 2) {  // two bins per round trip here as well
+    const int c0 = cnt[i], c1 = i + 1 < i1 ? cnt[i + 1] : 0;
     cnt[nbins + i] = run;
-    run += (cnt[i] + 63) >> 6;
+    run += (c0 + 63) >> 6;
+    if (i + 1 < i1) cnt[nbins + i + 1] = run;
+    run += (c1 + 63) >> 6;
   }
   if (tid == 1023) a.ws[2] = part[1023];
 }
@@ -760,7 +875,8 @@ long local_corr_ws_ints(int B, int H, int W, int radius) {
   const long tiles = (long)B * ((H + LC_TQ - 1) / LC_TQ) * ((W + LC_TQ - 1) / LC_TQ);
   const int ts = lc_bin_ts(radius), P = 2 * radius + 2;
   const long nbins = (long)B * ((W + P) / ts + 1) * ((H + P) / ts + 1);
-  return 4 + 2 * tiles + 3 * nbins + 64 * (tiles + nbins);
+  // header | two tile lists | bin tables | item list | tile classes | band histograms of the LDS sort
+  return 4 + 2 * tiles + 3 * nbins + 64 * (tiles + nbins) + tiles + lc_sort_bands(B, (H + LC_TQ - 1) / LC_TQ) * nbins;
 }
 
 template <int R, typename T, typename TOUT, bool MFMA>
@@ -774,9 +890,15 @@ static int launch_tiled(const LocalCorrArgs& a0, hipStream_t stream) {
   const long nbins = (long)a.B * a.bin_nx * a.bin_ny;
   a.ws_bins = 4 + 2 * tiles;
   a.ws_qlist = a.ws_bins + 3 * (int)nbins;
-  // lc_bin: 1 = incoherent tiles through the bin-sorted LIST form, 0 = per-query gathers
-  const bool binned = tuning(SW_LC_BIN) != 0 && (long)a.B * a.H * a.W < (1l << 31) &&
+  // lc_bin: 1 / 2 = incoherent tiles through the bin-sorted LIST form, sorted with LDS counters / with device atomics;
+  // 0 = per-query gathers.  The LDS sort needs an image's bins in its LDS table; otherwise the atomic sort takes the call.
+  const int lc_bin = tuning(SW_LC_BIN);
+  const bool binned = lc_bin != 0 && (long)a.B * a.H * a.W < (1l << 31) &&
                       (a.bin_ts + P - 1) * (a.bin_ts + P - 1) <= LcGeom<R, MFMA>::PXMAX;
+  const bool lds_sort = binned && lc_bin == 1 && a.bin_nx * a.bin_ny <= LC_SORT_MAXBINS && 64 * ((long)tiles + nbins) < (1l << 31);
+  a.ws_tclass = a.ws_qlist + 64 * ((long)tiles + nbins);
+  a.ws_hist = a.ws_tclass + tiles;
+  a.sort_bands = lds_sort ? lc_sort_bands(a.B, (a.H + LC_TQ - 1) / LC_TQ) : 0;
   const size_t need = (size_t)local_corr_ws_ints(a.B, a.H, a.W, R) * sizeof(int);
   bool own_ws = false;
   if (!a.ws) {  // operator entry points: stream-ordered scratch (the model passes a slice of its arena)
@@ -807,14 +929,24 @@ static int launch_tiled(const LocalCorrArgs& a0, hipStream_t stream) {
   // at r = 2, 0.96 vs 0.91 at r = 3, profiles/r03_final_visit.log; the variant was removed in round 4.)
   if (binned) {
     // incoherent tiles: sort their queries by target bin, then the LIST form of the tile kernel (one item = <= 64 queries of a bin)
-    ROMA_CHECK_HIP(hipMemsetAsync(a.ws + a.ws_bins, 0, (size_t)3 * nbins * sizeof(int), stream));
-    ROMA_CHECK_HIP(hipMemsetAsync(a.ws + a.ws_qlist, 0xff, (size_t)64 * (tiles + nbins) * sizeof(int), stream));
-    hipLaunchKernelGGL((local_corr_bin_kernel<R, false>), dim3((unsigned)tiles), dim3(64), 0, stream, a);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(local_corr_bin_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL((local_corr_bin_kernel<R, true>), dim3((unsigned)tiles), dim3(64), 0, stream, a);
-    ROMA_LAUNCH_CHECK();
+    if (lds_sort) {
+      const dim3 sgrid((unsigned)a.sort_bands, (unsigned)a.B);
+      hipLaunchKernelGGL((local_corr_sort_kernel<R, false>), sgrid, dim3(LC_SORT_NTHR), 0, stream, a);
+      ROMA_LAUNCH_CHECK();
+      hipLaunchKernelGGL(local_corr_bin_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
+      ROMA_LAUNCH_CHECK();
+      hipLaunchKernelGGL((local_corr_sort_kernel<R, true>), sgrid, dim3(LC_SORT_NTHR), 0, stream, a);
+      ROMA_LAUNCH_CHECK();
+    } else {
+      ROMA_CHECK_HIP(hipMemsetAsync(a.ws + a.ws_bins, 0, (size_t)3 * nbins * sizeof(int), stream));
+      ROMA_CHECK_HIP(hipMemsetAsync(a.ws + a.ws_qlist, 0xff, (size_t)64 * (tiles + nbins) * sizeof(int), stream));
+      hipLaunchKernelGGL((local_corr_bin_kernel<R, false>), dim3((unsigned)tiles), dim3(64), 0, stream, a);
+      ROMA_LAUNCH_CHECK();
+      hipLaunchKernelGGL(local_corr_bin_scan_kernel, dim3(1), dim3(1024), 0, stream, a);
+      ROMA_LAUNCH_CHECK();
+      hipLaunchKernelGGL((local_corr_bin_kernel<R, true>), dim3((unsigned)tiles), dim3(64), 0, stream, a);
+      ROMA_LAUNCH_CHECK();
+    }
     static bool attr_set_l[64] = {false};
     if (dev < 0 || dev >= 64 || !attr_set_l[dev]) {
       ROMA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&local_corr_tile_kernel<R, T, TOUT, MFMA, true>),

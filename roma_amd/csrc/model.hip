@@ -707,8 +707,9 @@ int cholesky_solve_t(float* A, float* Rt, float* LT, float* Linv, float* LinvT, 
   const bool col = aug && tuning(SW_GP_COL) != 0 && d >= 64 && d % 64 == 0;
   static std::atomic<unsigned> solve_epoch{0};  // tags the in-launch hand-off flags of this solve (chol_col.hip)
   const unsigned epoch = col ? ++solve_epoch : 0u;
+  const int col_leader = col ? (int)tuning(SW_GP_COL_LEADER) : 0;  // once per solve: the columns hand work to each other
   for (int k = 0; k < nblk && col; ++k)
-    if (int rc = chol_col_launch(A, n, sA, LT, sLT, n, d, Linv, LinvT, k, nblk, batch, epoch, st)) return rc;
+    if (int rc = chol_col_launch(A, n, sA, LT, sLT, n, d, Linv, LinvT, k, nblk, batch, epoch, col_leader, st)) return rc;
   if (col)
     if (int rc = chol_col_restore_launch(A, n, sA, LT, sLT, n, batch, st)) return rc;
   for (int k = 0; k < nblk && !col; ++k) {

@@ -29,7 +29,7 @@ constexpr Row ROWS[] = {
     {SW_GEMM8P_MAXWG, "gemm8p_maxwg", nullptr, -1, 8, false, "gemm8p, measurement only: cap the persistent grid at n workgroups (a multiple of 8); unset = one per CU"},
     {SW_WS1X1, "ws1x1", "ROMA_WS1X1", 1, 0, false, "N = K = 576 refiner 1x1 on the weight-stationary kernel (1) or on the 256 x 192 tile kernel (0)"},
     {SW_LC_MODE, "lc_mode", "ROMA_LC_MODE", 0, 0, false, "local correlation: 0 tiled form + gather work list, 1 every tile on the gather list (key only), 2 per-pixel kernel"},
-    {SW_LC_BIN, "lc_bin", "ROMA_LC_BIN", 1, 0, false, "local correlation: queries of incoherent tiles sorted by target bin (1) or gathered per query (0)"},
+    {SW_LC_BIN, "lc_bin", "ROMA_LC_BIN", 1, 0, false, "local correlation: queries of incoherent tiles sorted by target bin, counters in LDS (1) or device atomics (2), or gathered per query (0)"},
     {SW_CONV64, "conv64", "ROMA_CONV64", 7, 0, false, "weight-stationary VGG front end, bit mask: 1 the Cin = 64 kernels, 2 the Cin = 128 kernel, 4 the fused first layer"},
     {SW_CONV_PATCH, "conv_patch", "ROMA_CONV_PATCH", 1, 0, false, "patch-resident 3x3 kernel for slab-major VGG layers (1) or gemm8p (0); environment 0 also packs tap-major weights"},
     {SW_ATTN_XCD, "attn_xcd", "ROMA_ATTN_XCD", 1, 0, false, "attention work items in per-XCD bands of (batch, head) (1) or in plain order (0)"},
@@ -40,7 +40,7 @@ constexpr Row ROWS[] = {
     {SW_DW_RING, "dw_ring", "ROMA_DW_RING", 1, 0, false, "depthwise 5x5: 0 register-prefetch kernel, 1 ring kernel for the large launches, 2 ring kernel for every shape it takes"},
     {SW_GP_COL, "gp_col", "ROMA_GP_COL", 1, 0, false, "GP Cholesky left-looking, one launch per block column (1) or the right-looking launch chain (0)"},
     {SW_POOL_PROJ, "pool_proj", "ROMA_POOL_PROJ", 1, 0, false, "max-pool + proj head of strides 1 / 2 in one pass (1) or as separate kernels (0)"},
-    {SW_GP_COL_LEADER, "gp_col_leader", "ROMA_GP_COL_LEADER", 1, 0, false, "block-column Cholesky: one leader workgroup factorises the diagonal block (1) or every workgroup its own copy (0)"},
+    {SW_GP_COL_LEADER, "gp_col_leader", "ROMA_GP_COL_LEADER", 1, 0, false, "block-column Cholesky: a leader workgroup factorises the diagonal block, its product formed one launch ahead (1) or in its own launch (2), or every workgroup its own copy (0)"},
     {SW_GEMM8P_MINM, nullptr, "ROMA_GEMM8P_MINM", 2048, 0, false, "gemm8p: smallest M it takes for the wide (N >= 2048) dense launches"},
     {SW_GEMM_NT, nullptr, "ROMA_GEMM_NT", 1, 0, false, "non-temporal output stores in the 16-bit GEMM row writer"},
     {SW_GEMM_F32_FILL, nullptr, "ROMA_GEMM_F32_FILL", 1, 0, false, "exact-f32 GEMMs below 192 tiles of 256 x 256 run on 128 x 128 tiles"},

@@ -50,10 +50,20 @@ def main():
             e1.record(st)
         return e0, e1
 
-    for col, leader in ((0, 1), (1, 0), (1, 1), (0, 1), (1, 0), (1, 1)):
+    # leader: 0 every workgroup its own copy of the diagonal block, 2 leader + followers, 1 the same with the leader's product
+    # formed one launch ahead (the default)
+    settings = ((0, 1), (1, 0), (1, 2), (1, 1), (0, 1), (1, 0), (1, 2), (1, 1))
+    stream_counts = (1, 2)
+    # `bench_gp.py 1:2 streams=1`: only gp_col = 1, gp_col_leader = 2 on one stream (a kernel trace of one setting, e.g. for
+    # tools/latency_chains_trace.py)
+    picked = [tuple(int(x) for x in a.split(":")) for a in sys.argv[1:] if ":" in a]
+    for a in sys.argv[1:]:
+        if a.startswith("streams="):
+            stream_counts = (int(a.split("=")[1]),)
+    for col, leader in picked or settings:
         assert lib.roma_tuning(b"gp_col", col) == 0
         assert lib.roma_tuning(b"gp_col_leader", leader) == 0
-        for nst in (1, 2):
+        for nst in stream_counts:
             for _ in range(2):
                 for i in range(nst):
                     solve(i)
