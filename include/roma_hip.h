@@ -171,7 +171,7 @@ int roma_destroy(roma_handle_t h);
  * "attn_exp2" assumes q pre-scaled by log2 e and the "gemm_dbg" experiment bits produce wrong outputs by design. */
 int roma_tuning(const char* key, int value);
 /* The switch table as a JSON array, one object per row in table order: {"key": str | null, "env": str | null, "default": n,
- * "override": n | null, "value": n, "tools_only_env": bool, "doc": str}; "value" is what a launch would see now.  Size query
+ * "override": n | null, "value": n, "doc": str}; "value" is what a launch would see now.  Size query
  * as roma_profile_report (buf == NULL: bytes needed).  Touches no device; each library describes its own table. */
 long roma_tuning_describe(char* buf, long nbytes);
 /* measuring tool (tools/bench_gemm_ablation.py): after a GEMM launched with the "gemm_dbg" trace bit (32768), copies the
@@ -259,8 +259,8 @@ int roma_op_refiner_input(const void* feat, long ldf, const float* flow, void* d
 int roma_op_dwconv5x5(const void* in, void* out, const float* w, const float* bias, int B, int H, int W, int Cp, int dt,
                       void* stream);
 /* One fused ConvRefiner block (matcher.py:88-117 create_block): out = conv1x1(relu(bn(dwconv5x5(in)))), BN folded into
- * dw_w/dw_b.  bf16 only, Cp in {24, 144} (narrow scales) or 576 (round 5: the stride-4 scale, all output channels per
- * workgroup); in/out [B,H,W,Cp] must not alias; pw bf16 [Cp][Cp], pw_b f32 [Cp]. */
+ * dw_w/dw_b.  bf16 only, Cp in {24, 144} (the narrow scales); in/out [B,H,W,Cp] must not alias; pw bf16 [Cp][Cp],
+ * pw_b f32 [Cp]. */
 int roma_op_refiner_block(const void* in, void* out, const float* dw_w, const float* dw_b, const void* pw,
                           const float* pw_b, int B, int H, int W, int Cp, int dt, void* stream);
 /* The LAST block of a narrow ConvRefiner with its 1x1 composed with out_conv (two linear maps back to back, matcher.py:92-122,

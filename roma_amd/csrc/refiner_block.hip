@@ -1,17 +1,16 @@
-// Fused depthwise-5x5 (+folded BN, ReLU) -> 1x1 convolution for the narrow ConvRefiner scales.  See refiner_block.h.
+// Fused depthwise-5x5 (+folded BN, ReLU) -> 1x1 convolution for the stride-2 ConvRefiner (C = 144).  See refiner_block.h.
+// (C = 24 runs on the wave-private kernel of refiner_block24w.hip; refiner_block_launch below dispatches.)
 //
-// One 256-thread workgroup owns a strip of SY image rows x PX pixels and all CP channels:
+// One 256-thread workgroup owns a strip of SY image rows x PX = 28 pixels and all 144 channels:
 //   * depthwise phase: the rolling-window stencil of dwconv5x5_kernel (elementwise.hip) - one thread = 4 channels x
-//     4 x-positions, each input row loaded once and fed to the 5 output rows it touches (v_pk_fma_f32), next input
-//     row prefetched.  The finished output row (after ReLU) is packed to bf16 into an LDS tile Xt[row][px][k]
-//     (80 / 304 byte pixel rows: conflict-free for the 16-byte MFMA fragment reads) instead of HBM;
-//   * every R = 2 output rows: barrier, the 4 waves run out[ch][px] = Wpw[ch][:] . Xt[px][:] on
-//     v_mfma_f32_32x32x16_bf16 (channels on the MFMA "i" side, so every lane ends up with 4 consecutive channels of
-//     one pixel), add the bias, pack to bf16 into a contiguous LDS image of the output rows, barrier, and the whole
-//     workgroup streams those rows to HBM with 16-byte lane-contiguous stores (a row segment PX*CP*2 B is contiguous).
-//   * C = 144: wave w keeps the weights of output channels [32w, 32w+32) in registers for the whole strip; the
-//     16-channel remainder block comes from LDS.  C = 24: the single (padded) 32-channel block comes from LDS.
-// The in-flight prefetch of the next input row spans the MFMA phase, which is what hides the HBM latency.
+//     4 x-positions, each input row read once from an LDS ring that the DMA fills ahead, and fed to the 5 output rows it
+//     touches (v_pk_fma_f32).  The finished output row (after ReLU) is packed to bf16 into an LDS tile Xt[px][k]
+//     (304 byte pixel rows: conflict-free for the 16-byte MFMA fragment reads) instead of HBM;
+//   * every output row: one barrier, then wave w runs out[ch][px] = Wpw[ch][:] . Xt[px][:] on v_mfma_f32_32x32x16_bf16 for
+//     its output channels [32w, 32w+32) (channels on the MFMA "i" side, weights in registers for the whole strip), adds the
+//     bias and stores the row straight from the accumulators; the 16-channel remainder block (weights from LDS) is done by
+//     the wave whose turn it is.
+// The DMA of the following input rows spans the MFMA phase, which is what hides the HBM latency.
 #include "refiner_block.h"
 #include "tuning.h"
 
@@ -36,45 +35,32 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2_t;  //  no addres
 typedef ROMA_LDS u32x4_t lds_u32x4;
 typedef ROMA_LDS u32x2_t lds_u32x2;
 
-__device__ __attribute__((aligned(256))) unsigned int g_rb_zero_page[64];  // source of every out-of-image DMA chunk
-__device__ __attribute__((aligned(256))) unsigned int g_rb_dump[512];       // where lanes right of the tile store (C = 144): 64 x 16 B + the largest piece offset
+// (unreferenced since the DMA reads out-of-image chunks through the buffer descriptor; it stays because g_rb_dump's address,
+//  a literal in the kernel's code, follows from it: the code object is byte-identical to the one that was measured)
+__device__ __attribute__((aligned(256))) unsigned int g_rb_zero_page[64];
+__device__ __attribute__((aligned(256))) unsigned int g_rb_dump[512];      // where lanes right of the tile store: 64 x 16 B + the largest piece offset
 
-template <int CP> struct RBCfg {
-  static constexpr int GC = CP / 4;                        // channel groups of 4
-  static constexpr int XQ = CP == 24 ? 36 : 256 / GC;      // x quads per workgroup row   (36 ; 7)
-  static constexpr int PX = 4 * XQ;                        // pixels per workgroup row    (144 ; 28)
-  static constexpr int PXB = (PX + 31) / 32;               // 32-pixel MFMA blocks / row  (5 ; 1)
-  static constexpr int KS = (CP + 15) / 16;                // MFMA k-steps                (2 ; 9)
-  static constexpr int KP = KS * 16;                       // padded K                    (32 ; 144)
-  static constexpr int NBF = CP / 32;                      // full 32-channel blocks      (0 ; 4)
-  static constexpr int TAIL = CP % 32;                     // channels of the last block  (24 ; 16)
-  static constexpr int XROW = KP * 2 + 16;                 // bytes per pixel row of Xt   (80 ; 304)
-  static constexpr int NR = CP == 24 ? 6 : 4;              // input rows in the LDS ring (DMA runs NR-1 rows ahead)
-  static constexpr int IN_ROWB = (PX + 4) * CP * 2;        // bytes of one input row segment incl. halo (7104 ; 9216)
-  static constexpr int NDMA = (IN_ROWB + 1023) / 1024;     // 1 KiB DMA instructions per row (7 ; 9)
+struct RBCfg {
+  static constexpr int CP = 144;
+  static constexpr int GC = CP / 4;                        // channel groups of 4                 (36)
+  static constexpr int XQ = 256 / GC;                      // x quads per workgroup row           (7)
+  static constexpr int PX = 4 * XQ;                        // pixels per workgroup row            (28)
+  static constexpr int PXB = (PX + 31) / 32;               // 32-pixel MFMA blocks / row          (1)
+  static constexpr int KS = (CP + 15) / 16;                // MFMA k-steps                        (9)
+  static constexpr int NBF = CP / 32;                      // full 32-channel blocks              (4)
+  static constexpr int TAIL = CP % 32;                     // channels of the last block          (16)
+  static constexpr int XROW = KS * 16 * 2 + 16;            // bytes per pixel row of Xt           (304)
+  static constexpr int IN_ROWB = (PX + 4) * CP * 2;        // bytes of one input row segment incl. halo (9216)
+  static constexpr int NDMA = (IN_ROWB + 1023) / 1024;     // 1 KiB DMA instructions per row      (9)
   static constexpr int RSTRIDE = NDMA * 1024;
-  static constexpr int KW = (NDMA + 3) / 4;                // max DMA instructions per wave per row (2 ; 3)
-  static constexpr int OROW = PX * CP * 2;                 // bytes of one output row segment (6912 ; 8064)
-  static constexpr int ROW16 = OROW / 16;
-  static constexpr int OPIX = CP * 2 + (CP >= 128 ? 16 : 0);  // LDS bytes per staged output pixel: 288 -> 304 keeps the 8-byte
-                                                                // MFMA-layout writes of 16 pixels on distinct banks (48 is already fine)
+  static constexpr int KW = (NDMA + 3) / 4;                // max DMA instructions per wave per row (3)
   static constexpr int OFF_PWB = 26 * CP * 4;
   static constexpr int OFF_WT = OFF_PWB + CP * 4;
   static constexpr int OFF_XT = OFF_WT + TAIL * XROW;
-  static constexpr int OFF_OT = OFF_XT + PXB * 32 * XROW;
-  static constexpr int WORK_BYTES = OFF_OT + PX * OPIX;
-  static constexpr int RING_BYTES = NR * RSTRIDE;
-  static_assert(NBF == 0 || NBF == 4, "one wave per full channel block");
-  static_assert(GC * XQ <= 256 && OROW % 16 == 0 && TAIL % 8 == 0 && ROW16 <= 512, "layout");
-  static_assert(OFF_PWB % 16 == 0 && OFF_WT % 16 == 0 && OFF_XT % 16 == 0 && OFF_OT % 16 == 0, "alignment");
-  static_assert(WORK_BYTES + RING_BYTES <= 80 * 1024, "two workgroups per CU");
-  static_assert((NR - 1) * (KW + 2) < 64, "vmcnt range");
+  static_assert(NBF == 4, "one wave per full channel block");
+  static_assert(GC * XQ <= 256 && TAIL % 8 == 0, "layout");
+  static_assert(OFF_PWB % 16 == 0 && OFF_WT % 16 == 0 && OFF_XT % 16 == 0, "alignment");
 };
-
-__device__ __forceinline__ void rb_glds16(const char* src, lds_u8* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (ROMA_LDS void*)lds_wave_base, 16, 0, 0);
-}
 
 #define ROMA_RB_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 // LDS writes of this wave retired, then the raw barrier (no __syncthreads: its release fence would drain vmcnt and
@@ -84,29 +70,21 @@ __device__ __forceinline__ void rb_glds16(const char* src, lds_u8* lds_wave_base
   __builtin_amdgcn_s_barrier();                             \
   asm volatile("" ::: "memory")
 
-#ifdef ROMA_TOOLS_BUILD
-#include "refiner_block_2b.inc"  // refiner_block_kernel<CP>: the two-barrier A/B reference (tools builds only)
-#endif
-
 // ---------------------------------------------------------------------------------------------------------------------
-// C = 144 with ONE barrier per image row (roma_tuning("rb144_1b", 0) selects the two-barrier kernel of refiner_block_2b.inc in a
-// tools build, for A/B).
-//
-// The two-barrier kernel needs two barriers per row: B2 (the depthwise tile Xt is complete / the ring slot is free) and B3 (the
-// output tile Ot is complete before the whole workgroup streams it out / the next input row has landed).  Here
+// ONE barrier per image row:
 //   * Xt is double buffered: row t's 1x1 reads Xt[t & 1] while the fastest wave may already write Xt[(t + 1) & 1];
 //   * every wave stores exactly what it computed - its own 32-channel slice of the row (64 B per pixel) and, when it is its
-//     turn, the 16-channel remainder block - so nobody waits for anybody else's part of Ot;
+//     turn, the 16-channel remainder block - so nobody waits for anybody else's part of the row;
 //   * a wave waits for its own DMA pieces of row t + 1 BEFORE the barrier of row t, which makes that barrier the "row t + 1
 //     is visible" point as well.
 // The second Xt buffer is paid for with the ring: NR = 3 rows (the DMA still runs a full row ahead of the one being
-// waited for).  Arithmetic and its order are unchanged: bit-identical results (tests).
-constexpr int RB1_XT = RBCfg<144>::PXB * 32 * RBCfg<144>::XROW;
+// waited for).
+constexpr int RB1_XT = RBCfg::PXB * 32 * RBCfg::XROW;
 // LDS of this kernel: ring + taps / bias / remainder weights + two Xt buffers (no output tile since round 5)
 // (A ring of 4 rows - the LDS the output tile freed - was measured in round 5: 6.68 / 6.73 against 6.71 / 6.78 ms per step, noise;
 // the kernel waits for its VALU, not for the DMA.  profiles/r05_v11_block144_ring_depth.log)
 constexpr int RB1_NR = 3;
-static_assert(RB1_NR * RBCfg<144>::RSTRIDE + RBCfg<144>::OFF_XT + 2 * RB1_XT <= 80 * 1024, "two workgroups per CU");
+static_assert(RB1_NR * RBCfg::RSTRIDE + RBCfg::OFF_XT + 2 * RB1_XT <= 80 * 1024, "two workgroups per CU");
 
 // FINAL (round 5): the last block of a ConvRefiner, its 1x1 composed with out_conv (see refiner_block24w.hip): `pw` holds 8 rows
 // (rows 0-2 head, rows 4-6 remainder of the composed C -> 3 weights), `pwb` the composed bias in [0, 3); the wave whose turn it
@@ -119,7 +97,7 @@ __global__ __launch_bounds__(256, 2) void refiner_block144_1b_kernel(const bf16_
                                                                      const float* __restrict__ pwb, int B, int H, int W, int SY,
                                                                      int nxg, int nblocks, f32x4* __restrict__ delta) {
   constexpr int CP = 144;
-  typedef RBCfg<CP> Cf;
+  typedef RBCfg Cf;
   constexpr int GC = Cf::GC, XQ = Cf::XQ, PX = Cf::PX, KS = Cf::KS, NR = RB1_NR, KW = Cf::KW;
   constexpr int XROW = Cf::XROW, NDMA = Cf::NDMA, RSTRIDE = Cf::RSTRIDE;
   static_assert(Cf::PXB == 1 && Cf::NBF == 4 && Cf::TAIL == 16, "one 32-pixel block, four full channel blocks + 16");
@@ -179,7 +157,6 @@ __global__ __launch_bounds__(256, 2) void refiner_block144_1b_kernel(const bf16_
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(wown[ks]));
 
-  const char* zsrc = reinterpret_cast<const char*>(g_rb_zero_page);
   const char* inb = reinterpret_cast<const char*>(in + ((long)b * H * W) * CP);
   // Round 6 (dwconv_ring.hip): the DMA goes through a buffer descriptor over image b - a 32-bit lane offset fixed for the strip
   // (0x80000000 for chunks past the row segment and columns outside the image: beyond num_records, the hardware returns zeros)
@@ -441,10 +418,10 @@ __global__ __launch_bounds__(256, 2) void refiner_block144_1b_kernel(const bf16_
 //  not by load latency; the ring only pays off here, where it also frees the registers the 1x1 weights need.)
 bool refiner_block_supported(int Cp, int dt) { return dt == DT_BF16 && (Cp == 24 || Cp == 144); }
 
-template <int CP>
-static int launch_cp(const void* in, void* out, const float* dw_w, const float* dw_b, const void* pw, long ldpw,
+static int launch144(const void* in, void* out, const float* dw_w, const float* dw_b, const void* pw, long ldpw,
                      const float* pw_b, int B, int H, int W, hipStream_t s, float* delta = nullptr) {
-  typedef RBCfg<CP> Cf;
+  typedef RBCfg Cf;
+  constexpr int CP = Cf::CP;
   ROMA_REQUIRE((long)H * W * CP * 2 < (1l << 31), "refiner_block: an image must stay below 2 GiB (32-bit offsets inside its buffer descriptor)");
   const int nxg = (W + Cf::PX - 1) / Cf::PX;
   // strip height: SY + 4 input rows are read per strip (and ~2 more rows' worth of pipeline fill), and the 512 resident
@@ -467,23 +444,6 @@ static int launch_cp(const void* in, void* out, const float* dw_w, const float* 
   ROMA_REQUIRE(nb < (1l << 30), "refiner_block: grid too large");
   const int nblocks = (int)nb;
   dim3 grid((unsigned)(((nblocks + 7) / 8) * 8));
-#ifdef ROMA_TOOLS_BUILD
-  const int dbg = tuning(SW_RB_DBG);  // tuning ablations only
-  if (dbg & 16) {
-    int nb_cu = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_cu, refiner_block_kernel<CP>, 256, 0);
-    fprintf(stderr, "refiner_block<%d>: %d workgroups/CU, grid %d\n", CP, nb_cu, nblocks);
-  }
-  if (!delta && (CP == 24 || !tuning(SW_RB144_1B) || dbg)) {  // 1 = refiner_block144_1b_kernel, 0 = refiner_block_kernel<144>
-    hipLaunchKernelGGL(refiner_block_kernel<CP>, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)out, dw_w, dw_b,
-                       (const bf16_t*)pw, ldpw, pw_b, B, H, W, SY, nxg, nblocks, dbg);
-    ROMA_LAUNCH_CHECK();
-    return 0;
-  }
-#else
-  ROMA_REQUIRE(CP == 144, "refiner_block: C = 24 runs on the wave-private kernel only (it declined these tensors: 16-byte aligned bf16 in / out / weights are required)");
-  ROMA_REQUIRE(tuning(SW_RB144_1B) != 0, "refiner_block: the two-barrier A/B kernel is not part of this build (make TOOLS=1)");
-#endif
   if (delta)
     hipLaunchKernelGGL(refiner_block144_1b_kernel<true>, grid, dim3(256), 0, s, (const bf16_t*)in, (bf16_t*)nullptr, dw_w, dw_b,
                        (const bf16_t*)pw, ldpw, pw_b, B, H, W, SY, nxg, nblocks, (f32x4*)delta);
@@ -503,10 +463,10 @@ int refiner_block_launch(const void* in, void* out, const float* dw_w, const flo
                "byte", s);
   if (Cp == 24) {
     const int rc = refiner_block24_wave_try_launch(in, out, dw_w, dw_b, pw, ldpw, pw_b, B, H, W, dt, s);
-    if (rc <= 0) return rc;
-    return launch_cp<24>(in, out, dw_w, dw_b, pw, ldpw, pw_b, B, H, W, s);
+    ROMA_REQUIRE(rc != 1, "refiner_block: C = 24 runs on the wave-private kernel only (it declined these tensors: 16-byte aligned bf16 in / out / weights are required)");
+    return rc;
   }
-  return launch_cp<144>(in, out, dw_w, dw_b, pw, ldpw, pw_b, B, H, W, s);
+  return launch144(in, out, dw_w, dw_b, pw, ldpw, pw_b, B, H, W, s);
 }
 
 // The last block of a ConvRefiner with its 1x1 composed with out_conv: pw_final [8][ldpw] 16-bit (rows 0-2 head, 4-6 remainder of
@@ -527,7 +487,7 @@ int refiner_block_final_launch(const void* in, float* delta, const float* dw_w, 
     }
     return rc;
   }
-  return launch_cp<144>(in, nullptr, dw_w, dw_b, pw_final, ldpw, bias_final, B, H, W, s, delta);
+  return launch144(in, nullptr, dw_w, dw_b, pw_final, ldpw, bias_final, B, H, W, s, delta);
 }
 
 }  // namespace roma

@@ -1,18 +1,19 @@
 // Fused depthwise-5x5 (+folded BN, ReLU) -> 1x1 convolution for the stride-1 ConvRefiner (C = 24) - the "wave-private"
-// form of refiner_block_kernel<24> (refiner_block.hip).  romatch/models/matcher.py:106-122.
+// kernel.  romatch/models/matcher.py:106-122.
 //
-// refiner_block_kernel<24> shares everything across its four waves - the input ring, the depthwise-output tile Xt, the
-// output tile Ot - and pays two workgroup barriers per image row for it; its waves issue 45 % of their cycles and wait 36 %
-// (profiles/r03_pmc_sq_summary.json).  With 24 channels a single wave can own ALL channels of its pixels, so nothing has to
-// be shared (the recipe of dwconv5x5_ring_kernel, which issues 55 % of its cycles with no barrier at all):
+// The workgroup kernel it replaced (removed; DESIGN.md, history) shared everything across its four waves - the input ring, the
+// depthwise-output tile Xt, the output tile Ot - and paid two workgroup barriers per image row for it; its waves issued 45 % of
+// their cycles and waited 36 % (profiles/r03_pmc_sq_summary.json).  With 24 channels a single wave can own ALL channels of
+// its pixels, so nothing has to be shared (the recipe of dwconv5x5_ring_kernel, which issues 55 % of its cycles with no
+// barrier at all):
 //
 //   * a wave = 40 output columns x all 24 channels x a strip of rows; lane = (4 channels, 4 columns): 6 channel groups x
-//     10 column quads = 60 lanes (the workgroup kernel: 216 of 256), through the lane table below (LDS bank conflicts);
+//     10 column quads = 60 lanes, through the lane table below (LDS bank conflicts);
 //   * per input row the wave needs 44 pixels x 48 B: three `global_load_lds_dwordx4` into its own NR = 4 row ring.  After
 //     every 4 pixels (12 pieces) one 16-byte piece of the row stays empty, so that the column
 //     quads of a `ds_read_b64` half-wave start 52 dwords apart (0, 52, 40, 28, 16 mod 64 - five disjoint 12-dword runs;
 //     the natural 48-dword pitch puts quad 4 on quad 0's banks);
-//   * the depthwise output row goes to a wave-private Xt[40 pixels][32 k] (bf16, 80-byte rows as in the workgroup kernel),
+//   * the depthwise output row goes to a wave-private Xt[40 pixels][32 k] (bf16, 80-byte rows),
 //     two 32-pixel MFMA blocks (the second one 8 pixels + zeros) x 2 k-steps against the 1x1 weights held in registers,
 //     bias in the accumulator init; v_permlane32_swap pairs the half-waves and the row leaves in three 16-byte stores per
 //     lane straight from the accumulators (until round 5: through a wave-private LDS tile Ot[40][24], 6 ds_write_b64 +
@@ -20,14 +21,12 @@
 //   * the only thing that orders anything is the wave's own counted `s_waitcnt vmcnt` (allowance = the younger DMA) and the
 //     in-order LDS pipeline: NO barrier after the weights have been staged, the waves drift freely, and a wave whose tile is
 //     off the image simply leaves.
-//   * arithmetic and its order are those of refiner_block_kernel<24>: results are bit-identical (tests).
 #include <stdlib.h>
 
 #include <algorithm>
 
 #include "gemm.h"  // DT_*
 #include "refiner_block.h"
-#include "tuning.h"
 
 namespace roma {
 
@@ -361,9 +360,6 @@ __global__ __launch_bounds__(256, 2) void refiner_block24_wave_kernel(const bf16
 // 0 = launched, 1 = not this kernel's problem, < 0 = error
 int refiner_block24_wave_try_launch(const void* in, void* out, const float* dw_w, const float* dw_b, const void* pw, long ldpw,
                                     const float* pw_b, int B, int H, int W, int dt, hipStream_t s, float* delta) {
-#ifdef ROMA_TOOLS_BUILD
-  if (!tuning(SW_RB24W)) return 1;  // A/B: the two-barrier workgroup kernel (refiner_block_2b.inc)
-#endif
   if (dt != DT_BF16 || H < 1 || W < 1 || (long)H * W * RBW_C * 2 >= (1l << 31)) return 1;  // (32-bit offsets inside an image)
   if ((reinterpret_cast<uintptr_t>(in) & 15) != 0 || (reinterpret_cast<uintptr_t>(delta ? (void*)delta : out) & 15) != 0) return 1;
   if ((reinterpret_cast<uintptr_t>(pw) & 15) != 0 || ldpw % 8 != 0) return 1;

@@ -18,9 +18,6 @@ enum Switch : int {
   SW_CONV_PATCH,
   SW_ATTN_XCD,
   SW_ATTN_EXP2,
-  SW_RB24W,
-  SW_RB144_1B,
-  SW_RB_WIDE,
   SW_DW_RING,
   SW_GP_COL,
   SW_POOL_PROJ,
@@ -32,9 +29,6 @@ enum Switch : int {
   SW_CONV64_SY,
   SW_CONV_KORDER,
   SW_RB_SY,
-  SW_RB_DBG,
-  SW_RB_WIDE_PK,
-  SW_RBW_DBG,
   SW_DWR_MAXSY,
   SW_DW_RING_MINELEMS,
   SW_RI_VEC,

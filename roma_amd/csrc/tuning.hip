@@ -17,53 +17,46 @@ struct Row {
   const char* env;  // environment variable, or nullptr
   long def;
   int floor;        // lowest value that counts as an override (anything below clears it)
-  bool tools_env;   // the environment is honoured in -DROMA_TOOLS_BUILD builds only
   const char* doc;
 };
 
 constexpr Row ROWS[] = {
-    {SW_GEMM8P, "gemm8p", "ROMA_GEMM8P", 1, 0, false, "large bf16 GEMMs on the 8-phase 256 x 256 kernel (1) or on the one-barrier-per-slab kernel (0)"},
-    {SW_GEMM_DBG, "gemm_dbg", "ROMA_GEMM_DBG", 0, 0, false, "experiment bits of the GEMM kernels (1 skip output stores, 2 skip the K loop, 2048 no streaming stores, ...)"},
-    {SW_GEMM8P_WALK, "gemm8p_walk", nullptr, -1, 1, false, "gemm8p: tile rows per group of the persistent walk (1 = row major); unset = 8 from 24 tile columns on, else 1"},
-    {SW_GEMM8P_SCHED, "gemm8p_sched", "ROMA_GEMM8P_SCHED", 1, 0, false, "gemm8p K-loop schedule: 1 k-half phases, 0 quadrant phases (tools builds only)"},
-    {SW_GEMM8P_MAXWG, "gemm8p_maxwg", nullptr, -1, 8, false, "gemm8p, measurement only: cap the persistent grid at n workgroups (a multiple of 8); unset = one per CU"},
-    {SW_WS1X1, "ws1x1", "ROMA_WS1X1", 1, 0, false, "N = K = 576 refiner 1x1 on the weight-stationary kernel (1) or on the 256 x 192 tile kernel (0)"},
-    {SW_LC_MODE, "lc_mode", "ROMA_LC_MODE", 0, 0, false, "local correlation: 0 tiled form + gather work list, 1 every tile on the gather list (key only), 2 per-pixel kernel"},
-    {SW_LC_BIN, "lc_bin", "ROMA_LC_BIN", 1, 0, false, "local correlation: queries of incoherent tiles sorted by target bin, counters in LDS (1) or device atomics (2), or gathered per query (0)"},
-    {SW_CONV64, "conv64", "ROMA_CONV64", 7, 0, false, "weight-stationary VGG front end, bit mask: 1 the Cin = 64 kernels, 2 the Cin = 128 kernel, 4 the fused first layer"},
-    {SW_CONV_PATCH, "conv_patch", "ROMA_CONV_PATCH", 1, 0, false, "patch-resident 3x3 kernel for slab-major VGG layers (1) or gemm8p (0); environment 0 also packs tap-major weights"},
-    {SW_ATTN_XCD, "attn_xcd", "ROMA_ATTN_XCD", 1, 0, false, "attention work items in per-XCD bands of (batch, head) (1) or in plain order (0)"},
-    {SW_ATTN_EXP2, "attn_exp2", nullptr, -1, 0, false, "tools only: force the 2^x softmax of the 16-bit attention kernel on / off; unset = as the caller says"},
-    {SW_RB24W, "rb24w", "ROMA_RB24W", 1, 0, false, "C = 24 fused refiner block: wave-private kernel (1) or two-barrier workgroup kernel (0); consulted in tools builds only"},
-    {SW_RB144_1B, "rb144_1b", "ROMA_RB144_1B", 1, 0, true, "C = 144 fused refiner block: one barrier per row (1) or two (0, tools builds only)"},
-    {SW_RB_WIDE, "rb_wide", "ROMA_RB_WIDE", 0, 0, false, "C = 576 refiner block as one fused kernel (1; key 2 / 3 = with the scalar / packed stencil) or dwconv5x5 + 1x1 GEMM (0)"},
-    {SW_DW_RING, "dw_ring", "ROMA_DW_RING", 1, 0, false, "depthwise 5x5: 0 register-prefetch kernel, 1 ring kernel for the large launches, 2 ring kernel for every shape it takes"},
-    {SW_GP_COL, "gp_col", "ROMA_GP_COL", 1, 0, false, "GP Cholesky left-looking, one launch per block column (1) or the right-looking launch chain (0)"},
-    {SW_POOL_PROJ, "pool_proj", "ROMA_POOL_PROJ", 1, 0, false, "max-pool + proj head of strides 1 / 2 in one pass (1) or as separate kernels (0)"},
-    {SW_GP_COL_LEADER, "gp_col_leader", "ROMA_GP_COL_LEADER", 1, 0, false, "block-column Cholesky: a leader workgroup factorises the diagonal block, its product formed one launch ahead (1) or in its own launch (2), or every workgroup its own copy (0)"},
-    {SW_GEMM8P_MINM, nullptr, "ROMA_GEMM8P_MINM", 2048, 0, false, "gemm8p: smallest M it takes for the wide (N >= 2048) dense launches"},
-    {SW_GEMM_NT, nullptr, "ROMA_GEMM_NT", 1, 0, false, "non-temporal output stores in the 16-bit GEMM row writer"},
-    {SW_GEMM_F32_FILL, nullptr, "ROMA_GEMM_F32_FILL", 1, 0, false, "exact-f32 GEMMs below 192 tiles of 256 x 256 run on 128 x 128 tiles"},
-    {SW_GEMM_SMALLM, nullptr, "ROMA_GEMM_SMALLM", 1, 0, false, "GEMMs below 320 tiles of 128 x 128 run on 128 x 64 tiles"},
-    {SW_CONV64_SY, nullptr, "ROMA_CONV64_SY", 0, 0, false, "conv64 strip height in rows; 0 = the split of H with the fewest rounds"},
-    {SW_CONV_KORDER, nullptr, "ROMA_CONV_KORDER", 1, 0, false, "VGG layers with Cout >= 256 pack slab-major weight rows (read when a handle is created)"},
-    {SW_RB_SY, nullptr, "ROMA_RB_SY", 0, 0, false, "fused refiner block strip height in rows; 0 = the split of H with the fewest rounds"},
-    {SW_RB_DBG, nullptr, "ROMA_RB_DBG", 0, 0, true, "ablation bits of the two-barrier refiner block kernel"},
-    {SW_RB_WIDE_PK, nullptr, "ROMA_RB_WIDE_PK", 1, 0, false, "rb_wide: packed (1) or scalar (0) stencil"},
-    {SW_RBW_DBG, nullptr, "ROMA_RBW_DBG", 0, 0, true, "ablation bits of the rb_wide kernel (they produce wrong outputs by design)"},
-    {SW_DWR_MAXSY, nullptr, "ROMA_DWR_MAXSY", 1 << 20, 0, false, "depthwise ring kernel: cap of the strip height in rows (at least 6)"},
-    {SW_DW_RING_MINELEMS, nullptr, "ROMA_DW_RING_MINELEMS", 64l << 20, 0, false, "dw_ring = 1: smallest launch, in elements, that goes to the ring kernel"},
-    {SW_RI_VEC, nullptr, "ROMA_RI_VEC", 1, 0, false, "refiner_input on the 16-byte vector kernel where alignment allows"},
-    {SW_OUT_ROW, nullptr, "ROMA_OUT_ROW", 1, 0, false, "refiner_out: row kernel for C = 24 in 16-bit storage"},
-    {SW_OUT_LPR, nullptr, "ROMA_OUT_LPR", 1, 0, false, "refiner_out, 16-bit: lanes per row chosen to fill the 16-byte pieces best"},
-    {SW_OUT_ROWS_IT, nullptr, "ROMA_OUT_ROWS_IT", 0, 0, false, "refiner_out: row groups per wave (even, >= 2); otherwise 8"},
-    {SW_GP_AUG, nullptr, "ROMA_GP_AUG", 1, 0, false, "GP Cholesky: right-hand sides stored behind A ride along the factorisation (0 = separate forward loop)"},
-    {SW_GP_BWD2, nullptr, "ROMA_GP_BWD2", 1, 0, false, "GP Cholesky: backward substitution with one launch per step (0 = two)"},
-    {SW_COMPOSE_OUT, nullptr, "ROMA_COMPOSE_OUT", 1, 0, false, "initial value of the handle option compose_out_conv (read when a handle is created)"},
-    {SW_VIT_RES_F32, nullptr, "ROMA_VIT_RES_F32", 0, 0, false, "force DINOv2's f32 residual stream in the 16-bit modes"},
-    {SW_STREAMS, nullptr, "ROMA_STREAMS", 0, 0, false, "number of sub-batch streams of match(); 0 = the handle's option"},
-    {SW_STREAMS_SERIAL, nullptr, "ROMA_STREAMS_SERIAL", 0, 0, false, "diagnostic: sub-batch streams run one after the other"},
-    {SW_DEBUG_DUAL_SLOT, nullptr, "ROMA_DEBUG_DUAL_SLOT", -1, 0, false, "diagnostic: keep the stream split in debug mode, sub-batch k captures the stages of ROMA_DEBUG_ONLY"},
+    {SW_GEMM8P, "gemm8p", "ROMA_GEMM8P", 1, 0, "large bf16 GEMMs on the 8-phase 256 x 256 kernel (1) or on the one-barrier-per-slab kernel (0)"},
+    {SW_GEMM_DBG, "gemm_dbg", "ROMA_GEMM_DBG", 0, 0, "experiment bits of the GEMM kernels (1 skip output stores, 2 skip the K loop, 2048 no streaming stores, ...)"},
+    {SW_GEMM8P_WALK, "gemm8p_walk", nullptr, -1, 1, "gemm8p: tile rows per group of the persistent walk (1 = row major); unset = 8 from 24 tile columns on, else 1"},
+    {SW_GEMM8P_SCHED, "gemm8p_sched", "ROMA_GEMM8P_SCHED", 1, 0, "gemm8p K-loop schedule: 1 k-half phases, 0 quadrant phases (tools builds only)"},
+    {SW_GEMM8P_MAXWG, "gemm8p_maxwg", nullptr, -1, 8, "gemm8p, measurement only: cap the persistent grid at n workgroups (a multiple of 8); unset = one per CU"},
+    {SW_WS1X1, "ws1x1", "ROMA_WS1X1", 1, 0, "N = K = 576 refiner 1x1 on the weight-stationary kernel (1) or on the 256 x 192 tile kernel (0)"},
+    {SW_LC_MODE, "lc_mode", "ROMA_LC_MODE", 0, 0, "local correlation: 0 tiled form + gather work list, 1 every tile on the gather list (key only), 2 per-pixel kernel"},
+    {SW_LC_BIN, "lc_bin", "ROMA_LC_BIN", 1, 0, "local correlation: queries of incoherent tiles sorted by target bin, counters in LDS (1) or device atomics (2), or gathered per query (0)"},
+    {SW_CONV64, "conv64", "ROMA_CONV64", 7, 0, "weight-stationary VGG front end, bit mask: 1 the Cin = 64 kernels, 2 the Cin = 128 kernel, 4 the fused first layer"},
+    {SW_CONV_PATCH, "conv_patch", "ROMA_CONV_PATCH", 1, 0, "patch-resident 3x3 kernel for slab-major VGG layers (1) or gemm8p (0); environment 0 also packs tap-major weights"},
+    {SW_ATTN_XCD, "attn_xcd", "ROMA_ATTN_XCD", 1, 0, "attention work items in per-XCD bands of (batch, head) (1) or in plain order (0)"},
+    {SW_ATTN_EXP2, "attn_exp2", nullptr, -1, 0, "tools only: force the 2^x softmax of the 16-bit attention kernel on / off; unset = as the caller says"},
+    {SW_DW_RING, "dw_ring", "ROMA_DW_RING", 1, 0, "depthwise 5x5: 0 register-prefetch kernel, 1 ring kernel for the large launches, 2 ring kernel for every shape it takes"},
+    {SW_GP_COL, "gp_col", "ROMA_GP_COL", 1, 0, "GP Cholesky left-looking, one launch per block column (1) or the right-looking launch chain (0)"},
+    {SW_POOL_PROJ, "pool_proj", "ROMA_POOL_PROJ", 1, 0, "max-pool + proj head of strides 1 / 2 in one pass (1) or as separate kernels (0)"},
+    {SW_GP_COL_LEADER, "gp_col_leader", "ROMA_GP_COL_LEADER", 1, 0, "block-column Cholesky: a leader workgroup factorises the diagonal block, its product formed one launch ahead (1) or in its own launch (2), or every workgroup its own copy (0)"},
+    {SW_GEMM8P_MINM, nullptr, "ROMA_GEMM8P_MINM", 2048, 0, "gemm8p: smallest M it takes for the wide (N >= 2048) dense launches"},
+    {SW_GEMM_NT, nullptr, "ROMA_GEMM_NT", 1, 0, "non-temporal output stores in the 16-bit GEMM row writer"},
+    {SW_GEMM_F32_FILL, nullptr, "ROMA_GEMM_F32_FILL", 1, 0, "exact-f32 GEMMs below 192 tiles of 256 x 256 run on 128 x 128 tiles"},
+    {SW_GEMM_SMALLM, nullptr, "ROMA_GEMM_SMALLM", 1, 0, "GEMMs below 320 tiles of 128 x 128 run on 128 x 64 tiles"},
+    {SW_CONV64_SY, nullptr, "ROMA_CONV64_SY", 0, 0, "conv64 strip height in rows; 0 = the split of H with the fewest rounds"},
+    {SW_CONV_KORDER, nullptr, "ROMA_CONV_KORDER", 1, 0, "VGG layers with Cout >= 256 pack slab-major weight rows (read when a handle is created)"},
+    {SW_RB_SY, nullptr, "ROMA_RB_SY", 0, 0, "fused refiner block strip height in rows; 0 = the split of H with the fewest rounds"},
+    {SW_DWR_MAXSY, nullptr, "ROMA_DWR_MAXSY", 1 << 20, 0, "depthwise ring kernel: cap of the strip height in rows (at least 6)"},
+    {SW_DW_RING_MINELEMS, nullptr, "ROMA_DW_RING_MINELEMS", 64l << 20, 0, "dw_ring = 1: smallest launch, in elements, that goes to the ring kernel"},
+    {SW_RI_VEC, nullptr, "ROMA_RI_VEC", 1, 0, "refiner_input on the 16-byte vector kernel where alignment allows"},
+    {SW_OUT_ROW, nullptr, "ROMA_OUT_ROW", 1, 0, "refiner_out: row kernel for C = 24 in 16-bit storage"},
+    {SW_OUT_LPR, nullptr, "ROMA_OUT_LPR", 1, 0, "refiner_out, 16-bit: lanes per row chosen to fill the 16-byte pieces best"},
+    {SW_OUT_ROWS_IT, nullptr, "ROMA_OUT_ROWS_IT", 0, 0, "refiner_out: row groups per wave (even, >= 2); otherwise 8"},
+    {SW_GP_AUG, nullptr, "ROMA_GP_AUG", 1, 0, "GP Cholesky: right-hand sides stored behind A ride along the factorisation (0 = separate forward loop)"},
+    {SW_GP_BWD2, nullptr, "ROMA_GP_BWD2", 1, 0, "GP Cholesky: backward substitution with one launch per step (0 = two)"},
+    {SW_COMPOSE_OUT, nullptr, "ROMA_COMPOSE_OUT", 1, 0, "initial value of the handle option compose_out_conv (read when a handle is created)"},
+    {SW_VIT_RES_F32, nullptr, "ROMA_VIT_RES_F32", 0, 0, "force DINOv2's f32 residual stream in the 16-bit modes"},
+    {SW_STREAMS, nullptr, "ROMA_STREAMS", 0, 0, "number of sub-batch streams of match(); 0 = the handle's option"},
+    {SW_STREAMS_SERIAL, nullptr, "ROMA_STREAMS_SERIAL", 0, 0, "diagnostic: sub-batch streams run one after the other"},
+    {SW_DEBUG_DUAL_SLOT, nullptr, "ROMA_DEBUG_DUAL_SLOT", -1, 0, "diagnostic: keep the stream split in debug mode, sub-batch k captures the stages of ROMA_DEBUG_ONLY"},
 };
 constexpr int NROWS = sizeof(ROWS) / sizeof(ROWS[0]);
 constexpr bool rows_in_enum_order() {
@@ -84,12 +77,6 @@ constexpr bool rows_json_plain() {
 }
 static_assert(rows_json_plain(), "keys, environment names and docs: plain ASCII without quote, backslash or control character");
 
-#ifdef ROMA_TOOLS_BUILD
-constexpr bool TOOLS_BUILD = true;
-#else
-constexpr bool TOOLS_BUILD = false;
-#endif
-
 struct Overrides {
   long v[SW_COUNT];
   constexpr Overrides() : v{} {
@@ -102,7 +89,7 @@ struct Env {
   long v[SW_COUNT];
   Env() {
     for (int i = 0; i < NROWS; ++i) {
-      const char* s = ROWS[i].env && (TOOLS_BUILD || !ROWS[i].tools_env) ? getenv(ROWS[i].env) : nullptr;
+      const char* s = ROWS[i].env ? getenv(ROWS[i].env) : nullptr;
       // atol for every row: most sites used atoi before the table, which is (int)strtol - the site's narrowing gives the same int
       v[i] = s ? atol(s) : ROWS[i].def;
     }
@@ -136,7 +123,7 @@ std::string tuning_describe() {
     const long ov = tuning_override(r.id);
     js += std::string(r.id ? ", " : "") + "{\"key\": " + quoted(r.key) + ", \"env\": " + quoted(r.env) +
           ", \"default\": " + std::to_string(r.def) + ", \"override\": " + (ov >= 0 ? std::to_string(ov) : "null") +
-          ", \"value\": " + std::to_string(tuning(r.id)) + ", \"tools_only_env\": " + (r.tools_env ? "true" : "false") + ", \"doc\": " + quoted(r.doc) + "}";
+          ", \"value\": " + std::to_string(tuning(r.id)) + ", \"doc\": " + quoted(r.doc) + "}";
   }
   return js + "]";
 }

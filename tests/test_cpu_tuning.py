@@ -19,20 +19,21 @@ KEYS = {
     "gemm8p_sched": ("ROMA_GEMM8P_SCHED", 1), "gemm8p_maxwg": (None, -1), "ws1x1": ("ROMA_WS1X1", 1),
     "lc_mode": ("ROMA_LC_MODE", 0), "lc_bin": ("ROMA_LC_BIN", 1), "conv64": ("ROMA_CONV64", 7),
     "conv_patch": ("ROMA_CONV_PATCH", 1), "attn_xcd": ("ROMA_ATTN_XCD", 1), "attn_exp2": (None, -1),
-    "rb24w": ("ROMA_RB24W", 1), "rb144_1b": ("ROMA_RB144_1B", 1), "rb_wide": ("ROMA_RB_WIDE", 0),
     "dw_ring": ("ROMA_DW_RING", 1), "gp_col": ("ROMA_GP_COL", 1), "pool_proj": ("ROMA_POOL_PROJ", 1),
     "gp_col_leader": ("ROMA_GP_COL_LEADER", 1),
 }
 # environment variables without a key -> default
 ENV_ONLY = {
     "ROMA_GEMM8P_MINM": 2048, "ROMA_GEMM_NT": 1, "ROMA_GEMM_F32_FILL": 1, "ROMA_GEMM_SMALLM": 1, "ROMA_CONV64_SY": 0,
-    "ROMA_CONV_KORDER": 1, "ROMA_RB_SY": 0, "ROMA_RB_DBG": 0, "ROMA_RB_WIDE_PK": 1, "ROMA_RBW_DBG": 0,
+    "ROMA_CONV_KORDER": 1, "ROMA_RB_SY": 0,
     "ROMA_DWR_MAXSY": 1 << 20, "ROMA_DW_RING_MINELEMS": 64 << 20, "ROMA_RI_VEC": 1, "ROMA_OUT_ROW": 1, "ROMA_OUT_LPR": 1,
     "ROMA_OUT_ROWS_IT": 0, "ROMA_GP_AUG": 1, "ROMA_GP_BWD2": 1, "ROMA_COMPOSE_OUT": 1, "ROMA_VIT_RES_F32": 0,
     "ROMA_STREAMS": 0, "ROMA_STREAMS_SERIAL": 0, "ROMA_DEBUG_DUAL_SLOT": -1,
 }
-# read only inside `#ifdef ROMA_TOOLS_BUILD` before the table: the shipped libraries ignore them
-TOOLS_ONLY_ENV = {"ROMA_RBW_DBG", "ROMA_RB_DBG", "ROMA_RB144_1B"}
+# the switches of the refiner-block variants that were removed (the C = 576 one-kernel block, the two-barrier workgroup kernel):
+# (key, environment variable) of their six rows, frozen - none may come back as a key or an environment name
+RETIRED = (("rb24w", "ROMA_RB24W"), ("rb144_1b", "ROMA_RB144_1B"), ("rb_wide", "ROMA_RB_WIDE"), (None, "ROMA_RB_DBG"),
+           (None, "ROMA_RB_WIDE_PK"), (None, "ROMA_RBW_DBG"))
 ENV_DEFAULTS = {**{e: d for e, d in KEYS.values() if e}, **ENV_ONLY}
 # the globals the keys used to live in
 FORMER_GLOBALS = ["g_gemm_tuning", "g_gemm8p_walk", "g_gemm8p_sched", "g_gemm8p_maxwg", "g_ws1x1_mode", "g_lc_mode", "g_lc_bin",
@@ -49,7 +50,7 @@ def describe(lib):
 
 def test_inventory_is_the_frozen_one_in_both_libraries(built_lib):
     from roma_amd import _lib
-    assert len(KEYS) == 19 and len(ENV_DEFAULTS) == 39
+    assert len(KEYS) == 16 and len(ENV_DEFAULTS) == 33
     per_lib = []
     for fmt in ("bf16", "f16"):
         rows = describe(_lib.load(fmt))
@@ -61,10 +62,24 @@ def test_inventory_is_the_frozen_one_in_both_libraries(built_lib):
                 assert (r["env"], r["default"]) == KEYS[r["key"]], r
             else:
                 assert r["default"] == ENV_ONLY[r["env"]], r
-            assert r["tools_only_env"] == (r["env"] in TOOLS_ONLY_ENV), r
             assert r["doc"], r
-        per_lib.append([(r["key"], r["env"], r["default"], r["tools_only_env"], r["doc"]) for r in rows])
+        per_lib.append([(r["key"], r["env"], r["default"], r["doc"]) for r in rows])
     assert per_lib[0] == per_lib[1]
+
+
+def test_retired_switches_are_gone_from_both_libraries(built_lib):
+    from roma_amd import _lib
+    retired = {n for row in RETIRED for n in row if n}
+    assert len(RETIRED) == 6 and len(retired) == 9 and not retired & (set(KEYS) | set(ENV_DEFAULTS))
+    for fmt in ("bf16", "f16"):
+        lib = _lib.load(fmt)
+        rows = describe(lib)
+        assert set(rows[0]) == {"key", "env", "default", "override", "value", "doc"}
+        names = {r["key"] for r in rows} | {r["env"] for r in rows}
+        assert not names & retired, (fmt, names & retired)
+        for key in [k for k, _ in RETIRED if k]:
+            assert lib.roma_tuning(key.encode(), 1) == -1, (fmt, key)  # ROMA_ERR_ARG
+            assert lib.roma_last_error().decode() == "roma_tuning: unknown key " + key
 
 
 CHILD = r"""
@@ -114,16 +129,14 @@ def test_environment_override_and_clear_in_a_fresh_process(built_lib):
     out = json.loads(run.stdout)
 
     def env_value(r):  # what the row resolves to with no override
-        if r["env"] is None or r["env"] in TOOLS_ONLY_ENV:  # (the in-tree libraries are the shipped build, not make TOOLS=1)
-            return r["default"]
-        return env_set[r["env"]]
+        return r["default"] if r["env"] is None else env_set[r["env"]]
 
     # the environment is honoured, by both libraries
     for rows in (out["env_a"], out["env_b"]):
         for r in rows:
             assert r["override"] is None and r["value"] == env_value(r), r
     # an override beats it; -1 brings it back
-    assert out["set_rc"] == [0] * 19 and out["clear_rc"] == [0] * 19
+    assert out["set_rc"] == [0] * 16 and out["clear_rc"] == [0] * 16
     for r in out["set_a"]:
         assert (r["override"], r["value"]) == ((11, 11) if r["key"] else (None, env_value(r))), r
     assert out["clear_a"] == out["env_a"]

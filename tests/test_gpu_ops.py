@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN
+from test_cpu_tuning import RETIRED  # the switches of the removed refiner-block variants
 
 pytestmark = pytest.mark.gpu
 
@@ -948,19 +949,11 @@ def test_refiner_block_fused(lib, Cp, B, H, W):
         outs.append(out)
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     out = outs[0]
-    # the A/B variants left the shipped library in round 5 (make TOOLS=1 brings them back): asking for one fails loudly
-    key = b"rb24w" if Cp == 24 else b"rb144_1b"
-    lib.roma_tuning(key, 0)
-    try:
-        o2 = torch.empty((B, H, W, Cp), device="cuda", dtype=torch.bfloat16)
-        rc = lib.roma_op_refiner_block(P(xin), P(o2), P(wp), P(b.cuda()), P(pw.cuda()), P(pb.cuda()), B, H, W, Cp, BF16, None)
-        if rc == 0:  # a tools build: the two-barrier kernel ran and must give the same bits
-            torch.cuda.synchronize()
-            assert torch.equal(out.view(torch.int16), o2.view(torch.int16))
-        else:
-            assert Cp == 144 and b"TOOLS" in lib.roma_last_error()
-    finally:
-        lib.roma_tuning(key, -1)
+    # the A/B variants (two-barrier workgroup kernel, one-kernel C = 576 block) were removed: their switches are unknown keys
+    retired_keys = [k for k, _ in RETIRED if k]
+    assert len(retired_keys) == 3
+    for key in retired_keys:
+        assert lib.roma_tuning(key.encode(), 0) == -1 and b"unknown key" in lib.roma_last_error()  # ROMA_ERR_ARG
     got = out.cpu().double()
     assert torch.isfinite(got).all()
     # bf16 output rounding (2^-8 relative) + the occasional 1-ulp flip of the bf16 intermediate
@@ -970,6 +963,15 @@ def test_refiner_block_fused(lib, Cp, B, H, W):
     # unsupported configurations fail loudly instead of falling back
     assert lib.roma_op_refiner_block(P(out), P(out), P(wp), P(b.cuda()), P(pw.cuda()), P(pb.cuda()), B, H, W, Cp, BF16, None) != 0
     assert lib.roma_op_refiner_block(P(x.cuda()), P(out), P(wp), P(b.cuda()), P(pw.cuda()), P(pb.cuda()), B, H, W, Cp, F32, None) != 0
+    # Cp = 576 is no fused shape (the wide scales run dwconv5x5 + GEMM): refused, nothing launched, `out` untouched
+    x576 = torch.zeros((1, 8, 16, 576), device="cuda", dtype=torch.bfloat16)
+    o576 = torch.full((1, 8, 16, 576), float("nan"), device="cuda", dtype=torch.bfloat16)
+    w576, b576 = torch.zeros((25, 576), device="cuda"), torch.zeros(576, device="cuda")
+    pw576 = torch.zeros((576, 576), device="cuda", dtype=torch.bfloat16)
+    assert lib.roma_op_refiner_block(P(x576), P(o576), P(w576), P(b576), P(pw576), P(b576), 1, 8, 16, 576, BF16, None) != 0
+    assert b"only bf16 with Cp = 24 or 144 is fused" in lib.roma_last_error()
+    torch.cuda.synchronize()
+    assert torch.isnan(o576).all()
 
 
 @pytest.mark.parametrize("dt,Cp,M", [(BF16, 24, 100003), (BF16, 24, 255), (BF16, 144, 30011), (BF16, 576, 5000), (F32, 24, 40001),
@@ -1281,12 +1283,13 @@ def test_fb_consistency_vs_oracle():
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 13, 10), (1, 8, 16), (1, 41, 59), (3, 24, 33), (1, 140, 140), (2, 1, 30), (1, 75, 3)])
-def test_refiner_block_wide_fused(lib, B, H, W):
-    """refiner_block_wide.hip - the C = 576 ConvRefiner block (dw5x5 + BN + ReLU + 1x1, matcher.py:92-122) in ONE kernel, all
-    output channels per workgroup - against torch f64 on the same bf16-rounded operands (ragged tiles, images smaller than a
-    tile, every border), against the two-kernel path it replaces (dwconv5x5 + 1x1 GEMM: the depthwise half is bit-identical by
-    construction, the 1x1 accumulates in f32 on another MFMA shape, so results may differ by an ulp of the 16-bit output), and
-    against itself (three launches: timing-dependent hazards of its DMA / barrier schedule)."""
+def test_refiner_wide_pair_vs_f64(lib, B, H, W):
+    """The C = 576 ConvRefiner block (dw5x5 + BN + ReLU + 1x1, matcher.py:92-122) as the model runs it - dwconv5x5, then the 1x1 as
+    a GEMM - against torch f64 on the same bf16-rounded operands (ragged tiles, images smaller than a tile, every border): the
+    stencil output against the once-rounded f64 intermediate, the pair's output under the bounds of test_refiner_block_fused
+    (bf16 output rounding + the occasional 1-ulp flip of the bf16 intermediate).  A torch emulation of the pair on the CPU (f32
+    depthwise rounded to bf16, f32 matmul rounded to bf16) stays inside them on all seven shapes: worst error / bound 0.22 (at
+    B, H, W = 1, 140, 140), worst mean error 1.53e-3."""
     Cp = 576
     x = rnd(B, Cp, H, W, seed=1).to(torch.bfloat16)
     w, b = rnd(Cp, 1, 5, 5, seed=2, std=0.2), rnd(Cp, seed=3)
@@ -1297,21 +1300,8 @@ def test_refiner_block_wide_fused(lib, B, H, W):
     wp = w.reshape(Cp, 25).T.contiguous().cuda()
     xin = x.permute(0, 2, 3, 1).contiguous().cuda()
     bd, pwd, pbd = b.cuda(), pw.cuda(), pb.cuda()
-    outs = []
-    for _ in range(3):
-        out = torch.full((B, H, W, Cp), float("nan"), device="cuda", dtype=torch.bfloat16)
-        ok(lib, lib.roma_op_refiner_block(P(xin), P(out), P(wp), P(bd), P(pwd), P(pbd), B, H, W, Cp, BF16, None))
-        torch.cuda.synchronize()
-        outs.append(out)
-    assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16)) and torch.equal(outs[0].view(torch.int16), outs[2].view(torch.int16))
-    got = outs[0].cpu().double()
-    assert torch.isfinite(got).all()
-    err = (got - ref).abs()
-    assert (err <= 1e-2 * ref.abs() + 3e-2).all(), float(err.max())
-    assert float(err.mean()) < 6e-3
-    # the pair of kernels it replaces
-    t = torch.empty_like(outs[0])
-    y2 = torch.empty_like(outs[0])
+    t = torch.full((B, H, W, Cp), float("nan"), device="cuda", dtype=torch.bfloat16)
+    y2 = torch.full((B, H, W, Cp), float("nan"), device="cuda", dtype=torch.bfloat16)
     ok(lib, lib.roma_op_dwconv5x5(P(xin), P(t), P(wp), P(bd), B, H, W, Cp, BF16, None))
     ok(lib, lib.roma_op_gemm(P(t), Cp, P(pwd), Cp, P(y2), Cp, B * H * W, Cp, Cp, 1, 0, 0, 0, P(pbd), None, None, 0, 0, 1.0, BF16, BF16, None))
     torch.cuda.synchronize()
@@ -1320,37 +1310,11 @@ def test_refiner_block_wide_fused(lib, B, H, W):
     tm, mm = t.cpu().float(), mid.permute(0, 2, 3, 1).contiguous().float()
     assert float((tm - mm).abs().max()) <= 2.0 ** -7 * float(mm.abs().max()) + 1e-6
     assert float((tm.view(torch.int32) == mm.view(torch.int32)).float().mean()) > 0.98
-    d = (outs[0].float() - y2.float()).abs()
-    assert float(d.max()) <= 2.0 ** -7 * float(y2.float().abs().max()) + 1e-6, float(d.max())  # within one bf16 ulp of each other
-    assert float((outs[0].view(torch.int16) == y2.view(torch.int16)).float().mean()) > 0.98
-
-
-def test_refiner_block_wide_repeated_launches_under_load(lib):
-    """150 launches of the fused C = 576 block while a GEMM runs on a second stream: every one bit-identical to the quiet
-    launch (the kernel orders its LDS-DMA with vmcnt(0) + workgroup barriers; a hazard would be timing dependent)."""
-    B, H, W, Cp = 4, 140, 140, 576
-    x = rnd(B, H, W, Cp, seed=1).to(torch.bfloat16).cuda()
-    w, b = (rnd(25, Cp, seed=2, std=0.2)).cuda(), rnd(Cp, seed=3).cuda()
-    pw, pb = rnd(Cp, Cp, seed=4, std=Cp ** -0.5).to(torch.bfloat16).cuda(), rnd(Cp, seed=5).cuda()
-    ref = torch.empty_like(x)
-    torch.cuda.synchronize()
-    ok(lib, lib.roma_op_refiner_block(P(x), P(ref), P(w), P(b), P(pw), P(pb), B, H, W, Cp, BF16, None))
-    torch.cuda.synchronize()
-    A = rnd(8192, 1024, seed=6).to(torch.bfloat16).cuda()
-    Wg = rnd(1024, 1024, seed=7, std=0.03).to(torch.bfloat16).cuda()
-    Cg = torch.empty((8192, 1024), device="cuda", dtype=torch.bfloat16)
-    side = torch.cuda.Stream()
-    out = torch.empty_like(ref)
-    bad = 0
-    for it in range(150):
-        if it % 4 == 0:
-            ok(lib, lib.roma_op_gemm(P(A), 1024, P(Wg), 1024, P(Cg), 1024, 8192, 1024, 1024, 1, 0, 0, 0, None, None, None, 0, 0, 1.0,
-                                     BF16, BF16, C.c_void_p(side.cuda_stream)))
-        out.fill_(float("nan"))
-        ok(lib, lib.roma_op_refiner_block(P(x), P(out), P(w), P(b), P(pw), P(pb), B, H, W, Cp, BF16, None))
-        bad += int(not torch.equal(out.view(torch.int16), ref.view(torch.int16)))
-    torch.cuda.synchronize()
-    assert bad == 0, f"{bad} of 150 launches differ"
+    got = y2.cpu().double()
+    assert torch.isfinite(got).all()
+    err = (got - ref).abs()
+    assert (err <= 1e-2 * ref.abs() + 3e-2).all(), float(err.max())
+    assert float(err.mean()) < 6e-3
 
 
 @pytest.mark.parametrize("Cp,B,H,W", [(24, 2, 13, 10), (24, 1, 75, 301), (24, 3, 3, 200), (24, 1, 290, 150), (144, 2, 13, 10),

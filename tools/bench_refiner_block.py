@@ -1,5 +1,4 @@
-"""refiner_block_kernel<144 | 24> alone at the benchmark's sizes; ROMA_RB_DBG (1 no depthwise phase, 2 no 1x1 phase, 4 no
-output stores, 8 no ring refill) ablates its phases - one process per value (the switch is read once)."""
+"""The fused refiner blocks (C = 144 and C = 24) alone at the benchmark's sizes."""
 import ctypes as C
 import hashlib
 import os
@@ -38,7 +37,7 @@ def run(B, H, W, Cp):
     us = e0.elapsed_time(e1) * 1e3 / n
     gb = 2.0 * B * H * W * Cp * 2 / 1e9
     h = hashlib.sha1(y.cpu().view(torch.int16).numpy().tobytes()).hexdigest()[:12]
-    print(f"dbg={os.environ.get('ROMA_RB_DBG', '0'):>2s} B{B} {H}x{W} C={Cp}: {us:8.1f} us {gb / us * 1e3:6.2f} TB/s  sha1 {h}", flush=True)
+    print(f"B{B} {H}x{W} C={Cp}: {us:8.1f} us {gb / us * 1e3:6.2f} TB/s  sha1 {h}", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,4 +1,4 @@
-"""Who runs next to whom: concurrency analysis of a rocprofv3 --kernel-trace CSV of the two-stream bench (tools/r04_final.sh).
+"""Who runs next to whom: concurrency analysis of a rocprofv3 --kernel-trace CSV of the two-stream bench.
 
     python tools/stream_overlap.py <..._kernel_trace.csv[.gz]>
 
