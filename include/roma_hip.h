@@ -500,6 +500,42 @@ int roma_op_triangulate(const float* matches, const float* certainty, const int*
 int roma_op_depth_consistency(const float* points, const unsigned char* flags, const double* R, const double* t, const double* K_a,
                               const double* K_b, int W_a, int H_a, int W_b, int H_b, int B, int H, int W, double rel_thresh,
                               unsigned char* out_consistent, float* out_err, void* stream);
+/* Image preprocessing: Pillow's 8-bit bicubic resize (Image.resize((w, h), Image.BICUBIC) on a mode-RGB image, which is what
+ * transforms.Resize(size, BICUBIC) does to a PIL image) of a batch of packed RGB images of mixed sizes to one or two target sizes,
+ * then / 255 and the ImageNet mean / std of the matcher's host path - bit-identical to that path (roma_amd/matcher.py:
+ * _pil_to_normalised), restated in numpy by tools/pil_resample_ref.py.  The output is what roma_match takes: float32 NCHW.
+ * Pillow resamples in fixed point in TWO PASSES, HORIZONTAL FIRST, THEN VERTICAL, and the intermediate image is rounded and clamped
+ * to uint8 between the passes (so no float bicubic can match it, and the order matters):
+ *   PRECISION_BITS = 22
+ *   bicubic(x), a = -0.5:  x = |x|;  x < 1: ((a+2)x - (a+3)) x x + 1;   x < 2: (((x-5)x + 8)x - 4) a;   else 0
+ *   coefficients of one axis, in -> out, all in float64, no contraction, sums in index order:
+ *     scale = in / out;  fs = max(scale, 1);  support = 2 fs;  ss = 1 / fs
+ *     for each output xx:  center = (xx + 0.5) scale
+ *         xmin = max(0, (int)(center - support + 0.5));  xmax = min(in, (int)(center + support + 0.5));  n = xmax - xmin
+ *         k[i] = bicubic((i + xmin - center + 0.5) ss), i < n;   ww = sum k[i];   if ww != 0: k[i] /= ww
+ *         K[i] = (int)(k[i] * 2^22 + 0.5) if k[i] >= 0 else (int)(k[i] * 2^22 - 0.5)        ((int) truncates toward zero)
+ *   one pass, per channel:  s = 2^21 + sum_i pixel[xmin + i] * K[i]  (int32);   out = clamp(s >> 22, 0, 255)   (arithmetic shift)
+ *   an axis whose size does not change is skipped (the pass is not run); both unchanged = a copy
+ * then, all in float32, out = (float32(u) / float32(255) - mean_c) / std_c with mean = (0.485, 0.456, 0.406), std = (0.229, 0.224,
+ * 0.225); normalize = 0 stops after the / 255 (what visualize_warp feeds on).  Evaluated through a table of 3 x 256 entries.
+ * src DEVICE u8, 4-byte aligned, src_bytes long: the images, each contiguous [H, W, 3]; desc = {byte offset into src, H, W} per
+ * image (int64 x 3, any offset alignment), once on the HOST (it sizes the grid and the workspace and is validated) and once on the
+ * DEVICE (what the kernels read; 8-byte aligned).  An image whose device descriptor exceeds the largest H or W of the host copy, or
+ * src_bytes, is skipped by the kernels: its output is left unwritten, nothing is read or written out of bounds.  targets_hw HOST
+ * int32 [n_targets, 2] = (h, w), n_targets 1 or 2 (the coarse and the upsample resolution of one matcher from one upload); out0
+ * (and out1 for the second target, NULL when there is one) DEVICE f32 [n_images, 3, h_t, w_t].  workspace: DEVICE, 16-byte aligned,
+ * roma_op_preprocess_workspace(desc_host, n_images, targets_hw, n_targets) bytes (-1 for arguments that are refused): the
+ * normalisation table, the coefficient tables and the uint8 [H, w_t, 3] intermediates (rows padded to whole dwords), in equal
+ * slots sized by the largest image.  Three kernels in one enqueue on `stream` (coefficient and normalisation tables, in float64
+ * with contraction off; horizontal pass; vertical pass + table lookup), no host read, no synchronisation; every output bit is
+ * independent of the batch, of the order of the images and of the run.
+ * Refused on the host before anything is enqueued (nonzero, text in roma_last_error): a null pointer; n_targets not 1 or 2;
+ * n_images < 1 or > 65535; a target below 1 or above 32768; an image with H or W below 1 or above 32768, a negative offset, or
+ * offset + 3 H W > src_bytes; src, desc_dev or workspace not aligned as stated. */
+long roma_op_preprocess_workspace(const long long* desc_host, int n_images, const int* targets_hw, int n_targets);
+int roma_op_preprocess(const unsigned char* src, long long src_bytes, const long long* desc_host, const long long* desc_dev,
+                       int n_images, const int* targets_hw, int n_targets, int normalize, float* out0, float* out1, void* workspace,
+                       void* stream);
 /* ---- Tiny RoMa (romatch/models/tiny.py), matcher side; the XFeat backbone is the caller's (model_zoo/__init__.py:24-27).
  * All tensors f32, channels-last unless noted.  corr_volume (tiny.py:182-196) = roma_op_gemm with A = feats of image B
  * [H1*W1, C], W = feats of image A [H0*W0, C], alpha = 1/sqrt(C), batch = pairs: cv [B, H1*W1, H0*W0]. */

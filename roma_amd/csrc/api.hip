@@ -28,6 +28,7 @@
 #include "pose_refine.h"
 #include "geometry.h"
 #include "triangulate.h"
+#include "preprocess.h"
 
 namespace roma {
 static thread_local std::string g_err;
@@ -615,6 +616,16 @@ int roma_op_depth_consistency(const float* points, const unsigned char* flags, c
                               unsigned char* out_consistent, float* out_err, void* stream) {
   return depth_consistency_launch(points, flags, R, t, K_a, K_b, W_a, H_a, W_b, H_b, B, H, W, rel_thresh, out_consistent, out_err,
                                   S(stream));
+}
+// ---- image preprocessing: Pillow-exact bicubic resize + normalisation (preprocess.hip)
+long roma_op_preprocess_workspace(const long long* desc_host, int n_images, const int* targets_hw, int n_targets) {
+  return preprocess_workspace_bytes(desc_host, n_images, targets_hw, n_targets);
+}
+int roma_op_preprocess(const unsigned char* src, long long src_bytes, const long long* desc_host, const long long* desc_dev,
+                       int n_images, const int* targets_hw, int n_targets, int normalize, float* out0, float* out1, void* workspace,
+                       void* stream) {
+  return preprocess_launch(src, src_bytes, desc_host, desc_dev, n_images, targets_hw, n_targets, normalize, out0, out1, workspace,
+                           S(stream));
 }
 // ---- Tiny RoMa matcher side (tiny.hip)
 int roma_op_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, void* stream) {

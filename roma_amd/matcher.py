@@ -302,6 +302,24 @@ class RegressionMatcher:
                                           ptr(warp), ptr(cert), C.c_void_p(stream)))
         return warp, cert
 
+    def match_images(self, ims_A, ims_B, *, device=None):
+        """`match()` for a batch of decoded images: two sequences of B images each (paths, PIL RGB images, uint8 ndarrays or uint8
+        tensors [H, W, 3], of any sizes), or two single images.  All 2B images are resized and normalised on the device by ONE
+        `roma_amd.preprocess_images` call - to the coarse resolution and, with `upsample_preds`, to `upsample_res` from the same
+        upload - bit-identically to the host path of `match()`; the tensors then take the tensor path of `match()` (chunks of
+        `max_batch`).  Returns what `match()` returns: (warp [B, H, 2W, 4] | [B, H, W, 4], certainty [B, H, 2W] | [B, H, W])."""
+        from .preprocess import preprocess_images
+        if not isinstance(ims_A, (list, tuple)) and not isinstance(ims_B, (list, tuple)):
+            ims_A, ims_B = [ims_A], [ims_B]
+        if not (isinstance(ims_A, (list, tuple)) and isinstance(ims_B, (list, tuple))) or len(ims_A) != len(ims_B):
+            raise ValueError("match_images: ims_A and ims_B must be two single images or two sequences of equal length")
+        B = len(ims_A)
+        sizes = [(self.h_resized, self.w_resized)] + ([tuple(self.upsample_res)] if self.upsample_preds else [])
+        out = preprocess_images(list(ims_A) + list(ims_B), sizes, normalize=True, device=device if device is not None else self.device)
+        if not self.upsample_preds:
+            return self.match(out[0][:B], out[0][B:])
+        return self.match(out[0][:B], out[0][B:], im_A_high_res=out[1][:B], im_B_high_res=out[1][B:])
+
     # ------------------------------------------------------------------ forward / forward_symmetric / backbone features
     _SCALES = (16, 8, 4, 2, 1)
     _FEAT_C = {16: 1024, 8: 512, 4: 256, 2: 128, 1: 64}
