@@ -1,7 +1,7 @@
 // Depthwise 5x5 (+folded BN, ReLU) for the WIDE ConvRefiner scales (C = 576 / 1152 / 1408; 16-bit storage) - the
-// "wave-private ring" form of dwconv5x5_kernel (elementwise.hip).  romatch/models/matcher.py:106-122.
+// "wave-private ring" form of dwconv5x5_kernel (dwconv5x5.hip).  romatch/models/matcher.py:106-122.
 //
-// What bounds the register-prefetch kernel (elementwise.hip) is not bytes and not FMAs: at 254 VGPRs it runs two waves
+// What bounds the register-prefetch kernel (dwconv5x5.hip) is not bytes and not FMAs: at 254 VGPRs it runs two waves
 // per SIMD, each with ONE input row (8 x 8-byte loads per lane) in flight, i.e. 32 KiB per CU - against an HBM latency of
 // 2-3 us under load that is ~4 TB/s by Little's law - and its waves issue only 42 % of their cycles
 // (profiles/r02_pmc_sq_summary.json).  The LDS-DMA ring of round 1 fixed the depth but bought a workgroup barrier per

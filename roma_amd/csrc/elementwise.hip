@@ -1,32 +1,16 @@
-// HBM-bound kernels of the RoMa match() path for gfx950 (see elementwise.h).
-// Conventions: channels-last activations, 16-byte (or 8-byte for bf16 quads) vector accesses,
-// one wave64 per row for row reductions, f32 math everywhere.
+// HBM-bound kernels of the RoMa match() path for gfx950 (see elementwise.h); the ConvRefiner's are refiner_input.hip,
+// refiner_out.hip and dwconv5x5.hip.  Conventions: channels-last activations, 16-byte (or 8-byte for bf16 quads) vector
+// accesses, one wave64 per row for row reductions, f32 math everywhere.
 #include <algorithm>
-#include "elementwise.h"
-#include "tuning.h"
+#include "elementwise_device.h"
 #include "chol_diag.h"
-#include <stdio.h>
-
-#include <stdlib.h>
-#include "gemm.h"  // DT_*
 
 namespace roma {
-
-#define ROMA_DT_SWITCH(dt, T, ...)            \
-  if ((dt) == DT_F32) { using T = float; __VA_ARGS__; } else { using T = bf16_t; __VA_ARGS__; }
 
 __device__ inline float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
   return v;
-}
-
-// torch.linspace(-1+1/n, 1-1/n, n)[i] in f32 (symmetric two-sided evaluation like ATen)
-__device__ inline float pix_coord(int i, int n) {
-  const float start = (float)(-1.0 + 1.0 / n), end = (float)(1.0 - 1.0 / n);
-  if (n == 1) return start;
-  const float step = (end - start) / (float)(n - 1);
-  return (i < n / 2) ? start + step * (float)i : end - step * (float)(n - 1 - i);
 }
 
 // ------------------------------------------------------------------ LayerNorm
@@ -532,821 +516,6 @@ int cls_to_flow_launch(const float* logits, long ld, float* flow, float* cert, l
   ROMA_REQUIRE(ld % 4 == 0 && ld >= 4097, "cls_to_flow: bad leading dimension");
   dim3 grid((unsigned)((M + 3) / 4));
   hipLaunchKernelGGL(cls_to_flow_kernel, grid, dim3(256), 0, s, logits, ld, flow, cert, M);
-  ROMA_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------ refiner input: [x | grid_sample(y, flow) | disp_emb | . | 0]
-template <typename T>
-__global__ __launch_bounds__(256) void refiner_input_kernel(const RefinerInputArgs a) {
-  const int lane = threadIdx.x & 63;
-  const long HW = (long)a.H * a.W;
-  const long pix = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (pix >= (long)a.B * HW) return;
-  const int b = (int)(pix / HW);
-  const long p = pix - (long)b * HW;
-  const int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
-  const T* feat = reinterpret_cast<const T*>(a.feat);
-  const T* fq = feat + ((long)b * HW + p) * a.ldf;
-  const int simg = (b + a.shift) % a.nimg;
-  const T* fs = feat + (long)simg * HW * a.ldf;
-  T* d = reinterpret_cast<T*>(a.d) + pix * a.ldd;
-  const float wx = a.flow[pix * 2 + 0], wy = a.flow[pix * 2 + 1];
-  float ix = ((wx + 1.f) * a.W - 1.f) * 0.5f, iy = ((wy + 1.f) * a.H - 1.f) * 0.5f;
-  ix = fminf(fmaxf(ix, -1.0e6f), 1.0e6f);
-  iy = fminf(fmaxf(iy, -1.0e6f), 1.0e6f);
-  const float fx0 = floorf(ix), fy0 = floorf(iy);
-  const int x0 = (int)fx0, y0 = (int)fy0;
-  const float tx = ix - fx0, ty = iy - fy0;
-  const float wgt[4] = {(1.f - tx) * (1.f - ty), tx * (1.f - ty), (1.f - tx) * ty, tx * ty};
-  bool ok[4];
-  long off[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int yy = y0 + (t >> 1), xx = x0 + (t & 1);
-    ok[t] = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
-    off[t] = ((long)yy * a.W + xx) * a.ldf;
-  }
-  for (int c = lane * 4; c < a.C; c += 256) {
-    ElemIO<T>::st4(d + c, ElemIO<T>::ld4(fq + c));
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-      if (ok[t]) {
-        const f32x4 v = ElemIO<T>::ld4(fs + off[t] + c);
-        acc += wgt[t] * v;
-      }
-    ElemIO<T>::st4(d + a.C + c, acc);
-  }
-  const float dx = a.disp_scale * (wx - pix_coord(x, a.W)), dy = a.disp_scale * (wy - pix_coord(y, a.H));
-  for (int e = lane; e < a.E; e += 64) {
-    const float v = a.emb_w[e * 2 + 0] * dx + a.emb_w[e * 2 + 1] * dy + a.emb_b[e];
-    ElemIO<T>::st(d + 2 * a.C + e, v);
-  }
-  for (long c = 2 * a.C + a.E + a.Kcorr + lane; c < a.ldd; c += 64) ElemIO<T>::st(d + c, 0.f);
-}
-
-// small / odd channel counts (stride-1 refiner: C = 9): one thread per (pixel, padded channel slot)
-template <typename T>
-__global__ __launch_bounds__(256) void refiner_input_small_kernel(const RefinerInputArgs a) {
-  const long HW = (long)a.H * a.W;
-  const int slots = (int)a.ldd;
-  const long total = (long)a.B * HW * slots;
-  const T* feat = reinterpret_cast<const T*>(a.feat);
-  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-    const int c = (int)(idx % slots);
-    const long pix = idx / slots;
-    const int b = (int)(pix / HW);
-    const long p = pix - (long)b * HW;
-    T* d = reinterpret_cast<T*>(a.d) + pix * a.ldd;
-    if (c < a.C) {
-      ElemIO<T>::st(d + c, ElemIO<T>::ld(feat + ((long)b * HW + p) * a.ldf + c));
-    } else if (c < 2 * a.C) {
-      const int cc = c - a.C;
-      const int simg = (b + a.shift) % a.nimg;
-      const T* fs = feat + (long)simg * HW * a.ldf;
-      const float wx = a.flow[pix * 2 + 0], wy = a.flow[pix * 2 + 1];
-      float ix = ((wx + 1.f) * a.W - 1.f) * 0.5f, iy = ((wy + 1.f) * a.H - 1.f) * 0.5f;
-      ix = fminf(fmaxf(ix, -1.0e6f), 1.0e6f);
-      iy = fminf(fmaxf(iy, -1.0e6f), 1.0e6f);
-      const float fx0 = floorf(ix), fy0 = floorf(iy);
-      const int x0 = (int)fx0, y0 = (int)fy0;
-      const float tx = ix - fx0, ty = iy - fy0;
-      const float wgt[4] = {(1.f - tx) * (1.f - ty), tx * (1.f - ty), (1.f - tx) * ty, tx * ty};
-      float acc = 0.f;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int yy = y0 + (t >> 1), xx = x0 + (t & 1);
-        if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W)
-          acc += wgt[t] * ElemIO<T>::ld(fs + ((long)yy * a.W + xx) * a.ldf + cc);
-      }
-      ElemIO<T>::st(d + c, acc);
-    } else if (c < 2 * a.C + a.E) {
-      const int e = c - 2 * a.C;
-      const int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
-      const float dx = a.disp_scale * (a.flow[pix * 2 + 0] - pix_coord(x, a.W));
-      const float dy = a.disp_scale * (a.flow[pix * 2 + 1] - pix_coord(y, a.H));
-      ElemIO<T>::st(d + c, a.emb_w[e * 2 + 0] * dx + a.emb_w[e * 2 + 1] * dy + a.emb_b[e]);
-    } else if (c >= 2 * a.C + a.E + a.Kcorr) {
-      ElemIO<T>::st(d + c, 0.f);
-    }
-  }
-}
-
-// stride-1 refiner (C = 9, E = 6, 24 output channels): one thread per pixel, whole rows as 16-byte vectors
-template <typename T> struct VecIO;
-template <> struct VecIO<float> {
-  static constexpr int CV = 4;
-  typedef f32x4 Raw;  // 16 bytes as loaded; cvt() turns them into CV floats (the same values ld() delivers)
-  __device__ static inline Raw ldraw(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-  __device__ static inline void cvt(const Raw& x, float* v) { v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3]; }
-  __device__ static inline void ld(const float* p, float* v) {
-    const f32x4 x = *reinterpret_cast<const f32x4*>(p);
-    v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
-  }
-  __device__ static inline void st(float* p, const float* v) { *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]}; }
-};
-template <> struct VecIO<bf16_t> {
-  static constexpr int CV = 8;
-  typedef uint4 Raw;
-  __device__ static inline Raw ldraw(const bf16_t* p) { return *reinterpret_cast<const uint4*>(p); }
-  __device__ static inline void cvt(const Raw& u, float* v) {
-    v[0] = h16_lo(u.x); v[1] = h16_hi(u.x);
-    v[2] = h16_lo(u.y); v[3] = h16_hi(u.y);
-    v[4] = h16_lo(u.z); v[5] = h16_hi(u.z);
-    v[6] = h16_lo(u.w); v[7] = h16_hi(u.w);
-  }
-  __device__ static inline void ld(const bf16_t* p, float* v) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    v[0] = h16_lo(u.x); v[1] = h16_hi(u.x);
-    v[2] = h16_lo(u.y); v[3] = h16_hi(u.y);
-    v[4] = h16_lo(u.z); v[5] = h16_hi(u.z);
-    v[6] = h16_lo(u.w); v[7] = h16_hi(u.w);
-  }
-  __device__ static inline void st(bf16_t* p, const float* v) {
-    uint4 u;
-    u.x = pack_bf16x2(v[0], v[1]);
-    u.y = pack_bf16x2(v[2], v[3]);
-    u.z = pack_bf16x2(v[4], v[5]);
-    u.w = pack_bf16x2(v[6], v[7]);
-    *reinterpret_cast<uint4*>(p) = u;
-  }
-};
-
-template <typename T, int C, int E>
-__global__ __launch_bounds__(256) void refiner_input_pix_kernel(const RefinerInputArgs a) {
-  constexpr int LDF = 16, LDD = 24;
-  const long HW = (long)a.H * a.W;
-  const long pix = (long)blockIdx.x * 256 + threadIdx.x;
-  if (pix >= (long)a.B * HW) return;
-  const int b = (int)(pix / HW);
-  const long p = pix - (long)b * HW;
-  const int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
-  const T* feat = reinterpret_cast<const T*>(a.feat);
-  const T* fq = feat + ((long)b * HW + p) * LDF;
-  const int simg = (b + a.shift) % a.nimg;
-  const T* fs = feat + (long)simg * HW * LDF;
-  if constexpr (sizeof(T) == 2) {
-    // bf16: 16-byte accesses - a pixel's 16 feature channels are two loads (were three 8-byte ones), its 24 output channels
-    // three stores (were six): this kernel is bound by the number of memory instructions, not by bytes
-    static_assert(C <= 16 && 2 * C + E <= LDD && LDD == 24 && LDF == 16, "layout");
-    float q[16], xh[16];
-    VecIO<T>::ld(fq, q);
-    VecIO<T>::ld(fq + 8, q + 8);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) xh[j] = 0.f;
-    const float wx = a.flow[pix * 2 + 0], wy = a.flow[pix * 2 + 1];
-    float ix = ((wx + 1.f) * a.W - 1.f) * 0.5f, iy = ((wy + 1.f) * a.H - 1.f) * 0.5f;
-    ix = fminf(fmaxf(ix, -1.0e6f), 1.0e6f);
-    iy = fminf(fmaxf(iy, -1.0e6f), 1.0e6f);
-    const float fx0 = floorf(ix), fy0 = floorf(iy);
-    const int x0 = (int)fx0, y0 = (int)fy0;
-    const float tx = ix - fx0, ty = iy - fy0;
-    const float wgt[4] = {(1.f - tx) * (1.f - ty), tx * (1.f - ty), (1.f - tx) * ty, tx * ty};
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int yy = y0 + (t >> 1), xx = x0 + (t & 1);
-      if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) {
-        const T* r = fs + ((long)yy * a.W + xx) * LDF;
-        float v[16];
-        VecIO<T>::ld(r, v);
-        VecIO<T>::ld(r + 8, v + 8);
-#pragma unroll
-        for (int j = 0; j < C; ++j) xh[j] += wgt[t] * v[j];
-      }
-    }
-    const float dx = a.disp_scale * (wx - pix_coord(x, a.W)), dy = a.disp_scale * (wy - pix_coord(y, a.H));
-    float o[LDD];
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      o[c] = q[c];
-      o[C + c] = xh[c];
-    }
-#pragma unroll
-    for (int e = 0; e < E; ++e) o[2 * C + e] = a.emb_w[e * 2 + 0] * dx + a.emb_w[e * 2 + 1] * dy + a.emb_b[e];
-#pragma unroll
-    for (int c = 2 * C + E; c < LDD; ++c) o[c] = 0.f;
-    T* d = reinterpret_cast<T*>(a.d) + pix * LDD;
-#pragma unroll
-    for (int c8 = 0; c8 < LDD / 8; ++c8) VecIO<T>::st(d + c8 * 8, o + c8 * 8);
-    return;
-  }
-  float q[12], xh[12];
-#pragma unroll
-  for (int c4 = 0; c4 < 3; ++c4) {
-    const f32x4 v = ElemIO<T>::ld4(fq + c4 * 4);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      q[c4 * 4 + j] = v[j];
-      xh[c4 * 4 + j] = 0.f;
-    }
-  }
-  const float wx = a.flow[pix * 2 + 0], wy = a.flow[pix * 2 + 1];
-  float ix = ((wx + 1.f) * a.W - 1.f) * 0.5f, iy = ((wy + 1.f) * a.H - 1.f) * 0.5f;
-  ix = fminf(fmaxf(ix, -1.0e6f), 1.0e6f);
-  iy = fminf(fmaxf(iy, -1.0e6f), 1.0e6f);
-  const float fx0 = floorf(ix), fy0 = floorf(iy);
-  const int x0 = (int)fx0, y0 = (int)fy0;
-  const float tx = ix - fx0, ty = iy - fy0;
-  const float wgt[4] = {(1.f - tx) * (1.f - ty), tx * (1.f - ty), (1.f - tx) * ty, tx * ty};
-  // (guarded taps on purpose: the branch-free form that helps the vector kernel below - clamped address + select - was
-  //  measured SLOWER here, 0.94 vs 0.78 ms per step)
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int yy = y0 + (t >> 1), xx = x0 + (t & 1);
-    if (yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) {
-      const T* r = fs + ((long)yy * a.W + xx) * LDF;
-#pragma unroll
-      for (int c4 = 0; c4 < 3; ++c4) {
-        const f32x4 v = ElemIO<T>::ld4(r + c4 * 4);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xh[c4 * 4 + j] += wgt[t] * v[j];
-      }
-    }
-  }
-  const float dx = a.disp_scale * (wx - pix_coord(x, a.W)), dy = a.disp_scale * (wy - pix_coord(y, a.H));
-  float o[LDD];
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    o[c] = q[c];
-    o[C + c] = xh[c];
-  }
-#pragma unroll
-  for (int e = 0; e < E; ++e) o[2 * C + e] = a.emb_w[e * 2 + 0] * dx + a.emb_w[e * 2 + 1] * dy + a.emb_b[e];
-#pragma unroll
-  for (int c = 2 * C + E; c < LDD; ++c) o[c] = 0.f;
-  T* d = reinterpret_cast<T*>(a.d) + pix * LDD;
-#pragma unroll
-  for (int c4 = 0; c4 < LDD / 4; ++c4) ElemIO<T>::st4(d + c4 * 4, f32x4{o[c4 * 4], o[c4 * 4 + 1], o[c4 * 4 + 2], o[c4 * 4 + 3]});
-}
-
-// ------------------------------------------------------------------ depthwise 5x5 + BN(folded) + ReLU
-// One thread = one 16-byte channel vector (4 f32 / 8 bf16) x 4 consecutive x positions of one row; the 5x8 input
-// window is walked row by row so each loaded vector feeds up to 4 outputs.  Workgroups are remapped so that each
-// XCD (private L2) owns a contiguous band of image rows: the 5-row vertical reuse then hits that XCD's L2 instead of
-// being replicated in all eight.
-// refiner input, vectorised: LPP lanes (a power of two) share one pixel, 64/LPP pixels per wave, 16 bytes per lane
-// per access.  The wave-per-pixel kernel above left 48 of 64 lanes idle at C = 64 (stride-2 refiner, 4.2 M pixels).
-template <typename T>
-__global__ __launch_bounds__(256) void refiner_input_vec_kernel(const RefinerInputArgs a, int lpp) {
-  constexpr int CV = VecIO<T>::CV;
-  const int lane = threadIdx.x & 63;
-  const int sub = lane & (lpp - 1), pw = lane / lpp, ppw = 64 / lpp;
-  const long HW = (long)a.H * a.W;
-  const long pix = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * ppw + pw;
-  if (pix >= (long)a.B * HW) return;
-  const int b = (int)(pix / HW);
-  const long p = pix - (long)b * HW;
-  const int y = (int)(p / a.W), x = (int)(p - (long)y * a.W);
-  const T* feat = reinterpret_cast<const T*>(a.feat);
-  const T* fq = feat + ((long)b * HW + p) * a.ldf;
-  const int simg = (b + a.shift) % a.nimg;
-  const T* fs = feat + (long)simg * HW * a.ldf;
-  T* d = reinterpret_cast<T*>(a.d) + pix * a.ldd;
-  const float wx = a.flow[pix * 2 + 0], wy = a.flow[pix * 2 + 1];
-  float ix = ((wx + 1.f) * a.W - 1.f) * 0.5f, iy = ((wy + 1.f) * a.H - 1.f) * 0.5f;
-  ix = fminf(fmaxf(ix, -1.0e6f), 1.0e6f);
-  iy = fminf(fmaxf(iy, -1.0e6f), 1.0e6f);
-  const float fx0 = floorf(ix), fy0 = floorf(iy);
-  const int x0 = (int)fx0, y0 = (int)fy0;
-  const float tx = ix - fx0, ty = iy - fy0;
-  const float wgt[4] = {(1.f - tx) * (1.f - ty), tx * (1.f - ty), (1.f - tx) * ty, tx * ty};
-  bool ok[4];
-  long off[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int yy = y0 + (t >> 1), xx = x0 + (t & 1);
-    ok[t] = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;  // zeros padding: out-of-image taps are dropped (select below)
-    off[t] = ((long)min(max(yy, 0), a.H - 1) * a.W + min(max(xx, 0), a.W - 1)) * a.ldf;  // always a valid address
-  }
-  for (int c = sub * CV; c < a.C; c += lpp * CV) {
-    *reinterpret_cast<uint4*>(d + c) = *reinterpret_cast<const uint4*>(fq + c);
-    float r[CV];
-#pragma unroll
-    for (int j = 0; j < CV; ++j) r[j] = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {  // branch-free: the four tap loads of a channel piece are in flight together
-      float tv[CV];
-      VecIO<T>::ld(fs + off[t] + c, tv);
-#pragma unroll
-      for (int j = 0; j < CV; ++j) r[j] = ok[t] ? r[j] + wgt[t] * tv[j] : r[j];
-    }
-    VecIO<T>::st(d + a.C + c, r);
-  }
-  const float dx = a.disp_scale * (wx - pix_coord(x, a.W)), dy = a.disp_scale * (wy - pix_coord(y, a.H));
-  for (int e = sub; e < a.E; e += lpp) {
-    const float v = a.emb_w[e * 2 + 0] * dx + a.emb_w[e * 2 + 1] * dy + a.emb_b[e];
-    ElemIO<T>::st(d + 2 * a.C + e, v);
-  }
-  for (long c = 2 * a.C + a.E + a.Kcorr + sub; c < a.ldd; c += lpp) ElemIO<T>::st(d + c, 0.f);
-}
-
-int refiner_input_launch(const RefinerInputArgs& a, hipStream_t s) {
-  const long npix = (long)a.B * a.H * a.W;
-  // grid_sample warp + concat writer (matcher.py:132-148,166).  Algorithmic bytes: x and the sampled y
-  // read once (2 s C), the flow (8), the written row of d without the correlation slice another kernel fills
-  const double es = a.dt == DT_F32 ? 4.0 : 2.0;
-  char pname[64];
-  snprintf(pname, sizeof pname, "refiner_input_warp<C=%d,%s>", a.C, a.dt == DT_F32 ? "f32" : ROMA_H16_NAME);
-  ProfScope ps(pname, (double)npix * (2.0 * a.C * es + 8.0 + (double)(a.ldd - a.Kcorr) * es), "byte", s);
-  if (a.C == 9 && a.E == 6 && a.Kcorr == 0 && a.ldf == 16 && a.ldd == 24) {
-    dim3 grid((unsigned)((npix + 255) / 256));
-    ROMA_DT_SWITCH(a.dt, T, hipLaunchKernelGGL((refiner_input_pix_kernel<T, 9, 6>), grid, dim3(256), 0, s, a));
-    ROMA_LAUNCH_CHECK();
-    return 0;
-  }
-  if (a.C % 4 != 0 || a.C < 32) {
-    const long total = npix * a.ldd;
-    dim3 grid((unsigned)std::min<long>((total + 255) / 256, 1 << 20));
-    ROMA_DT_SWITCH(a.dt, T, hipLaunchKernelGGL(refiner_input_small_kernel<T>, grid, dim3(256), 0, s, a));
-    ROMA_LAUNCH_CHECK();
-    return 0;
-  }
-  ROMA_REQUIRE(a.ldf % 4 == 0 && a.ldd % 4 == 0, "refiner_input: strides must be multiples of 4");
-  {
-    const int cv = a.dt == DT_F32 ? 4 : 8;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(a.feat) | reinterpret_cast<uintptr_t>(a.d)) & 15) == 0;
-    const bool vec_off = tuning(SW_RI_VEC) == 0;  // A/B debugging only
-    if (!vec_off && aligned && a.C % cv == 0 && a.ldf % cv == 0 && a.ldd % cv == 0) {
-      int lpp = 1;
-      while (lpp < 64 && lpp * cv < a.C) lpp *= 2;
-      const long per_wg = 4 * (64 / lpp);
-      dim3 vgrid((unsigned)((npix + per_wg - 1) / per_wg));
-      ROMA_DT_SWITCH(a.dt, T, hipLaunchKernelGGL(refiner_input_vec_kernel<T>, vgrid, dim3(256), 0, s, a, lpp));
-      ROMA_LAUNCH_CHECK();
-      return 0;
-    }
-  }
-  dim3 grid((unsigned)((npix + 3) / 4));
-  ROMA_DT_SWITCH(a.dt, T, hipLaunchKernelGGL(refiner_input_kernel<T>, grid, dim3(256), 0, s, a));
-  ROMA_LAUNCH_CHECK();
-  return 0;
-}
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
-
-// Rolling-window form.  The stencil is NOT HBM-bound on MI355X when written naively: 25 MAC per 2-byte element put
-// it on the VALU / vector-L1 path (a first version re-loaded the 25 weight vectors and 6 input rows per 8 outputs
-// and ran at 1.4 TB/s with the texture path saturated).  Here one thread owns 4 channels x 4 x-positions and walks a
-// strip of rows top to bottom:
-//   * its 25 x 4 weights stay in registers for the whole strip (one load per thread, not per output),
-//   * each input row is loaded ONCE (8 vectors) and feeds the 5 output rows it touches (5 rolling accumulator
-//     slots that are rotated after every row), i.e. 200 packed-f32 FMAs (v_pk_fma_f32) per 8 loads,
-//   * the next input row is prefetched while the current one is multiplied.
-// Workgroups are remapped so each XCD owns a contiguous band of strips (private L2 sees the 4-row halo once).
-template <typename T> struct RawVec;
-template <> struct RawVec<float> {
-  typedef f32x4 raw;
-  __device__ static inline raw ld(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-  __device__ static inline raw zero() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
-  __device__ static inline raw mask(raw r, uint32_t m) {  // bitwise AND keeps the load unconditional (no branch)
-    return f32x4{__uint_as_float(__float_as_uint(r[0]) & m), __uint_as_float(__float_as_uint(r[1]) & m),
-                 __uint_as_float(__float_as_uint(r[2]) & m), __uint_as_float(__float_as_uint(r[3]) & m)};
-  }
-  __device__ static inline void cvt(raw r, f32x2& a, f32x2& b) { a = f32x2{r[0], r[1]}; b = f32x2{r[2], r[3]}; }
-  __device__ static inline void st(float* p, f32x2 a, f32x2 b) { *reinterpret_cast<f32x4*>(p) = f32x4{a[0], a[1], b[0], b[1]}; }
-};
-template <> struct RawVec<bf16_t> {
-  typedef uint2 raw;
-  __device__ static inline raw ld(const bf16_t* p) { return *reinterpret_cast<const uint2*>(p); }
-  __device__ static inline raw zero() { return make_uint2(0, 0); }
-  __device__ static inline raw mask(raw r, uint32_t m) { return make_uint2(r.x & m, r.y & m); }
-  __device__ static inline void cvt(raw r, f32x2& a, f32x2& b) {
-    a = f32x2{h16_lo(r.x), h16_hi(r.x)};
-    b = f32x2{h16_lo(r.y), h16_hi(r.y)};
-  }
-  __device__ static inline void st(bf16_t* p, f32x2 a, f32x2 b) {
-    uint2 u;
-    u.x = pack_bf16x2(a[0], a[1]);
-    u.y = pack_bf16x2(b[0], b[1]);
-    *reinterpret_cast<uint2*>(p) = u;
-  }
-};
-
-template <typename T>
-__global__ __launch_bounds__(256, 2) void dwconv5x5_kernel(const T* in, T* out, const float* w, const float* bias, int B,
-                                                           int H, int W, int Cp, int SY, int GC, int nchunk, int nxg,
-                                                           int nblocks) {
-  typedef typename RawVec<T>::raw raw_t;
-  extern __shared__ __attribute__((aligned(16))) float wsm[];  // [25][GC*4] weights + [GC*4] bias of this channel chunk
-  const int per_xcd = (nblocks + 7) / 8;
-  const long lb = (long)(blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-  if (lb >= nblocks) return;
-  const int chunk = (int)(lb % nchunk);
-  long r = lb / nchunk;
-  const int xg = (int)(r % nxg);
-  r /= nxg;
-  const int yt = (H + SY - 1) / SY;
-  const int ys = (int)(r % yt) * SY;
-  const int b = (int)(r / yt);
-  const int XQ = 256 / GC;
-  const int cg = threadIdx.x % GC, xq = threadIdx.x / GC;
-  const int c0 = chunk * GC * 4;
-  constexpr int cw = 256;  // fixed LDS row stride: weight reads become base + immediate offset
-  // stage this chunk's 25 x (GC*4) weights + bias as float4s; all loads are issued before the first LDS write
-  // (a dword-at-a-time loop serialised 26 dependent global loads = ~40 us per workgroup)
-  {
-    const int q4 = GC;                   // float4 columns actually used per row
-    const int nvec = 26 * q4;            // <= 26 * 64
-    f32x4 tmp[7];
-#pragma unroll
-    for (int it = 0; it < 7; ++it) {
-      const int i = threadIdx.x + 256 * it;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (i < nvec) {
-        const int t = i / q4, cq = i - t * q4;
-        const int ch = c0 + cq * 4;
-        if (ch < Cp) v = *reinterpret_cast<const f32x4*>(t < 25 ? w + (long)t * Cp + ch : bias + ch);
-      }
-      tmp[it] = v;
-    }
-#pragma unroll
-    for (int it = 0; it < 7; ++it) {
-      const int i = threadIdx.x + 256 * it;
-      if (i < nvec) {
-        const int t = i / q4, cq = i - t * q4;
-        *reinterpret_cast<f32x4*>(&wsm[t * cw + cq * 4]) = tmp[it];
-      }
-    }
-  }
-  __syncthreads();
-  const int c = c0 + cg * 4;
-  const int xb = (xg * XQ + xq) * 4;
-  if (xq >= XQ || c >= Cp || xb >= W) return;
-  const int sy = min(SY, H - ys);
-
-  const f32x4 bx = *reinterpret_cast<const f32x4*>(&wsm[25 * cw + cg * 4]);
-  const f32x2 bias0 = f32x2{bx[0], bx[1]}, bias1 = f32x2{bx[2], bx[3]};
-  f32x2 acc[5][4][2];
-#pragma unroll
-  for (int s5 = 0; s5 < 5; ++s5)
-#pragma unroll
-    for (int px = 0; px < 4; ++px) {
-      acc[s5][px][0] = bias0;
-      acc[s5][px][1] = bias1;
-    }
-  bool colok[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) colok[j] = (xb - 2 + j >= 0) && (xb - 2 + j < W);
-  long colofs[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) colofs[j] = (long)min(max(xb - 2 + j, 0), W - 1) * Cp;
-  const T* base = in + ((long)b * H * W) * Cp + c;
-  T* obase = out + ((long)b * H * W) * Cp + c;
-
-// branch-free row load: out-of-image taps read a clamped (valid) address and are zeroed by a select afterwards
-#define ROMA_DW_LOAD_ROW(TT, DST)                                                                         \
-  {                                                                                                       \
-    const int yy_ = ys - 2 + (TT);                                                                        \
-    const bool rok_ = yy_ >= 0 && yy_ < H;                                                                \
-    const T* rowp_ = base + (long)min(max(yy_, 0), H - 1) * W * Cp;                                       \
-    _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                       \
-      DST[j] = RawVec<T>::mask(RawVec<T>::ld(rowp_ + colofs[j]), (rok_ && colok[j]) ? 0xffffffffu : 0u);  \
-    }                                                                                                     \
-  }
-
-  // acc[k] holds output row o = t - 4 + k while input row t is processed (tap row ky = 4 - k)
-  raw_t cur[8], nxt[8];
-  ROMA_DW_LOAD_ROW(0, cur);
-#pragma nounroll
-  for (int t = 0; t < sy + 4; ++t) {
-    ROMA_DW_LOAD_ROW(t + 1, nxt);
-    f32x2 v[8][2];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) RawVec<T>::cvt(cur[j], v[j][0], v[j][1]);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-      const int ky = 4 - k;
-#pragma unroll
-      for (int kx = 0; kx < 5; ++kx) {
-        const f32x4 wx = *reinterpret_cast<const f32x4*>(&wsm[(ky * 5 + kx) * cw + cg * 4]);
-        const f32x2 w0 = f32x2{wx[0], wx[1]}, w1 = f32x2{wx[2], wx[3]};
-#pragma unroll
-        for (int px = 0; px < 4; ++px) {
-          acc[k][px][0] = v[px + kx][0] * w0 + acc[k][px][0];
-          acc[k][px][1] = v[px + kx][1] * w1 + acc[k][px][1];
-        }
-      }
-    }
-    const int o = t - 4;
-    if (o >= 0) {
-      T* orow = obase + ((long)(ys + o) * W + xb) * Cp;
-#pragma unroll
-      for (int px = 0; px < 4; ++px) {
-        if (xb + px < W) {
-          f32x2 a0 = acc[0][px][0], a1 = acc[0][px][1];
-          a0 = f32x2{fmaxf(a0[0], 0.f), fmaxf(a0[1], 0.f)};
-          a1 = f32x2{fmaxf(a1[0], 0.f), fmaxf(a1[1], 0.f)};
-          RawVec<T>::st(orow + (long)px * Cp, a0, a1);
-        }
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int px = 0; px < 4; ++px) {
-        acc[k][px][0] = acc[k + 1][px][0];
-        acc[k][px][1] = acc[k + 1][px][1];
-      }
-#pragma unroll
-    for (int px = 0; px < 4; ++px) {
-      acc[4][px][0] = bias0;
-      acc[4][px][1] = bias1;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) cur[j] = nxt[j];
-  }
-}
-
-#undef ROMA_DW_LOAD_ROW
-
-int dwconv5x5_launch(const void* in, void* out, const float* w, const float* bias, int B, int H, int W, int Cp,
-                     int dt, hipStream_t s) {
-  ROMA_REQUIRE(Cp % 4 == 0, "dwconv5x5: padded channel count must be a multiple of 4");
-  ROMA_REQUIRE(in != out, "dwconv5x5: in and out must not alias");
-  {  // wide 16-bit problems: the wave-private LDS-DMA ring form (dwconv_ring.hip), bit-identical
-    const int rc = dwconv5x5_ring_try_launch(in, out, w, bias, B, H, W, Cp, dt, s);
-    if (rc <= 0) return rc;
-  }
-  const int CG = Cp / 4;
-  const int nchunk = (CG + 63) / 64;
-  const int GC = (CG + nchunk - 1) / nchunk;  // channel groups (of 4) per workgroup, <= 64
-  const int XQ = 256 / GC;                    // x tiles (of 4 pixels) per workgroup
-  const int nxg = ((W + 3) / 4 + XQ - 1) / XQ;
-  // strip height: SY + 4 input rows are read per strip, so 36-row strips cost 11 % extra rows against 25 % for
-  // 16-row strips - as long as there are still enough workgroups to fill 256 CUs x 2
-  int SY = 36;
-  if ((long)B * ((H + 35) / 36) * nxg * nchunk < 1024) SY = 16;
-  const long nb = (long)B * ((H + SY - 1) / SY) * nxg * nchunk;
-  const int nblocks = (int)nb;
-  dim3 grid((unsigned)(((nblocks + 7) / 8) * 8));
-  const size_t lds = (size_t)26 * 256 * sizeof(float);  // fixed 256-float rows (see kernel)
-  ProfScope ps(dt == DT_F32 ? "dwconv5x5_kernel<f32>" : "dwconv5x5_kernel<" ROMA_H16_NAME ">",
-               2.0 * (double)B * H * W * Cp * (dt == DT_F32 ? 4.0 : 2.0), "byte", s);
-  ROMA_DT_SWITCH(dt, T, hipLaunchKernelGGL(dwconv5x5_kernel<T>, grid, dim3(256), lds, s, (const T*)in, (T*)out, w, bias, B, H, W, Cp, SY, GC, nchunk, nxg, nblocks));
-  ROMA_LAUNCH_CHECK();
-  return 0;
-}
-
-// ------------------------------------------------------------------ out_conv + flow / certainty update
-template <typename T, int G>
-__global__ __launch_bounds__(256) void refiner_out_kernel(const T* d, long ldd, const float* w, const float* bb, float* flow,
-                                                          float* cert, long M, int Cp, float sx, float sy) {
-  const int lane = threadIdx.x & 63;
-  const int sub = lane % G, rw = lane / G;
-  constexpr int RPW = 64 / G;
-  const long row = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + rw;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-  if (row < M) {
-    for (int c = sub * 4; c < Cp; c += G * 4) {
-      const f32x4 v = ElemIO<T>::ld4(d + row * ldd + c);
-      const f32x4 w0 = *reinterpret_cast<const f32x4*>(w + c);
-      const f32x4 w1 = *reinterpret_cast<const f32x4*>(w + Cp + c);
-      const f32x4 w2 = *reinterpret_cast<const f32x4*>(w + 2 * Cp + c);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        a0 = fmaf(v[j], w0[j], a0);
-        a1 = fmaf(v[j], w1[j], a1);
-        a2 = fmaf(v[j], w2[j], a2);
-      }
-    }
-  }
-#pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) {
-    a0 += __shfl_xor(a0, off);
-    a1 += __shfl_xor(a1, off);
-    a2 += __shfl_xor(a2, off);
-  }
-  if (row < M && sub == 0) {
-    flow[row * 2 + 0] += sx * (a0 + bb[0]);
-    flow[row * 2 + 1] += sy * (a1 + bb[1]);
-    cert[row] += a2 + bb[2];
-  }
-}
-
-// Vectorised form: LPR lanes (a power of two) share a row, 16 bytes per lane per access, and a wave walks ROWS_IT
-// groups of 64/LPR rows with its out_conv weights held in registers.  (The kernel above re-read 48 bytes of f32
-// weights from L1/L2 for every 8 bytes of activations and left 28 of 64 lanes idle at Cp = 144: 4x off the HBM bound.)
-template <typename T, int NK>
-__global__ __launch_bounds__(256) void refiner_out_vec_kernel(const T* d, long ldd, const float* w, const float* bb,
-                                                              float* flow, float* cert, long M, int Cp, float sx, float sy,
-                                                              int lpr, int rows_it) {
-  constexpr int CV = VecIO<T>::CV;
-  const int lane = threadIdx.x & 63;
-  const int sub = lane & (lpr - 1), rw = lane / lpr, rpw = 64 / lpr;
-  // the lane's 3 x NK x CV out_conv weights, fetched as 16-byte pieces with a clamped index and selected afterwards (Cp is a
-  // multiple of CV, refiner_out_launch checks w's alignment).  As 120 guarded 4-byte loads - a branch around each - this
-  // prologue took a third of a workgroup's life at Cp = 576 (round 6, late: tools/bench_refiner_out.py).
-  float wr[NK][3][CV];
-#pragma unroll
-  for (int k = 0; k < NK; ++k) {
-    const int c = (sub + k * lpr) * CV;
-    const bool okc = c < Cp;
-#pragma unroll
-    for (int o = 0; o < 3; ++o)
-#pragma unroll
-      for (int j4 = 0; j4 < CV; j4 += 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(w + (long)o * Cp + (okc ? c : 0) + j4);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) wr[k][o][j4 + u] = okc ? t[u] : 0.f;
-      }
-  }
-  const float b0 = bb[0], b1 = bb[1], b2 = bb[2];
-  const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * rpw * rows_it + rw;
-  // Round 6 (late): the row groups are software-pipelined - the 16-byte pieces (and flow / certainty) of group it + 1 are
-  // requested BEFORE the ~240 VALU instructions and the shuffle reduction of group it, into a second register set (the loop
-  // runs in pairs, so the two sets swap roles without moves).  The `#pragma unroll 4` this replaces never happened (rows_it
-  // is a run-time value): a wave had 5 x 16 bytes per lane in flight, waited, computed with nothing in flight - 1.9 TB/s
-  // at Cp = 576 / 1152 (profiles/r06_final_bench_mixed_kernel_stats.csv of commit 49f591d: 0.98 ms per step for 1.83 GB).
-  // Same loads, same arithmetic in the same order: bit-identical.
-  typedef typename VecIO<T>::Raw Raw;
-  struct Group {
-    Raw v[NK];
-    float f0, f1, c0;
-  };
-  auto fetch = [&](Group& g, long row) __attribute__((always_inline)) {
-    // branch-free loads (clamped row and chunk, select afterwards): inside exec-masked blocks hipcc waits for every load on
-    // its own, and this kernel is nothing but loads (1.5 TB/s at Cp = 144 with the guarded form)
-    const long rowc = row < M ? row : M - 1;
-    // the running flow / certainty are fetched with the activations, not after the reduction (a dependent
-    // load -> add -> store tail per row group otherwise)
-    g.f0 = flow[rowc * 2 + 0];
-    g.f1 = flow[rowc * 2 + 1];
-    g.c0 = cert[rowc];
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-      const int c = (sub + k * lpr) * CV;
-      g.v[k] = VecIO<T>::ldraw(d + rowc * ldd + (c < Cp ? c : 0));
-    }
-  };
-  auto finish = [&](const Group& g, long row) __attribute__((always_inline)) {
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < NK; ++k) {
-      float v[CV];
-      VecIO<T>::cvt(g.v[k], v);
-      const bool ok = (sub + k * lpr) * CV < Cp;
-#pragma unroll
-      for (int j = 0; j < CV; ++j) {
-        const float x = ok ? v[j] : 0.f;
-        a0 = fmaf(x, wr[k][0][j], a0);
-        a1 = fmaf(x, wr[k][1][j], a1);
-        a2 = fmaf(x, wr[k][2][j], a2);
-      }
-    }
-    for (int off = lpr >> 1; off >= 1; off >>= 1) {
-      a0 += __shfl_xor(a0, off);
-      a1 += __shfl_xor(a1, off);
-      a2 += __shfl_xor(a2, off);
-    }
-    if (row < M && sub == 0) {
-      flow[row * 2 + 0] = g.f0 + sx * (a0 + b0);
-      flow[row * 2 + 1] = g.f1 + sy * (a1 + b1);
-      cert[row] = g.c0 + (a2 + b2);
-    }
-  };
-  Group ga, gb;
-  fetch(ga, row0);
-  for (int it = 0; it < rows_it; it += 2) {  // rows_it is even (refiner_out_launch)
-    const long row = row0 + (long)it * rpw;
-    fetch(gb, row + rpw);
-    finish(ga, row);
-    if (it + 2 < rows_it) fetch(ga, row + 2 * rpw);  // uniform
-    finish(gb, row + rpw);
-  }
-}
-
-// Narrow rows (bf16, Cp = 24: the stride-1 refiner, 12 M pixels per call): ONE LANE PER ROW.  The shared-row kernel above
-// gives such a row to two lanes (3 chunks: the second lane idles in the second piece, 2.8 TB/s); here a lane reads its
-// row's NCH 16-byte chunks itself (the 48-byte lane stride leaves every fetched line fully used across the NCH loads,
-// L1 serves the repeats), keeps all 3 x Cp weights in registers over ROWS rows, needs no shuffles, and the running
-// flow / certainty are lane-contiguous 8- and 4-byte accesses.
-template <int NCH, int ROWS>
-__global__ __launch_bounds__(256) void refiner_out_row_kernel(const bf16_t* d, long ldd, const float* w, const float* bb,
-                                                              float* flow, float* cert, long M, int Cp, float sx, float sy) {
-  float wr[3][NCH * 8];
-#pragma unroll
-  for (int o = 0; o < 3; ++o)
-#pragma unroll
-    for (int j = 0; j < NCH * 8; ++j) wr[o][j] = j < Cp ? w[(long)o * Cp + j] : 0.f;
-  const float b0 = bb[0], b1 = bb[1], b2 = bb[2];
-  const long row0 = (long)blockIdx.x * 256 * ROWS + threadIdx.x;
-#pragma unroll 2
-  for (int it = 0; it < ROWS; ++it) {
-    const long row = row0 + (long)it * 256;
-    if (row >= M) break;
-    const f32x2 f = *reinterpret_cast<const f32x2*>(flow + row * 2);
-    const float c0 = cert[row];
-    float v[NCH][8];
-#pragma unroll
-    for (int k = 0; k < NCH; ++k) VecIO<bf16_t>::ld(d + row * ldd + k * 8, v[k]);
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-#pragma unroll
-    for (int k = 0; k < NCH; ++k)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        a0 = fmaf(v[k][j], wr[0][k * 8 + j], a0);
-        a1 = fmaf(v[k][j], wr[1][k * 8 + j], a1);
-        a2 = fmaf(v[k][j], wr[2][k * 8 + j], a2);
-      }
-    *reinterpret_cast<f32x2*>(flow + row * 2) = f32x2{f[0] + sx * (a0 + b0), f[1] + sy * (a1 + b1)};
-    cert[row] = c0 + (a2 + b2);
-  }
-}
-
-// flow / certainty += the per-pixel deltas the FINAL refiner blocks wrote (refiner_block.h): flow [M][2], cert [M], delta [M][4]
-__global__ __launch_bounds__(256) void refiner_apply_delta_kernel(const f32x4* __restrict__ delta, float* __restrict__ flow,
-                                                                  float* __restrict__ cert, long M, float sx, float sy) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < M; i += (long)gridDim.x * 256) {
-    const f32x4 d = delta[i];
-    f32x2 f = *reinterpret_cast<const f32x2*>(flow + 2 * i);
-    f[0] += sx * d[0];
-    f[1] += sy * d[1];
-    *reinterpret_cast<f32x2*>(flow + 2 * i) = f;
-    cert[i] += d[2];
-  }
-}
-
-int refiner_apply_delta_launch(const float* delta, float* flow, float* cert, long M, float sx, float sy, hipStream_t s) {
-  ROMA_REQUIRE((reinterpret_cast<uintptr_t>(delta) & 15) == 0 && (reinterpret_cast<uintptr_t>(flow) & 7) == 0, "refiner_apply_delta: alignment");
-  const long nb = std::min<long>((M + 255) / 256, 256 * 32);
-  hipLaunchKernelGGL(refiner_apply_delta_kernel, dim3((unsigned)nb), dim3(256), 0, s, (const f32x4*)delta, flow, cert, M, sx, sy);
-  ROMA_LAUNCH_CHECK();
-  return 0;
-}
-
-int refiner_out_launch(const void* d, long ldd, int dt, const float* w, const float* b, float* flow, float* cert,
-                       long M, int Cp, float sx, float sy, hipStream_t s) {
-  ROMA_REQUIRE(Cp % 4 == 0 && ldd % 4 == 0, "refiner_out: channel padding must be a multiple of 4");
-  const int row_env = tuning(SW_OUT_ROW);
-  if (row_env && dt == DT_BF16 && Cp == 24 && ldd % 8 == 0 && (reinterpret_cast<uintptr_t>(d) & 15) == 0 &&
-      (reinterpret_cast<uintptr_t>(flow) & 7) == 0) {
-    constexpr int ROWS = 8;
-    dim3 grid((unsigned)((M + 256l * ROWS - 1) / (256l * ROWS)));
-    hipLaunchKernelGGL((refiner_out_row_kernel<3, ROWS>), grid, dim3(256), 0, s, (const bf16_t*)d, ldd, w, b, flow, cert, M, Cp, sx, sy);
-    ROMA_LAUNCH_CHECK();
-    return 0;
-  }
-  {
-    const int cv = dt == DT_F32 ? 4 : 8;
-    const int chunks = Cp / cv;
-    if (Cp % cv == 0 && ldd % cv == 0 && (reinterpret_cast<uintptr_t>(d) & 15) == 0 && (reinterpret_cast<uintptr_t>(w) & 15) == 0 && chunks >= 1) {
-      int lpr = 1;
-      while (lpr < 64 && lpr * 2 <= chunks) lpr *= 2;       // largest power of two <= chunks (<= 64)
-      // bf16: chunk counts just above a power of two (18, 72, 144) leave 44 % of the lane-pieces of that split empty (the
-      // second piece has 2 / 8 / 16 active lanes of 16 / 64 / 64): take the power of two that fills the pieces best with
-      // at most 5 per lane (18 = 4 x 5 - 2, 72 = 16 x 5 - 8, 144 = 32 x 5 - 16: 90 %), which also shortens the shuffle
-      // reduction.  The f32 mode keeps its split (bit-for-bit history of the parity runs).
-      const int lpr_env = tuning(SW_OUT_LPR);
-      if (dt == DT_BF16 && lpr_env) {
-        int best_l = lpr;
-        double best_e = (double)chunks / ((double)lpr * ((chunks + lpr - 1) / lpr));
-        for (int l = lpr / 2; l >= 2; l /= 2) {
-          const int n = (chunks + l - 1) / l;
-          if (n > 5) break;
-          const double e = (double)chunks / ((double)l * n);
-          if (e > best_e + 1e-9) {
-            best_e = e;
-            best_l = l;
-          }
-        }
-        lpr = best_l;
-      }
-      const int nk = (chunks + lpr - 1) / lpr;              // 16-byte pieces per lane per row
-      if (nk <= 6) {
-        // 8 row groups per wave.  (With the weight prologue as guarded scalar loads 32 groups were 1.5 x faster than 8; with the
-        // 16-byte prologue 8 and 16 are equal and 32 loses on the sub-batch sizes - profiles/r06_v39_*.  ROMA_OUT_ROWS_IT: A/B, even.)
-        const int rows_it_env = tuning(SW_OUT_ROWS_IT);
-        const int rows_it = rows_it_env >= 2 ? rows_it_env & ~1 : 8;
-        const long rows_per_block = 4l * (64 / lpr) * rows_it;
-        dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block));
-#define ROMA_ROV(NKV)                                                                                          \
-  ROMA_DT_SWITCH(dt, T, hipLaunchKernelGGL((refiner_out_vec_kernel<T, NKV>), grid, dim3(256), 0, s, (const T*)d, ldd, w, b, \
-                                           flow, cert, M, Cp, sx, sy, lpr, rows_it))
-        if (nk <= 1) { ROMA_ROV(1); }
-        else if (nk == 2) { ROMA_ROV(2); }
-        else if (nk == 3) { ROMA_ROV(3); }
-        else if (nk == 5) { ROMA_ROV(5); }
-        else { ROMA_ROV(6); }
-#undef ROMA_ROV
-        ROMA_LAUNCH_CHECK();
-        return 0;
-      }
-    }
-  }
-  const int chunks = Cp / 4;
-#define ROMA_RO(G)                                                                                          \
-  {                                                                                                         \
-    const long rows_per_block = 4 * (64 / G);                                                               \
-    dim3 grid((unsigned)((M + rows_per_block - 1) / rows_per_block));                                       \
-    ROMA_DT_SWITCH(dt, T, hipLaunchKernelGGL((refiner_out_kernel<T, G>), grid, dim3(256), 0, s, (const T*)d, ldd, w, b, \
-                                             flow, cert, M, Cp, sx, sy));                                   \
-  }
-  if (chunks <= 8) ROMA_RO(8)
-  else if (chunks <= 16) ROMA_RO(16)
-  else if (chunks <= 32) ROMA_RO(32)
-  else ROMA_RO(64)
-#undef ROMA_RO
   ROMA_LAUNCH_CHECK();
   return 0;
 }

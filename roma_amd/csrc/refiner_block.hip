@@ -2,7 +2,7 @@
 // (C = 24 runs on the wave-private kernel of refiner_block24w.hip; refiner_block_launch below dispatches.)
 //
 // One 256-thread workgroup owns a strip of SY image rows x PX = 28 pixels and all 144 channels:
-//   * depthwise phase: the rolling-window stencil of dwconv5x5_kernel (elementwise.hip) - one thread = 4 channels x
+//   * depthwise phase: the rolling-window stencil of dwconv5x5_kernel (dwconv5x5.hip) - one thread = 4 channels x
 //     4 x-positions, each input row read once from an LDS ring that the DMA fills ahead, and fed to the 5 output rows it
 //     touches (v_pk_fma_f32).  The finished output row (after ReLU) is packed to bf16 into an LDS tile Xt[px][k]
 //     (304 byte pixel rows: conflict-free for the 16-byte MFMA fragment reads) instead of HBM;
@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void refiner_block144_1b_kernel(const bf16_
 
 // (A stand-alone depthwise kernel on the same LDS-DMA ring was measured for the wide scales, C = 576 / 1152 / 1408:
 //  0.541 vs 0.504 ms at 16x216x216x576, 0.299 vs 0.266 ms at 16x108x108x1152 - slower than the register-prefetch
-//  kernel in elementwise.hip.  The depthwise phase is bound by its 200 v_pk_fma_f32 + 25 LDS weight reads per row,
+//  kernel in dwconv5x5.hip.  The depthwise phase is bound by its 200 v_pk_fma_f32 + 25 LDS weight reads per row,
 //  not by load latency; the ring only pays off here, where it also frees the registers the 1x1 weights need.)
 bool refiner_block_supported(int Cp, int dt) { return dt == DT_BF16 && (Cp == 24 || Cp == 144); }
 

@@ -696,7 +696,7 @@ def test_refiner_out_conv_kernel_prologue_and_pipeline(built_lib, bdir):
     import re
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from audit_asm_reads import extract_code_object
-    obj = os.path.join(ROOT, "roma_amd", "csrc", bdir, "elementwise.o")
+    obj = os.path.join(ROOT, "roma_amd", "csrc", bdir, "refiner_out.o")
     if not os.path.exists(obj):
         pytest.skip("object files not present (library shipped pre-built)")
     dis = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", extract_code_object(obj)], capture_output=True, text=True,
@@ -739,7 +739,8 @@ def test_isa_audit_no_packed_f32_instruction_reads_an_sgpr_that_is_rewritten_nex
     """Round 4: a v_pk_fma_f32 whose SGPR source the NEXT scalar instruction rewrites can see the new value in its last 16-lane
     pass on gfx950 (one channel of 16 pixels of the refiner input off by a few per cent, once in ~50 two-stream calls:
     profiles/r04_v10_pk_sgpr_hazard.md).  hipcc's SLP vectoriser / f32x2 lowering emit the pattern freely, so the library is
-    built without SLP and - outside the four stencil sources - without packed-f32 instructions, and every object is audited."""
+    built without SLP and - outside the Makefile's PK_SRCS, the sources that use v_pk_fma_f32 on purpose with VGPR operands -
+    without the packed-f32 target feature: those objects hold no packed-f32 instruction at all, and every object is audited."""
     import glob
     objs = sorted(glob.glob(os.path.join(ROOT, "roma_amd", "csrc", bdir, "*.o")))
     if len(objs) < 10:
@@ -747,6 +748,20 @@ def test_isa_audit_no_packed_f32_instruction_reads_an_sgpr_that_is_rewritten_nex
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "audit_pk_sgpr.py")] + objs, capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0 and "AUDIT OK" in out.stdout, out.stdout[-3000:] + out.stderr[-2000:]
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from audit_asm_reads import disassemble
+    (pk_line,) = re.findall(r"^PK_SRCS\s*=\s*(.*)$", open(os.path.join(ROOT, "roma_amd", "csrc", "Makefile")).read(), re.M)
+    pk_srcs = pk_line.split()
+    assert pk_srcs and all(os.path.join(ROOT, "roma_amd", "csrc", bdir, s + ".o") in objs for s in pk_srcs), pk_srcs
+    for obj in objs:
+        if os.path.basename(obj)[:-2] in pk_srcs:
+            continue
+        try:
+            dis = disassemble(obj)
+        except RuntimeError:
+            continue  # host-only object
+        found = re.findall(r"\bv_pk_(?:fma|mul|add)_f32\b", dis)
+        assert not found, "%s is not in PK_SRCS but holds %d packed-f32 instruction(s)" % (os.path.basename(obj), len(found))
 
 
 @pytest.mark.parametrize("bdir", BUILD_DIRS)

@@ -43,13 +43,17 @@ print(json.dumps(runs))
 """
 
 
-def child(env_extra, *args):
+def run_child(cmd, env_extra):
     env = {k: v for k, v in os.environ.items() if not k.startswith("ROMA_") or k == "ROMA_LIB_DIR"}
     env.update(env_extra)
-    run = subprocess.run([sys.executable, "-c", CHILD, ROOT, *args], capture_output=True, text=True, timeout=120, env=env)
+    run = subprocess.run(cmd, capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
     assert run.returncode >= 0, "the child died on signal %d - nothing more is started\n%s" % (-run.returncode, run.stderr)
-    assert run.returncode == 0, run.stderr
-    return json.loads(run.stdout.strip().splitlines()[-1])
+    assert run.returncode == 0, run.stdout[-3000:] + run.stderr[-3000:]
+    return run.stdout
+
+
+def child(env_extra, *args):
+    return json.loads(run_child([sys.executable, "-c", CHILD, ROOT, *args], env_extra).strip().splitlines()[-1])
 
 
 def test_environment_and_override_select_the_gemm_kernel():
@@ -62,3 +66,13 @@ def test_environment_and_override_select_the_gemm_kernel():
     assert env_off["kernels"] and not on8p(env_off), env_off
     assert on8p(overridden), overridden
     assert clean["sha"] == env_off["sha"] == overridden["sha"]
+
+
+def test_refiner_input_wave_per_pixel_kernel_with_the_vector_kernel_switched_off():
+    """refiner_input_kernel<T> (one wave per pixel) is what refiner_input_launch falls back to when a buffer is not 16-byte
+    aligned, and no aligned case reaches it: test_refiner_input_grid_sample_warp runs the vector kernel for C = 512 / 256 / 64.
+    ROMA_RI_VEC=0 is the documented A/B switch that turns the vector kernel off, so the same test - same shapes, same bounds -
+    in a child with that environment runs the wave-per-pixel kernel for f32 and 16-bit at those three widths."""
+    out = run_child([sys.executable, "-m", "pytest", "-q", "-p", "no:cacheprovider", "-m", "gpu",
+                     os.path.join("tests", "test_gpu_ops.py") + "::test_refiner_input_grid_sample_warp"], {"ROMA_RI_VEC": "0"})
+    assert "8 passed" in out and "skipped" not in out and "failed" not in out, out[-3000:]
