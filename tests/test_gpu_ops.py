@@ -1,6 +1,7 @@
 """Operator parity on a real MI355X: every HIP kernel, called through the C ABI (ctypes), against a
 plain torch-CPU fp32/fp64 evaluation of the same operator and - where the reference defines the
 operator - against goldens produced by the reference itself (tests/golden/ops_reference.npz)."""
+import collections
 import ctypes as C
 import math
 import os
@@ -16,6 +17,16 @@ from test_cpu_tuning import RETIRED  # the switches of the removed refiner-block
 pytestmark = pytest.mark.gpu
 
 F32, BF16 = 0, 1
+
+# A storage format for the test bodies shared with tests/test_gpu_f16.py: the library built for it, its dtype code, the torch
+# dtype of the same bits, and the divisor of every 16-bit bound (1 for bfloat16 - the bounds below are bfloat16's - and 8 for
+# binary16: 11 significand bits against 8).  Bounds that are f32-level do not take the divisor.
+Fmt = collections.namedtuple("Fmt", "lib dt tdt div")
+
+
+def fmt_of(lib, dt):
+    """the formats of libroma_hip.so"""
+    return Fmt(lib, dt, torch.float32 if dt == F32 else torch.bfloat16, 1.0)
 
 
 _KEEP = []
@@ -129,8 +140,13 @@ def test_gemm_bf16_residual_in_place(lib, M, N, K):
     """x = bf16(x + ls * (A W^T + b)) with x bf16, updated in place - the residual update of the DINOv2 blocks in bf16
     mode (small 4-wave tiles, ragged last m-tile, the persistent 8-wave kernel).  The branch is rounded to bf16 before
     the add (like the reference's bf16 backbone), so the bound is one rounding of the branch plus one of the sum."""
-    A, W, b = rnd(M, K, seed=1).bfloat16(), rnd(N, K, seed=2, std=K ** -0.5).bfloat16(), rnd(N, seed=3)
-    s, r = rnd(N, seed=4), (3.0 * rnd(M, N, seed=5)).bfloat16()
+    gemm_residual_in_place_case(fmt_of(lib, BF16), M, N, K)
+
+
+def gemm_residual_in_place_case(f, M, N, K):
+    lib = f.lib
+    A, W, b = rnd(M, K, seed=1).to(f.tdt), rnd(N, K, seed=2, std=K ** -0.5).to(f.tdt), rnd(N, seed=3)
+    s, r = rnd(N, seed=4), (3.0 * rnd(M, N, seed=5)).to(f.tdt)
     branch = (A.double() @ W.double().T + b.double()) * s.double()
     ref = branch + r.double()
     Ad, Wd, bd, sd = A.cuda(), W.cuda(), b.cuda(), s.cuda()
@@ -139,7 +155,7 @@ def test_gemm_bf16_residual_in_place(lib, M, N, K):
         ok(lib, lib.roma_op_gemm_res_bf16(P(Ad), K, P(Wd), K, P(x), N, M, N, K, P(bd), P(sd), P(x), N, None))
         torch.cuda.synchronize()
         err = (x.cpu().double() - ref).abs()
-        bound = 2.0 ** -8 * (ref.abs() + branch.abs()) + 1e-3
+        bound = 2.0 ** -8 / f.div * (ref.abs() + branch.abs()) + 1e-3 / f.div
         assert bool((err <= bound).all()), float((err - bound).max())
     # misuse is refused, not silently mis-computed: N not a multiple of 8
     x = r.clone().cuda()
@@ -147,21 +163,32 @@ def test_gemm_bf16_residual_in_place(lib, M, N, K):
 
 
 def test_layernorm_bf16_input(lib):
-    x, w, b = (rnd(1603, 1024, seed=1, std=3.0) + 0.5).bfloat16(), rnd(1024, seed=2), rnd(1024, seed=3)
-    out = torch.empty((1603, 1024), device="cuda", dtype=torch.bfloat16)
-    ok(lib, lib.roma_op_layernorm_dt(P(x.cuda()), BF16, P(w.cuda()), P(b.cuda()), P(out), 1603, 1024, 1e-6, BF16, None))
+    layernorm_case(fmt_of(lib, BF16), 1603, True)
+
+
+def layernorm_case(f, M, in16):
+    """LayerNorm over D = 1024 to 16-bit output, from 16-bit input (roma_op_layernorm_dt) or from f32 (roma_op_layernorm)"""
+    lib = f.lib
+    x, w, b = rnd(M, 1024, seed=1, std=3.0) + 0.5, rnd(1024, seed=2), rnd(1024, seed=3)
+    out = torch.empty((M, 1024), device="cuda", dtype=f.tdt)
+    if in16:
+        x = x.to(f.tdt)
+        ok(lib, lib.roma_op_layernorm_dt(P(x.cuda()), f.dt, P(w.cuda()), P(b.cuda()), P(out), M, 1024, 1e-6, f.dt, None))
+    else:
+        ok(lib, lib.roma_op_layernorm(P(x.cuda()), P(w.cuda()), P(b.cuda()), P(out), M, 1024, 1e-6, f.dt, None))
     torch.cuda.synchronize()
     ref = F.layer_norm(x.double(), (1024,), w.double(), b.double(), 1e-6)
-    assert torch.allclose(out.cpu().double(), ref, atol=1e-3, rtol=2.0 ** -8)
-    # bf16 input with f32 output is not a supported combination: refused
-    o32 = torch.empty((1603, 1024), device="cuda")
-    assert lib.roma_op_layernorm_dt(P(x.cuda()), BF16, P(w.cuda()), P(b.cuda()), P(o32), 1603, 1024, 1e-6, F32, None) != 0
+    assert torch.allclose(out.cpu().double(), ref, atol=1e-3 / f.div, rtol=2.0 ** -8 / f.div), float((out.cpu().double() - ref).abs().max())
+    if in16:
+        # 16-bit input with f32 output is not a supported combination: refused
+        o32 = torch.empty((M, 1024), device="cuda")
+        assert lib.roma_op_layernorm_dt(P(x.cuda()), f.dt, P(w.cuda()), P(b.cuda()), P(o32), M, 1024, 1e-6, F32, None) != 0
 
 
 def test_qkv_scatter_big_m_bf16(lib):
     """QKV epilogue on the persistent 8-wave kernel (rows padded to Npad per image): B*N >= 8192 rows."""
-    _attention_case(lib, 6, 4, 64, 1601, BF16)
-    _attention_case(lib, 5, 2, 128, 1700, BF16)
+    _attention_case(fmt_of(lib, BF16), 6, 4, 64, 1601)
+    _attention_case(fmt_of(lib, BF16), 5, 2, 128, 1700)
 
 
 @pytest.mark.parametrize("dt", [F32, BF16])
@@ -412,9 +439,10 @@ def test_conv3x3_weight_stationary(lib, B, H, W, Cin, Cout):
     assert float((d / (outs[0].float().abs() + 1.0)).max()) <= 2.0 ** -7, float(d.max())
 
 
-def _attention_case(lib, B, heads, hd, N, dt):
+def _attention_case(f, B, heads, hd, N):
+    """roma_op_qkv_scatter_gemm + roma_op_attention in format f against f64 on the same rounded x and w"""
+    lib, dt, tdt = f.lib, f.dt, f.tdt
     D = heads * hd
-    tdt = torch.float32 if dt == F32 else torch.bfloat16
     x, w, b = rnd(B * N, D, seed=1).to(tdt), rnd(3 * D, D, seed=2, std=1.5 / math.sqrt(D)).to(tdt), rnd(3 * D, seed=3, std=0.1)
     npad = (N + 127) // 128 * 128
     q = torch.zeros((B, heads, npad, hd), device="cuda", dtype=tdt)
@@ -428,44 +456,66 @@ def _attention_case(lib, B, heads, hd, N, dt):
     qq, kk, vv = [t.transpose(1, 2) for t in torch.unbind(qkv, 2)]
     ref = F.scaled_dot_product_attention(qq, kk, vv).transpose(1, 2).reshape(B * N, D)
     # scatter layout check
-    assert torch.allclose(k.cpu().double()[:, :, :N], kk, atol=1e-4 if dt == F32 else 3e-2)
-    assert torch.allclose(vt.cpu().double()[:, :, :, :N], vv.transpose(2, 3), atol=1e-4 if dt == F32 else 3e-2)
-    tol = 2e-5 if dt == F32 else 6e-2  # bf16: P and V are quantised to bf16 before the second MFMA
+    assert torch.allclose(k.cpu().double()[:, :, :N], kk, atol=1e-4 if dt == F32 else 3e-2 / f.div)
+    assert torch.allclose(vt.cpu().double()[:, :, :, :N], vv.transpose(2, 3), atol=1e-4 if dt == F32 else 3e-2 / f.div)
+    tol = 2e-5 if dt == F32 else 6e-2 / f.div  # bf16: P and V are quantised to bf16 before the second MFMA
     err = (out.cpu().double() - ref).abs().max().item()
     assert err < tol, err
 
 
 @pytest.mark.parametrize("B,heads,hd,N", [(2, 16, 64, 65), (1, 16, 64, 257), (2, 8, 128, 64), (1, 8, 128, 200)])
 def test_attention_f32(lib, B, heads, hd, N):
-    _attention_case(lib, B, heads, hd, N, F32)
+    _attention_case(fmt_of(lib, F32), B, heads, hd, N)
 
 
 @pytest.mark.parametrize("B,heads,hd,N", [(2, 16, 64, 65), (1, 16, 64, 257), (2, 8, 128, 64), (1, 8, 128, 200), (1, 3, 64, 40),
                                           (2, 2, 64, 128), (1, 2, 64, 1601)])
 def test_attention_bf16(lib, B, heads, hd, N):
-    _attention_case(lib, B, heads, hd, N, BF16)
+    _attention_case(fmt_of(lib, BF16), B, heads, hd, N)
 
 
-def _attention_direct(lib, q, k, v, N, pad_garbage=False):
-    """roma_op_attention on hand-built operands: q [B,h,N,hd] (already scaled by 1/sqrt(hd)), k, v [B,h,N,hd]; bf16.
+def _attention_direct(f, q, k, v, N, pad_garbage=False):
+    """roma_op_attention on hand-built operands: q [B,h,N,hd] (already scaled by 1/sqrt(hd)), k, v [B,h,N,hd]; 16-bit format f.
     pad_garbage: rows N .. Npad of q / k and the matching V^T columns hold large finite numbers instead of zeros."""
+    lib = f.lib
     B, heads, _, hd = q.shape
     npad = (N + 127) // 128 * 128
     if pad_garbage:
         g = torch.Generator().manual_seed(99)
-        qd = (torch.randn(B, heads, npad, hd, generator=g) * 40.0).to(torch.bfloat16).cuda()
-        kd = (torch.randn(B, heads, npad, hd, generator=g) * 40.0).to(torch.bfloat16).cuda()
-        vtd = (torch.randn(B, heads, hd, npad, generator=g) * 40.0).to(torch.bfloat16).cuda()
+        qd = (torch.randn(B, heads, npad, hd, generator=g) * 40.0).to(f.tdt).cuda()
+        kd = (torch.randn(B, heads, npad, hd, generator=g) * 40.0).to(f.tdt).cuda()
+        vtd = (torch.randn(B, heads, hd, npad, generator=g) * 40.0).to(f.tdt).cuda()
     else:
-        qd = torch.zeros((B, heads, npad, hd), device="cuda", dtype=torch.bfloat16)
+        qd = torch.zeros((B, heads, npad, hd), device="cuda", dtype=f.tdt)
         kd = torch.zeros_like(qd)
-        vtd = torch.zeros((B, heads, hd, npad), device="cuda", dtype=torch.bfloat16)
+        vtd = torch.zeros((B, heads, hd, npad), device="cuda", dtype=f.tdt)
     qd[:, :, :N], kd[:, :, :N] = q.cuda(), k.cuda()
     vtd[:, :, :, :N] = v.transpose(2, 3).cuda()
-    out = torch.empty((B * N, heads * hd), device="cuda", dtype=torch.bfloat16)
-    ok(lib, lib.roma_op_attention(P(qd), P(kd), P(vtd), P(out), B, heads, N, npad, hd, BF16, BF16, None))
+    out = torch.empty((B * N, heads * hd), device="cuda", dtype=f.tdt)
+    ok(lib, lib.roma_op_attention(P(qd), P(kd), P(vtd), P(out), B, heads, N, npad, hd, f.dt, f.dt, None))
     torch.cuda.synchronize()
     return out.cpu().double().reshape(B, N, heads, hd).transpose(1, 2)
+
+
+def deferred_rescale_operands(tdt, hd, N):
+    """q, k, v [2, 3, N, hd] rounded to tdt with one late and one early key that dominate a third of the queries each, and
+    the scores q k^T in f64 (see test_attention_deferred_rescale)"""
+    B, heads = 2, 3
+    g = torch.Generator().manual_seed(5)
+    q = (torch.randn(B, heads, N, hd, generator=g) / math.sqrt(hd)).to(tdt)
+    k = torch.randn(B, heads, N, hd, generator=g).to(tdt)
+    v = torch.randn(B, heads, N, hd, generator=g).to(tdt)
+    late, early = N - 7, 3
+    qn = q.float() / q.float().norm(dim=-1, keepdim=True)
+    kf = k.float()
+    sel_late = torch.arange(N) % 3 == 0
+    sel_early = torch.arange(N) % 3 == 1
+    # one key per (b, head) can only align with one direction: use the mean direction of the selected queries, scaled up
+    kf[:, :, late] = 40.0 * math.sqrt(hd) * qn[:, :, sel_late].mean(dim=2) / qn[:, :, sel_late].mean(dim=2).norm(dim=-1, keepdim=True)
+    kf[:, :, early] = 40.0 * math.sqrt(hd) * qn[:, :, sel_early].mean(dim=2) / qn[:, :, sel_early].mean(dim=2).norm(dim=-1, keepdim=True)
+    k = kf.to(tdt)
+    sc = q.double() @ k.double().transpose(2, 3)
+    return q, k, v, sc, late
 
 
 @pytest.mark.parametrize("hd,N", [(64, 1601), (128, 1600), (64, 40)])
@@ -477,30 +527,33 @@ def test_attention_deferred_rescale(lib, hd, N):
     2^14, and for some queries by more than e^89 > 2^128, where the first attempt's 2^x overflows to +inf and the row sum
     is not finite.  Checked against an f64 softmax of the same bf16 operands (round 3 also compared with the
     always-rescaling round-1 kernel: 3.1e-2 both; that kernel is gone)."""
-    B, heads = 2, 3
-    g = torch.Generator().manual_seed(5)
-    q = (torch.randn(B, heads, N, hd, generator=g) / math.sqrt(hd)).to(torch.bfloat16)
-    k = torch.randn(B, heads, N, hd, generator=g).to(torch.bfloat16)
-    v = torch.randn(B, heads, N, hd, generator=g).to(torch.bfloat16)
-    late, early = N - 7, 3
-    qn = q.float() / q.float().norm(dim=-1, keepdim=True)
-    kf = k.float()
-    sel_late = torch.arange(N) % 3 == 0
-    sel_early = torch.arange(N) % 3 == 1
-    # one key per (b, head) can only align with one direction: use the mean direction of the selected queries, scaled up
-    kf[:, :, late] = 40.0 * math.sqrt(hd) * qn[:, :, sel_late].mean(dim=2) / qn[:, :, sel_late].mean(dim=2).norm(dim=-1, keepdim=True)
-    kf[:, :, early] = 40.0 * math.sqrt(hd) * qn[:, :, sel_early].mean(dim=2) / qn[:, :, sel_early].mean(dim=2).norm(dim=-1, keepdim=True)
-    k = kf.to(torch.bfloat16)
-    sc = q.double() @ k.double().transpose(2, 3)
+    deferred_rescale_case(fmt_of(lib, BF16), hd, N)
+
+
+def deferred_rescale_case(f, hd, N, top_jump=None, big_v=False):
+    """top_jump: the late key must also beat the earlier tiles by more than this for some query.  big_v: every tenth column of V
+    holds +-60000 (binary16 only: next to the top of its range); the bound of those columns grows with their |v|."""
+    q, k, v, sc, late = deferred_rescale_operands(f.tdt, hd, N)
     # the construction must really cross the threshold (2^14 = e^9.7) at the late tile for some queries, in both directions
     if N > 64:
         jump = sc[:, :, :, late] - sc[:, :, :, : (late // 64) * 64].amax(dim=-1)
         assert float(jump.max()) > 12.0 and float((-jump).max()) > 12.0, (float(jump.max()), float(jump.min()))
+        if top_jump is not None:
+            assert float(jump.max()) > top_jump, float(jump.max())
+    if big_v:
+        sign = torch.where(torch.arange(N) % 2 == 0, 1.0, -1.0)[None, None, :, None]
+        v = v.clone()
+        v[..., ::10] = (60000.0 * sign).to(f.tdt)
     ref = torch.softmax(sc, dim=-1) @ v.double()
-    o2 = _attention_direct(lib, q, k, v, N)
-    e2 = float((o2 - ref).abs().max())
-    assert e2 < 3e-2, e2  # |O| <= max |v| ~ 4; bf16 P and V
+    o2 = _attention_direct(f, q, k, v, N)
     assert torch.isfinite(o2).all()
+    if big_v:
+        # every error term is linear in V: a column's bound is the one below, stated for |v| <= 4, times max |v| / 4
+        tol = 3e-2 / f.div * (v.double().abs().amax(dim=(0, 1, 2)) / 4.0).clamp(min=1.0)
+        assert bool(((o2 - ref).abs() < tol).all()), float(((o2 - ref).abs() / tol).max())
+        return
+    e2 = float((o2 - ref).abs().max())
+    assert e2 < 3e-2 / f.div, e2  # |O| <= max |v| ~ 4; bf16 P and V
 
 
 @pytest.mark.parametrize("hd,N", [(64, 1601), (64, 65), (128, 1600), (64, 200)])
@@ -509,13 +562,17 @@ def test_attention_ignores_padding_rows(lib, hd, N):
     attention layout (DINOv2 vs decoder transformer share the workspace) left there.  The valid outputs must not depend on
     them BIT FOR BIT - the kernel takes a wave-wide decision (deferred rescale) in which padding queries must have no vote
     (they had one: run-to-run differences of the last patch token at 560 -> 864, profiles/r03_v24_attention_padding.log)."""
+    padding_rows_case(fmt_of(lib, BF16), hd, N)
+
+
+def padding_rows_case(f, hd, N):
     B, heads = 2, 4
     g = torch.Generator().manual_seed(11)
-    q = (torch.randn(B, heads, N, hd, generator=g) * 2.0 / math.sqrt(hd)).to(torch.bfloat16)
-    k = (torch.randn(B, heads, N, hd, generator=g) * 2.0).to(torch.bfloat16)
-    v = torch.randn(B, heads, N, hd, generator=g).to(torch.bfloat16)
-    clean = _attention_direct(lib, q, k, v, N)
-    dirty = _attention_direct(lib, q, k, v, N, pad_garbage=True)
+    q = (torch.randn(B, heads, N, hd, generator=g) * 2.0 / math.sqrt(hd)).to(f.tdt)
+    k = (torch.randn(B, heads, N, hd, generator=g) * 2.0).to(f.tdt)
+    v = torch.randn(B, heads, N, hd, generator=g).to(f.tdt)
+    clean = _attention_direct(f, q, k, v, N)
+    dirty = _attention_direct(f, q, k, v, N, pad_garbage=True)
     assert torch.isfinite(dirty).all()
     assert torch.equal(clean, dirty), float((clean - dirty).abs().max())
 
@@ -764,8 +821,12 @@ def test_refiner_input_grid_sample_warp(lib, dt, C, E, K, ldf, ldd, h, w):
     """roma_op_refiner_input (the F.grid_sample warp of matcher.py:132-134 fused with the concat writer and disp_emb) in
     isolation against torch float64: x copy, bilinear zero-padded sample of the support image (incl. out-of-range and
     exact-centre coordinates), displacement embedding, zero padding, correlation slice left untouched."""
+    refiner_input_case(fmt_of(lib, dt), C, E, K, ldf, ldd, h, w)
+
+
+def refiner_input_case(f, C, E, K, ldf, ldd, h, w):
+    lib, dt, tdt = f.lib, f.dt, f.tdt
     B, nimg, shift = 2, 4, 2
-    tdt = torch.float32 if dt == F32 else torch.bfloat16
     feat = torch.zeros(nimg, h * w, ldf)
     feat[:, :, :C] = rnd(nimg, h * w, C, seed=1)
     feat = feat.to(tdt)
@@ -788,7 +849,7 @@ def test_refiner_input_grid_sample_warp(lib, dt, C, E, K, ldf, ldd, h, w):
     ysrc = f64[[(b + shift) % nimg for b in range(B)], :, :C].reshape(B, h, w, C).permute(0, 3, 1, 2)
     xhat = F.grid_sample(ysrc, flow.double(), mode="bilinear", padding_mode="zeros", align_corners=False).permute(0, 2, 3, 1).reshape(B, h * w, C)
     emb = (disp_scale * (flow.double() - grid.double())).reshape(B, h * w, 2) @ emb_w.double().T + emb_b.double()
-    tol = 2e-5 if dt == F32 else 2e-2
+    tol = 2e-5 if dt == F32 else 2e-2 / f.div
     assert torch.allclose(got[:, :, :C], x, atol=0, rtol=0)
     assert torch.allclose(got[:, :, C:2 * C], xhat, atol=tol, rtol=tol), float((got[:, :, C:2 * C] - xhat).abs().max())
     assert torch.allclose(got[:, :, 2 * C:2 * C + E], emb, atol=tol, rtol=tol)
@@ -796,19 +857,32 @@ def test_refiner_input_grid_sample_warp(lib, dt, C, E, K, ldf, ldd, h, w):
     assert bool((got[:, :, 2 * C + E + K:] == 0.0).all())
 
 
-@pytest.mark.parametrize("b,h,w", [(2, 8, 8), (1, 12, 10)])
-def test_gp_posterior_vs_oracle(lib, b, h, w):
+GP_SHAPES = [(2, 8, 8), (1, 12, 10), (2, 12, 16)]
+
+
+@pytest.mark.parametrize("b,h,w,dt", [pytest.param(*s, F32, id="%d-%d-%d" % s) for s in GP_SHAPES] +
+                         [pytest.param(*s, BF16, id="%d-%d-%d-bf16" % s) for s in GP_SHAPES])
+def test_gp_posterior_vs_oracle(lib, b, h, w, dt):
     """roma_op_gp = GP.forward (matcher.py:291-323) in isolation against the CPU oracle (which is pinned on the
-    reference's gp16 stage by tests/test_cpu_oracle.py): cosine-kernel Gram matrices, blocked Cholesky, posterior mean."""
+    reference's gp16 stage by tests/test_cpu_oracle.py): cosine-kernel Gram matrices, blocked Cholesky, posterior mean.
+    n = h w: one 64-block; 120, padded to 128 with the identity; 192, the first size at which the look-ahead of the block-column
+    factorisation consumes a parked accumulator.  16-bit features (what the model's GP reads: row norms, 16-bit-in / f32-out
+    Gram GEMMs with the cosine-kernel epilogue) are the same problem on rounded inputs - products of 16-bit numbers are exact
+    in f32 and everything behind the Gram matrices is f32 - so the oracle gets the rounded features and the f32 bound holds."""
+    gp_case(fmt_of(lib, dt), b, h, w)
+
+
+def gp_case(f, b, h, w):
     from oracle import roma_oracle
-    x, y = rnd(b, 512, h, w, seed=1), rnd(b, 512, h, w, seed=2)
+    lib = f.lib
+    x, y = rnd(b, 512, h, w, seed=1).to(f.tdt), rnd(b, 512, h, w, seed=2).to(f.tdt)
     sd = {"decoder.gps.16.pos_conv.weight": rnd(512, 2, 1, 1, seed=3, std=0.5), "decoder.gps.16.pos_conv.bias": rnd(512, seed=4, std=0.5)}
-    ref = roma_oracle.gp_posterior(x, y, sd)                                   # [b, 512, h, w]
+    ref = roma_oracle.gp_posterior(x.float(), y.float(), sd)                   # [b, 512, h, w]
     xt = x.permute(0, 2, 3, 1).reshape(b, h * w, 512).contiguous().cuda()
     yt = y.permute(0, 2, 3, 1).reshape(b, h * w, 512).contiguous().cuda()
     mu = torch.empty(b, h * w, 512, device="cuda")
     ok(lib, lib.roma_op_gp(P(xt), P(yt), P(sd["decoder.gps.16.pos_conv.weight"].reshape(512, 2).contiguous().cuda()),
-                           P(sd["decoder.gps.16.pos_conv.bias"].cuda()), P(mu), b, h, w, F32, None))
+                           P(sd["decoder.gps.16.pos_conv.bias"].cuda()), P(mu), b, h, w, f.dt, None))
     torch.cuda.synchronize()
     got = mu.cpu().reshape(b, h, w, 512).permute(0, 3, 1, 2)
     assert torch.allclose(got, ref, atol=2e-4, rtol=1e-4), float((got - ref).abs().max())
@@ -979,9 +1053,13 @@ def test_refiner_block_fused(lib, Cp, B, H, W):
 def test_refiner_out_conv_update(lib, dt, Cp, M):
     """out_conv (3 x Cp, f32) fused with the running flow / certainty update - the lane-per-row kernel (bf16, Cp = 24) and the
     shared-row kernels against f64."""
-    import ctypes as C
-    tdt = torch.float32 if dt == F32 else torch.bfloat16
-    d = rnd(M, Cp, seed=1).to(tdt)
+    refiner_out_case(fmt_of(lib, dt), Cp, M)
+
+
+def refiner_out_case(f, Cp, M):
+    """the bounds are f32-level (16-bit d times f32 weights, f32 sums): the same for every storage format"""
+    lib, dt = f.lib, f.dt
+    d = rnd(M, Cp, seed=1).to(f.tdt)
     w, b = rnd(3, Cp, seed=2, std=Cp ** -0.5), rnd(3, seed=3)
     flow0, cert0 = rnd(M, 2, seed=4), rnd(M, seed=5)
     sx, sy = 0.25, 0.125
@@ -1018,17 +1096,22 @@ def test_pool_proj_fused_is_maxpool_plus_proj_gemm(lib, C, N, ldf, B, H, W):
     """pool_proj.hip (round 6): MaxPool2d(2) and the proj head of a VGG level (Conv2d 1x1 + folded BN, roma_models.py:156-160) in
     one pass over the un-pooled map - bit-identical to the two kernels it replaces (roma_op_maxpool2x2, roma_op_gemm) and equal
     to torch on the same bf16 operands; odd H / W (floor pooling, ragged 32-pixel column tiles, a last row without a partner)."""
-    x = F.relu(rnd(B, H, W, C, seed=1)).to(torch.bfloat16)                     # a post-ReLU map: never negative
-    pw = rnd(N, C, seed=2, std=C ** -0.5).to(torch.bfloat16)
+    pool_proj_case(fmt_of(lib, BF16), C, N, ldf, B, H, W)
+
+
+def pool_proj_case(f, C, N, ldf, B, H, W):
+    lib, dt = f.lib, f.dt
+    x = F.relu(rnd(B, H, W, C, seed=1)).to(f.tdt)                              # a post-ReLU map: never negative
+    pw = rnd(N, C, seed=2, std=C ** -0.5).to(f.tdt)
     pb = rnd(N, seed=3)
     xd, pwd, pbd = x.cuda(), pw.cuda(), pb.cuda()
-    pooled = torch.full((B, H // 2, W // 2, C), float("nan"), device="cuda", dtype=torch.bfloat16)
-    pf = torch.full((B, H * W, ldf), float("nan"), device="cuda", dtype=torch.bfloat16)
-    ok(lib, lib.roma_op_pool_proj(P(xd), P(pooled), P(pf), P(pwd), C, P(pbd), N, ldf, B, H, W, C, BF16, None))
+    pooled = torch.full((B, H // 2, W // 2, C), float("nan"), device="cuda", dtype=f.tdt)
+    pf = torch.full((B, H * W, ldf), float("nan"), device="cuda", dtype=f.tdt)
+    ok(lib, lib.roma_op_pool_proj(P(xd), P(pooled), P(pf), P(pwd), C, P(pbd), N, ldf, B, H, W, C, dt, None))
     pooled2 = torch.empty_like(pooled)
     pf2 = torch.zeros_like(pf)
-    ok(lib, lib.roma_op_maxpool2x2(P(xd), P(pooled2), B, H, W, C, BF16, None))
-    ok(lib, lib.roma_op_gemm(P(xd), C, P(pwd), C, P(pf2), ldf, B * H * W, N, C, 1, 0, 0, 0, P(pbd), None, None, 0, 0, 1.0, BF16, BF16, None))
+    ok(lib, lib.roma_op_maxpool2x2(P(xd), P(pooled2), B, H, W, C, dt, None))
+    ok(lib, lib.roma_op_gemm(P(xd), C, P(pwd), C, P(pf2), ldf, B * H * W, N, C, 1, 0, 0, 0, P(pbd), None, None, 0, 0, 1.0, dt, dt, None))
     torch.cuda.synchronize()
     assert torch.equal(pooled.view(torch.int16), pooled2.view(torch.int16))
     assert torch.equal(pf[:, :, :N].contiguous().view(torch.int16), pf2[:, :, :N].contiguous().view(torch.int16))
@@ -1036,7 +1119,7 @@ def test_pool_proj_fused_is_maxpool_plus_proj_gemm(lib, C, N, ldf, B, H, W):
     refp = F.max_pool2d(x.float().permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1)
     assert torch.equal(pooled.cpu().float(), refp)
     ref = x.double().reshape(B, H * W, C) @ pw.double().T + pb.double()
-    assert torch.allclose(pf[:, :, :N].cpu().double(), ref, atol=2e-2, rtol=1e-2)
+    assert torch.allclose(pf[:, :, :N].cpu().double(), ref, atol=2e-2 / f.div, rtol=1e-2 / f.div)
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 16, 24), (1, 9, 33), (3, 37, 70), (1, 560, 560), (2, 100, 864)])
@@ -1290,31 +1373,36 @@ def test_refiner_wide_pair_vs_f64(lib, B, H, W):
     (bf16 output rounding + the occasional 1-ulp flip of the bf16 intermediate).  A torch emulation of the pair on the CPU (f32
     depthwise rounded to bf16, f32 matmul rounded to bf16) stays inside them on all seven shapes: worst error / bound 0.22 (at
     B, H, W = 1, 140, 140), worst mean error 1.53e-3."""
+    refiner_wide_pair_case(fmt_of(lib, BF16), B, H, W)
+
+
+def refiner_wide_pair_case(f, B, H, W):
+    lib, dt = f.lib, f.dt
     Cp = 576
-    x = rnd(B, Cp, H, W, seed=1).to(torch.bfloat16)
+    x = rnd(B, Cp, H, W, seed=1).to(f.tdt)
     w, b = rnd(Cp, 1, 5, 5, seed=2, std=0.2), rnd(Cp, seed=3)
-    pw = rnd(Cp, Cp, seed=4, std=Cp ** -0.5).to(torch.bfloat16)
+    pw = rnd(Cp, Cp, seed=4, std=Cp ** -0.5).to(f.tdt)
     pb = rnd(Cp, seed=5)
-    mid = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=2, groups=Cp)).to(torch.bfloat16)
+    mid = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=2, groups=Cp)).to(f.tdt)
     ref = (F.conv2d(mid.double(), pw.double()[:, :, None, None], pb.double())).permute(0, 2, 3, 1)
     wp = w.reshape(Cp, 25).T.contiguous().cuda()
     xin = x.permute(0, 2, 3, 1).contiguous().cuda()
     bd, pwd, pbd = b.cuda(), pw.cuda(), pb.cuda()
-    t = torch.full((B, H, W, Cp), float("nan"), device="cuda", dtype=torch.bfloat16)
-    y2 = torch.full((B, H, W, Cp), float("nan"), device="cuda", dtype=torch.bfloat16)
-    ok(lib, lib.roma_op_dwconv5x5(P(xin), P(t), P(wp), P(bd), B, H, W, Cp, BF16, None))
-    ok(lib, lib.roma_op_gemm(P(t), Cp, P(pwd), Cp, P(y2), Cp, B * H * W, Cp, Cp, 1, 0, 0, 0, P(pbd), None, None, 0, 0, 1.0, BF16, BF16, None))
+    t = torch.full((B, H, W, Cp), float("nan"), device="cuda", dtype=f.tdt)
+    y2 = torch.full((B, H, W, Cp), float("nan"), device="cuda", dtype=f.tdt)
+    ok(lib, lib.roma_op_dwconv5x5(P(xin), P(t), P(wp), P(bd), B, H, W, Cp, dt, None))
+    ok(lib, lib.roma_op_gemm(P(t), Cp, P(pwd), Cp, P(y2), Cp, B * H * W, Cp, Cp, 1, 0, 0, 0, P(pbd), None, None, 0, 0, 1.0, dt, dt, None))
     torch.cuda.synchronize()
-    # the stand-alone stencil accumulates in f32, `mid` is the f64 result rounded once: equal up to one bf16 ulp, and
+    # the stand-alone stencil accumulates in f32, `mid` is the f64 result rounded once: equal up to one 16-bit ulp, and
     # almost everywhere bit for bit
     tm, mm = t.cpu().float(), mid.permute(0, 2, 3, 1).contiguous().float()
-    assert float((tm - mm).abs().max()) <= 2.0 ** -7 * float(mm.abs().max()) + 1e-6
+    assert float((tm - mm).abs().max()) <= 2.0 ** -7 / f.div * float(mm.abs().max()) + 1e-6
     assert float((tm.view(torch.int32) == mm.view(torch.int32)).float().mean()) > 0.98
     got = y2.cpu().double()
     assert torch.isfinite(got).all()
     err = (got - ref).abs()
-    assert (err <= 1e-2 * ref.abs() + 3e-2).all(), float(err.max())
-    assert float(err.mean()) < 6e-3
+    assert (err <= 1e-2 / f.div * ref.abs() + 3e-2 / f.div).all(), float(err.max())
+    assert float(err.mean()) < 6e-3 / f.div
 
 
 @pytest.mark.parametrize("Cp,B,H,W", [(24, 2, 13, 10), (24, 1, 75, 301), (24, 3, 3, 200), (24, 1, 290, 150), (144, 2, 13, 10),
@@ -1324,13 +1412,29 @@ def test_refiner_block_final_composed_out_conv(lib, Cp, B, H, W):
     with out_conv (linear o linear, matcher.py:92-122, 175-178) as ONE C -> 3 map on the MFMA - weights as a 16-bit head + 16-bit
     remainder in rows 0-2 / 4-6 of an 8-row matrix, bias in the accumulator - written as per-pixel deltas, and the pass that adds
     them to flow / certainty.  Against torch f64 on the same 16-bit-rounded depthwise output; three launches agree bit for bit."""
-    x = rnd(B, Cp, H, W, seed=1).to(torch.bfloat16)
-    w, b = rnd(Cp, 1, 5, 5, seed=2, std=0.2), rnd(Cp, seed=3)
-    wc = rnd(3, Cp, seed=4, std=Cp ** -0.5)          # the composed out_w . pw8 (f32 at pack time)
+    refiner_block_final_case(fmt_of(lib, BF16), Cp, B, H, W)
+
+
+def block_final_weights(tdt, Cp):
+    """the composed out_w . pw8 (f32 at pack time), its bias, and the 16-bit head / remainder split"""
+    wc = rnd(3, Cp, seed=4, std=Cp ** -0.5)
     bc = rnd(3, seed=5)
-    hi = wc.to(torch.bfloat16)
-    lo = (wc - hi.float()).to(torch.bfloat16)
-    pwf = torch.zeros(8, Cp, dtype=torch.bfloat16)
+    hi = wc.to(tdt)
+    lo = (wc - hi.float()).to(tdt)
+    return wc, bc, hi, lo
+
+
+def refiner_block_final_case(f, Cp, B, H, W, subnormal_share=None):
+    """subnormal_share: more than this share of the remainders must be subnormal numbers of the format (binary16 at Cp = 144)"""
+    lib, dt = f.lib, f.dt
+    x = rnd(B, Cp, H, W, seed=1).to(f.tdt)
+    w, b = rnd(Cp, 1, 5, 5, seed=2, std=0.2), rnd(Cp, seed=3)
+    wc, bc, hi, lo = block_final_weights(f.tdt, Cp)
+    if subnormal_share is not None:
+        tiny = float(torch.finfo(f.tdt).tiny)
+        sub = (lo.float().abs() < tiny) & (lo.float() != 0)
+        assert float(sub.float().mean()) > subnormal_share, float(sub.float().mean())
+    pwf = torch.zeros(8, Cp, dtype=f.tdt)
     pwf[0:3], pwf[4:7] = hi, lo
     bf = torch.zeros(Cp)
     bf[:3] = bc
@@ -1339,15 +1443,15 @@ def test_refiner_block_final_composed_out_conv(lib, Cp, B, H, W):
     # the depthwise half from the stand-alone kernel (same FMA order: its 16-bit output is what the fused kernel puts into LDS;
     # a torch f64 stencil rounds 1 in ~200 values to the neighbouring 16-bit number), checked against torch loosely
     t = torch.empty_like(xin)
-    ok(lib, lib.roma_op_dwconv5x5(P(xin), P(t), P(wp), P(b.cuda()), B, H, W, Cp, BF16, None))
+    ok(lib, lib.roma_op_dwconv5x5(P(xin), P(t), P(wp), P(b.cuda()), B, H, W, Cp, dt, None))
     torch.cuda.synchronize()
     mid = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=2, groups=Cp)).permute(0, 2, 3, 1)
-    assert float((t.cpu().double() - mid).abs().max()) <= 2.0 ** -7 * float(mid.abs().max())
+    assert float((t.cpu().double() - mid).abs().max()) <= 2.0 ** -7 / f.div * float(mid.abs().max())
     ref = torch.einsum("bhwc,oc->bhwo", t.cpu().double(), hi.double() + lo.double()) + bc.double()
     outs = []
     for _ in range(3):
         delta = torch.full((B, H, W, 4), float("nan"), device="cuda")
-        ok(lib, lib.roma_op_refiner_block_final(P(xin), P(delta), P(wp), P(b.cuda()), P(pwf.cuda()), P(bf.cuda()), B, H, W, Cp, BF16, None))
+        ok(lib, lib.roma_op_refiner_block_final(P(xin), P(delta), P(wp), P(b.cuda()), P(pwf.cuda()), P(bf.cuda()), B, H, W, Cp, dt, None))
         torch.cuda.synchronize()
         outs.append(delta)
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
