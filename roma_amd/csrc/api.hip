@@ -14,6 +14,7 @@
 #include "gemm.h"
 #include "local_corr.h"
 #include "pool_proj.h"
+#include "gp.h"
 #include "model.h"
 #include "refiner_block.h"
 #include "kde.h"

@@ -1,6 +1,6 @@
 // Left-looking block-column step of the GP's blocked Cholesky solve (matcher.py:291-323: L = cholesky(K_yy + sigma^2 I),
 // cholesky_solve) on the AUGMENTED system: one (n + d) x n matrix per image, K_yy on top and the d right-hand-side rows F^T
-// right behind it (model.hip gp_posterior), so that the forward substitution is part of the factorisation.
+// right behind it (gp.hip gp_posterior), so that the forward substitution is part of the factorisation.
 //
 // Rounds 1-5 ran the right-looking form: per 64-wide step k one chol_diag launch (8 workgroups on the whole chip), one
 // panel GEMM and one trailing-update GEMM (K = 64: output bound) - 75 dependent launches of 10 .. 110 us for n = 1600, 2.6 ms

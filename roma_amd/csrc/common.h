@@ -52,7 +52,7 @@ void set_error(const std::string& msg);
 #define ROMA_LAUNCH_CHECK() ROMA_CHECK_HIP(hipGetLastError())
 
 // f32 -> bfloat16 bits (round-to-nearest-even) whatever this build's own h16 is: ROMA_MIXED handles of the binary16 build pack
-// their DINOv2 weights for the bfloat16 library with it (model.hip)
+// their DINOv2 weights for the bfloat16 library with it (model_weights.hip)
 __host__ __device__ inline unsigned short f32_to_bfloat16_bits(float f) {
   union { uint32_t u; float f; } x;
   x.f = f;

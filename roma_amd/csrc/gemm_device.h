@@ -194,7 +194,7 @@ __device__ __forceinline__ void epi_staged_bf16(const f32x16 (&acc)[TN][TM], con
   constexpr int NPC = (32 * CPR) / 64;  // 16-byte pieces per lane per 32-row block
   const int l31 = lane & 31, h = lane >> 5;
   // HAS_S: a per-column scale (another 32 registers next to the 128 accumulators: the compiler spills).  The model does
-  // not need it - LayerScale is folded into the weights in bf16 mode (model.hip pack_weights) - it is kept for callers of
+  // not need it - LayerScale is folded into the weights in bf16 mode (model_weights.hip pack_weights) - it is kept for callers of
   // the operator entry point, only together with the bf16 residual; gemm_launch routes other uses to the generic epilogue.
   EpiCols<TN, FULL, HAS_S> cols;
   cols.load(a, nw0, h);

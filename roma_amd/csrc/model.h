@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/roma_hip.h"
+#include "arena.h"
 #include "common.h"
 #include "tuning.h"
 
@@ -60,32 +61,6 @@ struct RefinerW {
   float* ocf_b = nullptr;
 };
 
-class Arena {
- public:
-  char* base = nullptr;
-  size_t cap = 0, off = 0, peak = 0;
-  bool dry = true;
-  // set when a live allocation did not fit the planned capacity (an option changed between roma_finalize's dry run and the
-  // call): the request is then served from the START of the arena - aliased, so the call's results are garbage, but no
-  // kernel writes outside the hipMalloc'd workspace - and the entry point reports the error instead of returning results
-  bool overflow = false;
-  void reset() { off = 0; }
-  void* alloc(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    if (!dry && off + bytes > cap) {
-      overflow = true;
-      if (off > peak) peak = off;
-      return bytes <= cap ? (void*)base : nullptr;
-    }
-    void* p = dry ? reinterpret_cast<void*>((uintptr_t)0x1000 + off) : (void*)(base + off);
-    off += bytes;
-    if (off > peak) peak = off;
-    return p;
-  }
-  size_t mark() const { return off; }
-  void release(size_t m) { off = m; }
-};
-
 class Model {
  public:
   static constexpr int MAX_STREAMS_DECL = 4;
@@ -129,8 +104,7 @@ class Model {
   std::map<std::string, HostTensor> host;
 
   // packed weights (device)
-  float *c1_w = nullptr, *c1_b = nullptr;  // first VGG conv [27][64]
-  Lin vgg[12];                             // [1..11] implicit-GEMM convs (index 0 unused)
+  Lin vgg[12];  // [0]: first layer as a [64][32] GEMM (27 taps, zero padded); [1..11]: implicit-GEMM convs
   int vgg_cin[12] = {0}, vgg_cout[12] = {0};
   Lin patch;
   float *cls_tok = nullptr, *pos_emb = nullptr;  // pos-embed already resized to the coarse token grid
@@ -181,24 +155,31 @@ class Model {
   int check_contract();
   int pack_weights();
   int load_peer();
-  // fw != nullptr: ONE pass (roma_forward) - per-scale outputs copied out, no epilogue
-  int match_impl(int B, const float* ima, const float* imb, const float* ima_hr, const float* imb_hr, float* warp,
-                 float* cert, hipStream_t st, bool dry, Arena& arena, Arena& persist, const roma_forward_args_t* fw = nullptr);
   int dbg_save(const char* name, const void* p, size_t bytes, hipStream_t st);
   template <typename F> int upload_f32(const std::vector<float>& v, F** out);
   int upload_act(const std::vector<float>& v, void** out);
   int make_lin(const std::vector<float>& w, const std::vector<float>* b, int N, int K, Lin* out);
+
+  // ---- the match() schedule (model.hip): a driver over the passes and scales, and its stages
+  struct Call;   // what one call shares: sizes, stream, arenas, trace slot, token grid, transformer scratch
+  struct Pass;   // one pass (coarse / upsample): resolution, images, feature pyramid, current flow / certainty
+  struct Scale;  // one decoder scale of a pass: geometry, refiner weights, projected features, refiner buffers
+  // fw != nullptr: ONE pass (roma_forward) - per-scale outputs copied out, no epilogue
+  int match_impl(int B, const float* ima, const float* imb, const float* ima_hr, const float* imb_hr, float* warp,
+                 float* cert, hipStream_t st, bool dry, Arena& arena, Arena& persist, const roma_forward_args_t* fw = nullptr);
+  int fits(const Call& c);
+  int observe(const Call& c, const std::string& trace_name, const std::string& dbg_name, const void* p, size_t bytes,
+              long rows = 0, int ld = 0, int c0 = 0, int c1 = 0);
+  int encode_vgg(const Call& c, Pass& p);
+  int encode_dino(Call& c, Pass& p);
+  int seed_upsample_pass(const Call& c, const Pass& p, const float* flow_p1, const float* cert_p1);
+  int proj_head(const Call& c, const Pass& p, Scale& s);
+  int coarse_match(const Call& c, const Pass& p, const Scale& s);
+  int refiner_input(const Call& c, const Pass& p, Scale& s);
+  int refiner_chain(const Call& c, const Pass& p, const Scale& s, const void** d_last, bool* composed);
+  int refiner_out(const Call& c, const Pass& p, const Scale& s, const void* d_last, bool composed);
+  int next_scale(const Call& c, Pass& p, const Scale& s, float* cert16_keep);
+  int epilogue(const Call& c, const float* flow, const float* cert, const float* cert16_keep, float* warp_out, float* cert_out);
 };
-
-// GP match encoder for all directed pairs of a call (model.hip); scratch comes from `arena` (dry = plan sizes only)
-int gp_posterior(const void* pf, long ldf, int act_dt, int B, bool symmetric, int th, int tw, const float* gp_w,
-                 const float* gp_b, float* mu, long ld_mu, Arena& arena, hipStream_t st, bool dry);
-
-// Batched SPD solve via blocked Cholesky (see include/roma_hip.h roma_op_cholesky_solve_t)
-// strideA / strideR: batch strides of A and Rt in floats (0 = dense: n * n and d * n).  When Rt is stored right behind A
-// (Rt == A + n * n, strideA == strideR: one (n + d) x n matrix per item) the forward substitution is folded into the
-// factorisation loop - see cholesky_solve_t.
-int cholesky_solve_t(float* A, float* Rt, float* LT, float* Linv, float* LinvT, int n, int d, int batch, hipStream_t st,
-                     long strideA = 0, long strideR = 0);
 
 }  // namespace roma

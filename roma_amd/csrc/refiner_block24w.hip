@@ -84,7 +84,7 @@ __device__ __forceinline__ void rbw_glds16(const char* src, lds_u8* lds_wave_bas
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (ROMA_LDS void*)lds_wave_base, 16, 0, 0);
 }
 
-// FINAL (round 5): the LAST block of a ConvRefiner.  Its 1x1 convolution and out_conv are one composed C -> 3 map (model.hip,
+// FINAL (round 5): the LAST block of a ConvRefiner.  Its 1x1 convolution and out_conv are one composed C -> 3 map (model_weights.hip,
 // RefinerW::oc_w); `pw` then holds 8 rows - rows 0-2 the 16-bit head of the composed weights, rows 4-6 their 16-bit remainder
 // (hi + lo carries ~16 significant bits through the MFMA, which has 29 idle rows anyway) - `pwb` the composed bias in [0, 3),
 // and instead of a block output the kernel writes delta[pixel] = {d flow x, d flow y, d certainty, 0} (f32x4): no Ot, no

@@ -3,7 +3,7 @@ single-stream result of the same handle; reports the runs / pairs / bounding box
 
     python tools/stress_streams.py --pairs 3 --runs 400 [--fuse 0|1] [--amp bf16|f16|mixed|f32] [--seed S] [--trace]
 Kernel-selection switches come from the environment (ROMA_GEMM8P, ROMA_LC_MODE, ROMA_RI_VEC, ROMA_STREAMS_SERIAL ...),
-so one GPU visit can run a matrix of configurations (tools/r02_visit2.sh)."""
+so one GPU visit can run a matrix of configurations."""
 import argparse
 import os
 import sys
