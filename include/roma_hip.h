@@ -500,6 +500,60 @@ int roma_op_triangulate(const float* matches, const float* certainty, const int*
 int roma_op_depth_consistency(const float* points, const unsigned char* flags, const double* R, const double* t, const double* K_a,
                               const double* K_b, int W_a, int H_a, int W_b, int H_b, int B, int H, int W, double rel_thresh,
                               unsigned char* out_consistent, float* out_err, void* stream);
+/* Ground-truth warp from SENSOR depth - the reference's warp_kpts / get_gt_warp (romatch/utils/utils.py) - and the dense EPE / PCK
+ * metrics of a warp against it - MegadepthDenseBenchmark.geometric_dist in one pass.  The sensor-depth twin of
+ * roma_op_depth_consistency.  Restated operation by operation in numpy float64 by tools/gt_warp_ref.py.  All arithmetic is float64
+ * in the order written, with fp contraction off, except the one float32 line marked below; depth and key points are widened exactly.
+ *   sample(D [Hs, Ws], x, y), torch grid_sample bilinear, align_corners=False, zeros padding:
+ *     ix = ((x + 1) Ws - 1) / 2, iy likewise; x0 = floor(ix), y0 = floor(iy); weights w_nw = (x0+1-ix)(y0+1-iy),
+ *     w_ne = (ix-x0)(y0+1-iy), w_sw = (x0+1-ix)(iy-y0), w_se = (ix-x0)(iy-y0); result = v_nw w_nw + v_ne w_ne + v_sw w_sw + v_se w_se
+ *     added left to right, where a tap outside the map contributes 0 (not 0 times its weight).  In and out of range is decided in
+ *     float64 (0 <= x0 <= Ws - 1 and so on; NaN fails) before any conversion to an integer: a coordinate of 1e7 pixels or a
+ *     non-finite one samples 0 and forms no address.
+ *   key point (x, y) normalised in image 0:  px = W0 (x + 1) / 2, py = H0 (y + 1) / 2, d0 = sample(depth0, x, y), nonzero = d0 != 0
+ *   K0inv = adjugate / determinant of the general 3 x 3 K0 = [a b c; d e f; g h i]:  cofactors c00 = e i - f h, c01 = c h - b i,
+ *     c02 = b f - c e, c10 = f g - d i, c11 = a i - c g, c12 = c d - a f, c20 = d h - e g, c21 = b g - a h, c22 = a e - b d,
+ *     det = (a c00 + b c10) + c c20, K0inv[r][q] = c_rq / det; formed once per workgroup, not per thread
+ *   X = K0inv (px d0, py d0, d0), Y = R X + t, zc = Y_z, P = K1 Y: each row is (m0 v0 + m1 v1) + m2 v2 (then + t_r for Y)
+ *   u = P_x / (P_z + 1e-4), v = P_y / (P_z + 1e-4); covisible = u > 0 && u < W1 - 1 && v > 0 && v < H1 - 1
+ *   warped = (2 u / W1 - 1, 2 v / H1 - 1), written for every row, valid or not
+ *   d1 = sample(depth1, warped), rel = |(d1 - zc) / d1| (+-inf for a zero d1, NaN for 0 / 0); consistent = rel < rel_thresh (false
+ *   for NaN); valid = nonzero && covisible && consistent.
+ * roma_op_warp_kpts: kpts DEVICE [B, L, 2], float32 (kpts_f64 = 0) or float64 (1), or NULL: the key points are then the pixel
+ * centres of a grid_h x grid_w grid (L = grid_h grid_w, row-major), value j of n being float32((2 j + 1) / n - 1) formed in float64,
+ * rounded once to float32 and widened again - no grid tensor exists.  depth0 DEVICE f32 [B, H0, W0], depth1 f32 [B, H1, W1];
+ * T DEVICE f64 [B, t_rows, 4], t_rows 3 or 4 (rows 0..2 = [R | t], camera 0 to camera 1); K0, K1 DEVICE f64 [B, 3, 3].  Outputs,
+ * DEVICE, the first three nullable: valid u8 [B, L] (0 / 1), prob f32 [B, L] (0.0 / 1.0, get_gt_warp's form), rel f64 [B, L],
+ * warped f64 [B, L, 2].  One launch, no workspace, no host read; every bit is independent of B, of the order of the pairs and of
+ * the run.  Refused before anything is enqueued: a null required pointer, B < 0 or > 65535, L < 0, B L >= 2^31, t_rows not 3 or
+ * 4, kpts_f64 not 0 or 1, a depth size outside [1, 32768], kpts NULL with a grid outside [1, 32768]^2 or grid_h grid_w != L, kpts
+ * not aligned to its type, a negative (or NaN) rel_thresh.  B = 0 or L = 0 launches nothing.
+ * roma_op_dense_metrics: matches DEVICE f32, 16-byte aligned, pixel (b, r, c) at matches + b batch_stride + r row_stride + 4 c
+ * (strides in floats, multiples of 4: a contiguous [B, h, w, 4] warp has row_stride = 4 w, the left half of a symmetric
+ * [B, h, 2w, 4] warp row_stride = 8 w, read in place).  Columns 0:2 are the key points in image 1 (camera K1, depth1 [B, H1, W1]),
+ * columns 2:4 the prediction in image 2 (K2, depth2 [B, H2, W2]); the chain above gives valid and warped per pixel.  The pixel
+ * scale is the warp grid's (h, w), not depth2's size (the reference's convention):
+ *   prediction, in FLOAT32 as the reference forms it, then widened:  xh = float32(float32(w * float32(x^ + 1)) / 2), yh with h
+ *   truth in float64: tx = w (warped_x + 1) / 2, ty = h (warped_y + 1) / 2;  gd = sqrt(dx dx + dy dy), dx = xh - tx, dy = yh - ty
+ * Outputs, DEVICE: n_valid int64 [B]; n_below int64 [B, 3], valid pixels with gd < thr0, thr1, thr2; gd_sum f64 [B] over the valid
+ * pixels - each thread sums its pixels in ascending index, then a fixed tree over the wave, the waves in order, and the
+ * per-workgroup partials in index order by a finishing kernel; no float is added atomically; the workgroups of a pair do not
+ * depend on B, so the per-pair outputs are bit-identical for any batch and pair order.  epe f64 [1] = sum_b gd_sum / sum_b
+ * n_valid and pck f64 [3] = sum_b n_below / sum_b n_valid, the sums in pair order (NaN when no pixel of the batch is valid:
+ * the mean of an empty selection).  Nullable maps prob f32 [B, h, w] and gd f64 [B, h, w], NaN where prob == 0.  workspace:
+ * DEVICE, 8-byte aligned, roma_op_dense_metrics_workspace(B, h, w) bytes (-1 for sizes that are refused).  Two launches, no host
+ * read.  Refused before anything is enqueued: a null required pointer, B < 1 or > 65535, h or w outside [1, 32768], B h w >=
+ * 2^31, t_rows not 3 or 4, a depth size outside [1, 32768], strides that are not multiples of 4 or let rows overlap, matches or
+ * workspace not aligned as stated, a negative (or NaN) threshold, a workspace that is too small. */
+int roma_op_warp_kpts(const void* kpts, int kpts_f64, int grid_h, int grid_w, const float* depth0, const float* depth1, const double* T,
+                      int t_rows, const double* K0, const double* K1, int B, long L, int H0, int W0, int H1, int W1, double rel_thresh,
+                      unsigned char* out_valid, float* out_prob, double* out_rel, double* out_warped, void* stream);
+long roma_op_dense_metrics_workspace(int B, int h, int w);
+int roma_op_dense_metrics(const float* matches, long batch_stride, long row_stride, const float* depth1, const float* depth2,
+                          const double* T, int t_rows, const double* K1, const double* K2, int B, int h, int w, int H1, int W1, int H2,
+                          int W2, double rel_thresh, double thr0, double thr1, double thr2, long long* out_n_valid,
+                          long long* out_n_below, double* out_gd_sum, double* out_epe, double* out_pck, float* out_prob, double* out_gd,
+                          void* workspace, long workspace_bytes, void* stream);
 /* Image preprocessing: Pillow's 8-bit bicubic resize (Image.resize((w, h), Image.BICUBIC) on a mode-RGB image, which is what
  * transforms.Resize(size, BICUBIC) does to a PIL image) of a batch of packed RGB images of mixed sizes to one or two target sizes,
  * then / 255 and the ImageNet mean / std of the matcher's host path - bit-identical to that path (roma_amd/matcher.py:

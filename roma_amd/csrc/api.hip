@@ -29,6 +29,7 @@
 #include "pose_refine.h"
 #include "geometry.h"
 #include "triangulate.h"
+#include "gt_warp.h"
 #include "preprocess.h"
 
 namespace roma {
@@ -617,6 +618,23 @@ int roma_op_depth_consistency(const float* points, const unsigned char* flags, c
                               unsigned char* out_consistent, float* out_err, void* stream) {
   return depth_consistency_launch(points, flags, R, t, K_a, K_b, W_a, H_a, W_b, H_b, B, H, W, rel_thresh, out_consistent, out_err,
                                   S(stream));
+}
+// ---- ground-truth warp from depth and dense EPE / PCK metrics (gt_warp.hip)
+int roma_op_warp_kpts(const void* kpts, int kpts_f64, int grid_h, int grid_w, const float* depth0, const float* depth1, const double* T,
+                      int t_rows, const double* K0, const double* K1, int B, long L, int H0, int W0, int H1, int W1, double rel_thresh,
+                      unsigned char* out_valid, float* out_prob, double* out_rel, double* out_warped, void* stream) {
+  return warp_kpts_launch(kpts, kpts_f64, grid_h, grid_w, depth0, depth1, T, t_rows, K0, K1, B, L, H0, W0, H1, W1, rel_thresh, out_valid,
+                          out_prob, out_rel, out_warped, S(stream));
+}
+long roma_op_dense_metrics_workspace(int B, int h, int w) { return dense_metrics_workspace_bytes(B, h, w); }
+int roma_op_dense_metrics(const float* matches, long batch_stride, long row_stride, const float* depth1, const float* depth2,
+                          const double* T, int t_rows, const double* K1, const double* K2, int B, int h, int w, int H1, int W1, int H2,
+                          int W2, double rel_thresh, double thr0, double thr1, double thr2, long long* out_n_valid,
+                          long long* out_n_below, double* out_gd_sum, double* out_epe, double* out_pck, float* out_prob, double* out_gd,
+                          void* workspace, long workspace_bytes, void* stream) {
+  return dense_metrics_launch(matches, batch_stride, row_stride, depth1, depth2, T, t_rows, K1, K2, B, h, w, H1, W1, H2, W2, rel_thresh,
+                              thr0, thr1, thr2, out_n_valid, out_n_below, out_gd_sum, out_epe, out_pck, out_prob, out_gd, workspace,
+                              workspace_bytes, S(stream));
 }
 // ---- image preprocessing: Pillow-exact bicubic resize + normalisation (preprocess.hip)
 long roma_op_preprocess_workspace(const long long* desc_host, int n_images, const int* targets_hw, int n_targets) {

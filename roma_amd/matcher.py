@@ -501,6 +501,12 @@ class RegressionMatcher:
         kw.setdefault("symmetric", bool(self.symmetric))
         return triangulate_warp(warp, certainty, R, t, K_A, K_B, H_A, W_A, H_B, W_B, **kw)
 
+    def dense_metrics(self, dense_matches, depth1, depth2, T_1to2, K1, K2, **kw):
+        """Dense EPE / PCK of this matcher's warp against the ground truth from depth (`roma_amd.dense_metrics`; see there for the
+        arguments and what is returned).  For a symmetric warp pass its A -> B half, `warp[:, :, :w]`: it is read in place."""
+        from .gt_warp import dense_metrics
+        return dense_metrics(dense_matches, depth1, depth2, T_1to2, K1, K2, **kw)
+
     # ------------------------------------------------------------------ keypoint matching (matcher.py:732-773)
     def match_keypoints(self, x_A, x_B, warp, certainty, return_tuple=True, return_inds=False, max_dist=0.005, cert_th=0):
         """Mutual-nearest-neighbour matching of detector keypoints through the dense warp.

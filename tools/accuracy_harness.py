@@ -12,8 +12,8 @@ relative pose are analytic), with the same metric code path the real data takes:
     python tools/accuracy_harness.py --megadepth data/megadepth --weights roma_outdoor.pth --dinov2 dinov2_vitl14_pretrain.pth
 
 With random weights the numbers are meaningless (the matcher has not learnt anything); with the released weights the
-MegaDepth run must reproduce ACCEPTANCE below within the reference's own tolerances.  Metric functions work on CPU or GPU
-tensors; only `benchmark()` calls the matcher."""
+MegaDepth run must reproduce ACCEPTANCE below within the reference's own tolerances.  The torch metric functions work on CPU or
+GPU tensors; `benchmark()` calls the matcher and scores it with roma_amd.dense_metrics (--torch-metrics: with the torch functions)."""
 import argparse
 import json
 import os
@@ -70,18 +70,27 @@ def geometric_dist(depth1, depth2, T_1to2, K1, K2, dense_matches):
     return gd, (gd < 1.0).float().mean(), (gd < 3.0).float().mean(), (gd < 5.0).float().mean(), prob
 
 
-def benchmark(model, batches):
+def benchmark(model, batches, torch_metrics=False):
     """megadepth_dense_benchmark.py:47-116 over an iterable of batches {im_A, im_B, im_A_depth, im_B_depth, T_1to2, K1, K2}
     (what MegadepthBuilder's test_loftr split yields); `model` = roma_amd.RegressionMatcher with symmetric=False,
-    upsample_preds=False like the reference test."""
+    upsample_preds=False like the reference test.  The metric of a batch is roma_amd.dense_metrics (one pass on the device, read
+    back once per batch like the reference's own accumulation); torch_metrics=True (--torch-metrics) takes the torch
+    `geometric_dist` above instead - the second opinion for an A/B of the two."""
+    import roma_amd
     tot = {"epe": 0.0, "mega_pck_1": 0.0, "mega_pck_3": 0.0, "mega_pck_5": 0.0}
     n = 0
     for data in batches:
         dev = model.device if hasattr(model, "device") else "cuda:0"
         d = {k: v.to(dev) for k, v in data.items()}
         matches, _ = model.match(d["im_A"], d["im_B"], batched=True)
-        gd, p1, p3, p5, _ = geometric_dist(d["im_A_depth"], d["im_B_depth"], d["T_1to2"], d["K1"], d["K2"], matches)
-        tot["epe"] += float(gd.mean()); tot["mega_pck_1"] += float(p1); tot["mega_pck_3"] += float(p3); tot["mega_pck_5"] += float(p5)
+        pair = (d["im_A_depth"], d["im_B_depth"], d["T_1to2"], d["K1"], d["K2"])
+        if torch_metrics:
+            gd, p1, p3, p5, _ = geometric_dist(*pair, matches)
+            epe, pck = float(gd.mean()), (float(p1), float(p3), float(p5))
+        else:
+            m = roma_amd.dense_metrics(matches, *pair)
+            epe, pck = float(m.epe), m.pck.tolist()
+        tot["epe"] += epe; tot["mega_pck_1"] += pck[0]; tot["mega_pck_3"] += pck[1]; tot["mega_pck_5"] += pck[2]
         n += 1
     return {k: v / max(n, 1) for k, v in tot.items()}
 
@@ -280,6 +289,7 @@ def main():
     ap.add_argument("--weights", default=None)
     ap.add_argument("--dinov2", default=None)
     ap.add_argument("--res", type=int, default=560)
+    ap.add_argument("--torch-metrics", action="store_true", help="dense loop: the torch geometric_dist instead of roma_amd.dense_metrics")
     args = ap.parse_args()
     from roma_amd import roma_outdoor, synthetic
     if args.weights:
@@ -308,7 +318,7 @@ def main():
                           "note": "synthetic planar scenes" + ("" if args.weights else ", RANDOM weights: plumbing check only")}))
         return
     batches = [synthetic_planar_batch(2, args.res, args.res, seed=s) for s in range(args.synthetic)]
-    res = benchmark(model, batches)
+    res = benchmark(model, batches, torch_metrics=args.torch_metrics)
     print(json.dumps({"results": res, "acceptance_on_megadepth": {k: v[0] for k, v in ACCEPTANCE.items()},
                       "note": "synthetic planar scenes" + ("" if args.weights else ", RANDOM weights: plumbing check only")}))
 
