@@ -554,6 +554,42 @@ int roma_op_dense_metrics(const float* matches, long batch_stride, long row_stri
                           int W2, double rel_thresh, double thr0, double thr1, double thr2, long long* out_n_valid,
                           long long* out_n_below, double* out_gd_sum, double* out_epe, double* out_pck, float* out_prob, double* out_gd,
                           void* workspace, long workspace_bytes, void* stream);
+/* Warp morph rendering - the frames of the reference's demo/demo_3D_effect.py, F.grid_sample(image B, (1 - t) warp[..., :2] +
+ * t warp[..., 2:]) through tensor_to_pil for every t of a schedule - in one enqueue.  Restated operation by operation in numpy
+ * float32 by tools/morph_ref.py.  Per frame t and pixel, every step in float32 in the order written, one rounding per operation,
+ * fp contraction off:
+ *   weights     w0 = float32(1.0 - t), w1 = float32(t), formed in float64 and rounded once (what the reference's Python scalars become
+ *               when they multiply a float32 tensor); any real t, also outside [0, 1]
+ *   coordinate  gx = w0 ax + w1 bx, gy = w0 ay + w1 by for the warp row (ax, ay, bx, by): two rounded products, a rounded sum
+ *   unnormalise ix = ((gx + 1) w - 1) 0.5 clamped to +-1e6 as min(max(ix, -1e6), 1e6) (a NaN becomes -1e6), iy with h - as
+ *               visualize_warp_kernel
+ *   sample      x0 = floor(ix), y0 = floor(iy), tx = ix - x0, ty = iy - y0; taps (y0, x0), (y0, x0+1), (y0+1, x0), (y0+1, x0+1) with
+ *               weights (1-tx)(1-ty), tx (1-ty), (1-tx) ty, tx ty; per channel v = 0, then v = v + weight * value tap by tap in that
+ *               order, a tap outside the image having the value 0 (zeros padding; no texel it does not cover is read)
+ *   blend       with certainty c: v = c v + (1 - c) background (visualize_warp's blend over white, for background = 1)
+ *   uint8       (unsigned char)(min(max(v, 0), 1) * 255.f): truncation, as numpy_to_pil; NaN -> 0
+ * warp DEVICE f32, 16-byte aligned, pixel (b, r, c) at warp + b warp_batch_stride + r warp_row_stride + 4 c (strides in floats,
+ * multiples of 4, as roma_op_dense_metrics takes them: the left half of a symmetric [H, 2W, 4] warp is read in place).  image
+ * DEVICE, contiguous: f32 [B, 3, im_h, im_w] (image_u8 = 0) or uint8 [B, im_h, im_w, 3] (image_u8 = 1), used as float(u) / 255.f
+ * with a correctly rounded division - the same bits as the f32 form of the same picture; (im_h, im_w) is independent of (H, W).
+ * ts DEVICE f64 [T].  certainty: NULL, or DEVICE f32 with pixel (b, r, c) at certainty + b cert_batch_stride + r cert_row_stride +
+ * c.  out DEVICE: uint8 [B, T, H, W, 3] (out_f32 = 0) or f32 [B, T, 3, H, W] (out_f32 = 1, the frames before the uint8 step).
+ * workspace DEVICE, 16-byte aligned, roma_op_render_morph_workspace(B, im_h, im_w, T) bytes (-1 for sizes that are refused): a
+ * first kernel packs the picture into 16-byte (r, g, b, 0) texels there, so that a tap is one load, and the T weight pairs; the
+ * second renders, a wave taking 256 consecutive pixels of the flattened frame (four per lane, 64 apart), which load their warp
+ * rows once and loop over roma_op_render_morph_frame_chunk() frames - frame chunks and B are the other grid axes.  A wave's 768
+ * bytes of a uint8 frame leave as three coalesced dwords per lane where the frame's first byte is dword aligned (always when H W
+ * is a multiple of 4) and the wave is full, and byte by byte elsewhere.  Two
+ * launches on the caller's stream, no host read, no allocation; every bit is independent of B, of the pair's place and of the run.
+ * Refused before anything is enqueued: a null required pointer, B outside [1, 65535], T < 1 or > 65535 frame chunks, H, W, im_h or
+ * im_w outside [1, 32768], image_u8 or out_f32 not 0 or 1, B T H W 3 beyond 9e15, strides that are not multiples of 4 (warp) or
+ * let rows overlap, a pointer not aligned as stated, a NaN background, a workspace that is too small, out or workspace sharing a
+ * byte with an input or with each other. */
+int roma_op_render_morph_frame_chunk(void);
+long roma_op_render_morph_workspace(int B, int im_h, int im_w, long T);
+int roma_op_render_morph(const float* warp, long warp_batch_stride, long warp_row_stride, const void* image, int image_u8, const double* ts,
+                         const float* certainty, long cert_batch_stride, long cert_row_stride, float background, int B, long T, int H,
+                         int W, int im_h, int im_w, void* out, int out_f32, void* workspace, long workspace_bytes, void* stream);
 /* Image preprocessing: Pillow's 8-bit bicubic resize (Image.resize((w, h), Image.BICUBIC) on a mode-RGB image, which is what
  * transforms.Resize(size, BICUBIC) does to a PIL image) of a batch of packed RGB images of mixed sizes to one or two target sizes,
  * then / 255 and the ImageNet mean / std of the matcher's host path - bit-identical to that path (roma_amd/matcher.py:

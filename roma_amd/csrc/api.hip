@@ -30,6 +30,7 @@
 #include "geometry.h"
 #include "triangulate.h"
 #include "gt_warp.h"
+#include "morph.h"
 #include "preprocess.h"
 
 namespace roma {
@@ -635,6 +636,15 @@ int roma_op_dense_metrics(const float* matches, long batch_stride, long row_stri
   return dense_metrics_launch(matches, batch_stride, row_stride, depth1, depth2, T, t_rows, K1, K2, B, h, w, H1, W1, H2, W2, rel_thresh,
                               thr0, thr1, thr2, out_n_valid, out_n_below, out_gd_sum, out_epe, out_pck, out_prob, out_gd, workspace,
                               workspace_bytes, S(stream));
+}
+// ---- warp morph rendering: the frames of a parallax animation in one enqueue (morph.hip)
+int roma_op_render_morph_frame_chunk(void) { return render_morph_frame_chunk(); }
+long roma_op_render_morph_workspace(int B, int im_h, int im_w, long T) { return render_morph_workspace_bytes(B, im_h, im_w, T); }
+int roma_op_render_morph(const float* warp, long warp_batch_stride, long warp_row_stride, const void* image, int image_u8, const double* ts,
+                         const float* certainty, long cert_batch_stride, long cert_row_stride, float background, int B, long T, int H,
+                         int W, int im_h, int im_w, void* out, int out_f32, void* workspace, long workspace_bytes, void* stream) {
+  return render_morph_launch(warp, warp_batch_stride, warp_row_stride, image, image_u8, ts, certainty, cert_batch_stride, cert_row_stride,
+                             background, B, T, H, W, im_h, im_w, out, out_f32, workspace, workspace_bytes, S(stream));
 }
 // ---- image preprocessing: Pillow-exact bicubic resize + normalisation (preprocess.hip)
 long roma_op_preprocess_workspace(const long long* desc_host, int n_images, const int* targets_hw, int n_targets) {

@@ -507,6 +507,12 @@ class RegressionMatcher:
         from .gt_warp import dense_metrics
         return dense_metrics(dense_matches, depth1, depth2, T_1to2, K1, K2, **kw)
 
+    def render_morph(self, warp, image, ts, **kw):
+        """The frames of the warp morph animation (`roma_amd.render_morph`; see there for the arguments and what is returned).  For a
+        symmetric warp pass its A -> B half, `warp[:, :W]`: it is read in place."""
+        from .render import render_morph
+        return render_morph(warp, image, ts, **kw)
+
     # ------------------------------------------------------------------ keypoint matching (matcher.py:732-773)
     def match_keypoints(self, x_A, x_B, warp, certainty, return_tuple=True, return_inds=False, max_dist=0.005, cert_th=0):
         """Mutual-nearest-neighbour matching of detector keypoints through the dense warp.

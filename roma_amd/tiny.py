@@ -402,6 +402,11 @@ class TinyRoMa:
                                                 im_B_path=im_B_path, symmetric=symmetric, save_path=save_path,
                                                 unnormalize=unnormalize)
 
+    def render_morph(self, warp, image, ts, **kw):
+        """The frames of the warp morph animation (`roma_amd.render_morph`, as RegressionMatcher.render_morph)."""
+        from .render import render_morph
+        return render_morph(warp, image, ts, **kw)
+
 
 def tiny_roma_v1_outdoor(device, weights=None, xfeat=None):
     """model_zoo/__init__.py:18-28.  Offline there is neither the weight URL nor torch.hub: both arguments are required."""
