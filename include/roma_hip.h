@@ -590,6 +590,42 @@ long roma_op_render_morph_workspace(int B, int im_h, int im_w, long T);
 int roma_op_render_morph(const float* warp, long warp_batch_stride, long warp_row_stride, const void* image, int image_u8, const double* ts,
                          const float* certainty, long cert_batch_stride, long cert_row_stride, float background, int B, long T, int H,
                          int W, int im_h, int im_w, void* out, int out_f32, void* workspace, long workspace_bytes, void* stream);
+/* RegressionMatcher.match_keypoints (matcher.py:732-773) for B pairs in one enqueue: five launches whatever B is, no host read, no
+ * allocation, the result padded and counted so that it feeds roma_op_ransac and its neighbours through `counts`.  Restated in numpy
+ * float32 by tools/keypoints_ref.py.  For pair b let na = min(max(counts_a[b], 0), NA) and nb likewise (NULL counts: NA / NB); the
+ * definition is the reference's on the pair's first na rows of x_a [B, NA, 2] and nb rows of x_b [B, NB, 2] (normalised (x, y)):
+ *   sample    p_i = bilinear(warp[b][..., 2:4], x_a[b, i]), c_i = bilinear(certainty[b], x_a[b, i]): zeros padding,
+ *             align_corners = False, the tap rule, the +-1e6 clamp and the float32 expression of roma_op_sample_warp_at (same bits)
+ *   distance  d2(i, j) = fmaf(dy, dy, dx * dx) in float32 with (dx, dy) = p_i - x_b[b, j], the expression of roma_op_mutual_nn
+ *   pairs     (i, j) is returned iff d2(i, j) equals the minimum of row i over j < nb AND the minimum of column j over i < na AND
+ *             c_i > cert_th AND d2(i, j) < max_dist * max_dist - EVERY tied pair, as the reference's torch.nonzero returns them, in
+ *             row-major order (i ascending, then j ascending).  A NaN distance is never a minimum.
+ *   counts    total[b] (int64) = the number of such pairs; counts[b] (int32) = min(total[b], M); only the first M pairs in that order
+ *             are written.  Duplicate keypoints tie, so total[b] can exceed na: M is the caller's choice.
+ *   outputs   inds [B, M, 2] int32 (index into A, index into B); kpts_a, kpts_b [B, M, 2] f32 = the caller's own rows x_a[b, i] and
+ *             x_b[b, j] (not p_i); rows at or beyond counts[b] hold -1 in inds and 0 in both kpts.
+ *   sizes     NULL, or DEVICE f32 (H_A, W_A, H_B, W_B) of pair b at sizes + b sizes_batch_stride (stride 0: one row for all): kpts
+ *             then come out in pixels, (W * 0.5f) * (x + 1.0f) and (H * 0.5f) * (y + 1.0f) in float32 - to_pixel_coordinates' bits.
+ * All pointers DEVICE.  warp f32, 16-byte aligned, pixel (b, r, c) at warp + b warp_batch_stride + r warp_row_stride + 4 c (strides
+ * in floats, multiples of 4, as roma_op_render_morph takes them: the A -> B half of a symmetric [B, H, 2W, 4] warp is read in place);
+ * certainty f32, pixel (b, r, c) at certainty + b cert_batch_stride + r cert_row_stride + c.  Rows of x_a / x_b at or beyond the
+ * counts are never read.  workspace: 16-byte aligned, roma_op_match_keypoints_workspace(B, NA, NB) bytes (-1 for sizes that are
+ * refused); it starts with p [B, NA, 2] f32 and, at the next multiple of 16 bytes, c [B, NA] f32 (rows below na written), then
+ * holds the bits of the row and column minima and the int64 positions.
+ * A pair's outputs are a function of that pair's rows alone: bit-identical from run to run, for every B, every place in the batch
+ * and every padding width NA / NB.  No output position comes from an atomic; slices of a row's or column's candidates are merged
+ * by an integer minimum on the bits of d2 >= 0, which is the same in any order.
+ * Refused before anything is enqueued: a null pointer (x_a may be NULL where NA = 0, x_b where NB = 0; counts_a, counts_b and
+ * sizes are optional), B outside [1, 65535], NA or NB outside [0, 2^20], M outside [1, 2^31 - 1], H or W outside [1, 32768], warp
+ * strides that are not multiples of 4 or let rows overlap, certainty strides that let rows overlap, a sizes stride in (0, 4), warp
+ * or workspace not 16-byte aligned, another pointer not aligned to its type, a NaN max_dist or cert_th, a workspace that is too
+ * small.  NA = 0 or NB = 0 is valid and gives zero counts. */
+long roma_op_match_keypoints_workspace(int B, long NA, long NB);
+int roma_op_match_keypoints(const float* x_a, const float* x_b, const int* counts_a, const int* counts_b, const float* warp,
+                            long warp_batch_stride, long warp_row_stride, const float* certainty, long cert_batch_stride,
+                            long cert_row_stride, const float* sizes, long sizes_batch_stride, int B, long NA, long NB, int H, int W,
+                            float max_dist, float cert_th, long M, int* inds, float* kpts_a, float* kpts_b, int* counts,
+                            long long* total, void* workspace, long workspace_bytes, void* stream);
 /* Image preprocessing: Pillow's 8-bit bicubic resize (Image.resize((w, h), Image.BICUBIC) on a mode-RGB image, which is what
  * transforms.Resize(size, BICUBIC) does to a PIL image) of a batch of packed RGB images of mixed sizes to one or two target sizes,
  * then / 255 and the ImageNet mean / std of the matcher's host path - bit-identical to that path (roma_amd/matcher.py:

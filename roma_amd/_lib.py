@@ -120,6 +120,9 @@ SIGNATURES = {
     "roma_op_render_morph_frame_chunk": (_i, []),
     "roma_op_render_morph_workspace": (_l, [_i, _i, _i, _l]),
     "roma_op_render_morph": (_i, [_vp, _l, _l, _vp, _i, _vp, _vp, _l, _l, _f, _i, _l, _i, _i, _i, _i, _vp, _i, _vp, _l, _vp]),
+    "roma_op_match_keypoints_workspace": (_l, [_i, _l, _l]),
+    "roma_op_match_keypoints": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _l, _l, _i, _i, _f, _f, _l, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _l, _vp]),
     "roma_op_preprocess_workspace": (_l, [_vp, _i, _vp, _i]),
     "roma_op_preprocess": (_i, [_vp, C.c_longlong, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "roma_op_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),

@@ -19,6 +19,7 @@
 #include "refiner_block.h"
 #include "kde.h"
 #include "keypoints.h"
+#include "keypoints_batched.h"
 #include "tiny.h"
 #include "tuning.h"
 #include "vit.h"
@@ -645,6 +646,17 @@ int roma_op_render_morph(const float* warp, long warp_batch_stride, long warp_ro
                          int W, int im_h, int im_w, void* out, int out_f32, void* workspace, long workspace_bytes, void* stream) {
   return render_morph_launch(warp, warp_batch_stride, warp_row_stride, image, image_u8, ts, certainty, cert_batch_stride, cert_row_stride,
                              background, B, T, H, W, im_h, im_w, out, out_f32, workspace, workspace_bytes, S(stream));
+}
+// ---- match_keypoints for a batch of warps: padded, counted, no host read (keypoints_batched.hip)
+long roma_op_match_keypoints_workspace(int B, long NA, long NB) { return match_keypoints_workspace_bytes(B, NA, NB); }
+int roma_op_match_keypoints(const float* x_a, const float* x_b, const int* counts_a, const int* counts_b, const float* warp,
+                            long warp_batch_stride, long warp_row_stride, const float* certainty, long cert_batch_stride,
+                            long cert_row_stride, const float* sizes, long sizes_batch_stride, int B, long NA, long NB, int H, int W,
+                            float max_dist, float cert_th, long M, int* inds, float* kpts_a, float* kpts_b, int* counts,
+                            long long* total, void* workspace, long workspace_bytes, void* stream) {
+  return match_keypoints_launch(x_a, x_b, counts_a, counts_b, warp, warp_batch_stride, warp_row_stride, certainty, cert_batch_stride,
+                                cert_row_stride, sizes, sizes_batch_stride, B, NA, NB, H, W, max_dist, cert_th, M, inds, kpts_a, kpts_b,
+                                counts, total, workspace, workspace_bytes, S(stream));
 }
 // ---- image preprocessing: Pillow-exact bicubic resize + normalisation (preprocess.hip)
 long roma_op_preprocess_workspace(const long long* desc_host, int n_images, const int* targets_hw, int n_targets) {

@@ -559,6 +559,18 @@ class RegressionMatcher:
             return torch.cat((inds_A, inds_B), dim=-1)
         return torch.cat((x_A[inds_A], x_B[inds_B]), dim=-1)
 
+    def match_keypoints_batched(self, x_A, x_B, warp, certainty, counts_A=None, counts_B=None, **kw):
+        """`match_keypoints` for every pair of a batch in one enqueue, padded and counted (`roma_amd.match_keypoints`; see there
+        for the arguments and the `KeypointMatches` it returns).  Like `match_keypoints` it samples the warp it is given; for a
+        symmetric warp pass symmetric=True, which reads the A -> B half in place.  The output feeds the batched geometry directly:
+
+            warp, certainty = model.match(im_A, im_B)                                # [B, H, 2W, 4], [B, H, 2W] (symmetric)
+            m = model.match_keypoints_batched(x_A, x_B, warp, certainty, counts_A, counts_B, sizes=(H_A, W_A, H_B, W_B), symmetric=True)
+            F, mask, ok = roma_amd.find_fundamental(m.kpts_A, m.kpts_B, counts=m.counts)
+        """
+        from .keypoints import match_keypoints
+        return match_keypoints(x_A, x_B, warp, certainty, counts_A, counts_B, **kw)
+
     def conf_from_fb_consistency(self, flow_forward, flow_backward, th=2):
         """matcher.py:672-699: 1 where the backward flow maps the forward target back to within `th` pixels."""
         for t in (flow_forward, flow_backward):
