@@ -554,6 +554,50 @@ int roma_op_dense_metrics(const float* matches, long batch_stride, long row_stri
                           int W2, double rel_thresh, double thr0, double thr1, double thr2, long long* out_n_valid,
                           long long* out_n_below, double* out_gd_sum, double* out_epe, double* out_pck, float* out_prob, double* out_gd,
                           void* workspace, long workspace_bytes, void* stream);
+/* Scoring of the pose and homography benchmarks - the reference's compute_pose_error and pose_auc (romatch/utils/utils.py:115-147),
+ * the accuracy / mAP lines of its MegaDepth and ScanNet pose benchmarks and the corner distance of its HPatches benchmark
+ * (hpatches_sequences_homog_benchmark.py:89-104) - so that a loop of roma_op_essential / roma_op_recover_pose or roma_op_ransac
+ * calls is scored with no host read before the final summary.  Restated operation by operation in numpy float64 by
+ * tools/metrics_ref.py.  All arithmetic is float64 in the order written, with fp contraction off; clip(c) = c < -1 ? -1 : (c > 1 ?
+ * 1 : c) keeps a NaN; DEG = 180.0 / pi as a double (numpy's rad2deg factor).  Every kernel is one workgroup; every output is
+ * bit-identical from run to run.
+ * The ERROR LOG is device memory: double log[capacity] and long long state[2] = {count, dropped}, both zero at first.  The three
+ * entries that take (log, capacity, state) append their B values in the launch that computes them: the launch reads count, writes
+ * value i to log[count + i] where count + i < capacity, then stores count + B and adds the number of values that did not fit to
+ * dropped (count keeps counting them).  No host value takes part; successive appends are ordered by the stream.  log and state NULL:
+ * no log.
+ * roma_op_pose_error: R DEVICE f64 [B, 3, 3], t f64 [B, 3], ok u8 [B] or NULL (all ok), T_gt f64 [B, t_rows, 4], t_rows 3 or 4
+ * (rows 0..2 = [R_gt | t_gt]).  out_err f64 [B, 3] = (e_t, e_R, e_pose) in degrees:
+ *   n = sqrt((t0 t0 + t1 t1) + t2 t2) sqrt((g0 g0 + g1 g1) + g2 g2), a = acos(clip(((t0 g0 + t1 g1) + t2 g2) / n)) DEG,
+ *   e_t = (180 - a) < a ? 180 - a : a   (NaN for a t or t_gt of zero norm, as np.minimum keeps it)
+ *   tr = the nine products R[r][q] R_gt[r][q] added in row-major order (the trace of R^T R_gt), e_R = |acos(clip((tr - 1) / 2))| DEG
+ *   e_pose = e_R > e_t ? e_R : e_t   (Python's max(e_t, e_R): a NaN e_t stays)
+ *   a pair with ok == 0 gets (90, 90, 90) whatever R and t hold - the except branch of the benchmarks.
+ * e_pose is what goes to the log.
+ * roma_op_corner_error: H_pred DEVICE f64 [B, 3, 3], ok u8 [B] or NULL, H_gt f64 [B, 3, 3], sizes f64 [B, 4] = (w1, h1, w2, h2).
+ * out_err f64 [B]: for the corners (x, y) = (0, 0), (0, h1 - 1), (w1 - 1, 0), (w1 - 1, h1 - 1), in this order, and either matrix
+ *   X = (H00 x + H01 y) + H02, Y and Z likewise, p = (X / Z, Y / Z); d = sqrt(dx dx + dy dy) with dx = p_gt.x - p_pred.x;
+ *   out = ((((0 + d0) + d1) + d2) + d3) / 4 / (min(w2, h2) / 480), min(w2, h2) = w2 < h2 ? w2 : h2.
+ * ok == 0 replaces H_pred by [[0, 0, 0], [0, 0, 0], [0, 0, 1]] (the reference's stand-in); inf and NaN of a zero Z propagate.
+ * roma_op_error_log_append: values DEVICE f64 [B], already computed, appended as above.
+ * roma_op_error_summary: errors DEVICE f64, not negative (NaN and +inf allowed).  Their number N is n (state NULL, 0 <= n <= 65536)
+ * or min(state[0], capacity), read on the device (state the log's, errors its rows, capacity <= 65536).  thresholds HOST f64 [T],
+ * 1 <= T <= 16, positive and finite; they travel in the kernel arguments.  One launch.  Per threshold thr: L = the number of errors
+ * < thr (strictly, as searchsorted on the left and the benchmarks' `<`; NaN and +inf are never below), S their sum, M their
+ * maximum (0 for L = 0) - per thread (256) over its errors in ascending index, a shuffle tree over the wave (offsets 32 .. 1), the
+ * four waves in order; no float atomics.  out_n i64 [1] = N, out_below i64 [T] = L, out_acc f64 [T] = L / N, out_auc f64 [T] =
+ * (((L thr) - S) + M / 2) / (N thr): the trapezoid under the recall curve from 0 to thr that pose_auc sorts for, telescoped.
+ * N = 0 gives NaN in acc and auc (0 / 0).
+ * Refused before anything is enqueued: a null required pointer, B < 0 or > 65535, t_rows not 3 or 4, an array that is not 8-byte
+ * aligned, a log without its state or the reverse, capacity < 1, more than 65536 errors, T outside [1, 16], a threshold that is
+ * not positive and finite.  B = 0 launches nothing. */
+int roma_op_pose_error(const double* R, const double* t, const unsigned char* ok, const double* T_gt, int t_rows, int B, double* out_err,
+                       double* log, long capacity, long long* state, void* stream);
+int roma_op_corner_error(const double* H_pred, const unsigned char* ok, const double* H_gt, const double* sizes, int B, double* out_err,
+                         double* log, long capacity, long long* state, void* stream);
+int roma_op_error_log_append(const double* values, int B, double* log, long capacity, long long* state, void* stream);
+int roma_op_error_summary(const double* errors, long n, const long long* state, long capacity, const double* thresholds, int T,
+                          long long* out_n, long long* out_below, double* out_acc, double* out_auc, void* stream);
 /* Warp morph rendering - the frames of the reference's demo/demo_3D_effect.py, F.grid_sample(image B, (1 - t) warp[..., :2] +
  * t warp[..., 2:]) through tensor_to_pil for every t of a schedule - in one enqueue.  Restated operation by operation in numpy
  * float32 by tools/morph_ref.py.  Per frame t and pixel, every step in float32 in the order written, one rounding per operation,

@@ -13,11 +13,14 @@ from .geometry import (essential_magsac, essential_minimal, estimate_pose, estim
 from .triangulation import depth_consistency, triangulate, triangulate_warp  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 from .gt_warp import DenseMetrics, dense_metrics, get_gt_warp, warp_kpts  # noqa: F401
+from .metrics import (ErrorLog, ErrorSummary, PoseError, compute_pose_error, homography_corner_error,  # noqa: F401
+                      hpatches_coordinates, pose_auc, pose_error)
 from .render import morph_times, render_morph  # noqa: F401
 from .keypoints import KeypointMatches, match_keypoints  # noqa: F401
 from .tiny import TinyRoMa, tiny_roma_v1_outdoor  # noqa: F401
 
-__all__ = ["match_keypoints", "KeypointMatches", "render_morph", "morph_times", "warp_kpts", "get_gt_warp", "dense_metrics", "DenseMetrics", "preprocess_images", "triangulate", "triangulate_warp", "depth_consistency",
+__all__ = ["pose_error", "compute_pose_error", "homography_corner_error", "pose_auc", "ErrorLog", "ErrorSummary", "PoseError",
+           "hpatches_coordinates", "match_keypoints", "KeypointMatches", "render_morph", "morph_times", "warp_kpts", "get_gt_warp", "dense_metrics", "DenseMetrics", "preprocess_images", "triangulate", "triangulate_warp", "depth_consistency",
 "RegressionMatcher", "roma_model", "roma_outdoor", "roma_indoor", "local_corr", "local_correlation", "kde",
            "multinomial", "sample_matches", "find_homography", "find_fundamental", "find_essential", "recover_pose", "refine_pose", "estimate_pose",
            "refine_homography", "refine_fundamental", "estimate_pose_uncalibrated", "essential_minimal", "magsac", "essential_magsac",

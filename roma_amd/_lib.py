@@ -117,6 +117,10 @@ SIGNATURES = {
     "roma_op_dense_metrics_workspace": (_l, [_i, _i, _i]),
     "roma_op_dense_metrics": (_i, [_vp, _l, _l, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double,
                                   C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "roma_op_pose_error": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _l, _vp, _vp]),
+    "roma_op_corner_error": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _l, _vp, _vp]),
+    "roma_op_error_log_append": (_i, [_vp, _i, _vp, _l, _vp, _vp]),
+    "roma_op_error_summary": (_i, [_vp, _l, _vp, _l, C.POINTER(C.c_double), _i, _vp, _vp, _vp, _vp, _vp]),
     "roma_op_render_morph_frame_chunk": (_i, []),
     "roma_op_render_morph_workspace": (_l, [_i, _i, _i, _l]),
     "roma_op_render_morph": (_i, [_vp, _l, _l, _vp, _i, _vp, _vp, _l, _l, _f, _i, _l, _i, _i, _i, _i, _vp, _i, _vp, _l, _vp]),

@@ -31,6 +31,7 @@
 #include "geometry.h"
 #include "triangulate.h"
 #include "gt_warp.h"
+#include "metrics.h"
 #include "morph.h"
 #include "preprocess.h"
 
@@ -637,6 +638,22 @@ int roma_op_dense_metrics(const float* matches, long batch_stride, long row_stri
   return dense_metrics_launch(matches, batch_stride, row_stride, depth1, depth2, T, t_rows, K1, K2, B, h, w, H1, W1, H2, W2, rel_thresh,
                               thr0, thr1, thr2, out_n_valid, out_n_below, out_gd_sum, out_epe, out_pck, out_prob, out_gd, workspace,
                               workspace_bytes, S(stream));
+}
+// ---- pose / homography benchmark scoring: errors, the error log, accuracy and AUC (metrics.hip)
+int roma_op_pose_error(const double* R, const double* t, const unsigned char* ok, const double* T_gt, int t_rows, int B, double* out_err,
+                       double* log, long capacity, long long* state, void* stream) {
+  return pose_error_launch(R, t, ok, T_gt, t_rows, B, out_err, log, capacity, state, S(stream));
+}
+int roma_op_corner_error(const double* H_pred, const unsigned char* ok, const double* H_gt, const double* sizes, int B, double* out_err,
+                         double* log, long capacity, long long* state, void* stream) {
+  return corner_error_launch(H_pred, ok, H_gt, sizes, B, out_err, log, capacity, state, S(stream));
+}
+int roma_op_error_log_append(const double* values, int B, double* log, long capacity, long long* state, void* stream) {
+  return error_log_append_launch(values, B, log, capacity, state, S(stream));
+}
+int roma_op_error_summary(const double* errors, long n, const long long* state, long capacity, const double* thresholds, int T,
+                          long long* out_n, long long* out_below, double* out_acc, double* out_auc, void* stream) {
+  return error_summary_launch(errors, n, state, capacity, thresholds, T, out_n, out_below, out_acc, out_auc, S(stream));
 }
 // ---- warp morph rendering: the frames of a parallax animation in one enqueue (morph.hip)
 int roma_op_render_morph_frame_chunk(void) { return render_morph_frame_chunk(); }

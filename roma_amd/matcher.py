@@ -484,6 +484,8 @@ class RegressionMatcher:
             m, c, counts = model.sample_batched(warp, certainty, num=5000, seed=0, return_counts=True)
             kpts_A, kpts_B = model.to_pixel_coordinates(m, H_A, W_A, H_B, W_B)      # elementwise: [B, 5000, 2] each
             R, t, mask, ok = roma_amd.estimate_pose(kpts_A, kpts_B, K_A, K_B, norm_thresh, counts=counts)
+            roma_amd.pose_error(R, t, T_gt, ok=ok, log=log)                          # log = roma_amd.ErrorLog(): no read until
+            ...                                                                      # log.pose_summary() after the last pair
         """
         from .sampling import sample_matches
         return sample_matches(matches, certainty, num=num, sample_mode=self.sample_mode, sample_thresh=self.sample_thresh,
