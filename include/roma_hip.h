@@ -427,6 +427,45 @@ long roma_op_refine_pose_workspace(int B, int N);
 int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
                         const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
                         unsigned char* out_mask, int* out_info, void* workspace, long workspace_bytes, void* stream);
+/* Absolute pose: the camera pose (R, t), x_cam = R X + t, from rows of a 3-D point X and its image x - P3P RANSAC.  Restated in
+ * tools/absolute_pose_ref.py.  points3d DEVICE f32 [B, N, 3]; kpts DEVICE f32 [B, N, 2]; counts, seeds as for roma_op_ransac;
+ * camera_matrix DEVICE f64 [B, 3, 3] or NULL (kpts are normalised image coordinates): x_n = ((u - cx) / fx, (v - cy) / fy) and
+ * the threshold is divided by (fx + fy) / 2, as in roma_op_essential.  The 3-D rows are centred on the centroid of the finite
+ * rows and scaled to mean distance 1 first, so the f32 scoring is independent of the world origin.  Hypotheses: samples of 3
+ * rows, up to 4 poses each (every real solution with three positive depths, ascending in the solver's root; collinear samples
+ * give none).  A row is an inlier when its depth is positive and its reprojection error is below the threshold; a row with a
+ * non-finite entry never is; rounds, selection and the adaptive iteration count are roma_op_ransac's.  A model needs 4 inliers
+ * (the rows of its own sample always fit).  Outputs, all DEVICE: R f64 [B, 3, 3], t f64 [B, 3] (0 where no model), mask u8
+ * [B, N], ok u8 [B], info int32 [B, 5] = {rounds run, winning hypothesis, its slot, its inlier count, pair valid (at least 4
+ * finite rows that are not all one point)}.  No host synchronisation; bit-identical from run to run and independent of B.
+ * workspace: device memory of roma_op_absolute_pose_workspace(B, N) bytes. */
+long roma_op_absolute_pose_workspace(int B, int N);
+int roma_op_absolute_pose(const float* points3d, const float* kpts, const int* counts, const unsigned long long* seeds,
+                          const double* camera_matrix, int B, int N, float threshold, double conf, int max_iters, double* out_r,
+                          double* out_t, unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* workspace,
+                          long workspace_bytes, void* stream);
+/* The P3P solver alone: X DEVICE f64 [S, 3, 3] points, x DEVICE f64 [S, 3, 2] normalised image points -> R DEVICE f64
+ * [S, 4, 3, 3], t DEVICE f64 [S, 4, 3] (solutions in ascending order of the solver's root, unused slots 0), n DEVICE int32 [S]. */
+int roma_op_absolute_pose_minimal(const double* X, const double* x, int S, double* out_r, double* out_t, int* out_n, void* stream);
+/* Nonlinear refinement of an absolute pose: a Levenberg-Marquardt fit of (R, t) to the reprojection error in normalised image
+ * coordinates under the hard-truncated loss sum min(|r|^2, thr^2); the loop (lambda, retries, stopping rules) is
+ * roma_op_refine_pose's, with six parameters (R <- exp([w]x) R, t <- t + dt), two residuals per row and at least 3 active rows; a
+ * row whose depth is not positive is not active.  It runs on the normalised problem of roma_op_absolute_pose.  R DEVICE f64
+ * [B, 3, 3], t DEVICE f64 [B, 3]; points3d, kpts, counts, camera_matrix as for roma_op_absolute_pose; valid DEVICE u8 [B] or NULL
+ * (every pair): pairs to fit, the others are copied through; thr in pixels of camera_matrix (normalised units without one).
+ * Outputs, all DEVICE: R, t (the input bits when no step was accepted), mask u8 [B, N] (active under the returned pose; zeros
+ * for a pair that is not fitted), info int32 [B, 4] = {accepted steps, cost evaluations, active rows at the end, pair fitted}.
+ * One workgroup per pair runs the whole loop in one launch; bit-identical from run to run and independent of B. */
+int roma_op_refine_absolute_pose(const double* R, const double* t, const float* points3d, const float* kpts, const int* counts,
+                                 const unsigned char* valid, const double* camera_matrix, int B, int N, double thr, int max_steps,
+                                 double* out_r, double* out_t, unsigned char* out_mask, int* out_info, void* stream);
+/* Matches to rows of roma_op_absolute_pose through a depth map of image A: matches DEVICE f32 [B, N, 4] in normalised
+ * coordinates (columns 0:2 in A, 2:4 in B), depth_a DEVICE f32 [B, H, W], camera_a DEVICE f64 [B, 3, 3] at the depth map's size
+ * -> points DEVICE f32 [B, N, 3] in camera A's frame, kpts_b DEVICE f32 [B, N, 2] pixels of an (H_b, W_b) image.  Depth is
+ * bilinear (align_corners = False) from four neighbours that are all finite and positive (roma_op_depth_consistency's rule);
+ * otherwise the point is NaN, which the pose kernels ignore. */
+int roma_op_lift_matches(const float* matches, const float* depth_a, const double* camera_a, int B, int N, int H, int W, int H_b,
+                         int W_b, float* out_points, float* out_kpts_b, void* stream);
 /* Nonlinear refinement of a homography (model 0) or a fundamental matrix (model 1): a Levenberg-Marquardt fit under the
  * hard-truncated loss sum min(|r|^2, thr^2) of the forward reprojection error in image B (H: what cv2.findHomography(..., RANSAC)
  * ends with) or of the Sampson distance (F: what PoseLib's estimate_fundamental ends with); it follows roma_op_ransac /

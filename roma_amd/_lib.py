@@ -108,6 +108,11 @@ SIGNATURES = {
     "roma_op_recover_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_refine_pose_workspace": (_l, [_i, _i]),
     "roma_op_refine_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "roma_op_absolute_pose_workspace": (_l, [_i, _i]),
+    "roma_op_absolute_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "roma_op_absolute_pose_minimal": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "roma_op_refine_absolute_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
+    "roma_op_lift_matches": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "roma_op_refine_model_workspace": (_l, [_i, _i]),
     "roma_op_refine_model": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_triangulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double,

@@ -25,6 +25,7 @@
 #include "vit.h"
 #include "sampling.h"
 #include "sample_batched.h"
+#include "absolute_pose.h"
 #include "essential.h"
 #include "model_refine.h"
 #include "pose_refine.h"
@@ -597,6 +598,28 @@ int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, c
                         unsigned char* out_mask, int* out_info, void* workspace, long workspace_bytes, void* stream) {
   return refine_pose_launch(R, t, kpts_a, kpts_b, counts, valid, B, N, thr, max_steps, out_r, out_t, out_mask, out_info, workspace,
                             (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+// ---- absolute pose: P3P RANSAC, refinement, lifting (absolute_pose.hip)
+long roma_op_absolute_pose_workspace(int B, int N) { return (long)absolute_pose_workspace_bytes(B, N); }
+int roma_op_absolute_pose(const float* points3d, const float* kpts, const int* counts, const unsigned long long* seeds,
+                          const double* camera_matrix, int B, int N, float threshold, double conf, int max_iters, double* out_r,
+                          double* out_t, unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* workspace,
+                          long workspace_bytes, void* stream) {
+  return absolute_pose_launch(points3d, kpts, counts, seeds, camera_matrix, B, N, threshold, conf, max_iters, out_r, out_t, out_mask,
+                              out_ok, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+int roma_op_absolute_pose_minimal(const double* X, const double* x, int S_, double* out_r, double* out_t, int* out_n, void* stream) {
+  return absolute_pose_minimal_launch(X, x, S_, out_r, out_t, out_n, S(stream));
+}
+int roma_op_refine_absolute_pose(const double* R, const double* t, const float* points3d, const float* kpts, const int* counts,
+                                 const unsigned char* valid, const double* camera_matrix, int B, int N, double thr, int max_steps,
+                                 double* out_r, double* out_t, unsigned char* out_mask, int* out_info, void* stream) {
+  return refine_absolute_pose_launch(R, t, points3d, kpts, counts, valid, camera_matrix, B, N, thr, max_steps, out_r, out_t, out_mask,
+                                     out_info, S(stream));
+}
+int roma_op_lift_matches(const float* matches, const float* depth_a, const double* camera_a, int B, int N, int H, int W, int H_b,
+                         int W_b, float* out_points, float* out_kpts_b, void* stream) {
+  return lift_matches_launch(matches, depth_a, camera_a, B, N, H, W, H_b, W_b, out_points, out_kpts_b, S(stream));
 }
 // ---- homography / fundamental-matrix refinement (model_refine.hip)
 long roma_op_refine_model_workspace(int B, int N) { return (long)refine_model_workspace_bytes(B, N); }

@@ -29,11 +29,15 @@
 //   Prep               what is fixed for the pair and a row evaluation reads (the Hartley normalisation; empty for the pose)
 //   Aux                what a row evaluation reads of a state, computed once per state by aux(state, prep, Aux&), never per row
 //   Row                what the Jacobian reuses of the residual
-//   point(prep, a, b)                   the row as the fit sees it (LmPoint)
+//   point(prep, a, b)                   the row as the fit sees it (LmPoint), from one float2 of each row array
+//   row(prep, ka, kb, i)                optional, instead of point: row i read by the policy itself from the two arrays, in
+//                                       a layout and a point type of its own (absolute_pose.hip: 3-D points of three floats)
 //   residual(aux, point, Row&, e[NR])   the residuals of a row; returns |e|^2
 //   jacobian(state, aux, point, row, e, J[NR][NP])
 //   apply(state, delta[NP], State&)     the state after a step
 #pragma once
+#include <type_traits>
+
 #include "ransac.h"
 
 namespace roma {
@@ -50,6 +54,20 @@ constexpr int lm_sums(int NP) { return NP * (NP + 1) / 2 + NP + 1; }
 
 struct LmPoint {
   double x, y, u, v;
+};
+
+// where lm_fit gets row i from: P::row if the policy has one, else P::point on ka[i], kb[i]
+template <class P, class = void>
+struct LmRows {
+  __device__ static __forceinline__ LmPoint get(const typename P::Prep& q, const float2* ka, const float2* kb, int i) {
+    return P::point(q, ka[i], kb[i]);
+  }
+};
+template <class P>
+struct LmRows<P, std::void_t<decltype(&P::row)>> {
+  __device__ static __forceinline__ auto get(const typename P::Prep& q, const float2* ka, const float2* kb, int i) {
+    return P::row(q, ka, kb, i);
+  }
 };
 
 struct LmResult {
@@ -132,7 +150,7 @@ __device__ __forceinline__ double lm_cost(const typename P::Aux& ax, const typen
   double s[1] = {0.0};
   int cnt = 0;
   for (int i = threadIdx.x; i < n; i += LM_THREADS) {
-    const LmPoint w = P::point(q, ka[i], kb[i]);
+    const auto w = LmRows<P>::get(q, ka, kb, i);
     typename P::Row r;
     double e[P::NR];
     const double r2 = P::residual(ax, w, r, e);
@@ -157,7 +175,7 @@ __device__ __forceinline__ double lm_normal(const typename P::State& st, const t
   for (int k = 0; k < NS; ++k) acc[k] = 0.0;
   int cnt = 0;
   for (int i = threadIdx.x; i < n; i += LM_THREADS) {
-    const LmPoint w = P::point(q, ka[i], kb[i]);
+    const auto w = LmRows<P>::get(q, ka, kb, i);
     typename P::Row r;
     double e[P::NR];
     const double r2 = P::residual(ax, w, r, e);

@@ -503,6 +503,18 @@ class RegressionMatcher:
         kw.setdefault("symmetric", bool(self.symmetric))
         return triangulate_warp(warp, certainty, R, t, K_A, K_B, H_A, W_A, H_B, W_B, **kw)
 
+    def localize(self, matches, depth_A, K_A, K_B, H_B, W_B, **kw):
+        """The pose of camera B in camera A's frame from this matcher's matches and a depth map of A: `roma_amd.lift_matches`,
+        then `roma_amd.estimate_absolute_pose` (see there for the keywords and what is returned; x_B = R X_A + t) - visual
+        localisation of a query B against a database image A that has depth:
+
+            matches, certainty, counts = model.sample_batched(warp, certainty, return_counts=True)
+            R, t, mask, ok = model.localize(matches, depth_A, K_A, K_B, H_B, W_B, counts=counts)
+        """
+        from .absolute_pose import estimate_absolute_pose, lift_matches
+        points3d, kpts_B = lift_matches(matches, depth_A, K_A, H_B, W_B)
+        return estimate_absolute_pose(points3d, kpts_B, K_B, **kw)
+
     def dense_metrics(self, dense_matches, depth1, depth2, T_1to2, K1, K2, **kw):
         """Dense EPE / PCK of this matcher's warp against the ground truth from depth (`roma_amd.dense_metrics`; see there for the
         arguments and what is returned).  For a symmetric warp pass its A -> B half, `warp[:, :, :w]`: it is read in place."""

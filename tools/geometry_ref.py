@@ -231,10 +231,10 @@ def update_num_iters(conf, w, s, max_iters):
     return int(math.ceil(num / denom))
 
 
-def round_loop(n, s, slots, fin, seed, conf, max_iters, solve, key, smaller=False):
+def round_loop(n, s, slots, fin, seed, conf, max_iters, solve, key, smaller=False, shape=(3, 3)):
     """the sampling rounds of one pair, as every model and scoring runs them (csrc/ransac.h): ROUND hypotheses per round drawn by
-    draw_samples; solve(idx [k, s]) -> (models [k, slots, 3, 3], number of models [k]) on the samples that were drawn and hold
-    finite rows only; key(models [K, 3, 3]) -> (keys [K], inlier counts [K]): the inlier count itself, larger is better, or
+    draw_samples; solve(idx [k, s]) -> (models [k, slots, *shape], number of models [k]) on the samples that were drawn and hold
+    finite rows only; key(models [K, *shape]) -> (keys [K], inlier counts [K]): the inlier count itself, larger is better, or
     (smaller) a score, smaller is better, with the count carried along; the best key of the used slots (ties: lowest (h, slot))
     replaces the current model if it is strictly better; OpenCV's adaptive iteration count from the winner's inlier count;
     stop once ROUND * rounds reaches it or max_iters.
@@ -246,17 +246,17 @@ def round_loop(n, s, slots, fin, seed, conf, max_iters, solve, key, smaller=Fals
         idx, drawn = draw_samples(seed, hs, n, s)
         idx = np.where(drawn[:, None], idx, 0)
         ok = drawn & fin[idx].all(axis=1)
-        models = np.zeros((ROUND, slots, 3, 3))
+        models = np.zeros((ROUND, slots, *shape))
         nm = np.zeros(ROUND, dtype=np.int64)
         sel = np.nonzero(ok)[0]
         if len(sel):
             models[sel], nm[sel] = solve(idx[sel])
-        keys, counts = key(models.reshape(-1, 3, 3))
+        keys, counts = key(models.reshape(-1, *shape))
         keys = np.where((np.arange(slots)[None, :] < nm[:, None]).reshape(-1), keys, worst)
         k = int(np.argmin(keys) if smaller else np.argmax(keys))  # the first one: lowest (h, slot)
         if keys[k] < best_key if smaller else keys[k] > best_key:
             best_key, best, best_h, best_root = keys[k].item(), int(counts[k]), r * ROUND + k // slots, k % slots
-            cur = models.reshape(-1, 3, 3)[k].copy()
+            cur = models.reshape(-1, *shape)[k].copy()
             needed = update_num_iters(conf, best / n, s, max_iters)
         rounds = r + 1
         if rounds * ROUND >= min(max_iters, needed):
