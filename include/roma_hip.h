@@ -466,6 +466,26 @@ int roma_op_refine_absolute_pose(const double* R, const double* t, const float* 
  * otherwise the point is NaN, which the pose kernels ignore. */
 int roma_op_lift_matches(const float* matches, const float* depth_a, const double* camera_a, int B, int N, int H, int W, int H_b,
                          int W_b, float* out_points, float* out_kpts_b, void* stream);
+/* Bundle adjustment: B independent problems of V views (1 <= V <= 8) and N points, the cameras and the points refined together
+ * on the reprojection error by Levenberg-Marquardt with the Schur complement, under the hard-truncated loss
+ * sum min(|r|^2, thr_i^2) over the observations; lambda, retries and stopping rules are roma_op_refine_pose's.  points DEVICE
+ * f64 [B, N, 3]; kpts DEVICE f32 [B, V, N, 2] in pixels of their view, a non-finite entry: not observed; camera_matrices DEVICE
+ * f64 [B, V, 3, 3] or NULL (kpts are normalised image coordinates, and so is reproj_thresh); R DEVICE f64 [B, V, 3, 3], t DEVICE
+ * f64 [B, V, 3] with x_cam = R X + t; hold DEVICE u8 [B, V, 6] or NULL (nothing held): the camera parameters (three of the
+ * rotation update R <- exp([w]x) R, three of t) that stay - hold at least seven, or the gauge is left to the damping; counts
+ * DEVICE int32 [B] or NULL (N points each; later points are copied through); valid DEVICE u8 [B] or NULL (every problem);
+ * reproj_thresh in pixels of each view (divided by (fx + fy) / 2), +inf: plain least squares.  A point beyond counts[b], with a
+ * non-finite start or with fewer than two observations is not part of the problem.  Outputs, all DEVICE: points f64 [B, N, 3], R,
+ * t (the input bits when no step was accepted, and always for a point outside the problem), mask u8 [B, V, N] (active under
+ * the returned state; zeros for a problem that is not fitted), info int32 [B, 6] = {accepted steps, cost evaluations, active
+ * rows at the end, points adjusted, free camera parameters, problem fitted}, cost f64 [B, 2] = {start, end}.  The workspace
+ * (roma_op_bundle_adjust_workspace bytes, N <= 2^27, B V N < 2^31) holds the current and the trial points.  One workgroup per
+ * problem runs the whole loop in one launch; bit-identical from run to run and independent of B. */
+long roma_op_bundle_adjust_workspace(int B, int V, int N);
+int roma_op_bundle_adjust(const double* points, const float* kpts, const double* camera_matrices, const double* R, const double* t,
+                          const unsigned char* hold, const int* counts, const unsigned char* valid, int B, int V, int N,
+                          double reproj_thresh, int max_steps, double* out_points, double* out_r, double* out_t, unsigned char* out_mask,
+                          int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream);
 /* Nonlinear refinement of a homography (model 0) or a fundamental matrix (model 1): a Levenberg-Marquardt fit under the
  * hard-truncated loss sum min(|r|^2, thr^2) of the forward reprojection error in image B (H: what cv2.findHomography(..., RANSAC)
  * ends with) or of the Sampson distance (F: what PoseLib's estimate_fundamental ends with); it follows roma_op_ransac /

@@ -2,7 +2,7 @@
 
 Public surface mirrors the reference package (`romatch/__init__.py:2`): model factories and the
 local-correlation operator, plus the post-processing of `sample()` output (robust homography /
-fundamental / essential-matrix estimation, relative and absolute pose).  Everything numerical runs in libroma_hip.so (hand-written HIP, gfx950).
+fundamental / essential-matrix estimation, relative and absolute pose, bundle adjustment).  Everything numerical runs in libroma_hip.so (hand-written HIP, gfx950).
 """
 from .matcher import RegressionMatcher, roma_indoor, roma_model, roma_outdoor  # noqa: F401
 from .local_correlation import local_corr, local_correlation  # noqa: F401
@@ -11,6 +11,7 @@ from .sampling import multinomial, sample_matches  # noqa: F401
 from .geometry import (essential_magsac, essential_minimal, estimate_pose, estimate_pose_uncalibrated, find_essential,  # noqa: F401
                        find_fundamental, find_homography, magsac, recover_pose, refine_fundamental, refine_homography, refine_pose)
 from .absolute_pose import absolute_pose_minimal, estimate_absolute_pose, lift_matches, refine_absolute_pose  # noqa: F401
+from .bundle import BundleResult, bundle_adjust, reconstruct_pair  # noqa: F401
 from .triangulation import depth_consistency, triangulate, triangulate_warp  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 from .gt_warp import DenseMetrics, dense_metrics, get_gt_warp, warp_kpts  # noqa: F401
@@ -26,4 +27,5 @@ __all__ = ["pose_error", "compute_pose_error", "homography_corner_error", "pose_
            "multinomial", "sample_matches", "find_homography", "find_fundamental", "find_essential", "recover_pose", "refine_pose", "estimate_pose",
            "refine_homography", "refine_fundamental", "estimate_pose_uncalibrated", "essential_minimal", "magsac", "essential_magsac",
            "estimate_absolute_pose", "absolute_pose_minimal", "refine_absolute_pose", "lift_matches",
+           "bundle_adjust", "reconstruct_pair", "BundleResult",
            "TinyRoMa", "tiny_roma_v1_outdoor"]

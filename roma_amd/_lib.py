@@ -113,6 +113,9 @@ SIGNATURES = {
     "roma_op_absolute_pose_minimal": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "roma_op_refine_absolute_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
     "roma_op_lift_matches": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "roma_op_bundle_adjust_workspace": (_l, [_i, _i, _i]),
+    "roma_op_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                  _vp, _l, _vp]),
     "roma_op_refine_model_workspace": (_l, [_i, _i]),
     "roma_op_refine_model": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_triangulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double,

@@ -26,6 +26,7 @@
 #include "sampling.h"
 #include "sample_batched.h"
 #include "absolute_pose.h"
+#include "bundle.h"
 #include "essential.h"
 #include "model_refine.h"
 #include "pose_refine.h"
@@ -620,6 +621,16 @@ int roma_op_refine_absolute_pose(const double* R, const double* t, const float* 
 int roma_op_lift_matches(const float* matches, const float* depth_a, const double* camera_a, int B, int N, int H, int W, int H_b,
                          int W_b, float* out_points, float* out_kpts_b, void* stream) {
   return lift_matches_launch(matches, depth_a, camera_a, B, N, H, W, H_b, W_b, out_points, out_kpts_b, S(stream));
+}
+// ---- bundle adjustment: cameras and points together, Schur-complement LM (bundle.hip)
+long roma_op_bundle_adjust_workspace(int B, int V, int N) { return (long)bundle_adjust_workspace_bytes(B, V, N); }
+int roma_op_bundle_adjust(const double* points, const float* kpts, const double* camera_matrices, const double* R, const double* t,
+                          const unsigned char* hold, const int* counts, const unsigned char* valid, int B, int V, int N,
+                          double reproj_thresh, int max_steps, double* out_points, double* out_r, double* out_t, unsigned char* out_mask,
+                          int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream) {
+  return bundle_adjust_launch(points, kpts, camera_matrices, R, t, hold, counts, valid, B, V, N, reproj_thresh, max_steps, out_points,
+                              out_r, out_t, out_mask, out_info, out_cost, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0),
+                              S(stream));
 }
 // ---- homography / fundamental-matrix refinement (model_refine.hip)
 long roma_op_refine_model_workspace(int B, int N) { return (long)refine_model_workspace_bytes(B, N); }

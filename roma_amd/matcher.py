@@ -515,6 +515,20 @@ class RegressionMatcher:
         points3d, kpts_B = lift_matches(matches, depth_A, K_A, H_B, W_B)
         return estimate_absolute_pose(points3d, kpts_B, K_B, **kw)
 
+    def reconstruct(self, matches, K_A, K_B, H_A, W_A, H_B, W_B, **kw):
+        """Relative pose, 3-D points and their joint refinement from this matcher's matches: `to_pixel_coordinates`, then
+        `roma_amd.reconstruct_pair` (see there for the keywords - norm_thresh and reproj_thresh are required - and what is
+        returned) - a two-view reconstruction with nothing read back:
+
+            matches, certainty, counts = model.sample_batched(warp, certainty, return_counts=True)
+            R, t, points, mask, ok = model.reconstruct(matches, K_A, K_B, H_A, W_A, H_B, W_B, norm_thresh=1e-3,
+                                                       reproj_thresh=2.0, counts=counts)
+        """
+        from .bundle import _device_tensor, reconstruct_pair
+        matches = _device_tensor(matches, "matches")
+        kpts_A, kpts_B = self.to_pixel_coordinates(matches, H_A, W_A, H_B, W_B)
+        return reconstruct_pair(kpts_A, kpts_B, K_A, K_B, **kw)
+
     def dense_metrics(self, dense_matches, depth1, depth2, T_1to2, K1, K2, **kw):
         """Dense EPE / PCK of this matcher's warp against the ground truth from depth (`roma_amd.dense_metrics`; see there for the
         arguments and what is returned).  For a symmetric warp pass its A -> B half, `warp[:, :, :w]`: it is read in place."""
