@@ -1,20 +1,19 @@
 // Absolute pose on the device: the camera pose (R, t), x_cam = R X + t, from rows (X, x) of a 3-D point and its image - what a
 // caller does with the points of triangulate / a depth map and the matches of sample_batched (visual localisation, registering
 // a further image).  tools/absolute_pose_ref.py restates this file in numpy float64 expression by expression and is the oracle
-// of the GPU tests.  The pipeline is ransac.h's, with kernels of its own: a pose is 12 doubles and a row 5 floats, where
-// ransac.h fixes 9 and a float4.
+// of the GPU tests.  The RANSAC is ransac.h's pipeline under CountScoring with the model policy AbsPose below: a pose is 12
+// doubles (R row-major, then t) and a row the normalised 3-D point and its image point.
 //
-// Per pair b (counts[b] rows; later rows are never read):
-//   1. ap_norm_kernel: x_n = ((u - cx) / fx, (v - cy) / fy) and the threshold divided by (fx + fy) / 2 under a camera matrix;
-//      X' = s (X - c), c the centroid of the finite rows and s = 1 / their mean distance to it (f64 sums in block_sum order), so
-//      that the f32 scoring works on O(1) numbers wherever the world origin is.  The pose of the normalised problem is
-//      (R, t' = s (R c + t)); rows with a non-finite entry are stored as NaN.  Valid: at least 4 finite rows and s finite.
-//   2. rounds of RANSAC_ROUND hypotheses, ceil(max_iters / ROUND) times, no host synchronisation:
-//      ap_hyp_kernel     one lane per hypothesis: draw_sample<3>, the rows normalised in f64, p3p: up to 4 poses
-//      ap_score_kernel   one wave per hypothesis: popc(ballot) of the f32 inlier test z > 0, |p_xy - x_n z|^2 < thr^2 z^2
-//      ap_select_kernel  per pair: largest count (ties: lowest (h, slot); an earlier round keeps a tie), adaptive iteration count
-//   3. ap_mask_kernel + ap_finish_kernel: mask, ok (a model needs AP_MIN_INLIERS inliers: the three rows of a sample fit each of
-//      its solutions), t = t' / s - R c, info.
+// What AbsPose adds to the shared pipeline, per pair b (counts[b] rows; later rows are never read):
+//   normalise   x_n = ((u - cx) / fx, (v - cy) / fy) and the threshold divided by (fx + fy) / 2 under a camera matrix;
+//               X' = s (X - c), c the centroid of the finite rows and s = 1 / their mean distance to it (f64 sums in block_sum
+//               order), so that the f32 scoring works on O(1) numbers wherever the world origin is.  The pose of the normalised
+//               problem is (R, t' = s (R c + t)); rows with a non-finite entry are stored as NaN (ApRows: a float4 array of the
+//               points and a float2 array of the image points).  Valid: at least 4 finite rows and s finite.
+//   hypothesis  one lane per hypothesis: the three rows of the sample normalised in f64, p3p: up to 4 poses
+//   inlier      the f32 test z > 0, |p_xy - x_n z|^2 < thr^2 z^2
+//   model_out   t = t' / s - R c.  A model needs MIN_INLIERS = 4 inliers: the three rows of a sample fit each of its solutions.
+//               No refit (REFINE_ITERS = 0); the info row is {rounds, best_h, best_slot, best, valid}.
 // p3p: unit bearings f_i, squared sides a2 = |X2 - X3|^2, b2 = |X1 - X3|^2, c2 = |X1 - X2|^2, cosines ca = f2.f3, cb = f1.f3,
 // cg = f1.f2, depths s2 = u s1, s3 = v s1.  With A = a2 / b2, C = c2 / b2 the difference of the two conics the cosine laws give in
 // (u, v) is u D(v) = N(v), N = (1 - A + C) v^2 + 2 (A - C) cb v + (C - A - 1), D = 2 (ca v - cg), and N^2 - 2 cg N D + Q D^2 = 0
@@ -38,8 +37,35 @@ constexpr int AP_BISECT = 48, AP_NEWTON = 3, AP_GN = 3;
 constexpr double AP_DEN_EPS = 1e-9;        // |D(v)| below which u = N / D is not formed
 constexpr double AP_COLLINEAR_EPS = 1e-4;  // |d12 x d13| / (|d12| |d13|) below which the 3-D sample is collinear
 constexpr int AP_MIN_VALID = 4;            // finite rows below which a pair is not sampled
-constexpr int AP_MIN_INLIERS = 4;          // inliers below which a model is not accepted
-constexpr int AP_HYP_THREADS = 64;
+
+// ------------------------------------------------------------------------------------------------------------ normalisation
+struct ApNorm {
+  double c[3], s;               // X' = s (X - c)
+  double fx, fy, cx, cy;        // x_n = ((u - cx) / fx, (v - cy) / fy); identity without a camera matrix
+  __device__ __forceinline__ void apply(const float* X, float2 k, double (&Xn)[3], double (&xn)[2]) const {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) Xn[a] = ((double)X[a] - c[a]) * s;
+    xn[0] = ((double)k.x - cx) / fx;
+    xn[1] = ((double)k.y - cy) / fy;
+  }
+  // whether a row (3-D point, image point), normalised or not, holds finite values only
+  __device__ static bool finite(const double (&X)[3], const double (&x)[2]) {
+    return isfinite(X[0]) && isfinite(X[1]) && isfinite(X[2]) && isfinite(x[0]) && isfinite(x[1]);
+  }
+  // the threshold in normalised image coordinates: pixels over the mean focal length under a camera matrix
+  __device__ __forceinline__ double threshold(bool camera, double thr) const { return camera ? thr / ((fx + fy) / 2) : thr; }
+};
+
+__device__ __forceinline__ ApNorm camera_norm(const double* K) {
+  ApNorm nrm;
+  nrm.c[0] = nrm.c[1] = nrm.c[2] = 0.0;
+  nrm.s = 1.0;
+  nrm.fx = K ? K[0] : 1.0;
+  nrm.fy = K ? K[4] : 1.0;
+  nrm.cx = K ? K[2] : 0.0;
+  nrm.cy = K ? K[5] : 0.0;
+  return nrm;
+}
 
 // ------------------------------------------------------------------------------------------------------------ polynomials
 template <int D>
@@ -142,7 +168,7 @@ __device__ __forceinline__ int p3p(const double (&X)[3][3], const double (&x)[3]
     f[k][0] = x[k][0] / nrm;
     f[k][1] = x[k][1] / nrm;
     f[k][2] = 1.0 / nrm;
-    ok = ok && isfinite(x[k][0]) && isfinite(x[k][1]) && isfinite(X[k][0]) && isfinite(X[k][1]) && isfinite(X[k][2]);
+    ok = ok && ApNorm::finite(X[k], x[k]);
   }
   double d12[3], d13[3], d23[3], cr[3];
 #pragma unroll
@@ -244,266 +270,117 @@ __device__ __forceinline__ int p3p(const double (&X)[3][3], const double (&x)[3]
   return n;
 }
 
-// ------------------------------------------------------------------------------------------------------------ state, workspace
-struct ApNorm {
-  double c[3], s;               // X' = s (X - c)
-  double fx, fy, cx, cy;        // x_n = ((u - cx) / fx, (v - cy) / fy); identity without a camera matrix
-  __device__ __forceinline__ void apply(const float* X, float2 k, double (&Xn)[3], double (&xn)[2]) const {
-#pragma unroll
-    for (int a = 0; a < 3; ++a) Xn[a] = ((double)X[a] - c[a]) * s;
-    xn[0] = ((double)k.x - cx) / fx;
-    xn[1] = ((double)k.y - cy) / fy;
+// ------------------------------------------------------------------------------------------------------------ model policy
+struct ApIn {                   // the caller's rows: points3d [B, N, 3], kpts [B, N] pixels (normalised without a camera matrix)
+  const float* X;
+  const float2* k;
+  __device__ ApIn at(long row) const { return {X + 3 * row, k + row}; }
+};
+
+struct ApOut {                  // R [B, 9], t [B, 3]
+  double* r;
+  double* t;
+};
+
+// the normalised f32 rows, two arrays (the score kernel loads one float4 and one float2 per row): (X', Y', Z', 0) and x_n, [B * N]
+struct ApRows {
+  struct Row { float4 X; float2 x; };
+  float4* px;
+  float2* pi;
+  static size_t carve(ApRows& r, char* ws, size_t o, size_t rows) {
+    r.px = reinterpret_cast<float4*>(ws + o); o = align256(o + sizeof(float4) * rows);
+    r.pi = reinterpret_cast<float2*>(ws + o); o = align256(o + sizeof(float2) * rows);
+    return o;
+  }
+  __device__ ApRows at(long row) const { return {px + row, pi + row}; }
+  __device__ Row row(int i, int n) const {
+    return {i < n ? px[i] : make_float4(NAN, NAN, NAN, NAN), i < n ? pi[i] : make_float2(NAN, NAN)};
   }
 };
 
-struct ApState {
-  ApNorm nrm;
-  double cur[12];               // current pose of the normalised problem: R row-major, t'
-  alignas(16) float curf[12];   // the f32 copy the scoring reads
-  float thr2;                   // squared threshold in normalised image coordinates
-  int n, valid, best, best_h, best_slot, needed, rounds, done;
+struct AbsPose {
+  using Norm = ApNorm;
+  using In = ApIn;
+  using Out = ApOut;
+  using Rows = ApRows;
+  static constexpr int S = 3, SLOTS = AP_SLOTS, NM = 12, HYP_THREADS = 64, HYP_LANES = 1, REFINE_ITERS = 0, INFO = ABSOLUTE_POSE_INFO;
+  static constexpr int MIN_INLIERS = 4;  // the three rows of a sample fit each of its solutions
+  static constexpr bool SCORE_EVERY_SLOT = false;
+  static_assert(INFO == INFO_CORE);
+
+  // every thread of the workgroup: camera, centroid and scale over the finite rows (f64 sums in block_sum order), the rows;
+  // one threshold (t2a == t2b)
+  __device__ static bool normalise(ApIn in, int n, const double* K, float thr, double* sh, ApRows rows, ApNorm& nrm, float& t2a,
+                                   float& t2b) {
+    const int t = threadIdx.x;
+    nrm = camera_norm(K);
+    double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+    for (int i = t; i < n; i += 256) {
+      double Xn[3], xn[2];
+      nrm.apply(in.X + 3 * (long)i, in.k[i], Xn, xn);
+      if (ApNorm::finite(Xn, xn)) {
+        s0 += Xn[0]; s1 += Xn[1]; s2 += Xn[2]; s3 += 1;
+      }
+    }
+    const double cnt = block_sum(s3, sh);
+    const double c0 = block_sum(s0, sh) / cnt, c1 = block_sum(s1, sh) / cnt, c2 = block_sum(s2, sh) / cnt;
+    double dsum = 0;
+    for (int i = t; i < n; i += 256) {
+      double Xn[3], xn[2];
+      nrm.apply(in.X + 3 * (long)i, in.k[i], Xn, xn);
+      if (ApNorm::finite(Xn, xn)) {
+        const double d0 = Xn[0] - c0, d1 = Xn[1] - c1, d2 = Xn[2] - c2;
+        dsum += sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+      }
+    }
+    const double mean = block_sum(dsum, sh) / cnt;
+    nrm.c[0] = c0; nrm.c[1] = c1; nrm.c[2] = c2;
+    nrm.s = mean > 0 ? 1.0 / mean : INFINITY;
+    for (int i = t; i < n; i += 256) {
+      double Xn[3], xn[2];
+      nrm.apply(in.X + 3 * (long)i, in.k[i], Xn, xn);
+      const bool fin = ApNorm::finite(Xn, xn);
+      rows.px[i] = fin ? make_float4((float)Xn[0], (float)Xn[1], (float)Xn[2], 0.f) : make_float4(NAN, NAN, NAN, NAN);
+      rows.pi[i] = fin ? make_float2((float)xn[0], (float)xn[1]) : make_float2(NAN, NAN);
+    }
+    const double tn = nrm.threshold(K != nullptr, (double)thr);
+    t2a = t2b = (float)(tn * tn);
+    return cnt >= AP_MIN_VALID && isfinite(nrm.s);
+  }
+
+  // one lane per hypothesis: a row that is not finite makes p3p return no model
+  __device__ static void hypothesis(ApIn in, const int (&idx)[3], bool act, const ApNorm& nrm, int g, int, const Slots& sl) {
+    double X[3][3], x[3][2];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const long row = act ? idx[k] : 0;
+      nrm.apply(in.X + 3 * row, in.k[row], X[k], x[k]);
+    }
+    sl.n[g] = p3p(X, x, act, [&](int s, const double (&m)[12]) { store_model<12>(m, (long)g * AP_SLOTS + s, sl); });
+  }
+
+  // z > 0 and |p_xy - x_n z|^2 < thr^2 z^2 with p = R X' + t'; false for a NaN row
+  __device__ static bool inlier(const float* m, ApRows::Row r, float thr2, float) {
+    const float4 X = r.X;
+    const float2 x = r.x;
+    const float px = fmaf(m[0], X.x, fmaf(m[1], X.y, fmaf(m[2], X.z, m[9])));
+    const float py = fmaf(m[3], X.x, fmaf(m[4], X.y, fmaf(m[5], X.z, m[10])));
+    const float z = fmaf(m[6], X.x, fmaf(m[7], X.y, fmaf(m[8], X.z, m[11])));
+    const float ex = fmaf(-x.x, z, px), ey = fmaf(-x.y, z, py);
+    return z > 0.f && fmaf(ex, ex, ey * ey) < thr2 * (z * z);
+  }
+
+  // the pose of the caller's problem: t = t' / s - R c
+  __device__ static void model_out(const PairState<AbsPose>& P, bool good, ApOut out, int b) {
+    const double* m = P.cur;
+    const double* c = P.nrm.c;
+    for (int k = 0; k < 9; ++k) out.r[(long)b * 9 + k] = good ? m[k] : 0.0;
+    for (int r = 0; r < 3; ++r)
+      out.t[(long)b * 3 + r] = good ? m[9 + r] / P.nrm.s - ((m[3 * r] * c[0] + m[3 * r + 1] * c[1]) + m[3 * r + 2] * c[2]) : 0.0;
+  }
 };
 
-struct ApSlots {                // the models of one round: AP_SLOTS per hypothesis, B * R hypotheses
-  double* d;                    // [B * R * SLOTS][12]
-  float* f;                     // [B * R * SLOTS][12]
-  int* n;                       // models per hypothesis [B * R]
-  int* cnt;                     // inlier count per slot, -1 if unused [B * R * SLOTS]
-};
-
-struct ApCarve {
-  ApState* st;
-  float4* px;                   // normalised 3-D rows (X', Y', Z', 0) [B * N]
-  float2* pi;                   // normalised image rows [B * N]
-  ApSlots sl;
-  size_t bytes;
-};
-
-ApCarve ap_carve(void* ws, int B, int N) {
-  ApCarve c;
-  char* p = static_cast<char*>(ws);
-  size_t o = 0;
-  c.st = reinterpret_cast<ApState*>(p + o); o = align256(o + sizeof(ApState) * B);
-  c.px = reinterpret_cast<float4*>(p + o); o = align256(o + sizeof(float4) * (size_t)B * N);
-  c.pi = reinterpret_cast<float2*>(p + o); o = align256(o + sizeof(float2) * (size_t)B * N);
-  c.sl.d = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * 12 * AP_SLOTS * (size_t)B * R);
-  c.sl.f = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * 12 * AP_SLOTS * (size_t)B * R);
-  c.sl.n = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * (size_t)B * R);
-  c.sl.cnt = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * AP_SLOTS * (size_t)B * R);
-  c.bytes = o + 256;
-  return c;
-}
-
-__device__ __forceinline__ ApNorm camera_norm(const double* K) {
-  ApNorm nrm;
-  nrm.c[0] = nrm.c[1] = nrm.c[2] = 0.0;
-  nrm.s = 1.0;
-  nrm.fx = K ? K[0] : 1.0;
-  nrm.fy = K ? K[4] : 1.0;
-  nrm.cx = K ? K[2] : 0.0;
-  nrm.cy = K ? K[5] : 0.0;
-  return nrm;
-}
-
-// z > 0 and |p_xy - x_n z|^2 < thr^2 z^2 with p = R X' + t'; false for a NaN row
-__device__ __forceinline__ bool ap_inlier(const float* m, float4 X, float2 x, float thr2) {
-  const float px = fmaf(m[0], X.x, fmaf(m[1], X.y, fmaf(m[2], X.z, m[9])));
-  const float py = fmaf(m[3], X.x, fmaf(m[4], X.y, fmaf(m[5], X.z, m[10])));
-  const float z = fmaf(m[6], X.x, fmaf(m[7], X.y, fmaf(m[8], X.z, m[11])));
-  const float ex = fmaf(-x.x, z, px), ey = fmaf(-x.y, z, py);
-  return z > 0.f && fmaf(ex, ex, ey * ey) < thr2 * (z * z);
-}
-
-// ------------------------------------------------------------------------------------------------------------ kernels
-__global__ __launch_bounds__(256) void ap_norm_kernel(const float* __restrict__ pts3, const float2* __restrict__ kpts,
-                                                      const int* __restrict__ counts, const double* __restrict__ K, int N, float thr,
-                                                      int max_iters, ApState* __restrict__ st, float4* __restrict__ px,
-                                                      float2* __restrict__ pi) {
-  __shared__ double sh[256];
-  const int b = blockIdx.x, t = threadIdx.x;
-  const int n = counts ? min(max(counts[b], 0), N) : N;
-  const float* X = pts3 + (long)b * N * 3;
-  const float2* kp = kpts + (long)b * N;
-  ApNorm nrm = camera_norm(K ? K + (long)b * 9 : nullptr);
-  double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
-  for (int i = t; i < n; i += 256) {
-    double Xn[3], xn[2];
-    nrm.apply(X + 3 * (long)i, kp[i], Xn, xn);
-    if (isfinite(Xn[0]) && isfinite(Xn[1]) && isfinite(Xn[2]) && isfinite(xn[0]) && isfinite(xn[1])) {
-      s0 += Xn[0]; s1 += Xn[1]; s2 += Xn[2]; s3 += 1;
-    }
-  }
-  const double cnt = block_sum(s3, sh);
-  const double c0 = block_sum(s0, sh) / cnt, c1 = block_sum(s1, sh) / cnt, c2 = block_sum(s2, sh) / cnt;
-  double dsum = 0;
-  for (int i = t; i < n; i += 256) {
-    double Xn[3], xn[2];
-    nrm.apply(X + 3 * (long)i, kp[i], Xn, xn);
-    if (isfinite(Xn[0]) && isfinite(Xn[1]) && isfinite(Xn[2]) && isfinite(xn[0]) && isfinite(xn[1])) {
-      const double d0 = Xn[0] - c0, d1 = Xn[1] - c1, d2 = Xn[2] - c2;
-      dsum += sqrt((d0 * d0 + d1 * d1) + d2 * d2);
-    }
-  }
-  const double mean = block_sum(dsum, sh) / cnt;
-  nrm.c[0] = c0; nrm.c[1] = c1; nrm.c[2] = c2;
-  nrm.s = mean > 0 ? 1.0 / mean : INFINITY;
-  const bool valid = cnt >= AP_MIN_VALID && isfinite(nrm.s);
-  for (int i = t; i < n; i += 256) {
-    double Xn[3], xn[2];
-    nrm.apply(X + 3 * (long)i, kp[i], Xn, xn);
-    const bool fin = isfinite(Xn[0]) && isfinite(Xn[1]) && isfinite(Xn[2]) && isfinite(xn[0]) && isfinite(xn[1]);
-    px[(long)b * N + i] = fin ? make_float4((float)Xn[0], (float)Xn[1], (float)Xn[2], 0.f) : make_float4(NAN, NAN, NAN, NAN);
-    pi[(long)b * N + i] = fin ? make_float2((float)xn[0], (float)xn[1]) : make_float2(NAN, NAN);
-  }
-  if (t == 0) {
-    ApState& S = st[b];
-    S.nrm = nrm;
-    const double tn = K ? (double)thr / ((nrm.fx + nrm.fy) / 2) : (double)thr;
-    S.thr2 = (float)(tn * tn);
-    S.n = n;
-    S.valid = valid ? 1 : 0;
-    S.best = -1; S.best_h = -1; S.best_slot = -1;
-    S.needed = max_iters;
-    S.rounds = 0;
-    S.done = valid ? 0 : 1;
-    for (int k = 0; k < 12; ++k) { S.cur[k] = 0; S.curf[k] = 0; }
-  }
-}
-
-// one lane per (pair, hypothesis of the round); grid B * R / AP_HYP_THREADS
-__global__ __launch_bounds__(AP_HYP_THREADS) void ap_hyp_kernel(const float* __restrict__ pts3, const float2* __restrict__ kpts, int N,
-                                                                const unsigned long long* __restrict__ seeds,
-                                                                const ApState* __restrict__ st, int round, ApSlots sl) {
-  static_assert(R % AP_HYP_THREADS == 0, "a workgroup must not straddle two pairs");
-  const int g = blockIdx.x * AP_HYP_THREADS + threadIdx.x, b = g / R;
-  const ApState& P = st[b];
-  if (P.done) return;  // uniform over the workgroup
-  const int h = round * R + g % R;
-  int idx[3];
-  const bool act = draw_sample<3>(seeds[b], h, P.n, idx);
-  double X[3][3], x[3][2];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const long row = (long)b * N + (act ? idx[k] : 0);
-    P.nrm.apply(pts3 + 3 * row, kpts[row], X[k], x[k]);  // a non-finite row makes p3p return no model
-  }
-  sl.n[g] = p3p(X, x, act, [&](int s, const double (&m)[12]) {
-    const long slot = (long)g * AP_SLOTS + s;
-    float mf[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-      sl.d[slot * 12 + k] = m[k];
-      mf[k] = (float)m[k];
-    }
-    float4* o = reinterpret_cast<float4*>(sl.f + slot * 12);
-    o[0] = make_float4(mf[0], mf[1], mf[2], mf[3]);
-    o[1] = make_float4(mf[4], mf[5], mf[6], mf[7]);
-    o[2] = make_float4(mf[8], mf[9], mf[10], mf[11]);
-  });
-}
-
-// one wave per (pair, hypothesis): the hypothesis' poses (wave-uniform coefficients) against the pair's rows
-__global__ __launch_bounds__(256) void ap_score_kernel(const float4* __restrict__ px, const float2* __restrict__ pi, int N,
-                                                       const ApState* __restrict__ st, ApSlots sl) {
-  const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = g / R;
-  const ApState& P = st[b];
-  if (P.done) return;
-  const int nm = sl.n[g], n = P.n;
-  const float thr2 = P.thr2;
-  const float* mf = sl.f + (long)g * AP_SLOTS * 12;
-  const float4* X = px + (long)b * N;
-  const float2* x = pi + (long)b * N;
-  int c[AP_SLOTS];
-#pragma unroll
-  for (int r = 0; r < AP_SLOTS; ++r) c[r] = 0;
-  if (nm > 0) {
-    for (int i0 = 0; i0 < n; i0 += 64) {
-      const int i = i0 + lane;
-      const float4 p = i < n ? X[i] : make_float4(NAN, NAN, NAN, NAN);
-      const float2 q = i < n ? x[i] : make_float2(NAN, NAN);
-#pragma unroll
-      for (int r = 0; r < AP_SLOTS; ++r)
-        if (r < nm) c[r] += __popcll(__ballot(ap_inlier(mf + 12 * r, p, q, thr2)));
-    }
-  }
-  if (lane == 0) {
-    int* o = sl.cnt + (long)g * AP_SLOTS;
-#pragma unroll
-    for (int r = 0; r < AP_SLOTS; ++r) o[r] = r < nm ? c[r] : -1;
-  }
-}
-
-// one workgroup per pair: largest count of the round (ties: lowest (h, slot)), running best, adaptive iteration count, done flag
-__global__ __launch_bounds__(256) void ap_select_kernel(ApState* __restrict__ st, int round, double conf, int max_iters, ApSlots sl) {
-  __shared__ int sk[256];
-  __shared__ int si[256];
-  const int b = blockIdx.x, t = threadIdx.x;
-  ApState& P = st[b];
-  if (P.done) return;
-  const int* key = sl.cnt + (long)b * R * AP_SLOTS;
-  int bk = -1, bi = 0x7fffffff;
-  for (int k = t; k < R * AP_SLOTS; k += 256) {
-    const int v = key[k];
-    if (v > bk) { bk = v; bi = k; }  // k ascends: ties keep the lower slot
-  }
-  sk[t] = bk;
-  si[t] = bi;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (t < s) {
-      const int v = sk[t + s], i = si[t + s];
-      if (v > sk[t] || (v == sk[t] && i < si[t])) { sk[t] = v; si[t] = i; }
-    }
-    __syncthreads();
-  }
-  if (t == 0) {
-    const int v = sk[0], k = si[0];
-    if (v > P.best) {  // strictly: an earlier round's model keeps a tie
-      P.best = v;
-      P.best_h = round * R + k / AP_SLOTS;
-      P.best_slot = k % AP_SLOTS;
-      const double* m = sl.d + ((long)b * R * AP_SLOTS + k) * 12;
-      for (int q = 0; q < 12; ++q) { P.cur[q] = m[q]; P.curf[q] = (float)m[q]; }
-      P.needed = update_num_iters(conf, (double)v / P.n, 3, max_iters);
-    }
-    P.rounds = round + 1;
-    const long drawn = (long)(round + 1) * R;
-    P.done = drawn >= (long)min(max_iters, P.needed) ? 1 : 0;
-  }
-}
-
-// mask[b, i] = inlier of the accepted pose (rows beyond counts[b], and pairs without one: 0); grid (ceil(N / 256), B)
-__global__ __launch_bounds__(256) void ap_mask_kernel(const float4* __restrict__ px, const float2* __restrict__ pi, int N,
-                                                      const ApState* __restrict__ st, unsigned char* __restrict__ mask) {
-  const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= N) return;
-  const ApState& P = st[b];
-  bool in = false;
-  if (P.valid && P.best >= AP_MIN_INLIERS && i < P.n) in = ap_inlier(P.curf, px[(long)b * N + i], pi[(long)b * N + i], P.thr2);
-  mask[(long)b * N + i] = in ? 1 : 0;
-}
-
-// one thread per pair: ok flag, the pose of the caller's problem t = t' / s - R c, the info row
-__global__ __launch_bounds__(64) void ap_finish_kernel(int B, const ApState* __restrict__ st, double* __restrict__ out_r,
-                                                       double* __restrict__ out_t, unsigned char* __restrict__ ok, int* __restrict__ info) {
-  const int b = blockIdx.x * 64 + threadIdx.x;
-  if (b >= B) return;
-  const ApState& P = st[b];
-  const bool good = P.valid && P.best >= AP_MIN_INLIERS;
-  const double* m = P.cur;
-  const double* c = P.nrm.c;
-  for (int k = 0; k < 9; ++k) out_r[(long)b * 9 + k] = good ? m[k] : 0.0;
-  for (int r = 0; r < 3; ++r)
-    out_t[(long)b * 3 + r] = good ? m[9 + r] / P.nrm.s - ((m[3 * r] * c[0] + m[3 * r + 1] * c[1]) + m[3 * r + 2] * c[2]) : 0.0;
-  int* row = info + (long)b * ABSOLUTE_POSE_INFO;
-  row[0] = P.rounds;
-  row[1] = P.best_h;
-  row[2] = P.best_slot;
-  row[3] = P.best;
-  row[4] = P.valid;
-  ok[b] = good ? 1 : 0;
-}
-
+// ------------------------------------------------------------------------------------------------------------ the solver alone
 __global__ __launch_bounds__(64) void ap_minimal_kernel(const double* __restrict__ X, const double* __restrict__ x, int S,
                                                         double* __restrict__ out_r, double* __restrict__ out_t, int* __restrict__ out_n) {
   const int g = blockIdx.x * 64 + threadIdx.x;
@@ -610,14 +487,14 @@ __global__ __launch_bounds__(LM_THREADS) void abs_refine_kernel(const double* __
   const int n = counts ? min(max(counts[b], 0), N) : N;
   const float2* ka = reinterpret_cast<const float2*>(pts3 + (long)b * N * 3);  // read by AbsPoseFit::row alone
   const float2* kb = kpts + (long)b * N;
-  // the normalisation of absolute_pose_launch (the waves' sums in lm_reduce's order)
+  // the normalisation of AbsPose::normalise (the waves' sums in lm_reduce's order)
   ApNorm nrm = camera_norm(K ? K + (long)b * 9 : nullptr);
-  const double thr_n = K ? thr / ((nrm.fx + nrm.fy) / 2) : thr;
+  const double thr_n = nrm.threshold(K != nullptr, thr);
   double sum[3] = {0.0, 0.0, 0.0};
   int cnt = 0;
   for (int i = threadIdx.x; i < n; i += LM_THREADS) {
     const AbsPoseFit::Point w = AbsPoseFit::row(nrm, ka, kb, i);
-    if (isfinite(w.X[0]) && isfinite(w.X[1]) && isfinite(w.X[2]) && isfinite(w.x[0]) && isfinite(w.x[1])) {
+    if (ApNorm::finite(w.X, w.x)) {
       sum[0] += w.X[0]; sum[1] += w.X[1]; sum[2] += w.X[2];
       ++cnt;
     }
@@ -628,7 +505,7 @@ __global__ __launch_bounds__(LM_THREADS) void abs_refine_kernel(const double* __
   int cnt2 = 0;
   for (int i = threadIdx.x; i < n; i += LM_THREADS) {
     const AbsPoseFit::Point w = AbsPoseFit::row(nrm, ka, kb, i);
-    if (isfinite(w.X[0]) && isfinite(w.X[1]) && isfinite(w.X[2]) && isfinite(w.x[0]) && isfinite(w.x[1])) {
+    if (ApNorm::finite(w.X, w.x)) {
       const double d0 = w.X[0] - c0, d1 = w.X[1] - c1, d2 = w.X[2] - c2;
       ds[0] += sqrt((d0 * d0 + d1 * d1) + d2 * d2);
       ++cnt2;
@@ -716,7 +593,7 @@ __global__ __launch_bounds__(256) void lift_kernel(const float* __restrict__ mat
 
 }  // namespace
 
-size_t absolute_pose_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? ap_carve(nullptr, B, N).bytes : 0; }
+size_t absolute_pose_workspace_bytes(int B, int N) { return workspace_bytes<AbsPose, CountScoring>(B, N); }
 
 int absolute_pose_launch(const float* points3d, const float* kpts, const int* counts, const unsigned long long* seeds, const double* K,
                          int B, int N, float thr, double conf, int max_iters, double* out_r, double* out_t, unsigned char* out_mask,
@@ -724,24 +601,8 @@ int absolute_pose_launch(const float* points3d, const float* kpts, const int* co
   if (check_args<CountScoring>("absolute_pose", "conf", points3d && kpts && seeds && out_r && out_t && out_mask && out_ok && out_info && ws,
                                B, N, thr, conf, max_iters, 0, ws_bytes, absolute_pose_workspace_bytes(B, N)))
     return -1;
-  const ApCarve c = ap_carve(align_base<void*>(ws), B, N);
-  const float2* kp = reinterpret_cast<const float2*>(kpts);
-  hipLaunchKernelGGL(ap_norm_kernel, dim3(B), dim3(256), 0, s, points3d, kp, counts, K, N, thr, max_iters, c.st, c.px, c.pi);
-  ROMA_LAUNCH_CHECK();
-  const int rounds = (max_iters + R - 1) / R;
-  for (int r = 0; r < rounds; ++r) {
-    hipLaunchKernelGGL(ap_hyp_kernel, dim3(B * R / AP_HYP_THREADS), dim3(AP_HYP_THREADS), 0, s, points3d, kp, N, seeds, c.st, r, c.sl);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ap_score_kernel, dim3(B * R / 4), dim3(256), 0, s, c.px, c.pi, N, c.st, c.sl);
-    ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL(ap_select_kernel, dim3(B), dim3(256), 0, s, c.st, r, conf, max_iters, c.sl);
-    ROMA_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(ap_mask_kernel, dim3((N + 255) / 256, B), dim3(256), 0, s, c.px, c.pi, N, c.st, out_mask);
-  ROMA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ap_finish_kernel, dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, out_r, out_t, out_ok, out_info);
-  ROMA_LAUNCH_CHECK();
-  return 0;
+  return ransac_run<AbsPose, CountScoring>({points3d, reinterpret_cast<const float2*>(kpts)}, counts, seeds, K, B, N, thr, conf,
+                                           max_iters, 0, {out_r, out_t}, out_mask, out_ok, out_info, nullptr, ws, s);
 }
 
 int absolute_pose_minimal_launch(const double* X, const double* x, int S, double* out_r, double* out_t, int* out_n, hipStream_t s) {

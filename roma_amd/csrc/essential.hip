@@ -5,7 +5,8 @@
 // What E adds to the shared pipeline (Essential):
 //   normalise   x_n = ((x - cx) / fx, (y - cy) / fy) in f64 (identity without a camera matrix), thr_n = thr / ((fx + fy) / 2).
 //               No Hartley normalisation: it would break the essential constraints.
-//   hypothesis  16 lanes per hypothesis: Nister's five-point solver in f64 (below), up to 10 slots.
+//   hypothesis  16 lanes per hypothesis: the sample's rows normalised in f64 (ransac.h: load_sample), then Nister's five-point
+//               solver in f64 (below), up to 10 slots.
 //   res_terms   the f32 scoring's terms linear in the model: the epipolar terms (ransac.h: epipolar_terms).
 //   inlier      (CountScoring) from them: the Sampson test.  No refinement (REFINE_ITERS = 0: OpenCV has none here).
 //   residual2   (MagsacScoring) from them: squared Sampson distance in normalised camera coordinates.
@@ -553,13 +554,19 @@ struct Essential : Terms<Essential> {
       xb = (q.x - cx) / fx; yb = (q.y - cy) / fy;
     }
   };
-  static constexpr int S = 5, SLOTS = MAXR, HYP_THREADS = 256, HYP_LANES = G, REFINE_ITERS = 0, INFO = ESSENTIAL_INFO;
+  using In = PairIn;
+  using Rows = PairRows;
+  using Out = double*;  // [B, 9]
+  static constexpr int S = 5, SLOTS = MAXR, NM = 9, MIN_INLIERS = 1, HYP_THREADS = 256, HYP_LANES = G, REFINE_ITERS = 0;
+  static constexpr int INFO = ESSENTIAL_INFO;
   static constexpr int MAG_INFO = ESSENTIAL_MAGSAC_INFO, NT = 5, REFIT_MIN = 8;  // MAGSAC++: info, residual terms, rows of a step
   static constexpr bool SCORE_EVERY_SLOT = false;  // 10 slots, a few of them used: score only those
 
   // every thread of the workgroup: the pair's camera; pts written for every row; one threshold (t2a == t2b)
-  __device__ static bool normalise(const float2* A, const float2* Bp, int n, const double* K, float thr, double* sh, float4* pts,
-                                   Norm& nm, float& t2a, float& t2b) {
+  __device__ static bool normalise(PairIn in, int n, const double* K, float thr, double* sh, PairRows rows, Norm& nm, float& t2a,
+                                   float& t2b) {
+    const float2 *A = in.a, *Bp = in.b;
+    float4* pts = rows.p;
     const int t = threadIdx.x;
     double fx = 1, fy = 1, cx = 0, cy = 0;
     if (K) {
@@ -583,9 +590,10 @@ struct Essential : Terms<Essential> {
   }
 
   // the G lanes of a group: the hypothesis' valid models in slots 0 .. nsol - 1
-  __device__ static void hypothesis(const double (&xa)[5], const double (&ya)[5], const double (&xb)[5], const double (&yb)[5],
-                                    bool act, int g, int gl, const Slots& sl) {
+  __device__ static void hypothesis(PairIn in, const int (&idx)[S], bool act, const Norm& nrm, int g, int gl, const Slots& sl) {
     __shared__ double sm[GPB * LDS_PER];
+    double xa[S], ya[S], xb[S], yb[S];
+    act = load_sample(in, idx, act, nrm, xa, ya, xb, yb);
     double e[9];
     int rank, nsol;
     solve_e_group(xa, ya, xb, yb, act, sm + (threadIdx.x / G) * LDS_PER, gl, e, rank, nsol);
@@ -786,8 +794,8 @@ struct Essential : Terms<Essential> {
   }
 
   // E as found or as optimised
-  __device__ static void model_out(const PairState<Essential>& P, bool good, double* out) {
-    for (int k = 0; k < 9; ++k) out[k] = good ? P.cur[k] : 0.0;
+  __device__ static void model_out(const PairState<Essential>& P, bool good, double* out, int b) {
+    for (int k = 0; k < 9; ++k) out[(long)b * 9 + k] = good ? P.cur[k] : 0.0;
   }
 };
 
@@ -982,7 +990,7 @@ int e_launch(const char* op, const float* kpts_a, const float* kpts_b, const int
   if (check_args<Sc>(op, "prob", kpts_a && kpts_b && seeds && out_e && out_mask && out_ok && out_info && (out_score || !Sc::SCORES) && ws,
                      B, N, threshold, prob, max_iters, opt, ws_bytes, workspace_bytes<Essential, Sc>(B, N)))
     return -1;
-  return ransac_run<Essential, Sc>(kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, opt, out_e, out_mask, out_ok,
+  return ransac_run<Essential, Sc>({reinterpret_cast<const float2*>(kpts_a), reinterpret_cast<const float2*>(kpts_b)}, counts, seeds, K, B, N, threshold, prob, max_iters, opt, out_e, out_mask, out_ok,
                                    out_info, out_score, ws, s);
 }
 

@@ -5,8 +5,8 @@
 // What H and F add to the shared pipeline (Hartley<M>):
 //   normalise   Hartley normalisation of each image (centroid to 0, mean distance to sqrt 2) over the finite rows, f64
 //               fixed-order reductions; thresholds thr * s per image.
-//   hypothesis  one thread per hypothesis: 4-point DLT as an 8 x 8 solve with OpenCV's checkSubset (1 slot), or 7-point null
-//               space + cubic (up to 3 slots), f64.
+//   hypothesis  one thread per hypothesis: its sample's rows normalised in f64 (ransac.h: load_sample), then the 4-point DLT as
+//               an 8 x 8 solve with OpenCV's checkSubset (1 slot), or 7-point null space + cubic (up to 3 slots), f64.
 //   res_terms   the f32 scoring's terms linear in the model: reprojection error in image B and p_z (H), the epipolar terms (F).
 //   inlier      (CountScoring) from them: reprojection error in image B (H); distances to both epipolar lines, each image with
 //               its own scale (F).
@@ -188,7 +188,11 @@ struct Hartley : Terms<Model> {
       xb = (q.x - cb[0]) * sb; yb = (q.y - cb[1]) * sb;
     }
   };
-  static constexpr int HYP_THREADS = 64, HYP_LANES = 1, REFINE_ITERS = 3, INFO = RANSAC_INFO, MAG_INFO = MAGSAC_INFO;
+  using In = PairIn;
+  using Rows = PairRows;
+  using Out = double*;  // [B, 9]
+  static constexpr int NM = 9, MIN_INLIERS = 1, HYP_THREADS = 64, HYP_LANES = 1, REFINE_ITERS = 3, INFO = RANSAC_INFO;
+  static constexpr int MAG_INFO = MAGSAC_INFO;
   // score all (at most 3) slots of a hypothesis, used or not: every model's coefficients then stay in registers across the
   // point loop, where a branch per slot reloads them (35 % slower for F); unused slots hold zeros and their counts are dropped
   static constexpr bool SCORE_EVERY_SLOT = true;
@@ -201,8 +205,10 @@ struct Hartley : Terms<Model> {
   }
 
   // every thread of the workgroup: the pair's normalisation over its finite rows; pts written only for a valid pair
-  __device__ static bool normalise(const float2* A, const float2* Bp, int n, const double*, float thr, double* sh, float4* pts,
-                                   Norm& nm, float& t2a, float& t2b) {
+  __device__ static bool normalise(PairIn in, int n, const double*, float thr, double* sh, PairRows rows, Norm& nm, float& t2a,
+                                   float& t2b) {
+    const float2 *A = in.a, *Bp = in.b;
+    float4* pts = rows.p;
     const HartleyMoments m = hartley_moments(n, [&](int i, double& ax, double& ay, double& bx, double& by) {
       const float2 a = A[i], q = Bp[i];
       ax = a.x; ay = a.y; bx = q.x; by = q.y;
@@ -226,8 +232,10 @@ struct Hartley : Terms<Model> {
     return valid;
   }
 
-  __device__ static void hypothesis(const double* xa, const double* ya, const double* xb, const double* yb, bool act, int g, int,
-                                    const Slots& sl) {
+  template <int S>  // Model::S (Model is not complete here)
+  __device__ static void hypothesis(PairIn in, const int (&idx)[S], bool act, const Norm& nrm, int g, int, const Slots& sl) {
+    double xa[S], ya[S], xb[S], yb[S];
+    act = load_sample(in, idx, act, nrm, xa, ya, xb, yb);
     double m[Model::SLOTS][9];
     const int nm = act ? Model::solve(xa, ya, xb, yb, m) : 0;
     sl.n[g] = nm;
@@ -332,7 +340,8 @@ struct Hartley : Terms<Model> {
   }
 
   // de-normalise (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scale
-  __device__ static void model_out(const PairState<Model>& P, bool good, double* out) {
+  __device__ static void model_out(const PairState<Model>& P, bool good, double* out, int b) {
+    out += (long)b * 9;
     const Norm& q = P.nrm;
     double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (good) {
@@ -419,7 +428,7 @@ int hf_launch(const char* op, int model, const float* kpts_a, const float* kpts_
                      N, threshold, confidence, max_iters, opt, ws_bytes, hf_workspace_bytes<Sc>(B, N)))
     return -1;
   const auto run = model == RANSAC_HOMOGRAPHY ? ransac_run<Homography, Sc> : ransac_run<Fundamental, Sc>;
-  return run(kpts_a, kpts_b, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, opt, out_model, out_mask, out_ok,
+  return run({reinterpret_cast<const float2*>(kpts_a), reinterpret_cast<const float2*>(kpts_b)}, counts, seeds, nullptr, B, N, threshold, confidence, max_iters, opt, out_model, out_mask, out_ok,
              out_info, out_score, ws, s);
 }
 

@@ -1,15 +1,36 @@
 // Batched robust estimation on the device: one pipeline for every model and every scoring, templated on a model policy M
-// (geometry.hip: homography and fundamental matrix; essential.hip: essential matrix) and a scoring policy Sc (below:
-// CountScoring - RANSAC's inlier count; MagsacScoring - MAGSAC++).  tools/geometry_ref.py restates it in numpy float64
-// (round_loop) and is, with the models' and scorings' own restatements, the oracle of the GPU tests.
+// (geometry.hip: homography and fundamental matrix; essential.hip: essential matrix; absolute_pose.hip: camera pose from 3-D
+// points) and a scoring policy Sc (below: CountScoring - RANSAC's inlier count; MagsacScoring - MAGSAC++).
+// tools/geometry_ref.py restates it in numpy float64 (round_loop) and is, with the models' and scorings' own restatements,
+// the oracle of the GPU tests.
 //
-// Per pair b (counts[b] rows of kpts_a / kpts_b; later rows are never read):
-//   1. ransac_norm_kernel: M::normalise - the model's normalisation of both images, normalised f32 copies of the points
-//      (non-finite rows as NaN), squared thresholds in normalised units, whether the pair can be sampled.  MagsacScoring only:
+// What a model supplies:
+//   S, SLOTS, NM          rows of a minimal sample, models it can yield, doubles per model (9: a 3 x 3 matrix; 12: R and t)
+//   HYP_THREADS, HYP_LANES  workgroup size of ransac_hyp_kernel and lanes per hypothesis
+//   MIN_INLIERS           inliers below which a pair has no model (mask, ok)
+//   REFINE_ITERS, INFO, SCORE_EVERY_SLOT   least-squares refits under CountScoring (0: none; then refit is not needed), ints of
+//                         its info row (INFO_CORE, or one more: best_min), whether unused slots are scored as well (they hold zeros)
+//   In, Out               the caller's arrays, as passed to ransac_run: In has at(row) - the same arrays from that row on (the
+//                         two-view models: PairIn); Out is what model_out writes (the two-view models: double* [B, 9])
+//   Norm                  the pair's normalisation, kept in PairState
+//   Rows                  a view of the pair's normalised f32 rows in the workspace, passed by value: Row (one row in registers:
+//                         what inlier takes), carve (its arrays from the workspace), at(row), row(i, n) (row i, a NaN row for
+//                         i >= n) (the two-view models: PairRows, one float4 per row)
+//   normalise             every thread of 256: Norm, the Rows (non-finite rows as NaN), squared thresholds, whether the pair
+//                         can be sampled
+//   hypothesis            the lanes of one hypothesis: its sample's rows from In (the two-view models: load_sample), normalised in
+//                         f64, through the minimal solver into the hypothesis' slots (store_model) and Slots::n
+//   inlier                the f32 inlier test of one model on one Row; false for a NaN row
+//   model_out             the pair's model in the caller's terms (zeros unless good) into Out
+// and for MagsacScoring what its comment below lists.
+//
+// Per pair b (counts[b] rows of the input; later rows are never read):
+//   1. ransac_norm_kernel: M::normalise - the model's normalisation, normalised f32 copies of the rows (non-finite rows as
+//      NaN), squared thresholds in normalised units, whether the pair can be sampled.  MagsacScoring only:
 //      magsac_init_kernel - residual scales, V scale and threshold of the pair.
 //   2. rounds of RANSAC_ROUND hypotheses, enqueued ceil(max_iters / ROUND) times, no host synchronisation:
-//      ransac_hyp_kernel    M::HYP_LANES lanes per hypothesis: sample (counter-based, from (seed_b, h) only), normalised in
-//                           f64 (M::Norm::apply), then M::hypothesis: the f64 minimal solver, up to M::SLOTS models
+//      ransac_hyp_kernel    M::HYP_LANES lanes per hypothesis: sample (counter-based, from (seed_b, h) only), then
+//                           M::hypothesis: its rows normalised in f64, the f64 minimal solver, up to M::SLOTS models
 //      ransac_score_kernel  one wave per hypothesis, Sc::score: its models' inlier counts (popc(ballot) of M::inlier, -1 for
 //                           unused slots), or their sums of rho (+inf for unused slots) and the counts r < tau
 //      ransac_select_kernel per pair: the best key (largest count / smallest sum; ties: lowest (h, slot); an earlier round keeps
@@ -18,7 +39,7 @@
 //      ransac_mask_kernel (inliers of the current model); ransac_refit_kernel (Sc::refit: M::refit, a least-squares candidate on
 //      the mask, or M::wrefit, an IRLS step with the MAGSAC++ weights of the current model); ransac_accept_kernel (Sc::accept:
 //      the candidate is kept if its inlier count is not lower / its sum of rho strictly lower, else refinement stops).
-//   4. ransac_mask_kernel + ransac_finish_kernel: final mask (Sc::inlier), ok flag, M::model_out (model in pixel terms), info
+//   4. ransac_mask_kernel + ransac_finish_kernel: final mask (Sc::inlier), ok flag, M::model_out (model in the caller's terms), info
 //      row (write_info, then Sc::finish: MAGSAC++ adds the LO steps and the two scores).
 // Every flag and counter of the workspace is written with plain stores by one kernel and read by a later launch on the same
 // stream: no atomics and no hand-off inside a launch.  Results are bit-identical from run to run and independent of B.
@@ -150,11 +171,13 @@ __device__ __forceinline__ double det3(const double* f) {
   return f[0] * (f[4] * f[8] - f[5] * f[7]) - f[1] * (f[3] * f[8] - f[5] * f[6]) + f[2] * (f[3] * f[7] - f[4] * f[6]);
 }
 
+template <int NM = 9>
 __device__ __forceinline__ void to_f32(const double* m, float* mf) {  // the 12-float (three float4) copy the scoring reads
+  static_assert(NM <= 12);
 #pragma unroll
-  for (int k = 0; k < 9; ++k) mf[k] = (float)m[k];
+  for (int k = 0; k < NM; ++k) mf[k] = (float)m[k];
 #pragma unroll
-  for (int k = 9; k < 12; ++k) mf[k] = 0.f;
+  for (int k = NM; k < 12; ++k) mf[k] = 0.f;
 }
 
 // ---- symmetric PSD eigenproblems by one-sided (Hestenes) Jacobi on one wave (the refits' 9 x 9 normal equations).  Lane j < NC
@@ -228,8 +251,8 @@ __device__ void jacobi_min_vec(double (&a)[NC], double (&v)[NC], int lane, doubl
 template <class M>
 struct PairState {
   typename M::Norm nrm;         // the model's normalisation of the pair
-  double cur[9];                // current model in normalised coordinates
-  double cand[9];               // refit candidate
+  double cur[M::NM];            // current model in normalised coordinates
+  double cand[M::NM];           // refit candidate
   alignas(16) float curf[12];   // f32 copies the scoring reads
   alignas(16) float candf[12];
   float thr2a, thr2b;           // squared thresholds per image in normalised units
@@ -245,17 +268,18 @@ struct PairState {
 };
 
 struct Slots {                  // the models of one round: SLOTS per hypothesis, B * R hypotheses
-  double* d;                    // f64 models [B * R * SLOTS][9]
+  double* d;                    // f64 models [B * R * SLOTS][NM]
   float* f;                     // f32 copies [B * R * SLOTS][12]
   int* n;                       // models per hypothesis [B * R]
   int* cnt;                     // inlier count per slot, -1 if unused [B * R * SLOTS]
 };
 
+template <int NM = 9>
 __device__ __forceinline__ void store_model(const double* m, long slot, const Slots& sl) {
   float mf[12];
-  to_f32(m, mf);
+  to_f32<NM>(m, mf);
 #pragma unroll
-  for (int k = 0; k < 9; ++k) sl.d[slot * 9 + k] = m[k];
+  for (int k = 0; k < NM; ++k) sl.d[slot * NM + k] = m[k];
   float4* o = reinterpret_cast<float4*>(sl.f + slot * 12);
   o[0] = make_float4(mf[0], mf[1], mf[2], mf[3]);
   o[1] = make_float4(mf[4], mf[5], mf[6], mf[7]);
@@ -269,10 +293,42 @@ T align_base(void* ws) {  // the caller's workspace need not be 256-aligned: eve
   return reinterpret_cast<T>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
 }
 
+// ---- In, Rows and the sample load of the two-view models (H, F, E)
+struct PairIn {                 // kpts_a, kpts_b [B, N] pixel (E without a camera matrix: normalised) coordinates
+  const float2* a;
+  const float2* b;
+  __device__ PairIn at(long row) const { return {a + row, b + row}; }
+};
+
+struct PairRows {               // (xa, ya, xb, yb) normalised, [B * N]
+  using Row = float4;
+  float4* p;
+  static size_t carve(PairRows& r, char* ws, size_t o, size_t rows) {
+    r.p = reinterpret_cast<float4*>(ws + o);
+    return align256(o + sizeof(float4) * rows);
+  }
+  __device__ PairRows at(long row) const { return {p + row}; }
+  __device__ float4 row(int i, int n) const { return i < n ? p[i] : make_float4(NAN, NAN, NAN, NAN); }
+};
+
+// rows idx of the pair `in`, normalised in f64; returns whether the sample is usable (it was drawn, and its rows are finite)
+template <int S, class Norm>
+__device__ __forceinline__ bool load_sample(const PairIn& in, const int (&idx)[S], bool act, const Norm& nrm, double (&xa)[S],
+                                            double (&ya)[S], double (&xb)[S], double (&yb)[S]) {
+#pragma unroll
+  for (int k = 0; k < S; ++k) {
+    const float2 a = act ? in.a[idx[k]] : make_float2(0.f, 0.f);
+    const float2 q = act ? in.b[idx[k]] : make_float2(0.f, 0.f);
+    act = act && finite_row(a.x, a.y, q.x, q.y);
+    nrm.apply(a, q, xa[k], ya[k], xb[k], yb[k]);
+  }
+  return act;
+}
+
 template <class M, class Sc>
 struct Carve {
   PairState<M>* st;
-  float4* pts;
+  typename M::Rows rows;
   Slots sl;
   typename Sc::Ws w;            // what the scoring keeps next to them
   size_t bytes;
@@ -285,8 +341,8 @@ Carve<M, Sc> carve(void* ws, int B, int N) {
   char* p = static_cast<char*>(ws);
   size_t o = 0;
   c.st = reinterpret_cast<PairState<M>*>(p + o); o = align256(o + sizeof(PairState<M>) * B);
-  c.pts = reinterpret_cast<float4*>(p + o); o = align256(o + sizeof(float4) * (size_t)B * N);
-  c.sl.d = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * 9 * SL * (size_t)B * R);
+  o = M::Rows::carve(c.rows, p, o, (size_t)B * N);
+  c.sl.d = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * M::NM * SL * (size_t)B * R);
   c.sl.f = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * 12 * SL * (size_t)B * R);
   c.sl.n = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * (size_t)B * R);
   c.sl.cnt = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * SL * (size_t)B * R);
@@ -521,7 +577,7 @@ template <class M>
 __device__ __forceinline__ void settle(PairState<M>& P, bool keep, int c) {
   if (keep) {
     P.best = c;
-    for (int k = 0; k < 9; ++k) P.cur[k] = P.cand[k];
+    for (int k = 0; k < M::NM; ++k) P.cur[k] = P.cand[k];
     for (int k = 0; k < 12; ++k) P.curf[k] = P.candf[k];
   } else {
     P.stop = 1;
@@ -556,8 +612,8 @@ struct CountScoring {
 
   // the models' f32 inlier tests (M::inlier), popc(ballot) counts, -1 for unused slots
   template <class M>
-  __device__ static void score(const float* mf, int nm, const float4* __restrict__ Pp, const PairState<M>& P, const Ws&, int,
-                               int lane, long g, const Slots& sl) {
+  __device__ static void score(const float* mf, int nm, typename M::Rows rows, const PairState<M>& P, const Ws&, int, int lane,
+                               long g, const Slots& sl) {
     constexpr int SL = M::SLOTS;
     const int n = P.n;
     const float t2a = P.thr2a, t2b = P.thr2b;
@@ -566,8 +622,7 @@ struct CountScoring {
     for (int r = 0; r < SL; ++r) c[r] = 0;
     if (nm > 0) {
       for (int i0 = 0; i0 < n; i0 += 64) {
-        const int i = i0 + lane;
-        const float4 p = i < n ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
+        const typename M::Rows::Row p = rows.row(i0 + lane, n);
 #pragma unroll
         for (int r = 0; r < SL; ++r)
           if (M::SCORE_EVERY_SLOT || r < nm) c[r] += __popcll(__ballot(M::inlier(mf + 12 * r, p, t2a, t2b)));
@@ -581,7 +636,9 @@ struct CountScoring {
   }
 
   template <class M>
-  __device__ static bool inlier(const PairState<M>& P, const Ws&, int, float4 p) { return M::inlier(P.curf, p, P.thr2a, P.thr2b); }
+  __device__ static bool inlier(const PairState<M>& P, const Ws&, int, typename M::Rows::Row p) {
+    return M::inlier(P.curf, p, P.thr2a, P.thr2b);
+  }
 
   template <class M>
   __device__ static void refit(const float2* A, const float2* Bp, const float4*, PairState<M>& P, const Ws&, int,
@@ -591,15 +648,12 @@ struct CountScoring {
 
   // re-score the candidate; keep it if its count is not lower, else stop refining
   template <class M>
-  __device__ static void accept(const float4* __restrict__ Pp, PairState<M>& P, const Ws&, int, int lane) {
+  __device__ static void accept(typename M::Rows rows, PairState<M>& P, const Ws&, int, int lane) {
     const int n = P.n;
     const float t2a = P.thr2a, t2b = P.thr2b;
     int c = 0;
-    for (int i0 = 0; i0 < n; i0 += 64) {
-      const int i = i0 + lane;
-      const float4 p = i < n ? Pp[i] : make_float4(NAN, NAN, NAN, NAN);
-      c += __popcll(__ballot(M::inlier(P.candf, p, t2a, t2b)));
-    }
+    for (int i0 = 0; i0 < n; i0 += 64)
+      c += __popcll(__ballot(M::inlier(P.candf, rows.row(i0 + lane, n), t2a, t2b)));
     if (lane == 0) settle(P, c >= P.best, c);
   }
 
@@ -609,7 +663,8 @@ struct CountScoring {
 
 // MAGSAC++: the key is the sum of rho, smaller is better, the inlier count r < tau carried along for the adaptive iteration
 // count; refinement is IRLS local optimisation (M::wrefit), a step kept only if it lowers the sum of rho.  From the model it
-// needs residual2 / res_terms / r2_from / NT, res_scales, mag_thr2, wrefit, MAG_INFO.
+// needs residual2 / res_terms / r2_from / NT, res_scales, mag_thr2, wrefit, MAG_INFO, and it is written for the two-view models:
+// Rows = PairRows, In = PairIn, NM = 9.
 struct MagsacScoring {
   using Key = float;
   struct Ws {
@@ -653,14 +708,14 @@ struct MagsacScoring {
   // compensated f32 sum of rho per slot (lane partials over rows i = lane mod 64 ascending, then a fixed butterfly), and the
   // count r < tau
   template <class M>
-  __device__ static void score(const float* mf, int nm, const float4* __restrict__ Pp, const PairState<M>& P, const Ws& w, int b,
-                               int lane, long g, const Slots& sl) {
+  __device__ static void score(const float* mf, int nm, PairRows rows, const PairState<M>& P, const Ws& w, int b, int lane, long g,
+                               const Slots& sl) {
     constexpr int SL = M::SLOTS;
     float acc[SL];
     int c[SL];
 #pragma unroll
     for (int r = 0; r < SL; ++r) { acc[r] = 0.f; c[r] = 0; }
-    if (nm > 0) magsac_sums<M, SL>(mf, nm, Pp, P.n, w.ms[b], lane, acc, c);
+    if (nm > 0) magsac_sums<M, SL>(mf, nm, rows.p, P.n, w.ms[b], lane, acc, c);
     if (lane == 0) {
 #pragma unroll
       for (int r = 0; r < SL; ++r) {
@@ -688,8 +743,9 @@ struct MagsacScoring {
   // inlier's residual is a small difference of O(1) normalised terms), and paired this way the shared part of that error
   // cancels.  The inlier count is the candidate's own (what the mask kernel evaluates).
   template <class M>
-  __device__ static void accept(const float4* __restrict__ Pp, PairState<M>& P, const Ws& w, int b, int lane) {
+  __device__ static void accept(PairRows rows, PairState<M>& P, const Ws& w, int b, int lane) {
     constexpr int NT = M::NT;
+    const float4* __restrict__ Pp = rows.p;
     MagState& S = w.ms[b];
     float dm[9];
 #pragma unroll
@@ -737,16 +793,15 @@ struct MagsacScoring {
 
 // ------------------------------------------------------------------------------------------------------------ kernels
 template <class M>
-__global__ __launch_bounds__(256) void ransac_norm_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
-                                                          const int* __restrict__ counts, const double* __restrict__ K, int N, float thr,
-                                                          int max_iters, PairState<M>* __restrict__ st, float4* __restrict__ pts) {
+__global__ __launch_bounds__(256) void ransac_norm_kernel(typename M::In in, const int* __restrict__ counts,
+                                                          const double* __restrict__ K, int N, float thr, int max_iters,
+                                                          PairState<M>* __restrict__ st, typename M::Rows rows) {
   __shared__ double sh[256];
   const int b = blockIdx.x;
   const int n = counts ? min(max(counts[b], 0), N) : N;
   typename M::Norm nrm;
   float t2a, t2b;
-  const bool valid = M::normalise(ka + (long)b * N, kb + (long)b * N, n, K ? K + (long)b * 9 : nullptr, thr, sh,
-                                  pts + (long)b * N, nrm, t2a, t2b);
+  const bool valid = M::normalise(in.at((long)b * N), n, K ? K + (long)b * 9 : nullptr, thr, sh, rows.at((long)b * N), nrm, t2a, t2b);
   if (threadIdx.x == 0) {
     PairState<M>& S = st[b];
     S.nrm = nrm;
@@ -760,7 +815,7 @@ __global__ __launch_bounds__(256) void ransac_norm_kernel(const float2* __restri
     S.done = valid ? 0 : 1;
     S.stop = 0;
     S.cand_ok = 0;
-    for (int k = 0; k < 9; ++k) { S.cur[k] = 0; S.cand[k] = 0; }
+    for (int k = 0; k < M::NM; ++k) { S.cur[k] = 0; S.cand[k] = 0; }
     for (int k = 0; k < 12; ++k) { S.curf[k] = 0; S.candf[k] = 0; }
   }
 }
@@ -776,8 +831,8 @@ __global__ __launch_bounds__(64) void magsac_init_kernel(int B, float thr, const
 
 // HYP_LANES lanes per (pair, hypothesis of the round), HYP_THREADS per workgroup; grid B * R * HYP_LANES / HYP_THREADS
 template <class M>
-__global__ __launch_bounds__(M::HYP_THREADS) void ransac_hyp_kernel(const float2* __restrict__ ka, const float2* __restrict__ kb,
-                                                                    int N, const unsigned long long* __restrict__ seeds,
+__global__ __launch_bounds__(M::HYP_THREADS) void ransac_hyp_kernel(typename M::In in, int N,
+                                                                    const unsigned long long* __restrict__ seeds,
                                                                     const PairState<M>* __restrict__ st, int round, Slots sl) {
   constexpr int S = M::S, L = M::HYP_LANES;
   static_assert(R % (M::HYP_THREADS / L) == 0, "a workgroup must not straddle two pairs");
@@ -786,26 +841,18 @@ __global__ __launch_bounds__(M::HYP_THREADS) void ransac_hyp_kernel(const float2
   if (P.done) return;  // uniform over the workgroup: its hypotheses belong to one pair
   const int h = round * R + g % R;
   int idx[S];
-  bool act = draw_sample<S>(seeds[b], h, P.n, idx);
-  double xa[S], ya[S], xb[S], yb[S];
-#pragma unroll
-  for (int k = 0; k < S; ++k) {
-    const float2 a = act ? ka[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
-    const float2 q = act ? kb[(long)b * N + idx[k]] : make_float2(0.f, 0.f);
-    act = act && finite_row(a.x, a.y, q.x, q.y);
-    P.nrm.apply(a, q, xa[k], ya[k], xb[k], yb[k]);
-  }
-  M::hypothesis(xa, ya, xb, yb, act, g, threadIdx.x % L, sl);
+  const bool act = draw_sample<S>(seeds[b], h, P.n, idx);
+  M::hypothesis(in.at((long)b * N), idx, act, P.nrm, g, threadIdx.x % L, sl);
 }
 
 // one wave per (pair, hypothesis): the hypothesis' models (wave-uniform coefficients) against the pair's points (Sc::score)
 template <class M, class Sc>
-__global__ __launch_bounds__(256) void ransac_score_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
+__global__ __launch_bounds__(256) void ransac_score_kernel(typename M::Rows rows, int N, const PairState<M>* __restrict__ st,
                                                            typename Sc::Ws w, Slots sl) {
   const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = g / R;
   const PairState<M>& P = st[b];
   if (P.done) return;
-  Sc::template score<M>(sl.f + (long)g * M::SLOTS * 12, sl.n[g], pts + (long)b * N, P, w, b, lane, g, sl);
+  Sc::template score<M>(sl.f + (long)g * M::SLOTS * 12, sl.n[g], rows.at((long)b * N), P, w, b, lane, g, sl);
 }
 
 // one workgroup per pair: best key of the round (ties: lowest (h, slot)), running best, adaptive iteration count, done flag
@@ -847,9 +894,9 @@ __global__ __launch_bounds__(256) void ransac_select_kernel(PairState<M>* __rest
       P.best_min = c;
       P.best_h = round * R + k / SL;
       P.best_root = k % SL;
-      const double* m = sl.d + ((long)b * R * SL + k) * 9;
-      for (int q = 0; q < 9; ++q) P.cur[q] = m[q];
-      to_f32(P.cur, P.curf);
+      const double* m = sl.d + ((long)b * R * SL + k) * M::NM;
+      for (int q = 0; q < M::NM; ++q) P.cur[q] = m[q];
+      to_f32<M::NM>(P.cur, P.curf);
       P.needed = update_num_iters(conf, (double)c / P.n, M::S, max_iters);
     }
     P.rounds = round + 1;
@@ -858,15 +905,16 @@ __global__ __launch_bounds__(256) void ransac_select_kernel(PairState<M>* __rest
   }
 }
 
-// mask[b, i] = inlier of the current model (Sc::inlier; rows beyond counts[b], and pairs without a model: 0); grid (ceil(N / 256), B)
+// mask[b, i] = inlier of the current model (Sc::inlier; rows beyond counts[b], and pairs without a model: 0); grid (ceil(N / 256), B).
+// A pair that is not valid needs no test of its own: it starts with done = 1, so no round touches it and its best stays -1.
 template <class M, class Sc>
-__global__ __launch_bounds__(256) void ransac_mask_kernel(const float4* __restrict__ pts, int N, const PairState<M>* __restrict__ st,
+__global__ __launch_bounds__(256) void ransac_mask_kernel(typename M::Rows rows, int N, const PairState<M>* __restrict__ st,
                                                           typename Sc::Ws w, unsigned char* __restrict__ mask) {
   const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N) return;
   const PairState<M>& P = st[b];
   bool in = false;
-  if (P.best > 0 && i < P.n) in = Sc::template inlier<M>(P, w, b, pts[(long)b * N + i]);
+  if (P.best >= M::MIN_INLIERS && i < P.n) in = Sc::template inlier<M>(P, w, b, rows.at((long)b * N).row(i, P.n));
   mask[(long)b * N + i] = in ? 1 : 0;
 }
 
@@ -882,24 +930,24 @@ __global__ __launch_bounds__(256) void ransac_refit_kernel(const float2* __restr
 
 // one wave per pair: re-score the candidate and keep it or stop (Sc::accept)
 template <class M, class Sc>
-__global__ __launch_bounds__(64) void ransac_accept_kernel(const float4* __restrict__ pts, int N, PairState<M>* __restrict__ st,
+__global__ __launch_bounds__(64) void ransac_accept_kernel(typename M::Rows rows, int N, PairState<M>* __restrict__ st,
                                                            typename Sc::Ws w) {
   const int b = blockIdx.x, lane = threadIdx.x;
   PairState<M>& P = st[b];
   if (P.stop || !P.cand_ok) return;
-  Sc::template accept<M>(pts + (long)b * N, P, w, b, lane);
+  Sc::template accept<M>(rows.at((long)b * N), P, w, b, lane);
 }
 
-// one thread per pair: ok flag, M::model_out (model in pixel terms), the info row (write_info, then Sc::finish), Sc's scores
+// one thread per pair: ok flag, M::model_out (model in the caller's terms), the info row (write_info, then Sc::finish), Sc's scores
 template <class M, class Sc>
 __global__ __launch_bounds__(64) void ransac_finish_kernel(int B, const PairState<M>* __restrict__ st, typename Sc::Ws w,
-                                                           double* __restrict__ out, unsigned char* __restrict__ ok,
+                                                           typename M::Out out, unsigned char* __restrict__ ok,
                                                            int* __restrict__ info, double* __restrict__ score) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   const PairState<M>& P = st[b];
-  const bool good = P.valid && P.best > 0;
-  M::model_out(P, good, out + (long)b * 9);
+  const bool good = P.valid && P.best >= M::MIN_INLIERS;
+  M::model_out(P, good, out, b);
   int* row = info + (long)b * Sc::template INFO<M>;
   Sc::template finish<M>(P, w, b, row + write_info(P, row, Sc::template INFO_MIN<M>), score);
   ok[b] = good ? 1 : 0;
@@ -923,16 +971,15 @@ int check_args(const char* op, const char* conf, bool pointers, int B, int N, fl
   return 0;
 }
 
-// the launch sequence of the pipeline; K: [B, 3, 3] f64 camera matrices or NULL, read by M::normalise only; opt: the entry
-// point's `refine` or `lo_iters` (Sc::steps); out_score: NULL for a scoring without scores
+// the launch sequence of the pipeline; in, out_model: the model's input and output arrays (M::In, M::Out); K: [B, 3, 3] f64 camera
+// matrices or NULL, read by M::normalise only; opt: the entry point's `refine` or `lo_iters` (Sc::steps); out_score: NULL for a
+// scoring without scores.  The refit kernel is launched for the two-view models only and takes their arrays.
 template <class M, class Sc>
-int ransac_run(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K, int B,
-               int N, float thr, double conf, int max_iters, int opt, double* out_model, unsigned char* out_mask,
-               unsigned char* out_ok, int* out_info, double* out_score, void* ws, hipStream_t s) {
+int ransac_run(typename M::In in, const int* counts, const unsigned long long* seeds, const double* K, int B, int N, float thr,
+               double conf, int max_iters, int opt, typename M::Out out_model, unsigned char* out_mask, unsigned char* out_ok,
+               int* out_info, double* out_score, void* ws, hipStream_t s) {
   const Carve<M, Sc> c = carve<M, Sc>(align_base<void*>(ws), B, N);
-  const float2* ka = reinterpret_cast<const float2*>(kpts_a);
-  const float2* kb = reinterpret_cast<const float2*>(kpts_b);
-  hipLaunchKernelGGL(ransac_norm_kernel<M>, dim3(B), dim3(256), 0, s, ka, kb, counts, K, N, thr, max_iters, c.st, c.pts);
+  hipLaunchKernelGGL(ransac_norm_kernel<M>, dim3(B), dim3(256), 0, s, in, counts, K, N, thr, max_iters, c.st, c.rows);
   ROMA_LAUNCH_CHECK();
   if constexpr (Sc::INIT) {
     hipLaunchKernelGGL(magsac_init_kernel<M>, dim3((B + 63) / 64), dim3(64), 0, s, B, thr, c.st, c.w.ms);
@@ -940,10 +987,10 @@ int ransac_run(const float* kpts_a, const float* kpts_b, const int* counts, cons
   }
   const int rounds = (max_iters + R - 1) / R;
   for (int r = 0; r < rounds; ++r) {
-    hipLaunchKernelGGL(ransac_hyp_kernel<M>, dim3(B * R * M::HYP_LANES / M::HYP_THREADS), dim3(M::HYP_THREADS), 0, s, ka, kb, N,
-                       seeds, c.st, r, c.sl);
+    hipLaunchKernelGGL(ransac_hyp_kernel<M>, dim3(B * R * M::HYP_LANES / M::HYP_THREADS), dim3(M::HYP_THREADS), 0, s, in, N, seeds,
+                       c.st, r, c.sl);
     ROMA_LAUNCH_CHECK();
-    hipLaunchKernelGGL((ransac_score_kernel<M, Sc>), dim3(B * R / 4), dim3(256), 0, s, c.pts, N, c.st, c.w, c.sl);
+    hipLaunchKernelGGL((ransac_score_kernel<M, Sc>), dim3(B * R / 4), dim3(256), 0, s, c.rows, N, c.st, c.w, c.sl);
     ROMA_LAUNCH_CHECK();
     hipLaunchKernelGGL((ransac_select_kernel<M, Sc>), dim3(B), dim3(256), 0, s, c.st, c.w, r, conf, max_iters, c.sl);
     ROMA_LAUNCH_CHECK();
@@ -952,16 +999,16 @@ int ransac_run(const float* kpts_a, const float* kpts_b, const int* counts, cons
   if constexpr (Sc::template REFITS<M>) {
     for (int it = 0, n = Sc::template steps<M>(opt); it < n; ++it) {
       if (Sc::MASK_BEFORE_REFIT) {
-        hipLaunchKernelGGL((ransac_mask_kernel<M, Sc>), mgrid, dim3(256), 0, s, c.pts, N, c.st, c.w, out_mask);
+        hipLaunchKernelGGL((ransac_mask_kernel<M, Sc>), mgrid, dim3(256), 0, s, c.rows, N, c.st, c.w, out_mask);
         ROMA_LAUNCH_CHECK();
       }
-      hipLaunchKernelGGL((ransac_refit_kernel<M, Sc>), dim3(B), dim3(256), 0, s, ka, kb, c.pts, N, c.st, c.w, out_mask);
+      hipLaunchKernelGGL((ransac_refit_kernel<M, Sc>), dim3(B), dim3(256), 0, s, in.a, in.b, c.rows.p, N, c.st, c.w, out_mask);
       ROMA_LAUNCH_CHECK();
-      hipLaunchKernelGGL((ransac_accept_kernel<M, Sc>), dim3(B), dim3(64), 0, s, c.pts, N, c.st, c.w);
+      hipLaunchKernelGGL((ransac_accept_kernel<M, Sc>), dim3(B), dim3(64), 0, s, c.rows, N, c.st, c.w);
       ROMA_LAUNCH_CHECK();
     }
   }
-  hipLaunchKernelGGL((ransac_mask_kernel<M, Sc>), mgrid, dim3(256), 0, s, c.pts, N, c.st, c.w, out_mask);
+  hipLaunchKernelGGL((ransac_mask_kernel<M, Sc>), mgrid, dim3(256), 0, s, c.rows, N, c.st, c.w, out_mask);
   ROMA_LAUNCH_CHECK();
   hipLaunchKernelGGL((ransac_finish_kernel<M, Sc>), dim3((B + 63) / 64), dim3(64), 0, s, B, c.st, c.w, out_model, out_ok, out_info,
                      out_score);
