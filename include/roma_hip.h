@@ -486,6 +486,64 @@ int roma_op_bundle_adjust(const double* points, const float* kpts, const double*
                           const unsigned char* hold, const int* counts, const unsigned char* valid, int B, int V, int N,
                           double reproj_thresh, int max_steps, double* out_points, double* out_r, double* out_t, unsigned char* out_mask,
                           int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream);
+/* Multi-view tracks from pairwise index matches: what joins roma_op_match_keypoints over the pairs of V images (2 <= V <= 8) into
+ * the [V, N] observation table roma_op_triangulate_views and roma_op_bundle_adjust read.  Restated by tools/tracks_ref.py.
+ * inds DEVICE int32 [B, P, M, 2], 8-byte aligned: row (i, j) of pair p joins keypoint i of view pair_views[p][0] to keypoint j of
+ * view pair_views[p][1]; pair_views HOST int32 [P, 2], shared by all problems, P <= 64 (it is checked before any device work and
+ * travels in the kernel's arguments): both views in [0, V) and different, the same pair of views may occur more than once;
+ * match_counts DEVICE int32 [B, P] or NULL (M each): the rows of each pair that are read, later rows never are; num_kpts DEVICE
+ * int32 [B, V] or NULL (K each): a row with an index outside [0, num_kpts[v]) on either side - the -1 padding of
+ * roma_op_match_keypoints - is ignored and counted; x DEVICE f32 [B, V, K, 2] or NULL, with out_kpts: the keypoints themselves.
+ * Nodes are (v, i) with id v K + i, edges the rows that were used.  A connected component is a track when it has at least
+ * min_views (>= 2) nodes and no view twice; a component that holds two keypoints of one view is dropped whole and counted
+ * (OpenMVG's rule).  Tracks are numbered in ascending order of their smallest node id: the whole result depends on the edge set
+ * alone, not on the order of rows or pairs, on duplicate rows or on the thread schedule.
+ * Outputs, all DEVICE: tracks int32 [B, V, T], T = max_tracks: the keypoint index, -1 where the view is not in the track and for
+ * tracks at or beyond counts[b]; kpts f32 [B, V, T, 2] (NULL with x NULL): the keypoint's bits, NaN elsewhere - what
+ * roma_op_bundle_adjust and roma_op_triangulate_views read as "not observed"; counts int32 [B] = min(total, T); total int32 [B];
+ * info int32 [B, 4] = {rows used, rows ignored, components of >= 2 nodes, components dropped}.
+ * One workgroup per problem runs everything in one launch and never waits on another: labels by min-label hooking (atomicMin,
+ * the kernel's only atomic) and pointer jumping between workgroup barriers, until a round changes nothing (fewer than V K
+ * rounds: each one that changes anything removes a root); then conflicts, counting and a prefix sum over the roots in id order.
+ * Limits: K <= 65536 keypoints per view (2^19 nodes, four int32 each in the workspace of roma_op_build_tracks_workspace bytes),
+ * P <= 64, B <= 65535, B P M < 2^30, B V T < 2^30.  Every argument is checked before anything is enqueued; B == 0 launches
+ * nothing; bit-identical from run to run and independent of B. */
+long roma_op_build_tracks_workspace(int B, int V, int K, int P, int M);
+int roma_op_build_tracks(const int* inds, const int* pair_views, const int* match_counts, const int* num_kpts, const float* x, int B,
+                         int V, int K, int P, int M, int max_tracks, int min_views, int* out_tracks, float* out_kpts, int* out_counts,
+                         int* out_total, int* out_info, void* workspace, long workspace_bytes, void* stream);
+/* N-view triangulation: the 3-D point of every track from all the views that observe it, the poses given (x_cam = R X + t) -
+ * the point half of roma_op_bundle_adjust.  Float64 with fp contraction off; restated operation by operation by
+ * tools/triangulate_views_ref.py.  kpts DEVICE f32 [B, V, N, 2], 8-byte aligned, pixels of their view, a non-finite entry: the
+ * view does not observe the point; camera_matrices DEVICE f64 [B, V, 3, 3] or NULL (observations and thresholds are normalised);
+ * R DEVICE f64 [B, V, 3, 3], t DEVICE f64 [B, V, 3]; view_valid DEVICE u8 [B, V] or NULL: a view that is not valid (or whose pose or
+ * camera is not finite) contributes no observation - how an unregistered view is passed; counts DEVICE int32 [B] or NULL (N);
+ * valid DEVICE u8 [B] or NULL (every problem).  Per point, x_n = ((u - cx) / fx, (v - cy) / fy):
+ *   1. the observations in use: finite, of a valid view, not trimmed; fewer than min_views (>= 2) of them: DEGENERATE;
+ *   2. unit ray d_v = R_v^T (x_n, 1) / |.| from the centre c_v = -R_v^T t_v;
+ *   3. midpoint (sum (I - d d^T)) X = sum (I - d d^T) c by a 3 x 3 Cholesky factor; a pivot that is not finite or not above 1e-14 x
+ *      the largest diagonal entry (parallel rays): DEGENERATE;
+ *   4. up to gn_steps (0 .. 10) Gauss-Newton steps on sum |p_xy / z - x_n|^2, p = R_v X + t_v, over the observations in use:
+ *      analytic Jacobian, normal equations by the same factor; a step is kept only if its cost is finite and strictly lower, the
+ *      first rejected or failed step ends the loop - the cost never rises above the midpoint's;
+ *   5. trim = 1: e_v = |error| / thr_v with thr_v = max_reproj / ((fx_v + fy_v) / 2) (roma_op_bundle_adjust's rule; +inf switches the
+ *      test off); while the largest e_v exceeds 1 and at least 3 observations are in use, the worst one (the lowest view of a
+ *      tie) leaves the set and the point is computed again from 2 - at most V - 2 times.
+ * Outputs, all DEVICE: points f64 [B, N, 3], NaN where bit 1 or 2 is set, so the array feeds roma_op_bundle_adjust unchanged;
+ * reproj f32 [B, V, N]: the error in pixels of every finite observation of a valid view, trimmed ones included, NaN elsewhere;
+ * used u8 [B, V, N]: the observations of the final fit; parallax f32 [B, N]: the largest angle between two rays in use (the pair
+ * with the smallest dot product), degrees; flags u8 [B, N], roma_op_triangulate's bits: 1 skipped, 2 degenerate, 4 not
+ * 0 < depth < max_depth in a view in use, 8 an observation in use above max_reproj, 16 not parallax >= min_parallax; stats int32
+ * [B, 8] = {points considered, valid, degenerate, cheirality, reproj, parallax, observations trimmed, 0}, cleared on the stream by
+ * the same call.  One thread per point, the views staged once per workgroup; no workspace, no host read; bit-identical from
+ * run to run and independent of B.  Refused before anything is enqueued: a null required pointer, V outside [2, 8], B > 65535,
+ * B V N >= 2^31, a negative (or NaN) threshold, min_views outside [2, V], gn_steps outside [0, 10], trim not 0 or 1, kpts not
+ * 8-byte aligned.  B = 0 or N = 0 launches nothing. */
+int roma_op_triangulate_views(const float* kpts, const double* camera_matrices, const double* R, const double* t,
+                              const unsigned char* view_valid, const int* counts, const unsigned char* valid, int B, int V, int N,
+                              double max_reproj, double min_parallax, double max_depth, int min_views, int gn_steps, int trim,
+                              double* out_points, float* out_reproj, unsigned char* out_used, float* out_parallax,
+                              unsigned char* out_flags, int* out_stats, void* stream);
 /* Nonlinear refinement of a homography (model 0) or a fundamental matrix (model 1): a Levenberg-Marquardt fit under the
  * hard-truncated loss sum min(|r|^2, thr^2) of the forward reprojection error in image B (H: what cv2.findHomography(..., RANSAC)
  * ends with) or of the Sampson distance (F: what PoseLib's estimate_fundamental ends with); it follows roma_op_ransac /

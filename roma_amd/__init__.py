@@ -11,8 +11,9 @@ from .sampling import multinomial, sample_matches  # noqa: F401
 from .geometry import (essential_magsac, essential_minimal, estimate_pose, estimate_pose_uncalibrated, find_essential,  # noqa: F401
                        find_fundamental, find_homography, magsac, recover_pose, refine_fundamental, refine_homography, refine_pose)
 from .absolute_pose import absolute_pose_minimal, estimate_absolute_pose, lift_matches, refine_absolute_pose  # noqa: F401
-from .bundle import BundleResult, bundle_adjust, reconstruct_pair  # noqa: F401
-from .triangulation import depth_consistency, triangulate, triangulate_warp  # noqa: F401
+from .bundle import BundleResult, ViewsReconstruction, bundle_adjust, reconstruct_pair, reconstruct_views  # noqa: F401
+from .triangulation import ViewsTriangulation, depth_consistency, triangulate, triangulate_views, triangulate_warp  # noqa: F401
+from .tracks import Tracks, build_tracks  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 from .gt_warp import DenseMetrics, dense_metrics, get_gt_warp, warp_kpts  # noqa: F401
 from .metrics import (ErrorLog, ErrorSummary, PoseError, compute_pose_error, homography_corner_error,  # noqa: F401
@@ -27,5 +28,6 @@ __all__ = ["pose_error", "compute_pose_error", "homography_corner_error", "pose_
            "multinomial", "sample_matches", "find_homography", "find_fundamental", "find_essential", "recover_pose", "refine_pose", "estimate_pose",
            "refine_homography", "refine_fundamental", "estimate_pose_uncalibrated", "essential_minimal", "magsac", "essential_magsac",
            "estimate_absolute_pose", "absolute_pose_minimal", "refine_absolute_pose", "lift_matches",
-           "bundle_adjust", "reconstruct_pair", "BundleResult",
+           "bundle_adjust", "reconstruct_pair", "BundleResult", "build_tracks", "Tracks", "triangulate_views", "ViewsTriangulation",
+           "reconstruct_views", "ViewsReconstruction",
            "TinyRoMa", "tiny_roma_v1_outdoor"]

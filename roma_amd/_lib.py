@@ -116,6 +116,10 @@ SIGNATURES = {
     "roma_op_bundle_adjust_workspace": (_l, [_i, _i, _i]),
     "roma_op_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _vp, _l, _vp]),
+    "roma_op_build_tracks_workspace": (_l, [_i, _i, _i, _i, _i]),
+    "roma_op_build_tracks": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "roma_op_triangulate_views": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _i, _i, _i,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "roma_op_refine_model_workspace": (_l, [_i, _i]),
     "roma_op_refine_model": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_triangulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double,

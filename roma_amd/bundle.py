@@ -2,6 +2,15 @@
 reprojection error - the closing step after `estimate_pose` / `triangulate` / `estimate_absolute_pose`, which each fit one
 side with the other held.  Batched over independent problems of up to 8 views, one launch, no read-back.
 
+More than two views, from detector keypoints x[v] [K, 2] shared by the pairs (a, b) of V images, nothing read back:
+
+    km = model.match_keypoints(x_a, x_b, warp, cert)                       # one batch entry per pair
+    tr = build_tracks(km.inds, pairs, V, match_counts=km.counts, kpts=torch.stack(x))
+    rec = reconstruct_views(tr.kpts, K, norm_thresh, reproj_thresh, counts=tr.counts)
+
+`reconstruct_views` seeds on views 0 and 1, registers every further view in one shot against the seed pair's points,
+triangulates from all registered views and closes with `bundle_adjust`.
+
 Levenberg-Marquardt with the Schur complement under the truncated loss sum min(|r|^2, thr^2) over the observations; the
 constants and the accept / reject / stop rules are those of `refine_pose` (csrc/lm_fit.h).  The algorithm is restated in numpy
 float64 by tools/bundle_ref.py.  x_cam = R X + t.
@@ -25,6 +34,17 @@ class BundleResult(NamedTuple):
     mask: torch.Tensor    # [.., V, N] bool: the observations inside the threshold under the returned state
     info: torch.Tensor    # [.., 6] int32: accepted steps, cost evaluations, active rows, points adjusted, free camera parameters, fitted
     cost: torch.Tensor    # [.., 2] float64: truncated cost at the start and at the end (normalised image coordinates)
+
+
+class ViewsReconstruction(NamedTuple):
+    R: torch.Tensor        # [.., V, 3, 3] float64, x_cam = R X + t; view 0 is the identity; identity for a view that is not registered
+    t: torch.Tensor        # [.., V, 3] float64
+    points: torch.Tensor   # [.., N, 3] float64 in view 0's frame, NaN where there is none
+    mask: torch.Tensor     # [.., V, N] bool: the observations inside reproj_thresh under the returned state
+    view_ok: torch.Tensor  # [.., V] bool: the view is registered
+    ok: torch.Tensor       # [..] bool: the seed pair gave a pose
+    info: torch.Tensor     # [.., 6] int32: `bundle_adjust`'s
+    cost: torch.Tensor     # [.., 2] float64: `bundle_adjust`'s truncated cost at the start and at the end
 
 
 def _device_tensor(x, name):
@@ -164,3 +184,68 @@ def reconstruct_pair(kpts_A, kpts_B, K_A, K_B, norm_thresh, reproj_thresh, conf=
     if not single:
         return (*res, ok)
     return tuple(r[0] for r in res) if bool(ok[0]) else None
+
+
+def reconstruct_views(kpts, K, norm_thresh, reproj_thresh, conf=0.99999, max_iters=1000, seed=None, counts=None, method="ransac",
+                      max_steps=25, min_parallax=0.0):
+    """V views to a refined reconstruction with nothing read back - composition only.  kpts [B, V, N, 2] or [V, N, 2] pixels of
+    2 <= V <= 8 views, one row per track, a non-finite entry where the view does not observe it (`build_tracks`' kpts); K
+    [V, 3, 3], [3, 3] or [B, V, 3, 3]; norm_thresh the RANSAC threshold of `estimate_pose` in normalised coordinates,
+    reproj_thresh in pixels for everything after it; conf and max_iters go to both RANSAC runs (`estimate_pose` on the seed pair
+    and `estimate_absolute_pose` on the further views), seed, counts, method as for `estimate_pose`.
+
+      1. `estimate_pose(refine=True)` on views 0 and 1 (rows with a NaN are never inliers)
+      2. `triangulate_views` with only views 0 and 1 valid, max_reproj = reproj_thresh; points that are not valid become NaN
+      3. one `estimate_absolute_pose(refine=True)` call over the B (V - 2) further views against those points, seeds derived
+         from `seed`
+      4. `triangulate_views` over all registered views
+      5. `bundle_adjust` under the default hold, every view that is not registered held entirely and its observations NaN,
+         valid = the seed pair's ok
+
+    Registration is one shot against the seed pair's points: a view that shares no track with views 0 and 1 comes back with
+    view_ok false and the identity pose.  Returns ViewsReconstruction(R, t, points, mask, view_ok, ok, info, cost); the
+    single-problem form returns everything without the batch axis."""
+    from .absolute_pose import estimate_absolute_pose
+    from .geometry import _seeds, estimate_pose
+    from .triangulation import triangulate_views
+    if not isinstance(kpts, torch.Tensor) or kpts.dim() not in (3, 4) or kpts.shape[-1] != 2 or not 2 <= kpts.shape[-3] <= MAX_VIEWS:
+        raise ValueError(f"roma_amd.bundle: kpts must be a tensor [V, N, 2] or [B, V, N, 2] with 2 <= V <= {MAX_VIEWS}")
+    x = _device_tensor(kpts, "kpts")
+    single = x.dim() == 3
+    x = x.detach().to(torch.float32)
+    x = (x[None] if single else x).contiguous()
+    B, V, N, dev = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), x.device
+    K = _view_cameras(K, B, V, dev)
+    if K is None:
+        raise ValueError("roma_amd.bundle: K is required")
+    counts, seeds = _counts(counts, B, dev), _seeds(seed, B, dev)
+    f64 = dict(device=dev, dtype=torch.float64)
+    eye, nan = torch.eye(3, **f64), torch.full((), float("nan"), **f64)
+    R1, t1, _, ok = estimate_pose(x[:, 0], x[:, 1], K[:, 0], K[:, 1], norm_thresh, conf, max_iters, seeds, counts, refine=True, method=method)
+    view_ok = torch.zeros((B, V), device=dev, dtype=torch.bool)
+    view_ok[:, :2] = ok[:, None]
+    Rs = eye.expand(B, V, 3, 3).clone()
+    ts = torch.zeros((B, V, 3), **f64)
+    Rs[:, 1], ts[:, 1] = R1, t1.reshape(B, 3)
+    if V > 2:
+        tri = triangulate_views(x, K, Rs, ts, view_valid=view_ok, counts=counts, valid=ok, max_reproj=reproj_thresh, min_parallax=min_parallax)
+        pts = torch.where(tri.valid[..., None], tri.points, nan)
+        more = V - 2
+        Xr = pts[:, None].expand(B, more, N, 3).reshape(B * more, N, 3)
+        step = torch.arange(1, more + 1, device=dev, dtype=torch.int64) * 1000003
+        Rr, tr, _, okr = estimate_absolute_pose(Xr, x[:, 2:].reshape(B * more, N, 2), K[:, 2:].reshape(B * more, 3, 3), reproj_thresh,
+                                                conf=conf, max_iters=max_iters, seed=(seeds[:, None] + step).reshape(-1),
+                                                counts=None if counts is None else counts.repeat_interleave(more), refine=True,
+                                                max_steps=max_steps)
+        view_ok = torch.cat((view_ok[:, :2], okr.reshape(B, more) & ok[:, None]), dim=1)
+        Rs = torch.cat((Rs[:, :2], Rr.reshape(B, more, 3, 3)), dim=1)
+        ts = torch.cat((ts[:, :2], tr.reshape(B, more, 3)), dim=1)
+    Rs = torch.where(view_ok[..., None, None], Rs, eye).contiguous()
+    ts = torch.where(view_ok[..., None], ts, torch.zeros((), **f64)).contiguous()
+    tri = triangulate_views(x, K, Rs, ts, view_valid=view_ok, counts=counts, valid=ok, max_reproj=reproj_thresh, min_parallax=min_parallax)
+    pts = torch.where(tri.valid[..., None], tri.points, nan)
+    hold = default_hold(ts) | (~view_ok[..., None]).to(torch.uint8)
+    seen = torch.where(view_ok[:, :, None, None], x, torch.full((), float("nan"), device=dev, dtype=torch.float32))
+    out = bundle_adjust(pts, seen, K, Rs, ts, reproj_thresh, max_steps, hold=hold, counts=counts, valid=ok)
+    res = ViewsReconstruction(out.R, out.t, out.points, out.mask, view_ok, ok, out.info, out.cost)
+    return ViewsReconstruction(*(r[0] for r in res)) if single else res

@@ -32,6 +32,7 @@
 #include "pose_refine.h"
 #include "geometry.h"
 #include "triangulate.h"
+#include "tracks.h"
 #include "gt_warp.h"
 #include "metrics.h"
 #include "morph.h"
@@ -631,6 +632,23 @@ int roma_op_bundle_adjust(const double* points, const float* kpts, const double*
   return bundle_adjust_launch(points, kpts, camera_matrices, R, t, hold, counts, valid, B, V, N, reproj_thresh, max_steps, out_points,
                               out_r, out_t, out_mask, out_info, out_cost, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0),
                               S(stream));
+}
+// ---- multi-view tracks from pairwise index matches (tracks.hip) and their N-view triangulation (triangulate_views.hip)
+long roma_op_build_tracks_workspace(int B, int V, int K, int P, int M) { return (long)build_tracks_workspace_bytes(B, V, K, P, M); }
+int roma_op_build_tracks(const int* inds, const int* pair_views, const int* match_counts, const int* num_kpts, const float* x, int B,
+                         int V, int K, int P, int M, int max_tracks, int min_views, int* out_tracks, float* out_kpts, int* out_counts,
+                         int* out_total, int* out_info, void* workspace, long workspace_bytes, void* stream) {
+  return build_tracks_launch(inds, pair_views, match_counts, num_kpts, x, B, V, K, P, M, max_tracks, min_views, out_tracks, out_kpts,
+                             out_counts, out_total, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+int roma_op_triangulate_views(const float* kpts, const double* camera_matrices, const double* R, const double* t,
+                              const unsigned char* view_valid, const int* counts, const unsigned char* valid, int B, int V, int N,
+                              double max_reproj, double min_parallax, double max_depth, int min_views, int gn_steps, int trim,
+                              double* out_points, float* out_reproj, unsigned char* out_used, float* out_parallax,
+                              unsigned char* out_flags, int* out_stats, void* stream) {
+  return triangulate_views_launch(kpts, camera_matrices, R, t, view_valid, counts, valid, B, V, N, max_reproj, min_parallax, max_depth,
+                                  min_views, gn_steps, trim, out_points, out_reproj, out_used, out_parallax, out_flags, out_stats,
+                                  S(stream));
 }
 // ---- homography / fundamental-matrix refinement (model_refine.hip)
 long roma_op_refine_model_workspace(int B, int N) { return (long)refine_model_workspace_bytes(B, N); }

@@ -23,6 +23,9 @@ from .geometry import _cameras, _counts, _pair_batch, _pose_tensor, _ptr, _strea
 SKIPPED, DEGENERATE, CHEIRALITY, REPROJ, PARALLAX, CERTAINTY = 1, 2, 4, 8, 16, 32  # bits of `flags` (csrc/triangulate.h)
 
 Triangulation = namedtuple("Triangulation", "points depth_other reproj parallax flags valid stats")
+ViewsTriangulation = namedtuple("ViewsTriangulation", "points reproj used parallax flags valid stats")
+MAX_VIEWS = 8   # csrc/tracks.h: ROMA_TRACKS_MAX_VIEWS
+MAX_GN = 10     # TRIANGULATE_VIEWS_MAX_GN
 
 
 class WarpTriangulation(dict):
@@ -99,6 +102,78 @@ def triangulate(kpts_A, kpts_B, R, t, K_A=None, K_B=None, certainty=None, counts
     out, _ = _launch(m, certainty, R, t, K_A, K_B, counts, valid, 0, (0, 0, 0, 0), 0,
                      _thresholds(max_depth, max_reproj, min_parallax, min_certainty))
     return Triangulation(*(o[0] for o in out)) if single else out
+
+
+def _view_poses(K, R, t, view_valid, B, V, dev):
+    """the per-view arguments of `triangulate_views` as [B, V, ..] device tensors (K and view_valid may be None)"""
+    from .bundle import _view_cameras
+    R, t = _device_tensor(R, "R"), _device_tensor(t, "t")
+    if R.numel() != B * V * 9 or t.numel() != B * V * 3:
+        raise ValueError(f"roma_amd.triangulation: R and t must hold {B} x {V} poses, got {tuple(R.shape)} and {tuple(t.shape)}")
+    R = R.detach().to(device=dev, dtype=torch.float64).reshape(B, V, 3, 3).contiguous()
+    t = t.detach().to(device=dev, dtype=torch.float64).reshape(B, V, 3).contiguous()
+    if view_valid is not None:
+        view_valid = torch.as_tensor(view_valid).to(device=dev)
+        view_valid = view_valid[None].expand(B, V) if tuple(view_valid.shape) == (V,) else view_valid
+        if tuple(view_valid.shape) != (B, V):
+            raise ValueError(f"roma_amd.triangulation: view_valid must be [{V}] or [{B}, {V}], got {tuple(view_valid.shape)}")
+        view_valid = (view_valid != 0).to(torch.uint8).contiguous()
+    return _view_cameras(K, B, V, dev), R, t, view_valid
+
+
+def triangulate_views(kpts, K, R, t, view_valid=None, counts=None, valid=None, max_reproj=math.inf, min_parallax=0.0,
+                      max_depth=math.inf, min_views=2, gn_steps=3, trim=True):
+    """The 3-D point of every track from all the views that observe it, the poses given (`roma_op_triangulate_views`): the point
+    half of `bundle_adjust`, on the device with no host synchronisation.  kpts [B, V, N, 2] pixels of V <= 8 views (read as
+    float32; a non-finite entry: the view does not observe the point - what `build_tracks` writes), K [V, 3, 3], [3, 3] or
+    [B, V, 3, 3] (None: kpts are normalised image coordinates, and so is max_reproj), R [B, V, 3, 3], t [B, V, 3] with
+    x_cam = R X + t; view_valid [B, V] bool: a view that is not valid contributes no observation (an unregistered view);
+    counts [B] points per problem, valid [B] bool problems to triangulate.  [V, N, 2] with [V, ..] poses is one problem.
+
+    Per point, in float64 (restated by tools/triangulate_views_ref.py): the midpoint of the rays of the observations in use, up
+    to gn_steps (<= 10) Gauss-Newton steps on the reprojection error, each kept only if it lowers the cost; with trim, while
+    the largest error exceeds max_reproj (pixels of its view, divided by (fx + fy) / 2 as in `bundle_adjust`) and at least
+    three observations are in use, the worst one leaves and the point is computed again.
+
+    Returns ViewsTriangulation(points [B, N, 3] float64, reproj [B, V, N] float32 (pixels; every observation of a valid view,
+    trimmed ones included; NaN elsewhere), used [B, V, N] bool (the observations of the final fit), parallax [B, N] float32
+    (largest angle between two rays in use, degrees), flags [B, N] uint8, valid [B, N] bool = flags == 0, stats [B, 8] int32 =
+    (points considered, valid, degenerate, cheirality, reproj, parallax, observations trimmed, 0)).  Flag bits as for
+    `triangulate`: 1 skipped, 2 degenerate (fewer than min_views observations in use, parallel rays), 4 not 0 < depth <
+    max_depth in a view in use, 8 an observation in use above max_reproj, 16 parallax < min_parallax; points with bit 1 or 2
+    are NaN, so the array feeds `bundle_adjust` unchanged."""
+    th = tuple(float(x) for x in (max_reproj, min_parallax, max_depth))
+    if not all(x >= 0 for x in th):
+        raise ValueError("roma_amd.triangulation: max_reproj, min_parallax and max_depth must not be negative")
+    if not 0 <= int(gn_steps) <= MAX_GN:
+        raise ValueError(f"roma_amd.triangulation: need 0 <= gn_steps <= {MAX_GN}")
+    if not isinstance(kpts, torch.Tensor) or kpts.dim() not in (3, 4) or kpts.shape[-1] != 2:
+        raise ValueError("roma_amd.triangulation: kpts must be a tensor [V, N, 2] or [B, V, N, 2]")
+    single = kpts.dim() == 3
+    B, V, N = (1 if single else int(kpts.shape[0])), int(kpts.shape[-3]), int(kpts.shape[-2])
+    if not 2 <= V <= MAX_VIEWS or not 2 <= int(min_views) <= V:
+        raise ValueError(f"roma_amd.triangulation: need 2 <= V <= {MAX_VIEWS} views and 2 <= min_views <= V, got V = {V}")
+    if B * V * N >= 2 ** 31 or B > 65535:
+        raise ValueError(f"roma_amd.triangulation: {B} x {V} x {N} observations is more than one call takes")
+    x = _device_tensor(kpts, "kpts")
+    dev = x.device
+    x = x.detach().to(torch.float32).contiguous().reshape(B, V, N, 2)
+    K, R, t, view_valid = _view_poses(K, R, t, view_valid, B, V, dev)
+    counts, valid = _counts(counts, B, dev), _valid(valid, B, dev)
+    points = torch.full((B, N, 3), float("nan"), device=dev, dtype=torch.float64)
+    reproj = torch.full((B, V, N), float("nan"), device=dev, dtype=torch.float32)
+    used = torch.zeros((B, V, N), device=dev, dtype=torch.bool)
+    parallax = torch.full((B, N), float("nan"), device=dev, dtype=torch.float32)
+    flags = torch.full((B, N), SKIPPED, device=dev, dtype=torch.uint8)
+    stats = torch.zeros((B, 8), device=dev, dtype=torch.int32)
+    if B > 0 and N > 0:
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().roma_op_triangulate_views(
+                _ptr(x), _ptr(K), _ptr(R), _ptr(t), _ptr(view_valid), _ptr(counts), _ptr(valid), B, V, N, *th, int(min_views),
+                int(gn_steps), int(bool(trim)), _ptr(points), _ptr(reproj), _ptr(used), _ptr(parallax), _ptr(flags), _ptr(stats),
+                _stream(dev)))
+    out = ViewsTriangulation(points, reproj, used, parallax, flags, flags == 0, stats)
+    return ViewsTriangulation(*(o[0] for o in out)) if single else out
 
 
 def _consistency(points, flags, R, t, K_A, K_B, sizes, H, W, rel_thresh, want_err):
