@@ -211,6 +211,7 @@ __global__ __launch_bounds__(1024) void gray_instnorm_kernel(const float* __rest
   float* ob = out + (long)blockIdx.x * HW;
   const float invc = 1.f / (float)C;
   auto gray = [&](long p) {
+#pragma clang fp contract(off)  // the product rounded: fused into `- mean` below it, a single pixel (mean == gray) would not give 0
     float g = 0.f;
     for (int c = 0; c < C; ++c) g += ib[p * C + c];
     return g * invc;
@@ -364,7 +365,9 @@ __global__ __launch_bounds__(256) void tiny_final_kernel(const float* __restrict
   const int x = (int)(idx % W);
   const int y = (int)((idx / W) % H);
   *reinterpret_cast<f32x4*>(warp + idx * 4) = f32x4{tiny_pix_coord(x, W), tiny_pix_coord(y, H), m[idx * 3 + 0], m[idx * 3 + 1]};
-  cert[idx] = 1.f / (1.f + expf(-m[idx * 3 + 2]));
+  // below -87, 1 + e^-z == e^-z in f32 and e^-z overflows from -88.73 on (1 / inf = 0 where sigmoid is still ~1e-39): e^z
+  const float z = m[idx * 3 + 2];
+  cert[idx] = z < -87.f ? expf(z) : 1.f / (1.f + expf(-z));
 }
 
 int tiny_final_launch(const float* matches, float* warp, float* cert, int B, int H, int W, hipStream_t s) {

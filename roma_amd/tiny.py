@@ -85,7 +85,8 @@ def _compile_stack(m, dev):
         elif isinstance(leaf, nn.AvgPool2d):
             k = leaf.kernel_size if isinstance(leaf.kernel_size, int) else leaf.kernel_size[0]
             st = leaf.stride if isinstance(leaf.stride, int) else leaf.stride[0]
-            if k != st or leaf.padding not in (0, (0, 0)):
+            # avgpool_nhwc is AvgPool2d(k, k) with the floor output size and the divisor k*k, nothing else
+            if k != st or leaf.padding not in (0, (0, 0)) or leaf.ceil_mode or leaf.divisor_override is not None:
                 raise NotImplementedError(f"TinyRoMa backbone: unsupported pooling {leaf}")
             ops.append(dict(op="avgpool", k=k))
         elif isinstance(leaf, nn.Identity):
