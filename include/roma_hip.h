@@ -56,7 +56,7 @@ const char* roma_version(void);
 /* ABI stamp of the structures that cross the library boundary BETWEEN the two builds (roma_vit_args_t, roma_vit_block_t:
  * a ROMA_MIXED handle of libroma_hip_f16.so calls roma_vit_forward of libroma_hip.so): ROMA_ABI_VERSION * 100000 +
  * sizeof(roma_vit_args_t).  The sibling is refused unless the stamps are equal. */
-#define ROMA_ABI_VERSION 5
+#define ROMA_ABI_VERSION 6
 int roma_abi_stamp(void);
 /* the 16-bit format as THIS library's own internal calls see it (== roma_h16_format() unless another library's symbols
  * interpose: the sibling check of ROMA_MIXED and tests/test_cpu_oracle.py use it) */
@@ -75,7 +75,8 @@ typedef struct {
 } roma_vit_block_t;
 
 typedef struct {
-  int B, H, W;                      /* B pairs = 2B images: im_a[B,3,H,W], im_b[B,3,H,W] f32 (H, W multiples of 14) */
+  int B, H, W;                      /* B pairs = 2B images: im_a[B,3,H,W], im_b[B,3,H,W] f32 (H, W multiples of 14); im_b == NULL
+                                       (ABI 6): B images, all at im_a - read "B" for "2B" below */
   int act;                          /* ROMA_F32 or the library's 16-bit code */
   int bf16_residual;                /* 16-bit mode: residual stream in 16 bits (the reference's bf16 backbone) */
   const float *im_a, *im_b;
@@ -122,6 +123,32 @@ int roma_set_option_f(roma_handle_t h, const char* key, double value);
  * upsample_preds == 0.  warp_out: [B,Ho,2*Wo,4] (symmetric) or [B,Ho,Wo,4]; cert_out: [B,Ho,2*Wo] / [B,Ho,Wo]. */
 int roma_match(roma_handle_t h, int B, const float* im_a, const float* im_b, const float* im_a_hr,
                const float* im_b_hr, float* warp_out, float* cert_out, void* stream);
+/* ---- cached per-image features for image sets: encode every image ONCE, then match any pairs of the encoded images.
+ * Everything the decoder reads of an image is its projected feature maps (the proj heads of scales 16, 8, 4, 2, 1 of the coarse
+ * pass and of 8, 4, 2, 1 of the upsample pass), so one image's "pack" holds exactly those: per pass and scale [h_s * w_s, ldf] in
+ * the handle's activation type, ldf = C_s rounded up to 8 with C = 512, 512, 256, 64, 9, every segment on a 256-byte boundary
+ * (coarse 16, 8, 4, 2, 1, then upsample 8, 4, 2, 1 when the handle has an upsample resolution).  The layout is fixed at
+ * roma_finalize; roma_amd/encoded.py::pack_layout restates it.  About 120 MB per image in the 16-bit modes at 560 -> 864 and 240 MB
+ * in f32.  The raw VGG / DINOv2 pyramids are NOT cached (roma_forward's feat[] still computes them per call).
+ * The caller owns the feature buffer: N packs back to back, 16-byte aligned device memory.
+ *
+ * roma_encoded_bytes: bytes of one pack for this handle; -1 before roma_finalize. */
+long roma_encoded_bytes(roma_handle_t h);
+/* images [N,3,coarse_h,coarse_w] f32; images_hr [N,3,upsample_h,upsample_w] f32 or NULL (then only the coarse part of every pack
+ * is written and the packs serve upsample_preds == 0 only - the caller keeps track).  Runs the VGG19-BN pyramid, DINOv2 and the
+ * proj heads of the coarse pass, and with images_hr the pyramid and the proj heads of the upsample pass.  Any N >= 1; images are
+ * processed in chunks of 2 * max_batch out of the workspace planned at roma_finalize, on the caller's stream.  feats_bytes must
+ * be N * roma_encoded_bytes(h). */
+int roma_encode(roma_handle_t h, int N, const float* images, const float* images_hr, void* feats, long feats_bytes, void* stream);
+/* roma_match for the P pairs (idx_a_host[i], idx_b_host[i]) of the N encoded images in feats: the same schedule with the encoders
+ * and the proj heads left out - one gather kernel per scale copies the 2P projected maps (the P query images, then the P support
+ * images) to where the proj head would have written them, everything behind it runs unchanged.  Same options ("symmetric",
+ * "upsample_preds", "attenuate_cert", "compose_out_conv", "dual_stream" / "streams"), same output layout and - for packs written by
+ * roma_encode of the same handle configuration - the same bits as roma_match on those images.  P <= max_batch.  The indices are
+ * HOST arrays, range-checked against N before anything is enqueued: a bad index, a feats_bytes other than
+ * N * roma_encoded_bytes(h) or P > max_batch return an error with nothing launched. */
+int roma_match_encoded(roma_handle_t h, int P, const void* feats, long feats_bytes, int N, const int* idx_a_host,
+                       const int* idx_b_host, float* warp_out, float* cert_out, void* stream);
 /* ONE decoder pass with its per-scale correspondences exposed: RegressionMatcher.forward / forward_symmetric in eval mode
  * (matcher.py:631-670 -> Decoder.forward, matcher.py:395-527: corresps[s] = {"flow", "certainty"} for s = 16, 8, 4, 2, 1) and
  * extract_backbone_features (matcher.py:585-596).  upsample = 0: the coarse pass over images at the handle's coarse resolution

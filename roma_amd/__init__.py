@@ -15,6 +15,7 @@ from .bundle import BundleResult, ViewsReconstruction, bundle_adjust, reconstruc
 from .triangulation import ViewsTriangulation, depth_consistency, triangulate, triangulate_views, triangulate_warp  # noqa: F401
 from .tracks import Tracks, build_tracks  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
+from .encoded import EncodedImages, all_pairs, pack_layout  # noqa: F401
 from .gt_warp import DenseMetrics, dense_metrics, get_gt_warp, warp_kpts  # noqa: F401
 from .metrics import (ErrorLog, ErrorSummary, PoseError, compute_pose_error, homography_corner_error,  # noqa: F401
                       hpatches_coordinates, pose_auc, pose_error)
@@ -30,4 +31,5 @@ __all__ = ["pose_error", "compute_pose_error", "homography_corner_error", "pose_
            "estimate_absolute_pose", "absolute_pose_minimal", "refine_absolute_pose", "lift_matches",
            "bundle_adjust", "reconstruct_pair", "BundleResult", "build_tracks", "Tracks", "triangulate_views", "ViewsTriangulation",
            "reconstruct_views", "ViewsReconstruction",
+           "EncodedImages", "all_pairs", "pack_layout",
            "TinyRoMa", "tiny_roma_v1_outdoor"]

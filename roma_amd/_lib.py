@@ -51,6 +51,9 @@ SIGNATURES = {
     "roma_set_option": (_i, [_vp, C.c_char_p, _i]),
     "roma_set_option_f": (_i, [_vp, C.c_char_p, C.c_double]),
     "roma_match": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "roma_encoded_bytes": (_l, [_vp]),
+    "roma_encode": (_i, [_vp, _i, _vp, _vp, _vp, _l, _vp]),
+    "roma_match_encoded": (_i, [_vp, _i, _vp, _l, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp, _vp, _vp]),
     "roma_forward": (_i, [_vp, _i, _vp, _vp, C.POINTER(RomaForwardArgs), _vp]),
     "roma_debug_fetch": (_l, [_vp, C.c_char_p, _vp, _l]),
     "roma_debug_trace": (_l, [_vp, _i, _vp, _l, C.c_char_p, _l]),

@@ -187,6 +187,25 @@ int roma_match(roma_handle_t h, int B, const float* im_a, const float* im_b, con
   return h->m.match(B, im_a, im_b, im_a_hr, im_b_hr, warp_out, cert_out, S(stream));
 }
 
+long roma_encoded_bytes(roma_handle_t h) {
+  if (!h || !h->m.finalized) {
+    set_error("roma_encoded_bytes: null handle or roma_finalize not called yet");
+    return -1;
+  }
+  return h->m.pack.total;
+}
+
+int roma_encode(roma_handle_t h, int N, const float* images, const float* images_hr, void* feats, long feats_bytes, void* stream) {
+  ROMA_REQUIRE(h, "roma_encode: null handle");
+  return h->m.encode(N, images, images_hr, feats, feats_bytes, S(stream));
+}
+
+int roma_match_encoded(roma_handle_t h, int P, const void* feats, long feats_bytes, int N, const int* idx_a_host,
+                       const int* idx_b_host, float* warp_out, float* cert_out, void* stream) {
+  ROMA_REQUIRE(h, "roma_match_encoded: null handle");
+  return h->m.match_encoded(P, feats, feats_bytes, N, idx_a_host, idx_b_host, warp_out, cert_out, S(stream));
+}
+
 int roma_forward(roma_handle_t h, int B, const float* im_a, const float* im_b, const roma_forward_args_t* a, void* stream) {
   ROMA_REQUIRE(h, "roma_forward: null handle");
   return h->m.forward(B, im_a, im_b, a, S(stream));

@@ -10,6 +10,7 @@
 #include "../../include/roma_hip.h"
 #include "arena.h"
 #include "common.h"
+#include "encoded.h"
 #include "tuning.h"
 
 namespace roma {
@@ -147,11 +148,22 @@ class Model {
   int match(int B, const float* ima, const float* imb, const float* ima_hr, const float* imb_hr, float* warp,
             float* cert, hipStream_t st);
   int forward(int B, const float* ima, const float* imb, const roma_forward_args_t* fw, hipStream_t st);
+  // ---- cached per-image features (encoded.h): encoders + proj heads once per image, then match() on pairs of cached images
+  PackLayout pack;  // fixed at finalize
+  int encode(int N, const float* images, const float* images_hr, void* feats, long feats_bytes, hipStream_t st);
+  int match_encoded(int P, const void* feats, long feats_bytes, int N, const int* idx_a, const int* idx_b, float* warp, float* cert,
+                    hipStream_t st);
 
  private:
+  // the cache a match() schedule reads its projected features from: query image of pair i = idx_a[i], support = idx_b[i] (HOST
+  // arrays, range-checked by match_encoded)
+  struct EncodedIn {
+    const char* feats = nullptr;
+    const int *idx_a = nullptr, *idx_b = nullptr;
+  };
   int ensure_side_streams(int n);
   int match_streams(int B, const float* ima, const float* imb, const float* ima_hr, const float* imb_hr, float* warp,
-                    float* cert, hipStream_t st);
+                    float* cert, hipStream_t st, const EncodedIn* enc = nullptr);
   int check_contract();
   int pack_weights();
   int load_peer();
@@ -165,8 +177,17 @@ class Model {
   struct Pass;   // one pass (coarse / upsample): resolution, images, feature pyramid, current flow / certainty
   struct Scale;  // one decoder scale of a pass: geometry, refiner weights, projected features, refiner buffers
   // fw != nullptr: ONE pass (roma_forward) - per-scale outputs copied out, no epilogue
+  // enc != nullptr: no encoders and no proj heads - every scale's projected features are gathered from the cache
   int match_impl(int B, const float* ima, const float* imb, const float* ima_hr, const float* imb_hr, float* warp,
-                 float* cert, hipStream_t st, bool dry, Arena& arena, Arena& persist, const roma_forward_args_t* fw = nullptr);
+                 float* cert, hipStream_t st, bool dry, Arena& arena, Arena& persist, const roma_forward_args_t* fw = nullptr,
+                 const EncodedIn* enc = nullptr);
+  // encoders + proj heads of n images (both passes with `with_up`), scattered into the packs starting at `feats`
+  int encode_impl(int n, const float* im, const float* im_hr, char* feats, hipStream_t st, bool dry, bool with_up, Arena& arena,
+                  Arena& persist);
+  void token_grid(Call& c);
+  int decoder_scratch(Call& c);
+  int gather_head(const Call& c, const Pass& p, Scale& s, const EncodedIn& enc);
+  int scatter_head(const Call& c, const Pass& p, const Scale& s, char* feats);
   int fits(const Call& c);
   int observe(const Call& c, const std::string& trace_name, const std::string& dbg_name, const void* p, size_t bytes,
               long rows = 0, int ld = 0, int c0 = 0, int c1 = 0);

@@ -122,10 +122,20 @@ int Model::finalize() {
   cfg.symmetric = 1;
   cfg.upsample_preds = cfg.upsample_h > 0 ? 1 : 0;
   int rc = match_impl(cfg.max_batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, arena, persist);
+  // cached features (encoded.h): the layout of a pack, and the two schedules that use it - roma_match_encoded of max_batch
+  // pairs and roma_encode of a chunk of 2 * max_batch images - walk the same arenas; the peaks keep the maximum
+  int cf[5];
+  for (int i = 0; i < 5; ++i) cf[i] = ref[i].Cf;
+  pack = pack_layout(cfg.coarse_h, cfg.coarse_w, cfg.upsample_h, cfg.upsample_w, cf, act_dt == DT_F32 ? 4 : 2);
+  const EncodedIn plan_enc;
+  if (!rc) rc = match_impl(cfg.max_batch, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, arena, persist, nullptr, &plan_enc);
+  if (!rc) rc = encode_impl(2 * cfg.max_batch, nullptr, nullptr, nullptr, nullptr, true, cfg.upsample_h > 0, arena, persist);
   // side streams (model.h): every side sub-batch is at most floor(max_batch / 2) pairs; only the sizes are planned here
   Arena plan, plan_p;
   if (!rc && cfg.max_batch >= 2)
     rc = match_impl(cfg.max_batch / 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, plan, plan_p);
+  if (!rc && cfg.max_batch >= 2)
+    rc = match_impl(cfg.max_batch / 2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, plan, plan_p, nullptr, &plan_enc);
   cfg.symmetric = keep_sym;
   cfg.upsample_preds = keep_up;
   if (rc) return rc;
@@ -214,12 +224,50 @@ int Model::forward(int B, const float* ima, const float* imb, const roma_forward
   return match_impl(B, ima, imb, nullptr, nullptr, nullptr, nullptr, st, false, arena, persist, fw);
 }
 
+// Encoders and proj heads once per image.  Chunks of 2 * max_batch images: the image count the workspace was planned for.
+int Model::encode(int N, const float* images, const float* images_hr, void* feats, long feats_bytes, hipStream_t st) {
+  ROMA_REQUIRE(finalized, "roma_encode: call roma_finalize first");
+  ROMA_REQUIRE(N >= 1 && images && feats, "roma_encode: N < 1 or null image / feature pointer");
+  ROMA_REQUIRE(!images_hr || cfg.upsample_h > 0, "roma_encode: high-resolution images on a handle without an upsample resolution");
+  ROMA_REQUIRE(feats_bytes == (long)N * pack.total, "roma_encode: feats_bytes must be N * roma_encoded_bytes() = " +
+                                                        std::to_string((long)N * pack.total) + " (got " + std::to_string(feats_bytes) + ")");
+  ROMA_REQUIRE((reinterpret_cast<uintptr_t>(feats) & 15) == 0, "roma_encode: the feature buffer must be 16-byte aligned");
+  ROMA_CHECK_HIP(hipSetDevice(cfg.device));
+  const size_t im_lo = (size_t)3 * cfg.coarse_h * cfg.coarse_w, im_hi = (size_t)3 * cfg.upsample_h * cfg.upsample_w;
+  const int chunk = 2 * cfg.max_batch;
+  for (int i0 = 0; i0 < N; i0 += chunk)
+    if (int rc = encode_impl(std::min(chunk, N - i0), images + i0 * im_lo, images_hr ? images_hr + i0 * im_hi : nullptr,
+                             static_cast<char*>(feats) + (long)i0 * pack.total, st, false, images_hr != nullptr, arena, persist))
+      return rc;
+  return 0;
+}
+
+// match() on pairs of cached images: every index is checked here, on the host, before anything is enqueued
+int Model::match_encoded(int P, const void* feats, long feats_bytes, int N, const int* idx_a, const int* idx_b, float* warp, float* cert,
+                         hipStream_t st) {
+  ROMA_REQUIRE(finalized, "roma_match_encoded: call roma_finalize first");
+  ROMA_REQUIRE(P >= 1 && P <= cfg.max_batch, "roma_match_encoded: number of pairs out of range (max_batch)");
+  ROMA_REQUIRE(feats && idx_a && idx_b && warp && cert && N >= 1, "roma_match_encoded: null pointer or N < 1");
+  ROMA_REQUIRE(feats_bytes == (long)N * pack.total, "roma_match_encoded: feats_bytes must be N * roma_encoded_bytes() = " +
+                                                        std::to_string((long)N * pack.total) + " (got " + std::to_string(feats_bytes) + ")");
+  ROMA_REQUIRE((reinterpret_cast<uintptr_t>(feats) & 15) == 0, "roma_match_encoded: the feature buffer must be 16-byte aligned");
+  for (int i = 0; i < P; ++i)
+    ROMA_REQUIRE(idx_a[i] >= 0 && idx_a[i] < N && idx_b[i] >= 0 && idx_b[i] < N,
+                 "roma_match_encoded: pair " + std::to_string(i) + " = (" + std::to_string(idx_a[i]) + ", " + std::to_string(idx_b[i]) +
+                     ") names an image outside [0, " + std::to_string(N) + ")");
+  if (cfg.upsample_preds)
+    ROMA_REQUIRE(cfg.upsample_h > 0, "roma_match_encoded: upsample_preds set but the handle has no upsample resolution");
+  ROMA_CHECK_HIP(hipSetDevice(cfg.device));
+  const EncodedIn enc{static_cast<const char*>(feats), idx_a, idx_b};
+  return match_streams(P, nullptr, nullptr, nullptr, nullptr, warp, cert, st, &enc);
+}
+
 int Model::match_streams(int B, const float* ima, const float* imb, const float* ima_hr, const float* imb_hr, float* warp,
-                         float* cert, hipStream_t st) {
+                         float* cert, hipStream_t st, const EncodedIn* enc) {
   const int env_streams = tuning(SW_STREAMS);
   const bool serial_env = tuning(SW_STREAMS_SERIAL) != 0;
   const int ns = (debug && dbg_dual_slot() < 0) ? 1 : std::min(std::min(env_streams > 0 ? env_streams : n_streams, (int)MAX_STREAMS), B);
-  if (ns <= 1) return match_impl(B, ima, imb, ima_hr, imb_hr, warp, cert, st, false, arena, persist);
+  if (ns <= 1) return match_impl(B, ima, imb, ima_hr, imb_hr, warp, cert, st, false, arena, persist, nullptr, enc);
   if (int rc = ensure_side_streams(ns)) return rc;
   // fork: the side streams start after everything already queued on the caller's stream (inputs); join at the end
   const size_t im_lo = (size_t)3 * cfg.coarse_h * cfg.coarse_w, im_hi = (size_t)3 * cfg.upsample_h * cfg.upsample_w;
@@ -236,10 +284,12 @@ int Model::match_streams(int B, const float* ima, const float* imb, const float*
       ROMA_CHECK_HIP(hipEventRecord(ev_join[i - 1], sp));
       ROMA_CHECK_HIP(hipStreamWaitEvent(si, ev_join[i - 1], 0));
     }
+    EncodedIn sub;  // cached features: this sub-batch's slice of the pair list
+    if (enc) sub = EncodedIn{enc->feats, enc->idx_a + b0, enc->idx_b + b0};
     if (!rc)
-      rc = match_impl(bi, ima + b0 * im_lo, imb + b0 * im_lo, ima_hr ? ima_hr + b0 * im_hi : nullptr,
+      rc = match_impl(bi, ima ? ima + b0 * im_lo : nullptr, imb ? imb + b0 * im_lo : nullptr, ima_hr ? ima_hr + b0 * im_hi : nullptr,
                       imb_hr ? imb_hr + b0 * im_hi : nullptr, warp + b0 * px * 4, cert + b0 * px, si, false,
-                      i == 0 ? arena : side_arena[i - 1], i == 0 ? persist : side_persist[i - 1]);
+                      i == 0 ? arena : side_arena[i - 1], i == 0 ? persist : side_persist[i - 1], nullptr, enc ? &sub : nullptr);
     b0 += bi;
   }
   // always join, also on error: the caller's stream must not run ahead of work already queued on a side stream
@@ -334,7 +384,7 @@ int Model::observe(const Call& c, const std::string& trace_name, const std::stri
 // encoder: VGG19-BN pyramid (encoders.py:17-27) -> feat[0..3], and the projected maps of strides 1 / 2 where they are fused
 int Model::encode_vgg(const Call& c, Pass& p) {
   const bool dry = c.dry; hipStream_t st = c.st;
-  const int H = p.H, W = p.W, nimg = c.nimg, B = c.B;
+  const int H = p.H, W = p.W, nimg = c.nimg, B = c.B;  // B images at imA and B at imB; roma_encode: imB == nullptr, B == nimg
   const size_t esz = c.esz;
   const int fh[4] = {H, H / 2, H / 4, H / 8}, fw_[4] = {W, W / 2, W / 4, W / 8};
   const int fc[4] = {64, 128, 256, 512};
@@ -360,10 +410,10 @@ int Model::encode_vgg(const Call& c, Pass& p) {
   if (act_dt == DT_BF16 && (tuning(SW_CONV64) & 4) && (long)3 * H * W < (1l << 23)) {  // (its packed tap offsets)
     // first layer (Cin = 3), bf16: fused kernel straight from the f32 image (conv64.hip)
     RUN(conv3x3_c3_bf16_launch(p.imA, vgg[0].w, vgg[0].b, t0, B, H, W, st));
-    RUN(conv3x3_c3_bf16_launch(p.imB, vgg[0].w, vgg[0].b, c.at(t0, (long)B * H * W * 64), B, H, W, st));
+    if (p.imB) RUN(conv3x3_c3_bf16_launch(p.imB, vgg[0].w, vgg[0].b, c.at(t0, (long)B * H * W * 64), B, H, W, st));
   } else {  // im2col to K = 32, then the same MFMA GEMM as every other layer
     RUN(im2col3x3_c3_launch(p.imA, col1, B, H, W, act_dt, st));
-    RUN(im2col3x3_c3_launch(p.imB, c.at(col1, (long)B * H * W * 32), B, H, W, act_dt, st));
+    if (p.imB) RUN(im2col3x3_c3_launch(p.imB, c.at(col1, (long)B * H * W * 32), B, H, W, act_dt, st));
     GemmArgs g;
     g.A = col1; g.lda = 32; g.W = vgg[0].w; g.ldw = vgg[0].ldw; g.C = t0; g.ldc = 64;
     g.M = nimg * H * W; g.N = 64; g.K = 32; g.k_alg = 27; g.in_dt = act_dt; g.out_dt = act_dt; g.bias = vgg[0].b; g.act = ACT_RELU;
@@ -684,11 +734,101 @@ int Model::epilogue(const Call& c, const float* flow, const float* cert, const f
   return observe(c, "final_cert", "", cert_out, px * 4);
 }
 
+// ---------------------------------------------------------------- cached per-image features (encoded.h)
+// coarse token grid and the persistent attention buffers: the first allocations of every schedule
+void Model::token_grid(Call& c) {
+  c.th = cfg.coarse_h / 14; c.tw = cfg.coarse_w / 14; c.T = c.th * c.tw;
+  c.Npd = (int)round_up(c.T + 1, 128); c.Npt = (int)round_up(c.T, 128);
+  const size_t qkv_elems = std::max((size_t)c.nimg * 16 * c.Npd * 64, (size_t)c.ndp * 8 * c.Npt * 128);
+  c.qbuf = c.persist.alloc(qkv_elems * c.esz);
+  c.kbuf = c.persist.alloc(qkv_elems * c.esz);
+  c.vtbuf = c.persist.alloc(qkv_elems * c.esz);
+}
+
+// the transformer scratch of the coordinate decoder, where encode_dino would have allocated it
+int Model::decoder_scratch(Call& c) {
+  const long rows_t = (long)c.ndp * c.T;
+  c.ln = c.alloc((size_t)rows_t * 1024, c.esz);
+  c.ao = c.alloc((size_t)rows_t * 1024, c.esz);
+  c.hid = c.alloc((size_t)rows_t * 4096, c.esz);
+  return fits(c);
+}
+
+// In place of proj_head: s.pf [nimg, hw, ldf] = the maps of the B query images, then of the B support images, copied out of
+// their packs (the kernels behind read images i and i + shift of ONE buffer; teaching them an index table instead of copying
+// is a possible follow-up).  The indices were range-checked by match_encoded.
+int Model::gather_head(const Call& c, const Pass& p, Scale& s, const EncodedIn& enc) {
+  const bool dry = c.dry;
+  s.pf = c.arena.alloc(s.pf_bytes);
+  if (int rc = fits(c)) return rc;
+  const long seg = pack.off[p.up ? 1 : 0][s.si], slab = pack.bytes[p.up ? 1 : 0][s.si];
+  ROMA_REQUIRE(seg >= 0 && (size_t)slab * c.nimg == s.pf_bytes, "roma_match_encoded: the pack layout does not hold this scale");
+  for (int i0 = 0; i0 < c.nimg && !dry; i0 += SLAB_MAX) {
+    SlabTable t;
+    t.n = std::min((int)SLAB_MAX, c.nimg - i0);
+    for (int k = 0; k < t.n; ++k) {
+      const int i = i0 + k;
+      t.src_idx[k] = i < c.B ? enc.idx_a[i] : enc.idx_b[i - c.B];
+      t.dst_idx[k] = i;
+    }
+    RUN(slab_copy_launch(enc.feats + seg, pack.total, s.pf, slab, slab, t, c.st));
+  }
+  return observe(c, s.tp + "_proj", s.ins == 16 ? "proj16" : "", s.pf, s.pf_bytes);
+}
+
+// roma_encode: the projected maps of this chunk's images go to their packs
+int Model::scatter_head(const Call& c, const Pass& p, const Scale& s, char* feats) {
+  const bool dry = c.dry;
+  const long seg = pack.off[p.up ? 1 : 0][s.si], slab = pack.bytes[p.up ? 1 : 0][s.si];
+  ROMA_REQUIRE(seg >= 0 && (size_t)slab * c.nimg == s.pf_bytes, "roma_encode: the pack layout does not hold this scale");
+  for (int i0 = 0; i0 < c.nimg && !dry; i0 += SLAB_MAX) {
+    SlabTable t;
+    t.n = std::min((int)SLAB_MAX, c.nimg - i0);
+    for (int k = 0; k < t.n; ++k) t.src_idx[k] = t.dst_idx[k] = i0 + k;
+    RUN(slab_copy_launch(s.pf, slab, feats + seg, pack.total, slab, t, c.st));
+  }
+  return 0;
+}
+
+// n images through the encoders and the proj heads of one pass (coarse) or both; no decoder.  The images are one array: the
+// encoders run with imB == nullptr (B = nimg = n)
+int Model::encode_impl(int n, const float* im, const float* im_hr, char* feats, hipStream_t st, bool dry, bool with_up, Arena& arena,
+                       Arena& persist) {
+  Call c(arena, persist);
+  c.B = n; c.nimg = n; c.shift = 0; c.sym = false; c.ndp = 0;
+  c.esz = act_dt == DT_F32 ? 4 : 2;
+  c.st = st; c.dry = dry;
+  arena.reset();
+  persist.reset();
+  dbg_cur_slot = 0;
+  token_grid(c);
+  if (int rc = fits(c)) return rc;
+  for (int pass = 0; pass < (with_up ? 2 : 1); ++pass) {
+    Pass p;
+    p.up = pass == 1;
+    p.H = p.up ? cfg.upsample_h : cfg.coarse_h; p.W = p.up ? cfg.upsample_w : cfg.coarse_w;
+    p.imA = p.up ? im_hr : im;
+    const size_t pass_mark = arena.mark();
+    if (int rc = encode_vgg(c, p)) return rc;
+    if (!p.up)
+      if (int rc = encode_dino(c, p)) return rc;
+    for (int si = p.up ? 1 : 0; si < 5; ++si) {
+      Scale s(c, p, si, ref[si]);
+      const size_t scale_mark = arena.mark();
+      if (int rc = proj_head(c, p, s)) return rc;
+      if (int rc = scatter_head(c, p, s, feats)) return rc;
+      arena.release(scale_mark);
+    }
+    arena.release(pass_mark);
+  }
+  return 0;
+}
+
 // ---------------------------------------------------------------- the driver: passes x scales.  The order of the arena's
 // alloc / mark / release calls defines the workspace that roma_finalize plans with a dry run of this same code.
 int Model::match_impl(int B, const float* ima, const float* imb, const float* ima_hr, const float* imb_hr,
                       float* warp_out, float* cert_out, hipStream_t st, bool dry, Arena& arena, Arena& persist,
-                      const roma_forward_args_t* fw) {
+                      const roma_forward_args_t* fw, const EncodedIn* enc) {
   Call c(arena, persist);
   c.B = B; c.nimg = 2 * B; c.shift = B;
   c.sym = fw ? fw->symmetric != 0 : cfg.symmetric != 0;
@@ -709,12 +849,7 @@ int Model::match_impl(int B, const float* ima, const float* imb, const float* im
     ROMA_CHECK_HIP(hipMemsetAsync(trace_dev[c.tslot], 0, TRACE_MAX * sizeof(unsigned long long), st));
     trace_n[c.tslot] = 0;
   }
-  c.th = cfg.coarse_h / 14; c.tw = cfg.coarse_w / 14; c.T = c.th * c.tw;
-  c.Npd = (int)round_up(c.T + 1, 128); c.Npt = (int)round_up(c.T, 128);
-  const size_t qkv_elems = std::max((size_t)c.nimg * 16 * c.Npd * 64, (size_t)c.ndp * 8 * c.Npt * 128);
-  c.qbuf = persist.alloc(qkv_elems * c.esz);
-  c.kbuf = persist.alloc(qkv_elems * c.esz);
-  c.vtbuf = persist.alloc(qkv_elems * c.esz);
+  token_grid(c);
 
   // ---- results that live across the two passes
   float* cert16_keep = (float*)c.alloc((size_t)c.ndp * c.T, 4);
@@ -746,16 +881,21 @@ int Model::match_impl(int B, const float* ima, const float* imb, const float* im
     p.flow = pp_flow[pass][0]; p.cert = pp_cert[pass][0]; p.flow_alt = pp_flow[pass][1]; p.cert_alt = pp_cert[pass][1];
 
     const size_t pass_mark = arena.mark();
-    if (int rc = encode_vgg(c, p)) return rc;
-    if (!p.up)
-      if (int rc = encode_dino(c, p)) return rc;
+    if (enc) {  // cached features: no encoders; the coarse pass still needs the decoder's transformer scratch
+      if (!p.up)
+        if (int rc = decoder_scratch(c)) return rc;
+    } else {
+      if (int rc = encode_vgg(c, p)) return rc;
+      if (!p.up)
+        if (int rc = encode_dino(c, p)) return rc;
+    }
     if (p.up)
       if (int rc = seed_upsample_pass(c, p, flow_p1, cert_p1)) return rc;
     // decoder (matcher.py:395-527)
     for (int si = p.up ? 1 : 0; si < 5; ++si) {
       Scale s(c, p, si, ref[si]);
       const size_t scale_mark = arena.mark();
-      if (int rc = proj_head(c, p, s)) return rc;
+      if (int rc = enc ? gather_head(c, p, s, *enc) : proj_head(c, p, s)) return rc;
       if (s.ins == 16) {
         const size_t coarse_mark = arena.mark();  // behind s.pf, which the refiner below still reads
         if (int rc = coarse_match(c, p, s)) return rc;

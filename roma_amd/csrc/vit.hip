@@ -77,15 +77,15 @@ int vit_block_run(const roma_vit_block_t& w, void* x, int x_dt, long rows, int B
 // dinov2.py:192-237 (prepare_tokens_with_masks + blocks + norm) and encoders.py:64-65 (x_norm_patchtokens)
 int vit_forward(const roma_vit_args_t& a, hipStream_t st) {
   ROMA_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.H % 14 == 0 && a.W % 14 == 0, "vit_forward: bad image size");
-  ROMA_REQUIRE(a.blocks && a.nblocks > 0 && a.im_a && a.im_b && a.feat_out, "vit_forward: null argument");
+  ROMA_REQUIRE(a.blocks && a.nblocks > 0 && a.im_a && a.feat_out, "vit_forward: null argument");
   const int act_dt = a.act == ROMA_F32 ? DT_F32 : DT_BF16;
   const size_t esz = act_dt == DT_F32 ? 4 : 2;
-  const int nimg = 2 * a.B, th = a.H / 14, tw = a.W / 14, T = th * tw;
+  const int nimg = a.im_b ? 2 * a.B : a.B, th = a.H / 14, tw = a.W / 14, T = th * tw;  // im_b == NULL: B images, all at im_a
   const int Nd = T + 1, Npd = (int)round_up(Nd, 128);
   const long rows_d = (long)nimg * Nd;
   auto off = [&](void* p, long elems) -> void* { return static_cast<char*>(p) + elems * (long)esz; };
   VRUN(im2col_patch14_launch(a.im_a, a.col, a.B, a.H, a.W, a.patch_ldw, act_dt, st));
-  VRUN(im2col_patch14_launch(a.im_b, off(a.col, (long)a.B * T * a.patch_ldw), a.B, a.H, a.W, a.patch_ldw, act_dt, st));
+  if (a.im_b) VRUN(im2col_patch14_launch(a.im_b, off(a.col, (long)a.B * T * a.patch_ldw), a.B, a.H, a.W, a.patch_ldw, act_dt, st));
   {
     GemmArgs g;
     g.A = a.col; g.lda = a.patch_ldw; g.W = a.patch_w; g.ldw = a.patch_ldw; g.C = a.pt; g.ldc = 1024;

@@ -245,7 +245,6 @@ class RegressionMatcher:
         im_A = _check_input(im_A_input)
         im_B = _check_input(im_B_input)
         hs, ws = self.h_resized, self.w_resized
-        scale_factor = math.sqrt(hs * ws / (560 ** 2))  # matcher.py:805: from the CONFIGURED resolution
         call_hw = None
         if isinstance(im_A, Image.Image) and isinstance(im_B, Image.Image):
             a = _pil_to_normalised(im_A, (hs, ws))[None].to(device)
@@ -282,9 +281,7 @@ class RegressionMatcher:
                              "use one matcher (one handle) per GPU")
         self._ensure_handle(call_hw)
         lib = self._lib
-        for k in ("symmetric", "upsample_preds", "attenuate_cert", "debug", "vit_bf16_residual", "dual_stream", "trace", "compose_out_conv"):
-            _lib.check(lib.roma_set_option(self._handle, k.encode(), int(bool(getattr(self, k)))), lib=lib)
-        _lib.check(lib.roma_set_option_f(self._handle, b"coarse_scale_factor", float(scale_factor)), lib=lib)
+        self._push_options()
         B = a.shape[0]
         Ho, Wo = self.get_output_resolution() if self.upsample_preds else (a.shape[-2], a.shape[-1])
         Wout = 2 * Wo if self.symmetric else Wo
@@ -319,6 +316,135 @@ class RegressionMatcher:
         if not self.upsample_preds:
             return self.match(out[0][:B], out[0][B:])
         return self.match(out[0][:B], out[0][B:], im_A_high_res=out[1][:B], im_B_high_res=out[1][B:])
+
+    # ------------------------------------------------------------------ image sets: encode each image once, match any pairs
+    def _push_options(self):
+        """The mutable attributes of this matcher -> the current handle (what match() does before every call)."""
+        lib = self._lib
+        for k in ("symmetric", "upsample_preds", "attenuate_cert", "debug", "vit_bf16_residual", "dual_stream", "trace", "compose_out_conv"):
+            _lib.check(lib.roma_set_option(self._handle, k.encode(), int(bool(getattr(self, k)))), lib=lib)
+        scale_factor = math.sqrt(self.h_resized * self.w_resized / (560 ** 2))  # matcher.py:805: from the CONFIGURED resolution
+        _lib.check(lib.roma_set_option_f(self._handle, b"coarse_scale_factor", float(scale_factor)), lib=lib)
+
+    def encoded_bytes(self) -> int:
+        """Bytes of one image's feature pack for the current handle (roma_encoded_bytes; `roma_amd.encoded.pack_layout` restates it)."""
+        self._ensure_handle()
+        n = int(self._lib.roma_encoded_bytes(self._handle))
+        if n < 0:
+            raise _lib.RomaHipError(_lib.last_error(self._lib))
+        return n
+
+    @torch.inference_mode()
+    def encode_images(self, images, images_high_res=None, *, out=None):
+        """Runs the encoders (VGG19-BN pyramid, DINOv2) and the proj heads ONCE per image and keeps what the decoder reads: the
+        projected feature maps of every scale.  images: [N, 3, h, w] normalised device tensor (as match() takes); images_high_res:
+        [N, 3, *upsample_res], needed for `match_pairs` with `upsample_preds`.  Any N >= 1 (chunks of 2 * max_batch inside).  out:
+        optional contiguous uint8 device tensor of N * encoded_bytes() bytes to write into (16-byte aligned).  The raw backbone
+        pyramids are not kept (`extract_backbone_features` is unchanged).  Returns `roma_amd.encoded.EncodedImages`, about 120 MB per
+        image in the 16-bit modes at 560 -> 864."""
+        from .encoded import EncodedImages
+        self.train(False)
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[0] < 1:
+            raise ValueError("encode_images: images must be a tensor [N, 3, h, w] with N >= 1 (match_image_set takes decoded images)")
+        if images.device.type != "cuda":
+            raise _lib.RomaHipError(f"roma_amd.encode_images needs CUDA/HIP tensors (got {images.device}); there is no CPU fallback")
+        if images.device.index is not None and images.device.index != self.device.index:
+            raise ValueError(f"encode_images: inputs live on {images.device} but this matcher was built for {self.device}")
+        _check_input(images)
+        N, _, h, w = images.shape
+        call_hw = None
+        if h != self.h_resized or w != self.w_resized:
+            warn("Model resolution and batch resolution differ, may produce unexpected results")
+            call_hw = (h, w)
+        hr = None
+        if images_high_res is not None:
+            if not self.upsample_preds:
+                raise ValueError("encode_images: images_high_res given but upsample_preds is off (the handle has no upsample pass)")
+            hr = images_high_res
+            if not isinstance(hr, torch.Tensor) or hr.device != images.device or hr.dim() != 4 or hr.shape[0] != N or hr.shape[1] != 3:
+                raise ValueError("encode_images: images_high_res must be a tensor [N, 3, H, W] on the device of images")
+            if tuple(hr.shape[-2:]) != tuple(self.upsample_res):
+                raise RuntimeError(f"images_high_res is {tuple(hr.shape[-2:])} but upsample_res is {tuple(self.upsample_res)}")
+            hr = hr.float().contiguous()
+        self._ensure_handle(call_hw)
+        self._push_options()
+        lib = self._lib
+        pack = int(lib.roma_encoded_bytes(self._handle))
+        if out is None:
+            out = torch.empty(N * pack, device=images.device, dtype=torch.uint8)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device != images.device or not out.is_contiguous()
+              or out.numel() != N * pack or out.data_ptr() % 16):
+            raise ValueError(f"encode_images: out must be a contiguous, 16-byte aligned uint8 tensor of {N * pack} bytes on {images.device}")
+        im = images.float().contiguous()
+        stream = torch.cuda.current_stream(images.device).cuda_stream
+        with torch.cuda.device(images.device):
+            _lib.check(lib.roma_encode(self._handle, N, C.c_void_p(im.data_ptr()), C.c_void_p(hr.data_ptr()) if hr is not None else None,
+                                       C.c_void_p(out.data_ptr()), N * pack, C.c_void_p(stream)), lib=lib)
+        return EncodedImages(feats=out, n=int(N), pack_bytes=pack, key=self._built, has_upsample=hr is not None,
+                             weights_id=(id(self._weights), id(self._dinov2_weights)), weights=(self._weights, self._dinov2_weights))
+
+    @torch.inference_mode()
+    def match_pairs(self, encoded, pairs=None):
+        """match() for pairs of encoded images: `pairs` is a sequence or an int array [P, 2] of indices into `encoded` (default: all
+        i < j in lexicographic order, `roma_amd.encoded.all_pairs`); pair (i, j) has image i as A and image j as B.  Returns what
+        `match(X[pairs[:, 0]], X[pairs[:, 1]])` returns, bit for bit, without running an encoder: (warp [P, H, 2W, 4] | [P, H, W, 4],
+        certainty [P, H, 2W] | [P, H, W]).  Chunks of `max_batch` pairs.  Raises ValueError, before any library call, for an index
+        out of range, for an `EncodedImages` of another configuration (resolution, precision, max_batch, weights, device) and for
+        `upsample_preds` on packs encoded without high-resolution images."""
+        from .encoded import EncodedImages, check_pairs
+        self.train(False)
+        if not isinstance(encoded, EncodedImages):
+            raise ValueError("match_pairs: encoded must be what encode_images returned")
+        pv = check_pairs(pairs, encoded.n)
+        if encoded.weights_id != (id(self._weights), id(self._dinov2_weights)):
+            raise ValueError("match_pairs: these images were encoded with other weights")
+        if encoded.feats.device != self.device:
+            raise ValueError(f"match_pairs: the encoded images live on {encoded.feats.device}, this matcher on {self.device}")
+        if self.upsample_preds and not encoded.has_upsample:
+            raise ValueError("match_pairs: upsample_preds is set but the images were encoded without images_high_res (coarse-only packs)")
+        want = self._config_key((encoded.key[0], encoded.key[1]))
+        same = want == encoded.key or (want[2] == (0, 0) and want[:2] + want[3:] == encoded.key[:2] + encoded.key[3:])
+        # (a handle is never built here: packs of a configuration this matcher holds no handle for are refused)
+        if not same or encoded.key not in self._cache or encoded.feats.numel() != encoded.n * encoded.pack_bytes:
+            raise ValueError(f"match_pairs: the images were encoded for configuration {encoded.key} (coarse h, w, upsample (h, w), "
+                             f"precision, max_batch, device); this matcher now needs {want} - encode them again")
+        if self._built != encoded.key:  # a configuration used before: switch, no rebuild
+            self._cache.move_to_end(encoded.key)
+            self._handle, self._built = self._cache[encoded.key], encoded.key
+        self._push_options()
+        lib, dev = self._lib, encoded.feats.device
+        P = pv.shape[0]
+        Ho, Wo = self.get_output_resolution() if self.upsample_preds else (encoded.key[0], encoded.key[1])
+        Wout = 2 * Wo if self.symmetric else Wo
+        warp = torch.empty((P, Ho, Wout, 4), device=dev, dtype=torch.float32)
+        cert = torch.empty((P, Ho, Wout), device=dev, dtype=torch.float32)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        ip = C.POINTER(C.c_int)
+        with torch.cuda.device(dev):
+            for i0 in range(0, P, self.max_batch):
+                n = min(self.max_batch, P - i0)
+                ia, ib = np.ascontiguousarray(pv[i0:i0 + n, 0]), np.ascontiguousarray(pv[i0:i0 + n, 1])
+                _lib.check(lib.roma_match_encoded(self._handle, n, C.c_void_p(encoded.feats.data_ptr()), encoded.n * encoded.pack_bytes,
+                                                  encoded.n, ia.ctypes.data_as(ip), ib.ctypes.data_as(ip),
+                                                  C.c_void_p(warp[i0:i0 + n].data_ptr()), C.c_void_p(cert[i0:i0 + n].data_ptr()),
+                                                  C.c_void_p(stream)), lib=lib)
+        return warp, cert
+
+    def match_image_set(self, images, pairs=None, *, device=None):
+        """An image set in one go: `images` is a sequence of N decoded images of any sizes (paths, PIL RGB images, uint8 ndarrays or
+        uint8 tensors [H, W, 3], as `match_images` takes).  ONE `preprocess_images` call resizes and normalises all N on the device,
+        `encode_images` encodes each once, `match_pairs` matches `pairs` (default: all i < j).  Returns (warp, certainty, pairs) with
+        pairs as a list of (i, j) tuples - the form `build_tracks(..., pair_views=)` and `reconstruct_views` take."""
+        from .encoded import check_pairs
+        from .preprocess import preprocess_images
+        if not isinstance(images, (list, tuple)) or len(images) < 1:
+            raise ValueError("match_image_set: images must be a non-empty sequence of images")
+        pv = check_pairs(pairs, len(images))
+        sizes = [(self.h_resized, self.w_resized)] + ([tuple(self.upsample_res)] if self.upsample_preds else [])
+        out = preprocess_images(list(images), sizes, normalize=True, device=device if device is not None else self.device)
+        enc = self.encode_images(out[0], out[1] if self.upsample_preds else None)
+        warp, cert = self.match_pairs(enc, pv)
+        return warp, cert, [(int(i), int(j)) for i, j in pv]
 
     # ------------------------------------------------------------------ forward / forward_symmetric / backbone features
     _SCALES = (16, 8, 4, 2, 1)
