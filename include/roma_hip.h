@@ -242,7 +242,9 @@ int roma_op_conv3x3(const void* in, const void* w, const float* bias, void* out,
 int roma_op_conv3x3_slab(const void* in, const void* w, const float* bias, void* out, int B, int H, int W, int Cin, int Cout,
                          int relu, int dt, void* stream);
 /* Multi-head attention from a packed qkv activation [B*N, 3*heads*hd] (f32): out[B*N, heads*hd].
- * Workspace q,k,vt must hold B*heads*Npad*hd elements each, Npad = roundup(N,128), zero-initialised. */
+ * Workspace q,k,vt must hold B*heads*Npad*hd elements each, Npad = roundup(N,128), zero-initialised.
+ * roma_op_qkv_scatter_gemm writes the N tokens of every image only: the rows N .. Npad of q / k and the columns N .. Npad of
+ * V^T keep their zeros (roma_op_attention itself does not read them into a result). */
 int roma_op_attention(const void* q, const void* k, const void* vt, void* out, int B, int heads, int N, int npad, int hd,
                       int dt_in, int dt_out, void* stream);
 int roma_op_qkv_scatter_gemm(const void* A, const void* W, const float* bias, void* q, void* k, void* vt, int B, int N,
@@ -892,7 +894,8 @@ int roma_op_fb_consistency(const float* flow_fwd, const float* flow_bwd, int B, 
 int roma_op_maxpool2x2(const void* in, void* out, int B, int H, int W, int C, int dt, void* stream);
 /* MaxPool2d(2) + the proj head of a VGG pyramid level in one pass over the un-pooled map (encoders.py:17-27,
  * roma_models.py:156-160): in [B,H,W,C] 16-bit, C = 64 (N <= 32) or 128 (N <= 64) -> pooled [B,H/2,W/2,C] and
- * pf [B,H*W,ldf] = in . pw^T + pb (pw [N][ldw] 16-bit, pb f32 [N], columns N .. ldf zero).  Bit-identical to
+ * pf [B,H*W,ldf] = in . pw^T + pb (pw [N][ldw] 16-bit, pb f32 [N], columns N .. ldf zero; ldf any multiple of 8 from N up to
+ * 32 / 64, and nothing is written outside a pixel's ldf columns).  Bit-identical to
  * roma_op_maxpool2x2 + roma_op_gemm; roma_tuning("pool_proj", 0) makes the model use those two instead. */
 int roma_op_pool_proj(const void* in, void* pooled, void* pf, const void* pw, long ldw, const float* pb, int N, int ldf, int B, int H,
                       int W, int C, int dt, void* stream);

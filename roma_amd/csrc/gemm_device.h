@@ -395,6 +395,24 @@ __device__ __forceinline__ void epi_staged_qkv(const f32x16 (&acc)[TN][TM], cons
 #pragma unroll
       for (int i = 0; i < NPC; ++i) pv[i] = *reinterpret_cast<const uint4*>(ws + rdo[i]);
       if (a.dbg & 1) continue;
+      if (qt0 + 32 > a.ntok) {
+        // (wave-uniform) the one block of an image that holds padding tokens: they read the zero page, so their V is the bias.
+        // A piece is 8 tokens wide - tokens 8 tg .. 8 tg + 7 with tg = lane & 3 for every piece of the lane - so the values are
+        // masked, not the store: the columns ntok .. npad of V^T stay zero like the padding rows of q / k
+        const int nv = a.ntok - qt0 - 8 * (lane & 3);  // valid tokens of this lane's pieces
+        uint4 mk;
+        mk.x = (nv > 0 ? 0xffffu : 0u) | (nv > 1 ? 0xffff0000u : 0u);
+        mk.y = (nv > 2 ? 0xffffu : 0u) | (nv > 3 ? 0xffff0000u : 0u);
+        mk.z = (nv > 4 ? 0xffffu : 0u) | (nv > 5 ? 0xffff0000u : 0u);
+        mk.w = (nv > 6 ? 0xffffu : 0u) | (nv > 7 ? 0xffff0000u : 0u);
+#pragma unroll
+        for (int i = 0; i < NPC; ++i) {
+          pv[i].x &= mk.x;
+          pv[i].y &= mk.y;
+          pv[i].z &= mk.z;
+          pv[i].w &= mk.w;
+        }
+      }
 #pragma unroll
       for (int i = 0; i < NPC; ++i) *reinterpret_cast<uint4*>(vt + poff[i]) = pv[i];
     }

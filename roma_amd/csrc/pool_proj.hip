@@ -105,7 +105,8 @@ __global__ __launch_bounds__(256) void pool_proj_kernel(const bf16_t* __restrict
         const auto s0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
         const auto s1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
         const u32x4 st = {s0[0], s1[0], s0[1], s1[1]};
-        if (xok) *reinterpret_cast<u32x4*>(orow + c0 + 8 * h) = st;
+        // ldf % 16 == 8: the last pair has only its h = 0 half inside the row (the swaps above stay wave-wide)
+        if (xok && c0 + 8 * h < ldf) *reinterpret_cast<u32x4*>(orow + c0 + 8 * h) = st;
       }
     }
   }

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN
+from extents_cases import Plain  # today's allocation; tests/test_gpu_extents.py passes the guarded allocator instead
 from test_cpu_tuning import RETIRED  # the switches of the removed refiner-block variants
 
 pytestmark = pytest.mark.gpu
@@ -143,46 +144,52 @@ def test_gemm_bf16_residual_in_place(lib, M, N, K):
     gemm_residual_in_place_case(fmt_of(lib, BF16), M, N, K)
 
 
-def gemm_residual_in_place_case(f, M, N, K):
-    lib = f.lib
+def gemm_residual_in_place_case(f, M, N, K, alloc=None, pad=0):
+    """alloc: where the activation and the in-place output live (extents_cases.Plain: today's allocation); pad: ldc = ldr = N + pad"""
+    lib, al, ld = f.lib, alloc or Plain(), N + pad
     A, W, b = rnd(M, K, seed=1).to(f.tdt), rnd(N, K, seed=2, std=K ** -0.5).to(f.tdt), rnd(N, seed=3)
     s, r = rnd(N, seed=4), (3.0 * rnd(M, N, seed=5)).to(f.tdt)
     branch = (A.double() @ W.double().T + b.double()) * s.double()
     ref = branch + r.double()
-    Ad, Wd, bd, sd = A.cuda(), W.cuda(), b.cuda(), s.cuda()
+    Ad, Wd, bd, sd = al.inp(A), W.cuda(), b.cuda(), s.cuda()
     for _ in range(2):
-        x = r.clone().cuda()
-        ok(lib, lib.roma_op_gemm_res_bf16(P(Ad), K, P(Wd), K, P(x), N, M, N, K, P(bd), P(sd), P(x), N, None))
+        xw = al.out((M, ld), f.tdt)  # the pad columns keep what the allocator left there
+        xw[:, :N] = r.cuda()
+        x = xw[:, :N]
+        ok(lib, lib.roma_op_gemm_res_bf16(P(Ad), K, P(Wd), K, P(xw), ld, M, N, K, P(bd), P(sd), P(xw), ld, None))
         torch.cuda.synchronize()
         err = (x.cpu().double() - ref).abs()
         bound = 2.0 ** -8 / f.div * (ref.abs() + branch.abs()) + 1e-3 / f.div
         assert bool((err <= bound).all()), float((err - bound).max())
+        al.check()
     # misuse is refused, not silently mis-computed: N not a multiple of 8
     x = r.clone().cuda()
     assert lib.roma_op_gemm_res_bf16(P(Ad), K, P(Wd), K, P(x), N, M, N - 4, K, P(bd), P(sd), P(x), N, None) != 0
+    return xw
 
 
 def test_layernorm_bf16_input(lib):
     layernorm_case(fmt_of(lib, BF16), 1603, True)
 
 
-def layernorm_case(f, M, in16):
-    """LayerNorm over D = 1024 to 16-bit output, from 16-bit input (roma_op_layernorm_dt) or from f32 (roma_op_layernorm)"""
-    lib = f.lib
-    x, w, b = rnd(M, 1024, seed=1, std=3.0) + 0.5, rnd(1024, seed=2), rnd(1024, seed=3)
-    out = torch.empty((M, 1024), device="cuda", dtype=f.tdt)
+def layernorm_case(f, M, in16, alloc=None, D=1024):
+    """LayerNorm over D (1024 in the model) to 16-bit output, from 16-bit input (roma_op_layernorm_dt) or from f32 (roma_op_layernorm)"""
+    lib, al = f.lib, alloc or Plain()
+    x, w, b = rnd(M, D, seed=1, std=3.0) + 0.5, rnd(D, seed=2), rnd(D, seed=3)
+    out = al.out((M, D), f.tdt)
     if in16:
         x = x.to(f.tdt)
-        ok(lib, lib.roma_op_layernorm_dt(P(x.cuda()), f.dt, P(w.cuda()), P(b.cuda()), P(out), M, 1024, 1e-6, f.dt, None))
+        ok(lib, lib.roma_op_layernorm_dt(P(al.inp(x)), f.dt, P(w.cuda()), P(b.cuda()), P(out), M, D, 1e-6, f.dt, None))
     else:
-        ok(lib, lib.roma_op_layernorm(P(x.cuda()), P(w.cuda()), P(b.cuda()), P(out), M, 1024, 1e-6, f.dt, None))
+        ok(lib, lib.roma_op_layernorm(P(al.inp(x)), P(w.cuda()), P(b.cuda()), P(out), M, D, 1e-6, f.dt, None))
     torch.cuda.synchronize()
-    ref = F.layer_norm(x.double(), (1024,), w.double(), b.double(), 1e-6)
+    ref = F.layer_norm(x.double(), (D,), w.double(), b.double(), 1e-6)
     assert torch.allclose(out.cpu().double(), ref, atol=1e-3 / f.div, rtol=2.0 ** -8 / f.div), float((out.cpu().double() - ref).abs().max())
+    al.check()
     if in16:
         # 16-bit input with f32 output is not a supported combination: refused
-        o32 = torch.empty((M, 1024), device="cuda")
-        assert lib.roma_op_layernorm_dt(P(x.cuda()), f.dt, P(w.cuda()), P(b.cuda()), P(o32), M, 1024, 1e-6, F32, None) != 0
+        o32 = torch.empty((M, D), device="cuda")
+        assert lib.roma_op_layernorm_dt(P(x.cuda()), f.dt, P(w.cuda()), P(b.cuda()), P(o32), M, D, 1e-6, F32, None) != 0
 
 
 def test_qkv_scatter_big_m_bf16(lib):
@@ -439,17 +446,17 @@ def test_conv3x3_weight_stationary(lib, B, H, W, Cin, Cout):
     assert float((d / (outs[0].float().abs() + 1.0)).max()) <= 2.0 ** -7, float(d.max())
 
 
-def _attention_case(f, B, heads, hd, N):
+def _attention_case(f, B, heads, hd, N, alloc=None):
     """roma_op_qkv_scatter_gemm + roma_op_attention in format f against f64 on the same rounded x and w"""
-    lib, dt, tdt = f.lib, f.dt, f.tdt
+    lib, dt, tdt, al = f.lib, f.dt, f.tdt, alloc or Plain()
     D = heads * hd
     x, w, b = rnd(B * N, D, seed=1).to(tdt), rnd(3 * D, D, seed=2, std=1.5 / math.sqrt(D)).to(tdt), rnd(3 * D, seed=3, std=0.1)
     npad = (N + 127) // 128 * 128
-    q = torch.zeros((B, heads, npad, hd), device="cuda", dtype=tdt)
-    k = torch.zeros_like(q)
-    vt = torch.zeros((B, heads, hd, npad), device="cuda", dtype=tdt)
-    ok(lib, lib.roma_op_qkv_scatter_gemm(P(x.cuda()), P(w.cuda()), P(b.cuda()), P(q), P(k), P(vt), B, N, npad, heads, hd, D, dt, dt, None))
-    out = torch.empty((B * N, D), device="cuda", dtype=tdt)
+    q = al.out((B, heads, npad, hd), tdt, fill=0)
+    k = al.out((B, heads, npad, hd), tdt, fill=0)
+    vt = al.out((B, heads, hd, npad), tdt, fill=0)
+    ok(lib, lib.roma_op_qkv_scatter_gemm(P(al.inp(x)), P(w.cuda()), P(b.cuda()), P(q), P(k), P(vt), B, N, npad, heads, hd, D, dt, dt, None))
+    out = al.out((B * N, D), tdt)
     ok(lib, lib.roma_op_attention(P(q), P(k), P(vt), P(out), B, heads, N, npad, hd, dt, dt, None))
     torch.cuda.synchronize()
     qkv = (x.double() @ w.double().T + b.double()).reshape(B, N, 3, heads, hd)
@@ -461,6 +468,8 @@ def _attention_case(f, B, heads, hd, N):
     tol = 2e-5 if dt == F32 else 6e-2 / f.div  # bf16: P and V are quantised to bf16 before the second MFMA
     err = (out.cpu().double() - ref).abs().max().item()
     assert err < tol, err
+    al.check()
+    return q, k, vt, out
 
 
 @pytest.mark.parametrize("B,heads,hd,N", [(2, 16, 64, 65), (1, 16, 64, 257), (2, 8, 128, 64), (1, 8, 128, 200)])
@@ -824,8 +833,8 @@ def test_refiner_input_grid_sample_warp(lib, dt, C, E, K, ldf, ldd, h, w):
     refiner_input_case(fmt_of(lib, dt), C, E, K, ldf, ldd, h, w)
 
 
-def refiner_input_case(f, C, E, K, ldf, ldd, h, w):
-    lib, dt, tdt = f.lib, f.dt, f.tdt
+def refiner_input_case(f, C, E, K, ldf, ldd, h, w, alloc=None):
+    lib, dt, tdt, al = f.lib, f.dt, f.tdt, alloc or Plain()
     B, nimg, shift = 2, 4, 2
     feat = torch.zeros(nimg, h * w, ldf)
     feat[:, :, :C] = rnd(nimg, h * w, C, seed=1)
@@ -839,8 +848,8 @@ def refiner_input_case(f, C, E, K, ldf, ldd, h, w):
     flow[1, 1, 2] = torch.tensor([1.0, 1.0])                           # on the border: partly outside
     emb_w, emb_b = rnd(E, 2, seed=3, std=0.7), rnd(E, seed=4, std=0.1)
     disp_scale = 1.25 * 1.5428
-    d = torch.full((B, h * w, ldd), 7.0).to(tdt).cuda()                # sentinel: the correlation slice must survive
-    ok(lib, lib.roma_op_refiner_input(P(feat.cuda()), ldf, P(flow.cuda()), P(d), ldd, P(emb_w.cuda()), P(emb_b.cuda()), B, h, w, C,
+    d = al.out((B, h * w, ldd), tdt, fill=7.0)                         # sentinel: the correlation slice must survive
+    ok(lib, lib.roma_op_refiner_input(P(al.inp(feat)), ldf, P(al.inp(flow)), P(d), ldd, P(emb_w.cuda()), P(emb_b.cuda()), B, h, w, C,
                                       E, K, nimg, shift, disp_scale, dt, None))
     torch.cuda.synchronize()
     got = d.cpu().double()
@@ -855,6 +864,8 @@ def refiner_input_case(f, C, E, K, ldf, ldd, h, w):
     assert torch.allclose(got[:, :, 2 * C:2 * C + E], emb, atol=tol, rtol=tol)
     assert bool((got[:, :, 2 * C + E:2 * C + E + K] == 7.0).all())
     assert bool((got[:, :, 2 * C + E + K:] == 0.0).all())
+    al.check()
+    return d
 
 
 GP_SHAPES = [(2, 8, 8), (1, 12, 10), (2, 12, 16)]
@@ -872,20 +883,21 @@ def test_gp_posterior_vs_oracle(lib, b, h, w, dt):
     gp_case(fmt_of(lib, dt), b, h, w)
 
 
-def gp_case(f, b, h, w):
+def gp_case(f, b, h, w, alloc=None):
     from oracle import roma_oracle
-    lib = f.lib
+    lib, al = f.lib, alloc or Plain()
     x, y = rnd(b, 512, h, w, seed=1).to(f.tdt), rnd(b, 512, h, w, seed=2).to(f.tdt)
     sd = {"decoder.gps.16.pos_conv.weight": rnd(512, 2, 1, 1, seed=3, std=0.5), "decoder.gps.16.pos_conv.bias": rnd(512, seed=4, std=0.5)}
     ref = roma_oracle.gp_posterior(x.float(), y.float(), sd)                   # [b, 512, h, w]
-    xt = x.permute(0, 2, 3, 1).reshape(b, h * w, 512).contiguous().cuda()
-    yt = y.permute(0, 2, 3, 1).reshape(b, h * w, 512).contiguous().cuda()
-    mu = torch.empty(b, h * w, 512, device="cuda")
+    xt = al.inp(x.permute(0, 2, 3, 1).reshape(b, h * w, 512).contiguous())
+    yt = al.inp(y.permute(0, 2, 3, 1).reshape(b, h * w, 512).contiguous())
+    mu = al.out((b, h * w, 512), torch.float32)
     ok(lib, lib.roma_op_gp(P(xt), P(yt), P(sd["decoder.gps.16.pos_conv.weight"].reshape(512, 2).contiguous().cuda()),
                            P(sd["decoder.gps.16.pos_conv.bias"].cuda()), P(mu), b, h, w, f.dt, None))
     torch.cuda.synchronize()
     got = mu.cpu().reshape(b, h, w, 512).permute(0, 3, 1, 2)
     assert torch.allclose(got, ref, atol=2e-4, rtol=1e-4), float((got - ref).abs().max())
+    al.check()
 
 
 @pytest.mark.parametrize("hin,hout,nc", [(40, 70, 2), (70, 140, 1), (560, 108, 2), (8, 14, 1)])
@@ -1056,9 +1068,9 @@ def test_refiner_out_conv_update(lib, dt, Cp, M):
     refiner_out_case(fmt_of(lib, dt), Cp, M)
 
 
-def refiner_out_case(f, Cp, M):
+def refiner_out_case(f, Cp, M, alloc=None):
     """the bounds are f32-level (16-bit d times f32 weights, f32 sums): the same for every storage format"""
-    lib, dt = f.lib, f.dt
+    lib, dt, al = f.lib, f.dt, alloc or Plain()
     d = rnd(M, Cp, seed=1).to(f.tdt)
     w, b = rnd(3, Cp, seed=2, std=Cp ** -0.5), rnd(3, seed=3)
     flow0, cert0 = rnd(M, 2, seed=4), rnd(M, seed=5)
@@ -1066,12 +1078,13 @@ def refiner_out_case(f, Cp, M):
     o = d.double() @ w.double().T + b.double()
     ref_flow = flow0.double() + o[:, :2] * torch.tensor([sx, sy], dtype=torch.float64)
     ref_cert = cert0.double() + o[:, 2]
-    flow, cert = flow0.cuda(), cert0.cuda()
-    ok(lib, lib.roma_op_refiner_out(P(d.cuda()), Cp, dt, P(w.cuda()), P(b.cuda()), P(flow), P(cert), M, Cp, C.c_float(sx), C.c_float(sy), None))
+    flow, cert = al.inout(flow0), al.inout(cert0)
+    ok(lib, lib.roma_op_refiner_out(P(al.inp(d)), Cp, dt, P(w.cuda()), P(b.cuda()), P(flow), P(cert), M, Cp, C.c_float(sx), C.c_float(sy), None))
     torch.cuda.synchronize()
     tol = 2e-5 * max(1.0, (Cp / 24) ** 0.5)
     assert torch.allclose(flow.cpu().double(), ref_flow, atol=tol, rtol=1e-5)
     assert torch.allclose(cert.cpu().double(), ref_cert, atol=4 * tol, rtol=1e-5)
+    al.check()
 
 
 def test_maxpool_and_first_conv(lib):
@@ -1099,14 +1112,14 @@ def test_pool_proj_fused_is_maxpool_plus_proj_gemm(lib, C, N, ldf, B, H, W):
     pool_proj_case(fmt_of(lib, BF16), C, N, ldf, B, H, W)
 
 
-def pool_proj_case(f, C, N, ldf, B, H, W):
-    lib, dt = f.lib, f.dt
+def pool_proj_case(f, C, N, ldf, B, H, W, alloc=None):
+    lib, dt, al = f.lib, f.dt, alloc or Plain()
     x = F.relu(rnd(B, H, W, C, seed=1)).to(f.tdt)                              # a post-ReLU map: never negative
     pw = rnd(N, C, seed=2, std=C ** -0.5).to(f.tdt)
     pb = rnd(N, seed=3)
-    xd, pwd, pbd = x.cuda(), pw.cuda(), pb.cuda()
-    pooled = torch.full((B, H // 2, W // 2, C), float("nan"), device="cuda", dtype=f.tdt)
-    pf = torch.full((B, H * W, ldf), float("nan"), device="cuda", dtype=f.tdt)
+    xd, pwd, pbd = al.inp(x), pw.cuda(), pb.cuda()
+    pooled = al.out((B, H // 2, W // 2, C), f.tdt, fill=float("nan"))
+    pf = al.out((B, H * W, ldf), f.tdt, fill=float("nan"))
     ok(lib, lib.roma_op_pool_proj(P(xd), P(pooled), P(pf), P(pwd), C, P(pbd), N, ldf, B, H, W, C, dt, None))
     pooled2 = torch.empty_like(pooled)
     pf2 = torch.zeros_like(pf)
@@ -1120,6 +1133,8 @@ def pool_proj_case(f, C, N, ldf, B, H, W):
     assert torch.equal(pooled.cpu().float(), refp)
     ref = x.double().reshape(B, H * W, C) @ pw.double().T + pb.double()
     assert torch.allclose(pf[:, :, :N].cpu().double(), ref, atol=2e-2 / f.div, rtol=1e-2 / f.div)
+    al.check()
+    return pf, pooled
 
 
 @pytest.mark.parametrize("B,H,W", [(2, 16, 24), (1, 9, 33), (3, 37, 70), (1, 560, 560), (2, 100, 864)])
@@ -1424,9 +1439,9 @@ def block_final_weights(tdt, Cp):
     return wc, bc, hi, lo
 
 
-def refiner_block_final_case(f, Cp, B, H, W, subnormal_share=None):
+def refiner_block_final_case(f, Cp, B, H, W, subnormal_share=None, alloc=None):
     """subnormal_share: more than this share of the remainders must be subnormal numbers of the format (binary16 at Cp = 144)"""
-    lib, dt = f.lib, f.dt
+    lib, dt, al = f.lib, f.dt, alloc or Plain()
     x = rnd(B, Cp, H, W, seed=1).to(f.tdt)
     w, b = rnd(Cp, 1, 5, 5, seed=2, std=0.2), rnd(Cp, seed=3)
     wc, bc, hi, lo = block_final_weights(f.tdt, Cp)
@@ -1439,10 +1454,10 @@ def refiner_block_final_case(f, Cp, B, H, W, subnormal_share=None):
     bf = torch.zeros(Cp)
     bf[:3] = bc
     wp = w.reshape(Cp, 25).T.contiguous().cuda()
-    xin = x.permute(0, 2, 3, 1).contiguous().cuda()
+    xin = al.inp(x.permute(0, 2, 3, 1).contiguous())
     # the depthwise half from the stand-alone kernel (same FMA order: its 16-bit output is what the fused kernel puts into LDS;
     # a torch f64 stencil rounds 1 in ~200 values to the neighbouring 16-bit number), checked against torch loosely
-    t = torch.empty_like(xin)
+    t = al.out(xin.shape, xin.dtype)
     ok(lib, lib.roma_op_dwconv5x5(P(xin), P(t), P(wp), P(b.cuda()), B, H, W, Cp, dt, None))
     torch.cuda.synchronize()
     mid = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=2, groups=Cp)).permute(0, 2, 3, 1)
@@ -1450,7 +1465,7 @@ def refiner_block_final_case(f, Cp, B, H, W, subnormal_share=None):
     ref = torch.einsum("bhwc,oc->bhwo", t.cpu().double(), hi.double() + lo.double()) + bc.double()
     outs = []
     for _ in range(3):
-        delta = torch.full((B, H, W, 4), float("nan"), device="cuda")
+        delta = al.out((B, H, W, 4), torch.float32, fill=float("nan"))
         ok(lib, lib.roma_op_refiner_block_final(P(xin), P(delta), P(wp), P(b.cuda()), P(pwf.cuda()), P(bf.cuda()), B, H, W, Cp, dt, None))
         torch.cuda.synchronize()
         outs.append(delta)
@@ -1462,10 +1477,11 @@ def refiner_block_final_case(f, Cp, B, H, W, subnormal_share=None):
     print(f"refiner_block_final C={Cp}: max |delta - f64| = {float(err.max()):.2e} (|delta| max {scale:.2f})")
     assert float(err.max()) < 2e-5 * max(scale, 1.0) + 1e-5, (float(err.max()), scale)
     # the apply pass
-    flow, cert = rnd(B * H * W, 2, seed=6).cuda(), rnd(B * H * W, seed=7).cuda()
+    flow, cert = al.inout(rnd(B * H * W, 2, seed=6)), al.inout(rnd(B * H * W, seed=7))
     f0, c0 = flow.clone(), cert.clone()
     ok(lib, lib.roma_op_refiner_apply_delta(P(outs[0]), P(flow), P(cert), B * H * W, 0.25, 0.5, None))
     torch.cuda.synchronize()
     d = outs[0].reshape(-1, 4)
     assert torch.equal(flow[:, 0], f0[:, 0] + 0.25 * d[:, 0]) and torch.equal(flow[:, 1], f0[:, 1] + 0.5 * d[:, 1])
     assert torch.equal(cert, c0 + d[:, 2])
+    al.check()
