@@ -541,6 +541,53 @@ long roma_op_build_tracks_workspace(int B, int V, int K, int P, int M);
 int roma_op_build_tracks(const int* inds, const int* pair_views, const int* match_counts, const int* num_kpts, const float* x, int B,
                          int V, int K, int P, int M, int max_tracks, int min_views, int* out_tracks, float* out_kpts, int* out_counts,
                          int* out_total, int* out_info, void* workspace, long workspace_bytes, void* stream);
+/* Detector-free keypoints: the dense matches of an image set to per-view keypoints and index matches - what stands between
+ * roma_op_sample_matches over the P pairs of V images (2 <= V <= 8) and roma_op_build_tracks when no detector supplies
+ * keypoints.  The endpoints of all pairs that touch a view are quantised to a pixel grid, one keypoint per occupied cell stays,
+ * close keypoints of neighbouring cells are merged, and the rows are re-indexed.  Restated by tools/set_keypoints_ref.py.
+ * matches DEVICE f32 [B, P, N, 4], 16-byte aligned: rows (xA, yA, xB, yB) in normalised coordinates, A in view pair_views[p][0],
+ * B in view pair_views[p][1]; certainty DEVICE f32 [B, P, N]; counts DEVICE int32 [B, P] or NULL (N each): later rows are
+ * never read; pair_views HOST int32 [P, 2] as for roma_op_build_tracks; sizes HOST int32 [V, 2] = (H_v, W_v), each in
+ * [1, 65535]: the image sizes the caller's intrinsics refer to; cell in [1, 64] pixels; 0 <= radius <= cell pixels;
+ * 1 <= max_kpts = K <= 65536; one_to_one 0 or 1.
+ *   1. pixels: x_px = fl32(W_v / 2) * fl32(x + 1), y_px = fl32(H_v / 2) * fl32(y + 1): a product of a rounded sum, nothing fused.
+ *   2. an endpoint is valid when both are finite, 0 <= x_px < W_v and 0 <= y_px < H_v; a row is valid when n < counts, its
+ *      certainty c is finite and > 0 and both endpoints are valid.  An invalid row gets inds (-1, -1) and is counted.
+ *   3. cells: Gw_v = ceil(W_v / cell), Gh_v = ceil(H_v / cell); the cell of an endpoint is (int(floor(y_px)) / cell,
+ *      int(floor(x_px)) / cell) in integer division, its id g = cy Gw_v + cx.
+ *   4. key: the ordinal of an endpoint is o = (p N + n) 2 + side (A 0, B 1), its 64-bit key (bits of c) << 32 | (0xFFFFFFFF - o):
+ *      the certainty decides, then the earlier row.  The candidate of a (view, cell) is the valid endpoint in it with the largest
+ *      key; its float32 pixel position and its c are the position and the score of the cell.
+ *   5. suppression (radius > 0): a candidate survives unless one of the 8 neighbouring cells holds a candidate with a larger key
+ *      at squared distance d2 <= fl32(radius * radius), d2 = fmaf(dy, dy, fl32(dx * dx)) in float32.  One pass, a local-maximum
+ *      test: a suppressed candidate still suppresses.  radius == 0: every candidate survives.
+ *   6. cut: of more than K survivors of a view the K with the largest keys stay; total[b, v] counts them before the cut.
+ *   7. numbering: the keypoints of a view are its kept survivors in ascending cell id; num_kpts[b, v] = min(total, K).
+ *   8. assignment: with radius > 0 a valid endpoint takes the nearest kept keypoint among the 3 x 3 cells around its own with
+ *      d2 <= fl32(radius * radius), the larger key on a tie; with radius == 0 its own cell's keypoint if kept.  A row with an
+ *      endpoint that gets none has inds (-1, -1) and is counted.
+ *   9. one_to_one: within a pair, among the rows that still have indices, with the row key (bits of c) << 32 | (0xFFFFFFFF - n)
+ *      a row stays only if it has the largest row key among the rows with its A keypoint and among the rows with its B
+ *      keypoint - one pass, not iterated; the others become (-1, -1) and are counted.  (Two rows of a pair that share a
+ *      keypoint would put a view twice into a component, which roma_op_build_tracks drops whole.)
+ * Outputs, all DEVICE: kpts f32 [B, V, K, 2], 8-byte aligned, pixels, NaN at and beyond num_kpts - what roma_op_build_tracks and
+ * everything after it read as "not observed"; score f32 [B, V, K], 0 beyond num_kpts; num_kpts int32 [B, V]; total int32 [B, V];
+ * inds int32 [B, P, N, 2], 8-byte aligned: rows stay where they are ((-1, -1) for every row without indices, rows at and beyond
+ * counts included), so counts serves as roma_op_build_tracks' match_counts; kept int32 [B, P]: the rows of the pair with
+ * indices; info int32 [B, 6] = {rows read, rows invalid, rows without a keypoint, rows dropped by one_to_one, rows kept,
+ * candidates suppressed}.
+ * Everything is integer or max-selection logic: bit-identical from run to run and independent of B.  Seven kernels on the
+ * stream (clear, scatter by 64-bit atomicMax, suppress, a per-view scan of block counts with a radix select where a view
+ * exceeds K, number, assign, finish), every phase closed by a kernel boundary; no host synchronisation, no allocation.  The
+ * workspace (roma_op_keypoints_from_matches_workspace bytes for G_total = sum_v Gw_v Gh_v; 0 for an empty or refused problem)
+ * holds 12 bytes per cell, every view's grid padded to 1024 cells, and 16 bytes per (pair, keypoint); it need not be zero on
+ * entry.  Limits: Gw_v Gh_v <= 2^22 per view, B (G_total + 1024 V) <= 2^28, 2 P N < 2^32, B P N < 2^30, P <= 64, B <= 65535.
+ * Every argument is checked before anything is enqueued; B == 0 launches nothing. */
+long roma_op_keypoints_from_matches_workspace(int B, int V, int P, int N, long G_total, int K);
+int roma_op_keypoints_from_matches(const float* matches, const float* certainty, const int* counts, const int* pair_views,
+                                   const int* sizes, int B, int V, int P, int N, int cell, float radius, int max_kpts, int one_to_one,
+                                   float* out_kpts, float* out_score, int* out_num_kpts, int* out_total, int* out_inds, int* out_kept,
+                                   int* out_info, void* workspace, long workspace_bytes, void* stream);
 /* N-view triangulation: the 3-D point of every track from all the views that observe it, the poses given (x_cam = R X + t) -
  * the point half of roma_op_bundle_adjust.  Float64 with fp contraction off; restated operation by operation by
  * tools/triangulate_views_ref.py.  kpts DEVICE f32 [B, V, N, 2], 8-byte aligned, pixels of their view, a non-finite entry: the

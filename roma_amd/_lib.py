@@ -121,6 +121,9 @@ SIGNATURES = {
                                   _vp, _l, _vp]),
     "roma_op_build_tracks_workspace": (_l, [_i, _i, _i, _i, _i]),
     "roma_op_build_tracks": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
+    "roma_op_keypoints_from_matches_workspace": (_l, [_i, _i, _i, _i, _l, _i]),
+    "roma_op_keypoints_from_matches": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _l, _vp]),
     "roma_op_triangulate_views": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _i, _i, _i,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "roma_op_refine_model_workspace": (_l, [_i, _i]),

@@ -33,6 +33,7 @@
 #include "geometry.h"
 #include "triangulate.h"
 #include "tracks.h"
+#include "set_keypoints.h"
 #include "gt_warp.h"
 #include "metrics.h"
 #include "morph.h"
@@ -659,6 +660,18 @@ int roma_op_build_tracks(const int* inds, const int* pair_views, const int* matc
                          int* out_total, int* out_info, void* workspace, long workspace_bytes, void* stream) {
   return build_tracks_launch(inds, pair_views, match_counts, num_kpts, x, B, V, K, P, M, max_tracks, min_views, out_tracks, out_kpts,
                              out_counts, out_total, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+// ---- detector-free keypoints: the dense matches of an image set to per-view keypoints and index matches (set_keypoints.hip)
+long roma_op_keypoints_from_matches_workspace(int B, int V, int P, int N, long G_total, int K) {
+  return (long)keypoints_from_matches_workspace_bytes(B, V, P, N, G_total, K);
+}
+int roma_op_keypoints_from_matches(const float* matches, const float* certainty, const int* counts, const int* pair_views,
+                                   const int* sizes, int B, int V, int P, int N, int cell, float radius, int max_kpts, int one_to_one,
+                                   float* out_kpts, float* out_score, int* out_num_kpts, int* out_total, int* out_inds, int* out_kept,
+                                   int* out_info, void* workspace, long workspace_bytes, void* stream) {
+  return keypoints_from_matches_launch(matches, certainty, counts, pair_views, sizes, B, V, P, N, cell, radius, max_kpts, one_to_one,
+                                       out_kpts, out_score, out_num_kpts, out_total, out_inds, out_kept, out_info, workspace,
+                                       (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
 }
 int roma_op_triangulate_views(const float* kpts, const double* camera_matrices, const double* R, const double* t,
                               const unsigned char* view_valid, const int* counts, const unsigned char* valid, int B, int V, int N,

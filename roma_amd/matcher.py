@@ -446,6 +446,34 @@ class RegressionMatcher:
         warp, cert = self.match_pairs(enc, pv)
         return warp, cert, [(int(i), int(j)) for i, j in pv]
 
+    def set_keypoints(self, warp, certainty, pairs, sizes, num=5000, seed=None, **kw):
+        """Detector-free keypoints of an image set: `sample_batched(warp, certainty, num, seed, return_counts=True)` over the pair
+        axis of what `match_image_set` returned, then `roma_amd.keypoints_from_matches` (see there for cell, radius, max_kpts,
+        one_to_one and what is returned).  pairs: the (i, j) tuples of `match_image_set`; sizes: one (H, W) per image, the sizes
+        the intrinsics refer to.  Returns (SetKeypoints, counts [P]); counts is `build_tracks`' match_counts.  Nothing is read back."""
+        from .set_keypoints import keypoints_from_matches
+        m, c, counts = self.sample_batched(warp, certainty, num=num, seed=seed, return_counts=True)
+        return keypoints_from_matches(m, c, pairs, len(sizes), sizes, counts=counts, **kw), counts
+
+    def reconstruct_image_set(self, images, K, norm_thresh, reproj_thresh, *, pairs=None, num=5000, seed=None, max_tracks=None, **kw):
+        """2 .. 8 decoded images (as `match_image_set` takes them) to a refined reconstruction - composition only, no host read
+        after the image upload: `match_image_set`, `set_keypoints` with the sizes of the images, `build_tracks`, then
+        `roma_amd.reconstruct_views(tr.kpts, K, norm_thresh, reproj_thresh, counts=tr.counts, seed=seed)`.  Views 0 and 1 are the
+        seed pair, as `reconstruct_views` documents; K [V, 3, 3] or [3, 3] in pixels of the images as given.  **kw goes to
+        `keypoints_from_matches` (cell, radius, max_kpts, one_to_one).  Returns (ViewsReconstruction, Tracks, SetKeypoints)."""
+        from .bundle import reconstruct_views
+        from .preprocess import _as_uint8_hwc
+        from .tracks import MAX_VIEWS, build_tracks
+        if not isinstance(images, (list, tuple)) or not 2 <= len(images) <= MAX_VIEWS:
+            raise ValueError(f"reconstruct_image_set: images must be a sequence of 2 .. {MAX_VIEWS} images")
+        images = [_as_uint8_hwc(im, i) for i, im in enumerate(images)]  # decoded once: their shapes are the sizes
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        warp, cert, pairs = self.match_image_set(images, pairs)
+        kp, counts = self.set_keypoints(warp, cert, pairs, sizes, num=num, seed=seed, **kw)
+        tr = build_tracks(kp.inds, pairs, len(images), match_counts=counts, num_kpts=kp.num_kpts, kpts=kp.kpts, max_tracks=max_tracks)
+        rec = reconstruct_views(tr.kpts, K, norm_thresh, reproj_thresh, counts=tr.counts, seed=seed)
+        return rec, tr, kp
+
     # ------------------------------------------------------------------ forward / forward_symmetric / backbone features
     _SCALES = (16, 8, 4, 2, 1)
     _FEAT_C = {16: 1024, 8: 512, 4: 256, 2: 128, 1: 64}

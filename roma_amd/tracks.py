@@ -1,8 +1,16 @@
-"""Multi-view tracks on the device (`roma_op_build_tracks`, csrc/tracks.hip): the pairwise index matches `match_keypoints`
-returns for the pairs of V <= 8 images, joined into tracks - one keypoint per view - and laid out as the [V, N] observation table
-`triangulate_views`, `reconstruct_views` and `bundle_adjust` read.  One launch for a batch of problems, nothing read back.
+"""Multi-view tracks on the device (`roma_op_build_tracks`, csrc/tracks.hip): pairwise index matches over the pairs of V <= 8
+images, joined into tracks - one keypoint per view - and laid out as the [V, N] observation table `triangulate_views`,
+`reconstruct_views` and `bundle_adjust` read.  One launch for a batch of problems, nothing read back.
 
-The whole chain for V images with detector keypoints x[v] [K, 2] (pixels) and a matcher `model`:
+The whole chain for V images with a matcher `model` alone - RoMa is detector-free, so the keypoints are made from the matches
+(`roma_amd.keypoints_from_matches`; `model.reconstruct_image_set(images, K, norm_thresh, reproj_thresh)` is these lines):
+
+    warp, cert, pairs = model.match_image_set(images)                      # all i < j, each image encoded once
+    kp, counts = model.set_keypoints(warp, cert, pairs, sizes, num=5000)   # sizes: (H, W) per image
+    tr = build_tracks(kp.inds, pairs, V, match_counts=counts, num_kpts=kp.num_kpts, kpts=kp.kpts)
+    rec = reconstruct_views(tr.kpts, K, norm_thresh, reproj_thresh, counts=tr.counts)
+
+and with a detector's keypoints x[v] [K, 2] (pixels), matched through the warp by `match_keypoints`:
 
     pairs = [(a, b) for a in range(V) for b in range(a + 1, V)]
     warp, cert = model.match(torch.stack([im[a] for a, b in pairs]), torch.stack([im[b] for a, b in pairs]))
