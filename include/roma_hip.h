@@ -693,6 +693,77 @@ int roma_op_triangulate(const float* matches, const float* certainty, const int*
 int roma_op_depth_consistency(const float* points, const unsigned char* flags, const double* R, const double* t, const double* K_a,
                               const double* K_b, int W_a, int H_a, int W_b, int H_b, int B, int H, int W, double rel_thresh,
                               unsigned char* out_consistent, float* out_err, void* stream);
+/* Dense multi-view depth fusion: the depth maps of the pairs of an image set to one depth map per view and one point cloud - what
+ * joins the poses of roma_op_bundle_adjust to the dense product of a dense matcher.  B problems of V views (2 <= V <= 8) and P
+ * pairs (1 <= P <= 64) on a grid H x W.  Restated operation by operation in numpy float64 by tools/depth_fusion_ref.py.  All
+ * arithmetic is float64 in the order written, with fp contraction off; depths are read and stored as float32.
+ * points DEVICE f32 [B, P, H, Wd, 3], flags DEVICE u8 [B, P, H, Wd], certainty DEVICE f32 [B, P, H, Wd] or NULL (every weight 1): the
+ * outputs of ONE roma_op_triangulate call over the pairs (sym_w = W or 0) and the certainty it read, read in place; only
+ * points[..., 2], the depth, is read.  symmetric 1: Wd = 2W, the left half of pair p lies on the grid of view pair_views[p][0], the
+ * right half on the grid of view pair_views[p][1]; symmetric 0: Wd = W, only the first.  pair_views HOST int32 [P, 2]: both views in
+ * [0, V) and different, no ORDERED pair twice ((i, j) and (j, i) may both occur: a view has at most 2 (V - 1) = 14 hypotheses).
+ * cameras DEVICE f64 [B, V, 3, 3] IN GRID UNITS, applied by fx, fy, cx, cy: the image intrinsics scaled by W / W_img and H / H_img; the
+ * centre of grid cell (r, c) is (c + 0.5, r + 0.5).  R DEVICE f64 [B, V, 3, 3], t DEVICE f64 [B, V, 3], x_cam = R X + t, as
+ * roma_op_triangulate_views takes them.  view_valid DEVICE u8 [B, V] or NULL, valid DEVICE u8 [B] or NULL: a view that is not valid
+ * (every view of a problem that is not) has no depth, supports nothing, and the slots of its pairs are not usable in either view.
+ * Colour source, all three or none: images DEVICE u8, packed [H_img, W_img, 3] images; image_offsets HOST int64 [B, V] byte offsets
+ * into it; image_sizes HOST int32 [B, V, 2] = (H_img, W_img).  They travel in a kernel's arguments: B V <= 128 with out_colors.
+ *   1. hypotheses of pixel q of view v: its slots are the halves on v's grid, in ascending p (of one pair in both orders: the
+ *      order of the rows of pair_views).  A slot is usable when its flag byte is 0, its depth z is finite and > 0 and its weight
+ *      w (the certainty, or 1) is finite and > 0.
+ *   2. support: slot l supports slot k when both are usable and |z_l - z_k| <= rel_thresh * min(z_l, z_k) (one product); a slot
+ *      supports itself.  n_k = the supporters of k, s_k = the sum of their w and m_k = the sum of their w z (each product rounded),
+ *      both added in slot order starting from 0.
+ *   3. select: the usable slot with the largest n_k, then the largest s_k, then the lowest slot.  n < min_support (in [1, 14]):
+ *      depth NaN, weight 0, support = the best n (0 without a usable slot).  Otherwise depth = fl32(m_k / s_k), weight = fl32(s_k),
+ *      support = n.
+ *   4. cross-view check, on the maps of step 3, after a kernel boundary.  A pixel (r, c) of view v with depth z:
+ *      x = (((c + 0.5) - cx) / fx, ((r + 0.5) - cy) / fy), d = (z x0 - t0, z x1 - t1, z - t2), X_w = R_v^T d with
+ *      X_w[i] = (R[0][i] d0 + R[1][i] d1) + R[2][i] d2.  For every other valid view u: X' = R_u X_w + t_u with
+ *      X'[i] = ((R[i][0] X0 + R[i][1] X1) + R[i][2] X2) + t[i]; not X'_z > 0: no support.  g = (fx (X'_x / X'_z) + cx - 0.5,
+ *      fy (X'_y / X'_z) + cy - 0.5) is its position on u's grid (align_corners = False); x0 = floor(g_x), y0 = floor(g_y); support
+ *      only if 0 <= x0, x0 + 1 <= W - 1, 0 <= y0, y0 + 1 <= H - 1 and the four neighbours all have a depth; dd = the bilinear
+ *      expression of roma_op_depth_consistency on them; e = (X'_z - dd) / dd.  |e| <= rel_thresh sets bit u of seen; e < -rel_thresh
+ *      sets bit u of violated (the point floats in front of the surface u sees); e > rel_thresh sets neither (occluded in u).
+ *      keep = popcount(seen) >= min_consistent and popcount(violated) <= max_violations.
+ *   5. duplicates (dedupe = 1), after another kernel boundary, from step 4's keep alone: a kept pixel of view v is a duplicate
+ *      when for some u < v bit u of its seen is set and the pixel (floor(g_y + 0.5), floor(g_x + 0.5)) of u lies inside the grid and
+ *      is kept.
+ *   6. emission: the pixels that are kept and no duplicates are numbered in the order (view ascending, row-major pixel) by block
+ *      counts, one workgroup per problem for their exclusive prefix, and ballot ranks - independent of the schedule.  The first
+ *      max_points are written, total reports all of them.  The colour of a point is the image pixel that holds the centre of
+ *      its cell: (((2 r + 1) H_img) / (2 H), ((2 c + 1) W_img) / (2 W)) in integer division.
+ * Outputs, all DEVICE.  Per view: depth f32 [B, V, H, W] (NaN where none), weight f32, support u8, seen u8, violated u8 (bit masks
+ * over views), state u8 (bit 0 kept, bit 1 duplicate).  Cloud: points f32 [B, max_points, 3] = fl32(X_w), NaN padding; colors u8
+ * [B, max_points, 3] or NULL, 0 padding; cloud_weight f32 [B, max_points] (the pixel's weight), 0 padding; source int32
+ * [B, max_points, 2] = (view, r W + c), -1 padding; counts int32 [B] = min(total, max_points); total int32 [B]; stats int32 [B, 8] =
+ * {pixels with a usable slot, fused, kept, duplicates, emitted, pixels with a violation, 0, 0}: integer atomics, one per workgroup
+ * that has something to count, cleared on the stream by the same call.  Every element of every output is written.
+ * Five kernels on the stream (select, check, dedupe, scan, emit), one thread per pixel, the cameras and poses of the views staged
+ * once per workgroup; no host read; the workspace (roma_op_fuse_depth_maps_workspace bytes, 0 for an empty or refused problem:
+ * one byte per pixel and one int32 per block of 256 pixels) need not be cleared.  Bit-identical from run to run and independent
+ * of B.  Refused before anything is enqueued: a null required pointer, V outside [2, 8], P outside [1, 64], B > 65535, H or W
+ * below 1, symmetric or dedupe not 0 or 1, a negative (or NaN) rel_thresh, min_support outside [1, 14], min_consistent outside
+ * [0, 7], negative max_violations or max_points, a pair_views entry out of range, a pair of a view with itself, an ordered pair
+ * twice, a partial colour source or out_colors without one, B P H Wd, B V H W or 3 B max_points >= 2^31, a workspace that is too
+ * small.  B = 0 launches nothing. */
+long roma_op_fuse_depth_maps_workspace(int B, int V, int H, int W);
+int roma_op_fuse_depth_maps(const float* points, const unsigned char* flags, const float* certainty, const int* pair_views,
+                            const double* cameras, const double* R, const double* t, const unsigned char* view_valid,
+                            const unsigned char* valid, const unsigned char* images, const long long* image_offsets,
+                            const int* image_sizes, int B, int V, int P, int H, int W, int symmetric, double rel_thresh,
+                            int min_support, int min_consistent, int max_violations, int dedupe, int max_points, float* out_depth,
+                            float* out_weight, unsigned char* out_support, unsigned char* out_seen, unsigned char* out_violated,
+                            unsigned char* out_state, float* out_points, unsigned char* out_colors, float* out_cloud_weight,
+                            int* out_source, int* out_counts, int* out_total, int* out_stats, void* workspace, long workspace_bytes,
+                            void* stream);
+/* The pose of every pair from the poses of the views, x_cam = R X + t: R_ij = R_j R_i^T with R_ij[a][c] = (R_j[a][0] R_i[c][0] +
+ * R_j[a][1] R_i[c][1]) + R_j[a][2] R_i[c][2], t_ij[a] = t_j[a] - ((R_ij[a][0] t_i[0] + R_ij[a][1] t_i[1]) + R_ij[a][2] t_i[2]) - the
+ * (A to B) pose roma_op_triangulate takes for pair (i, j).  R DEVICE f64 [B, V, 3, 3], t DEVICE f64 [B, V, 3], pair_views HOST int32
+ * [P, 2] (1 <= P <= 64, both views in [0, V) and different); out_R DEVICE f64 [B, P, 3, 3], out_t DEVICE f64 [B, P, 3].  One launch,
+ * float64 with fp contraction off; restated by tools/depth_fusion_ref.py. */
+int roma_op_relative_poses(const double* R, const double* t, const int* pair_views, int B, int V, int P, double* out_R, double* out_t,
+                           void* stream);
 /* Ground-truth warp from SENSOR depth - the reference's warp_kpts / get_gt_warp (romatch/utils/utils.py) - and the dense EPE / PCK
  * metrics of a warp against it - MegadepthDenseBenchmark.geometric_dist in one pass.  The sensor-depth twin of
  * roma_op_depth_consistency.  Restated operation by operation in numpy float64 by tools/gt_warp_ref.py.  All arithmetic is float64

@@ -15,6 +15,7 @@ from .bundle import BundleResult, ViewsReconstruction, bundle_adjust, reconstruc
 from .triangulation import ViewsTriangulation, depth_consistency, triangulate, triangulate_views, triangulate_warp  # noqa: F401
 from .tracks import Tracks, build_tracks  # noqa: F401
 from .set_keypoints import SetKeypoints, keypoints_from_matches  # noqa: F401
+from .depth_fusion import DenseFusion, fuse_depth_maps, relative_poses  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 from .encoded import EncodedImages, all_pairs, pack_layout  # noqa: F401
 from .gt_warp import DenseMetrics, dense_metrics, get_gt_warp, warp_kpts  # noqa: F401
@@ -32,5 +33,6 @@ __all__ = ["pose_error", "compute_pose_error", "homography_corner_error", "pose_
            "estimate_absolute_pose", "absolute_pose_minimal", "refine_absolute_pose", "lift_matches",
            "bundle_adjust", "reconstruct_pair", "BundleResult", "build_tracks", "Tracks", "triangulate_views", "ViewsTriangulation",
            "reconstruct_views", "ViewsReconstruction", "keypoints_from_matches", "SetKeypoints",
+           "fuse_depth_maps", "relative_poses", "DenseFusion",
            "EncodedImages", "all_pairs", "pack_layout",
            "TinyRoMa", "tiny_roma_v1_outdoor"]

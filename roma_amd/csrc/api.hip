@@ -32,6 +32,7 @@
 #include "pose_refine.h"
 #include "geometry.h"
 #include "triangulate.h"
+#include "depth_fusion.h"
 #include "tracks.h"
 #include "set_keypoints.h"
 #include "gt_warp.h"
@@ -705,6 +706,27 @@ int roma_op_depth_consistency(const float* points, const unsigned char* flags, c
                               unsigned char* out_consistent, float* out_err, void* stream) {
   return depth_consistency_launch(points, flags, R, t, K_a, K_b, W_a, H_a, W_b, H_b, B, H, W, rel_thresh, out_consistent, out_err,
                                   S(stream));
+}
+// ---- dense multi-view depth fusion and the relative poses of the pairs of a set of views (depth_fusion.hip)
+long roma_op_fuse_depth_maps_workspace(int B, int V, int H, int W) { return (long)fuse_depth_maps_workspace_bytes(B, V, H, W); }
+int roma_op_fuse_depth_maps(const float* points, const unsigned char* flags, const float* certainty, const int* pair_views,
+                            const double* cameras, const double* R, const double* t, const unsigned char* view_valid,
+                            const unsigned char* valid, const unsigned char* images, const long long* image_offsets,
+                            const int* image_sizes, int B, int V, int P, int H, int W, int symmetric, double rel_thresh,
+                            int min_support, int min_consistent, int max_violations, int dedupe, int max_points, float* out_depth,
+                            float* out_weight, unsigned char* out_support, unsigned char* out_seen, unsigned char* out_violated,
+                            unsigned char* out_state, float* out_points, unsigned char* out_colors, float* out_cloud_weight,
+                            int* out_source, int* out_counts, int* out_total, int* out_stats, void* workspace, long workspace_bytes,
+                            void* stream) {
+  return fuse_depth_maps_launch(points, flags, certainty, pair_views, cameras, R, t, view_valid, valid, images, image_offsets,
+                                image_sizes, B, V, P, H, W, symmetric, rel_thresh, min_support, min_consistent, max_violations, dedupe,
+                                max_points, out_depth, out_weight, out_support, out_seen, out_violated, out_state, out_points,
+                                out_colors, out_cloud_weight, out_source, out_counts, out_total, out_stats, workspace,
+                                (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
+}
+int roma_op_relative_poses(const double* R, const double* t, const int* pair_views, int B, int V, int P, double* out_R, double* out_t,
+                           void* stream) {
+  return relative_poses_launch(R, t, pair_views, B, V, P, out_R, out_t, S(stream));
 }
 // ---- ground-truth warp from depth and dense EPE / PCK metrics (gt_warp.hip)
 int roma_op_warp_kpts(const void* kpts, int kpts_f64, int grid_h, int grid_w, const float* depth0, const float* depth1, const double* T,

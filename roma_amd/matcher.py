@@ -474,6 +474,71 @@ class RegressionMatcher:
         rec = reconstruct_views(tr.kpts, K, norm_thresh, reproj_thresh, counts=tr.counts, seed=seed)
         return rec, tr, kp
 
+    def fuse_image_set(self, warp, certainty, pairs, K, R, t, sizes, images=None, view_valid=None, **kw):
+        """The warps of an image set and the poses of its views to fused depth maps and one point cloud - composition only, nothing
+        read back.  warp [P, H, Wd, 4], certainty [P, H, Wd] and pairs as `match_image_set` returned them; K [V, 3, 3] or [3, 3] in
+        pixels of the images, sizes one (H_img, W_img) per image; R [V, 3, 3], t [V, 3] with x_cam = R X + t and view_valid [V]
+        (`reconstruct_views`' R, t, view_ok); images: V uint8 device tensors [H_img, W_img, 3], the colour source.
+
+          1. K is rescaled to the grid: rows 0 and 1 times W / W_img and H / H_img
+          2. `roma_amd.relative_poses` gives the pose of every pair
+          3. ONE `triangulate_warp` call over all pairs with the cameras in grid units and H_A = H, W_A = W, so images of mixed
+             sizes need no grouping; max_depth, max_reproj, min_parallax and min_certainty are passed through
+          4. `roma_amd.fuse_depth_maps` on its points and flags, read in place, with the certainty as the weight; every other
+             keyword goes there (rel_thresh, min_support, min_consistent, max_violations, dedupe, max_points)
+
+        Returns `roma_amd.DenseFusion` without a batch axis; its points are in the frame R and t refer to."""
+        from .bundle import _view_cameras
+        from .depth_fusion import fuse_depth_maps, relative_poses
+        from .triangulation import triangulate_warp
+        if not isinstance(warp, torch.Tensor) or warp.dim() != 4 or warp.shape[-1] != 4:
+            raise ValueError("fuse_image_set: warp must be the [P, H, Wd, 4] tensor match_image_set returned")
+        P, H, Wd = int(warp.shape[0]), int(warp.shape[1]), int(warp.shape[2])
+        symmetric = bool(kw.pop("symmetric", self.symmetric))
+        if P != len(pairs) or (symmetric and Wd % 2):
+            raise ValueError(f"fuse_image_set: {len(pairs)} pairs for a warp of shape {tuple(warp.shape)}")
+        W = Wd // 2 if symmetric else Wd
+        V = len(sizes)
+        if not 2 <= V <= 8 or any(len(s) != 2 or min(s) < 1 for s in sizes):
+            raise ValueError("fuse_image_set: sizes must hold one (H, W) for each of 2 .. 8 images")
+        tri_kw = {k: kw.pop(k) for k in ("max_depth", "max_reproj", "min_parallax", "min_certainty") if k in kw}
+        dev = warp.device
+        K_img = _view_cameras(K, 1, V, dev)[0]
+        # the scales are host numbers: rows times Python floats, nothing is uploaded
+        K_grid = torch.stack([torch.stack((K_img[v, 0] * (W / int(w_img)), K_img[v, 1] * (H / int(h_img)), K_img[v, 2]))
+                              for v, (h_img, w_img) in enumerate(sizes)])
+        R_ij, t_ij = relative_poses(R, t, pairs)
+        K_A, K_B = (torch.stack([K_grid[int(p[k])] for p in pairs]) for k in (0, 1))
+        tri = triangulate_warp(warp, certainty, R_ij, t_ij, K_A, K_B, H, W, symmetric=symmetric, **tri_kw)
+        # points_A and flags_A are views of the [P, H, Wd] outputs (as `triangulate_warp` documents): the whole grid, in place
+        pts, flg = tri.points_A, tri.flags_A
+        points = torch.as_strided(pts, (P, H, Wd, 3), (H * Wd * 3, Wd * 3, 3, 1), pts.storage_offset())
+        flags = torch.as_strided(flg, (P, H, Wd), (H * Wd, Wd, 1), flg.storage_offset())
+        return fuse_depth_maps(points, flags, certainty, pairs, K_grid, R, t, symmetric=symmetric, images=images, view_valid=view_valid, **kw)
+
+    def dense_reconstruct_image_set(self, images, K, norm_thresh, reproj_thresh, *, pairs=None, num=5000, seed=None, max_tracks=None,
+                                    fusion=None, **kw):
+        """2 .. 8 decoded images to a dense reconstruction - `reconstruct_image_set`'s steps with the warp and the certainty kept,
+        then `fuse_image_set(warp, certainty, pairs, K, rec.R, rec.t, sizes, images=<the uploaded images>, view_valid=rec.view_ok,
+        **fusion)`.  Composition only, no host read after the image upload.  fusion: a dict of keywords for `fuse_image_set`; **kw
+        goes to `keypoints_from_matches` as in `reconstruct_image_set`.  Returns (DenseFusion, ViewsReconstruction, Tracks,
+        SetKeypoints); the cloud is in view 0's frame and carries the colours of the images."""
+        from .bundle import reconstruct_views
+        from .preprocess import _as_uint8_hwc
+        from .tracks import MAX_VIEWS, build_tracks
+        if not isinstance(images, (list, tuple)) or not 2 <= len(images) <= MAX_VIEWS:
+            raise ValueError(f"dense_reconstruct_image_set: images must be a sequence of 2 .. {MAX_VIEWS} images")
+        images = [_as_uint8_hwc(im, i) for i, im in enumerate(images)]
+        sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+        images = [im if isinstance(im, torch.Tensor) else torch.from_numpy(im).to(self.device) for im in images]  # the upload
+        warp, cert, pairs = self.match_image_set(images, pairs)
+        kp, counts = self.set_keypoints(warp, cert, pairs, sizes, num=num, seed=seed, **kw)
+        tr = build_tracks(kp.inds, pairs, len(images), match_counts=counts, num_kpts=kp.num_kpts, kpts=kp.kpts, max_tracks=max_tracks)
+        rec = reconstruct_views(tr.kpts, K, norm_thresh, reproj_thresh, counts=tr.counts, seed=seed)
+        fused = self.fuse_image_set(warp, cert, pairs, K, rec.R, rec.t, sizes, images=[im.contiguous() for im in images],
+                                    view_valid=rec.view_ok, **(fusion or {}))
+        return fused, rec, tr, kp
+
     # ------------------------------------------------------------------ forward / forward_symmetric / backbone features
     _SCALES = (16, 8, 4, 2, 1)
     _FEAT_C = {16: 1024, 8: 512, 4: 256, 2: 128, 1: 64}
