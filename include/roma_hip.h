@@ -764,6 +764,55 @@ int roma_op_fuse_depth_maps(const float* points, const unsigned char* flags, con
  * float64 with fp contraction off; restated by tools/depth_fusion_ref.py. */
 int roma_op_relative_poses(const double* R, const double* t, const int* pair_views, int B, int V, int P, double* out_R, double* out_t,
                            void* stream);
+/* Point-cloud rendering: the N rows of a world-space point cloud splatted into C cameras per problem with a z-buffer, then an
+ * occlusion filter and a hole fill - depth, row index, colour and a mask per pixel of every frame.  What a dense reconstruction is
+ * looked at with (a turntable of novel views), localised against (the depth map of the whole cloud in a registered camera) and
+ * checked with (its depth in a camera that has sensor depth, or in one of its own).  Restated operation by operation in numpy
+ * float64 by tools/point_render_ref.py.  All arithmetic is float64 in the order written, with fp contraction off; depths are
+ * stored as float32.
+ * points DEVICE f32 [B, N, 3] world points, the cloud of roma_op_fuse_depth_maps with its NaN padding taken as it is; colors DEVICE
+ * u8 [B, N, 3] or NULL; counts DEVICE int32 [B] or NULL: rows n >= min(max(counts[b], 0), N) are ignored; valid DEVICE u8 [B] or
+ * NULL: a problem that is not valid renders empty.  cameras DEVICE f64 [B, C, 3, 3], applied by fx, fy, cx, cy, in units of the
+ * output pixel: the centre of pixel (r, c) is (c + 0.5, r + 0.5), the convention of roma_op_fuse_depth_maps.  R DEVICE f64
+ * [B, C, 3, 3], t DEVICE f64 [B, C, 3], x_cam = R X + t.  H, W: the size of every frame.  background = r | g << 8 | b << 16, the
+ * colour of a pixel without a point.
+ *   1. splat.  Row n of problem b is usable for camera k when its three coordinates are finite; near <= X'_z <= far with
+ *      X'[i] = ((R[i][0] X0 + R[i][1] X1) + R[i][2] X2) + t[i], X widened from float32; zf = fl32(X'_z) is finite and > 0;
+ *      u = fx (X'_x / X'_z) + cx and v = fy (X'_y / X'_z) + cy are finite; and -radius <= floor(u) < W + radius, -radius <=
+ *      floor(v) < H + radius, decided in double before any conversion to an integer.  With c0 = floor(u), r0 = floor(v) it offers
+ *      the key (bits(zf) << 32) | n to every pixel (r, c) of the image with |r - r0| <= radius and |c - c0| <= radius.  A pixel
+ *      holds the minimum of the keys offered to it - the nearest depth, then the lowest row; all ones means empty.  Integer minima
+ *      do not depend on the order of arrival.
+ *   2. occlusion filter (occlusion_radius o > 0), after a kernel boundary, on the raw buffer of step 1 only: a hit pixel of depth z
+ *      is removed when at least occlusion_count hit pixels q of its (2 o + 1)^2 window, clipped to the image, are nearer by more
+ *      than occlusion_rel: (double)z > (double)z_q * (1.0 + occlusion_rel), one product.  These are the points of a back surface
+ *      that show through the gaps of a nearer one.  o = 0 removes nothing.
+ *   3. fill (fill_radius f > 0), after another kernel boundary, from step 2's decisions alone: a pixel that is empty or removed
+ *      counts the surviving pixels (hit and not removed) of its clipped (2 f + 1)^2 window and with at least fill_min of them takes
+ *      the smallest of their keys.  f = 0 fills nothing.  Known: at a depth edge the nearer surface grows by up to o + f pixels -
+ *      the filter removes the far pixels next to the edge and the fill closes them with the near key.
+ *   4. resolve, per pixel from its final key or none.
+ * Outputs, all DEVICE, [B, C, H, W]: out_depth f32 = zf, NaN if empty; out_index int32 = the row, -1 if empty; out_color u8
+ * [B, C, H, W, 3] = the row's colour, background if empty, NULL exactly when colors is; out_mask u8: bit 0 hit in step 1, bit 1
+ * removed, bit 2 filled; out_stats int32 [B, C, 4] = {usable rows with (r0, c0) inside the image, pixels hit, pixels removed, pixels
+ * filled}: integer atomics, one per workgroup that has something to count, cleared on the stream by the same call.  Every element
+ * of every output is written.
+ * A clear (two memsets) and three kernels on the stream: splat with grid (blocks of 256 rows, camera, problem), the camera staged
+ * once per workgroup, 64-bit atomicMin behind a plain load of the current key (a key only ever decreases, so the load is exact: it
+ * can only skip an atomic that would change nothing); filter and fill with one thread per pixel.  No host read.  The workspace
+ * (roma_op_render_points_workspace bytes, 0 for an empty or refused problem: 8 bytes per pixel for the keys and one for step 2's
+ * decision) need not be cleared: the call initialises whatever it reads.  Bit-identical from run to run, independent of B and of C:
+ * a frame rendered alone equals the same frame in a batch.  Refused before anything is enqueued: a null required pointer, colors
+ * without out_color or the reverse, C < 1, B < 0 or B C > 65535, H or W below 1, N < 0 (N = 0 renders empty), radius,
+ * occlusion_radius or fill_radius outside [0, 4], occlusion_count or fill_min below 1, a negative (or NaN) occlusion_rel, near not
+ * > 0, far < near (or NaN; +inf is allowed), a background outside [0, 0xFFFFFF], 3 B C H W >= 2^31, a workspace that is too small.
+ * B = 0 launches nothing. */
+long roma_op_render_points_workspace(int B, int C, int H, int W);
+int roma_op_render_points(const float* points, const unsigned char* colors, const int* counts, const unsigned char* valid,
+                          const double* cameras, const double* R, const double* t, int B, int N, int C, int H, int W, int radius,
+                          double near, double far, int occlusion_radius, double occlusion_rel, int occlusion_count, int fill_radius,
+                          int fill_min, int background, unsigned char* out_color, float* out_depth, int* out_index,
+                          unsigned char* out_mask, int* out_stats, void* workspace, long workspace_bytes, void* stream);
 /* Ground-truth warp from SENSOR depth - the reference's warp_kpts / get_gt_warp (romatch/utils/utils.py) - and the dense EPE / PCK
  * metrics of a warp against it - MegadepthDenseBenchmark.geometric_dist in one pass.  The sensor-depth twin of
  * roma_op_depth_consistency.  Restated operation by operation in numpy float64 by tools/gt_warp_ref.py.  All arithmetic is float64

@@ -16,6 +16,7 @@ from .triangulation import ViewsTriangulation, depth_consistency, triangulate, t
 from .tracks import Tracks, build_tracks  # noqa: F401
 from .set_keypoints import SetKeypoints, keypoints_from_matches  # noqa: F401
 from .depth_fusion import DenseFusion, fuse_depth_maps, relative_poses  # noqa: F401
+from .point_render import PointRender, orbit_cameras, render_points  # noqa: F401
 from .preprocess import preprocess_images  # noqa: F401
 from .encoded import EncodedImages, all_pairs, pack_layout  # noqa: F401
 from .gt_warp import DenseMetrics, dense_metrics, get_gt_warp, warp_kpts  # noqa: F401
@@ -34,5 +35,6 @@ __all__ = ["pose_error", "compute_pose_error", "homography_corner_error", "pose_
            "bundle_adjust", "reconstruct_pair", "BundleResult", "build_tracks", "Tracks", "triangulate_views", "ViewsTriangulation",
            "reconstruct_views", "ViewsReconstruction", "keypoints_from_matches", "SetKeypoints",
            "fuse_depth_maps", "relative_poses", "DenseFusion",
+           "render_points", "orbit_cameras", "PointRender",
            "EncodedImages", "all_pairs", "pack_layout",
            "TinyRoMa", "tiny_roma_v1_outdoor"]

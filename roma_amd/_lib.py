@@ -135,6 +135,9 @@ SIGNATURES = {
     "roma_op_fuse_depth_maps": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i,
                                     _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_relative_poses": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "roma_op_render_points_workspace": (_l, [_i, _i, _i, _i]),
+    "roma_op_render_points": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _i, C.c_double, _i, _i,
+                                  _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
     "roma_op_warp_kpts": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _l, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "roma_op_dense_metrics_workspace": (_l, [_i, _i, _i]),
     "roma_op_dense_metrics": (_i, [_vp, _l, _l, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double,

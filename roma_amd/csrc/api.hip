@@ -33,6 +33,7 @@
 #include "geometry.h"
 #include "triangulate.h"
 #include "depth_fusion.h"
+#include "point_render.h"
 #include "tracks.h"
 #include "set_keypoints.h"
 #include "gt_warp.h"
@@ -727,6 +728,17 @@ int roma_op_fuse_depth_maps(const float* points, const unsigned char* flags, con
 int roma_op_relative_poses(const double* R, const double* t, const int* pair_views, int B, int V, int P, double* out_R, double* out_t,
                            void* stream) {
   return relative_poses_launch(R, t, pair_views, B, V, P, out_R, out_t, S(stream));
+}
+// ---- point-cloud rendering: z-buffered splat, occlusion filter, hole fill (point_render.hip)
+long roma_op_render_points_workspace(int B, int C, int H, int W) { return (long)render_points_workspace_bytes(B, C, H, W); }
+int roma_op_render_points(const float* points, const unsigned char* colors, const int* counts, const unsigned char* valid,
+                          const double* cameras, const double* R, const double* t, int B, int N, int C, int H, int W, int radius,
+                          double near, double far, int occlusion_radius, double occlusion_rel, int occlusion_count, int fill_radius,
+                          int fill_min, int background, unsigned char* out_color, float* out_depth, int* out_index,
+                          unsigned char* out_mask, int* out_stats, void* workspace, long workspace_bytes, void* stream) {
+  return render_points_launch(points, colors, counts, valid, cameras, R, t, B, N, C, H, W, radius, near, far, occlusion_radius,
+                              occlusion_rel, occlusion_count, fill_radius, fill_min, background, out_color, out_depth, out_index,
+                              out_mask, out_stats, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
 }
 // ---- ground-truth warp from depth and dense EPE / PCK metrics (gt_warp.hip)
 int roma_op_warp_kpts(const void* kpts, int kpts_f64, int grid_h, int grid_w, const float* depth0, const float* depth1, const double* T,

@@ -539,6 +539,15 @@ class RegressionMatcher:
                                     view_valid=rec.view_ok, **(fusion or {}))
         return fused, rec, tr, kp
 
+    def render_fusion(self, fusion, K, R, t, H, W, **kw):
+        """The cloud of a `DenseFusion` without a batch axis (`fuse_image_set`, `dense_reconstruct_image_set`) rendered into C
+        cameras: `roma_amd.render_points(fusion.points, K, R, t, H, W, colors=fusion.colors, counts=fusion.counts, **kw)`.  K
+        [C, 3, 3] or [3, 3] in pixels of the H x W frames, R [C, 3, 3], t [C, 3] in the frame of the cloud (`roma_amd.orbit_cameras`
+        makes a turntable of them).  Returns `roma_amd.PointRender`: the depth is what `lift_matches` / `localize` and
+        `dense_metrics` take for a camera that looks at the whole model.  Nothing is read back."""
+        from .point_render import render_points
+        return render_points(fusion.points, K, R, t, H, W, colors=fusion.colors, counts=fusion.counts, **kw)
+
     # ------------------------------------------------------------------ forward / forward_symmetric / backbone features
     _SCALES = (16, 8, 4, 2, 1)
     _FEAT_C = {16: 1024, 8: 512, 4: 256, 2: 128, 1: 64}
