@@ -6,6 +6,9 @@
 
 namespace roma {
 
+// x rounded up to the 256-byte alignment of every workspace region
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
 class Arena {
  public:
   char* base = nullptr;
@@ -17,7 +20,7 @@ class Arena {
   bool overflow = false;
   void reset() { off = 0; }
   void* alloc(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
+    off = align256(off);
     if (!dry && off + bytes > cap) {
       overflow = true;
       if (off > peak) peak = off;

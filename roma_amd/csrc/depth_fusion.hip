@@ -23,14 +23,17 @@
 
 #include <algorithm>
 
+#include "arena.h"
+#include "workgroup.h"
+
 // nothing here is fused: tools/depth_fusion_ref.py evaluates the same expressions in the same order
 #pragma clang fp contract(off)
 
 namespace roma {
 namespace {
 
-constexpr int FUSE_BLOCK = 256, FUSE_WAVES = FUSE_BLOCK / 64;
-constexpr int FUSE_SCAN = 1024, FUSE_SCAN_WAVES = FUSE_SCAN / 64;
+constexpr int FUSE_BLOCK = 256, FUSE_WAVES = FUSE_BLOCK / WAVE;
+constexpr int FUSE_SCAN = 1024, FUSE_SCAN_WAVES = FUSE_SCAN / WAVE;
 
 struct FuseParams {
   const float* points;
@@ -75,24 +78,6 @@ struct FView {
   double fx, fy, cx, cy, r[9], t[3];
   int on;
 };
-
-size_t fuse_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// One integer atomic per workgroup that has something to count: the waves' ballots meet in LDS first.  (One per wave was
-// measured: 93 000 waves adding to the two counters of one problem took 2 ms a kernel, forty times the rest of its work.)
-// Every thread of the workgroup calls it; wc holds one int per wave.
-__device__ __forceinline__ void fuse_count(int* dst, bool pred, int* wc) {
-  const int n = __popcll(__ballot(pred));
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < FUSE_WAVES; ++w) s += wc[w];
-    if (s) atomicAdd(dst, s);
-  }
-  __syncthreads();
-}
 
 __device__ __forceinline__ bool fuse_problem_on(const FuseParams& F, int b) { return !F.valid || F.valid[b] != 0; }
 __device__ __forceinline__ bool fuse_view_on(const FuseParams& F, int b, int v) {
@@ -192,8 +177,8 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_select_kernel(const FuseParam
   }
   const bool fused = best_n >= F.min_support;
   int* stats = F.stats + (long)b * FUSE_STATS;
-  fuse_count(stats + 0, usable != 0, wc);
-  fuse_count(stats + 1, in && fused, wc);
+  wg_count_add<FUSE_WAVES>(stats + 0, usable != 0, wc);
+  wg_count_add<FUSE_WAVES>(stats + 1, in && fused, wc);
   if (!in) return;
   const long at = ((long)b * F.V + v) * n + q;
   F.depth[at] = fused ? (float)(best_num / best_s) : __int_as_float(0x7fc00000);
@@ -238,8 +223,8 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_check_kernel(const FuseParams
   }
   const bool keep = fused && __popc(seen) >= F.min_consistent && __popc(violated) <= F.max_violations;
   int* stats = F.stats + (long)b * FUSE_STATS;
-  fuse_count(stats + 2, keep, wc);
-  fuse_count(stats + 5, violated != 0, wc);
+  wg_count_add<FUSE_WAVES>(stats + 2, keep, wc);
+  wg_count_add<FUSE_WAVES>(stats + 5, violated != 0, wc);
   if (!in) return;
   const long at = map0 + (long)v * n + q;
   F.seen[at] = (unsigned char)seen;
@@ -272,44 +257,24 @@ __global__ __launch_bounds__(FUSE_BLOCK) void fuse_dedupe_kernel(const FuseParam
       if (F.keep[map0 + (long)u * n + ((long)ny * F.W + (long)nx)] != 0) dup = true;
     }
   }
-  fuse_count(F.stats + (long)b * FUSE_STATS + 3, dup, wcnt);
+  wg_count_add<FUSE_WAVES>(F.stats + (long)b * FUSE_STATS + 3, dup, wcnt);
   if (in) F.state[at] = (unsigned char)((keep ? 1 : 0) | (dup ? 2 : 0));
-  const int cnt = __popcll(__ballot(keep && !dup));
-  if ((t & 63) == 0) wcnt[t >> 6] = cnt;
-  __syncthreads();
-  if (t == 0) {
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < FUSE_WAVES; ++w) s += wcnt[w];
-    F.bsum[((long)b * F.V + v) * F.nb + blockIdx.x] = s;
-  }
+  const int cnt = wg_count<FUSE_WAVES>(keep && !dup, wcnt);
+  if (t == 0) F.bsum[((long)b * F.V + v) * F.nb + blockIdx.x] = cnt;
 }
 
 // one workgroup per problem: bsum becomes its own exclusive prefix in block order (view-major)
 __global__ __launch_bounds__(FUSE_SCAN) void fuse_scan_kernel(const FuseParams F) {
   __shared__ int wt[FUSE_SCAN_WAVES];
-  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int b = blockIdx.x, t = threadIdx.x;
   const int nblk = F.V * F.nb, per = (nblk + FUSE_SCAN - 1) / FUSE_SCAN;
   int* bs = F.bsum + (long)b * nblk;
   const int lo = std::min(t * per, nblk), hi = std::min(lo + per, nblk);
   int mine = 0;
 #pragma unroll 1
   for (int i = lo; i < hi; ++i) mine += bs[i];
-  int inc = mine;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(inc, off);
-    inc += lane >= off ? up : 0;
-  }
-  if (lane == 63) wt[wave] = inc;
-  __syncthreads();
-  int before = 0, sum = 0;
-#pragma unroll
-  for (int w = 0; w < FUSE_SCAN_WAVES; ++w) {
-    before += w < wave ? wt[w] : 0;
-    sum += wt[w];
-  }
-  before += inc - mine;
+  int sum;
+  int before = wg_scan_exclusive<FUSE_SCAN_WAVES>(mine, wt, sum);
 #pragma unroll 1
   for (int i = lo; i < hi; ++i) {
     const int cnt = bs[i];
@@ -327,22 +292,20 @@ __global__ __launch_bounds__(FUSE_SCAN) void fuse_scan_kernel(const FuseParams F
 __global__ __launch_bounds__(FUSE_BLOCK) void fuse_emit_kernel(const FuseParams F, const FuseColors C) {
   __shared__ FView sv[FUSE_MAX_VIEWS];
   __shared__ int wcnt[FUSE_WAVES];
-  const int v = blockIdx.y, b = blockIdx.z, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int v = blockIdx.y, b = blockIdx.z, t = threadIdx.x;
   fuse_stage_views(F, b, sv);
   const int n = F.H * F.W, q = blockIdx.x * FUSE_BLOCK + t;
   const bool in = q < n;
   const long at = ((long)b * F.V + v) * n + q;
   const bool emit = in && F.state[at] == 1;
-  const unsigned long long bal = __ballot(emit);
-  if (lane == 0) wcnt[wave] = __popcll(bal);
-  __syncthreads();
   const int blk = v * F.nb + blockIdx.x;
+  const int before = F.bsum[(long)b * F.V * F.nb + blk];  // emitted by the earlier blocks; the load flies during the rank's barrier
+  int emitted;  // of the block: not needed
+  const int in_block = wg_rank<FUSE_WAVES>(emit, wcnt, emitted);
   const float nanf_ = __int_as_float(0x7fc00000);
   const long cloud = (long)b * F.max_points;
   if (emit) {
-    int rank = F.bsum[(long)b * F.V * F.nb + blk] + __popcll(bal & ((1ull << lane) - 1ull));
-#pragma unroll
-    for (int w = 0; w < FUSE_WAVES; ++w) rank += w < wave ? wcnt[w] : 0;
+    const int rank = before + in_block;
     if (rank < F.max_points) {
       const int r = q / F.W, c = q - r * F.W;
       double X[3];
@@ -418,8 +381,8 @@ FuseLayout fuse_layout(int B, int V, int H, int W) {
   const long n = (long)H * W, nb = (n + FUSE_BLOCK - 1) / FUSE_BLOCK;
   FuseLayout L;
   size_t at = 0;
-  L.keep = at, at += fuse_align((size_t)B * V * n);
-  L.bsum = at, at += fuse_align((size_t)B * V * nb * sizeof(int));
+  L.keep = at, at += align256((size_t)B * V * n);
+  L.bsum = at, at += align256((size_t)B * V * nb * sizeof(int));
   L.bytes = at + 256;  // the base is aligned to 256 inside what the caller gives
   return L;
 }

@@ -3,6 +3,8 @@
 
 #include <algorithm>
 
+#include "workgroup.h"
+
 namespace roma {
 
 // ------------------------------------------------------------------ bilinear sampling of (warp_B, certainty) at points
@@ -176,29 +178,18 @@ __global__ __launch_bounds__(256) void mutual_pairs_kernel(const float* __restri
   if (MODE == 0 && i < na) offs[i + 1] = n;
 }
 
-// in-place inclusive scan of v[1 .. n] (v[0] = 0): one workgroup, 1024-element chunks
+// in-place inclusive scan of v[1 .. n] (v[0] = 0): one workgroup, 1024-element chunks, wg_scan_exclusive per chunk and a running carry
 __global__ __launch_bounds__(1024) void scan_inclusive_kernel(long long* __restrict__ v, long n) {
-  __shared__ long long part[1024];
-  __shared__ long long carry;
-  if (threadIdx.x == 0) {
-    carry = 0;
-    v[0] = 0;
-  }
-  __syncthreads();
+  __shared__ long long wsum[1024 / WAVE];
+  if (threadIdx.x == 0) v[0] = 0;
+  long long carry = 0;
   for (long c0 = 1; c0 <= n; c0 += 1024) {
     const long idx = c0 + threadIdx.x;
-    part[threadIdx.x] = idx <= n ? v[idx] : 0;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-      const long long add = threadIdx.x >= (unsigned)off ? part[threadIdx.x - off] : 0;
-      __syncthreads();
-      part[threadIdx.x] += add;
-      __syncthreads();
-    }
-    if (idx <= n) v[idx] = part[threadIdx.x] + carry;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += part[1023];
-    __syncthreads();
+    const long long x = idx <= n ? v[idx] : 0;
+    long long tot;
+    const long long before = wg_scan_exclusive<1024 / WAVE>(x, wsum, tot);
+    if (idx <= n) v[idx] = carry + before + x;
+    carry += tot;
   }
 }
 

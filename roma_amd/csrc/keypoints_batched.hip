@@ -29,6 +29,8 @@
 
 #include <algorithm>
 
+#include "workgroup.h"
+
 namespace roma {
 namespace {
 
@@ -248,17 +250,16 @@ __global__ __launch_bounds__(KP_THREADS) void kp_pairs_kernel(const KpParams A) 
 
 // ------------------------------------------------------------------ 4. positions, counts and the padding rows; grid (B)
 // One workgroup per pair walks the (row, slice) entries in chunks of 1024 consecutive ones (coalesced loads and stores, the next
-// chunk's loads issued before this chunk's scan): a shuffle scan per wave, the 16 wave totals through LDS, a running carry.  An
-// entry of a slice that starts at or beyond nb was never written and counts as 0.
+// chunk's loads issued before this chunk's scan): wg_scan_exclusive per chunk and a running carry.  An entry of a slice that starts
+// at or beyond nb was never written and counts as 0.
 __global__ __launch_bounds__(1024) void kp_scan_kernel(const KpParams A) {
-  __shared__ long long wsum[16];
+  __shared__ long long wsum[1024 / WAVE];
   const int b = blockIdx.x;
   const long na = pair_rows(A.counts_a, b, A.NA), nb = pair_rows(A.counts_b, b, A.NB);
   const int S = A.cnt_slices;
   const int live_slices = (int)min((long)S, (nb + A.cnt_per - 1) / A.cnt_per);
   long long* offs = A.offs + (long)b * A.NA * S;
   const long n = na * S;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   auto load = [&](long k) -> long long { return (k < n && (int)((unsigned)k % (unsigned)S) < live_slices) ? offs[k] : 0; };  // n <= 2^23
   long long carry = 0;
   long long v_next = load(threadIdx.x);
@@ -266,23 +267,9 @@ __global__ __launch_bounds__(1024) void kp_scan_kernel(const KpParams A) {
     const long k = c0 + threadIdx.x;
     const long long v = v_next;
     v_next = load(k + 1024);  // the next chunk's loads fly during this chunk's scan; its entries are not rewritten yet
-    long long x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const long long y = __shfl_up(x, off);
-      if (lane >= off) x += y;
-    }
-    __syncthreads();  // the previous chunk's readers are done with wsum
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    long long before = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) {
-      const long long t = wsum[w];
-      if (w < wave) before += t;
-      tot += t;
-    }
-    if (k < n) offs[k] = carry + before + x - v;
+    long long tot;
+    const long long before = wg_scan_exclusive<1024 / WAVE>(v, wsum, tot);
+    if (k < n) offs[k] = carry + before;
     carry += tot;
   }
   const long long total = carry;

@@ -25,6 +25,9 @@
 
 #include <algorithm>
 
+#include "arena.h"
+#include "workgroup.h"
+
 // nothing here is fused: tools/point_render_ref.py evaluates the same expressions in the same order
 #pragma clang fp contract(off)
 
@@ -33,7 +36,7 @@ namespace {
 
 typedef unsigned long long u64;
 
-constexpr int RND_BLOCK = 256, RND_WAVES = RND_BLOCK / 64;
+constexpr int RND_BLOCK = 256, RND_WAVES = RND_BLOCK / WAVE;
 constexpr u64 RND_EMPTY = ~0ull;
 
 struct RenderParams {
@@ -56,23 +59,6 @@ struct RenderParams {
   u64* key;            // [B, C, H, W] workspace: the z-buffer
   unsigned char* dec;  // [B, C, H, W] workspace: bit 0 hit, bit 1 removed
 };
-
-size_t render_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// One integer atomic per workgroup that has something to count (depth_fusion.hip's fuse_count): every thread of the workgroup
-// calls it; wc holds one int per wave.
-__device__ __forceinline__ void render_count(int* dst, bool pred, int* wc) {
-  const int n = __popcll(__ballot(pred));
-  if ((threadIdx.x & 63) == 0) wc[threadIdx.x >> 6] = n;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < RND_WAVES; ++w) s += wc[w];
-    if (s) atomicAdd(dst, s);
-  }
-  __syncthreads();
-}
 
 __device__ __forceinline__ float render_key_depth(u64 key) { return __uint_as_float((unsigned)(key >> 32)); }
 
@@ -138,7 +124,7 @@ __global__ __launch_bounds__(RND_BLOCK) void render_splat_kernel(const RenderPar
       }
     }
   }
-  render_count(P.stats + frame * RENDER_STATS + 0, usable && r0 >= 0 && r0 < P.H && c0 >= 0 && c0 < P.W, wc);
+  wg_count_add<RND_WAVES>(P.stats + frame * RENDER_STATS + 0, usable && r0 >= 0 && r0 < P.H && c0 >= 0 && c0 < P.W, wc);
 }
 
 __global__ __launch_bounds__(RND_BLOCK) void render_filter_kernel(const RenderParams P) {
@@ -166,8 +152,8 @@ __global__ __launch_bounds__(RND_BLOCK) void render_filter_kernel(const RenderPa
     removed = nearer >= P.occ_count;
   }
   int* stats = P.stats + frame * RENDER_STATS;
-  render_count(stats + 1, hit, wc);
-  render_count(stats + 2, removed, wc);
+  wg_count_add<RND_WAVES>(stats + 1, hit, wc);
+  wg_count_add<RND_WAVES>(stats + 2, removed, wc);
   if (in) P.dec[frame * npx + q] = (unsigned char)((hit ? 1 : 0) | (removed ? 2 : 0));
 }
 
@@ -201,7 +187,7 @@ __global__ __launch_bounds__(RND_BLOCK) void render_fill_kernel(const RenderPara
     filled = alive >= P.fill_min;
     if (filled) key = best;
   }
-  render_count(P.stats + frame * RENDER_STATS + 3, filled, wc);
+  wg_count_add<RND_WAVES>(P.stats + frame * RENDER_STATS + 3, filled, wc);
   if (!in) return;
   const long at = frame * npx + q;
   const bool have = key != RND_EMPTY;
@@ -232,7 +218,7 @@ bool render_sizes_ok(int B, int C, int H, int W) {
 size_t render_points_workspace_bytes(int B, int C, int H, int W) {
   if (!render_sizes_ok(B, C, H, W)) return 0;
   const size_t npx = (size_t)B * C * H * W;
-  return render_align(npx * sizeof(u64)) + render_align(npx) + 256;  // the base is aligned to 256 inside what the caller gives
+  return align256(npx * sizeof(u64)) + align256(npx) + 256;  // the base is aligned to 256 inside what the caller gives
 }
 
 int render_points_launch(const float* points, const unsigned char* colors, const int* counts, const unsigned char* valid,
@@ -262,7 +248,7 @@ int render_points_launch(const float* points, const unsigned char* colors, const
   const size_t npx = (size_t)B * C * H * W;
   char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
   P.key = reinterpret_cast<u64*>(base);
-  P.dec = reinterpret_cast<unsigned char*>(base + render_align(npx * sizeof(u64)));
+  P.dec = reinterpret_cast<unsigned char*>(base + align256(npx * sizeof(u64)));
   P.points = points, P.colors = colors, P.counts = counts, P.valid = valid, P.cam = cameras, P.R = R, P.t = t;
   P.B = B, P.N = N, P.C = C, P.H = H, P.W = W;
   P.radius = radius, P.occ_radius = occlusion_radius, P.occ_count = occlusion_count, P.fill_radius = fill_radius, P.fill_min = fill_min;

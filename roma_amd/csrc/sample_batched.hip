@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "sampling.h"
+#include "workgroup.h"
 
 namespace roma {
 namespace {
@@ -40,6 +41,7 @@ struct PairState {      // one per pair and draw, at the head of the workspace
 constexpr int TIE_CHUNK = 2048;   // indices per workgroup of the tie count
 constexpr int KDE_TILE = 1024;    // reference rows per LDS tile
 constexpr int KDE_MAX_SLICES = 8;
+constexpr int TIE_WAVES = 256 / WAVE;  // of the workgroup that finds the cut
 
 __device__ __forceinline__ float round_to_half(float v) { return (float)(_Float16)v; }
 
@@ -58,29 +60,6 @@ __device__ __forceinline__ float race_key(float w, uint64_t seed, long i) {
 // (key bits, index): ordered like (key, index) for the non-negative keys of the race
 __device__ __forceinline__ unsigned long long pack_key(float key, int idx) {
   return ((unsigned long long)__float_as_uint(key) << 32) | (unsigned long long)(unsigned)idx;
-}
-
-// inclusive prefix sum of v over the 256 threads of the workgroup; wtot: 4 words of LDS
-__device__ __forceinline__ unsigned block_scan_incl(unsigned v, unsigned* wtot, unsigned* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned x = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned y = __shfl_up(x, off);
-    if (lane >= off) x += y;
-  }
-  __syncthreads();  // the previous call's readers are done with wtot
-  if (lane == 63) wtot[wave] = x;
-  __syncthreads();
-  unsigned before = 0, tot = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    const unsigned t = wtot[w];
-    if (w < wave) before += t;
-    tot += t;
-  }
-  *total = tot;
-  return x + before;
 }
 
 // grid (8, B): clears the pair's histogram and sets the states of both draws
@@ -177,7 +156,7 @@ __global__ __launch_bounds__(256) void sample_tie_count_kernel(const float* __re
 // one workgroup per pair: the index `cut` with exactly ties_left keys equal to T at indices <= cut; grid (1, B)
 __global__ __launch_bounds__(256) void sample_tie_cut_kernel(const float* __restrict__ keys, long n, PairState* st,
                                                              const unsigned* __restrict__ cnt, int nchunks) {
-  __shared__ unsigned wtot[4];
+  __shared__ unsigned wtot[TIE_WAVES];
   __shared__ unsigned found[2];  // the chunk that holds the cut, and how many of its ties are taken
   const int b = blockIdx.y;
   const float* kb = keys + (long)b * n;
@@ -190,9 +169,8 @@ __global__ __launch_bounds__(256) void sample_tie_cut_kernel(const float* __rest
     const int c = c0 + (int)threadIdx.x;
     const unsigned v = c < nchunks ? cb[c] : 0u;
     unsigned total;
-    const unsigned incl = block_scan_incl(v, wtot, &total);
+    const unsigned excl = running + wg_scan_exclusive<TIE_WAVES>(v, wtot, total);
     if (running + total >= need_all) {  // the same for every thread
-      const unsigned excl = running + incl - v;
       if (excl < need_all && need_all <= excl + v) found[0] = (unsigned)c, found[1] = need_all - excl;
       break;
     }
@@ -210,7 +188,7 @@ __global__ __launch_bounds__(256) void sample_tie_cut_kernel(const float* __rest
     const long i = base + r * 256 + threadIdx.x;
     const unsigned f = (i < n && __float_as_uint(kb[i]) == T) ? 1u : 0u;
     unsigned total;
-    const unsigned incl = run + block_scan_incl(f, wtot, &total);
+    const unsigned incl = run + wg_scan_exclusive<TIE_WAVES>(f, wtot, total) + f;
     if (f && incl == need) st[b].cut = (unsigned)i;
     run += total;
   }

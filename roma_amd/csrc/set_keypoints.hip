@@ -34,13 +34,16 @@
 
 #include <algorithm>
 
+#include "arena.h"
+#include "workgroup.h"
+
 // nothing here is fused: tools/set_keypoints_ref.py evaluates the same expressions; the one fused multiply-add is written out
 #pragma clang fp contract(off)
 
 namespace roma {
 namespace {
 
-constexpr int SKP_BLOCK = 1024, SKP_WAVES = SKP_BLOCK / 64;  // cells per workgroup of the grid kernels, one thread each
+constexpr int SKP_BLOCK = 1024, SKP_WAVES = SKP_BLOCK / WAVE;  // cells per workgroup of the grid kernels, one thread each
 constexpr int SKP_ROWS = 256;                                // rows per workgroup of the row kernels
 constexpr int SKP_MAX_BLOCKS = (int)(SET_KPTS_MAX_GRID / SKP_BLOCK);  // blocks of one view: the scan keeps them in LDS
 typedef unsigned long long u64;
@@ -69,8 +72,6 @@ struct SkpParams {
   int blk0[ROMA_TRACKS_MAX_VIEWS + 1];  // first block of every view in its problem
   unsigned char pv[ROMA_TRACKS_MAX_PAIRS][2];
 };
-
-size_t skp_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct SkpPoint {
   float x, y;
@@ -125,11 +126,6 @@ __device__ __forceinline__ float2 skp_key_point(const SkpParams& S, int b, u64 k
   return make_float2(((float)W * 0.5f) * (e.x + 1.0f), ((float)H * 0.5f) * (e.y + 1.0f));
 }
 
-__device__ __forceinline__ void skp_count(int* dst, bool pred) {
-  const int n = __popcll(__ballot(pred));
-  if (n && (threadIdx.x & 63) == 0) atomicAdd(dst, n);
-}
-
 __device__ __forceinline__ int skp_view_of_block(const SkpParams& S, int blk) {
   int v = 0;
 #pragma unroll
@@ -170,8 +166,8 @@ __global__ __launch_bounds__(SKP_ROWS) void skp_scatter_kernel(const SkpParams S
     atomicMax(grid + (long)S.blk0[vb] * SKP_BLOCK + (r.b.cy * S.Gw[vb] + r.b.cx), hi | (u64)(0xFFFFFFFFu - (o + 1u)));
   }
   int* info = S.info + (long)b * SET_KPTS_INFO;
-  skp_count(info + 0, r.read);
-  skp_count(info + 1, r.read && !r.valid);
+  wave_count_add(info + 0, r.read);
+  wave_count_add(info + 1, r.read && !r.valid);
 }
 
 __global__ __launch_bounds__(SKP_BLOCK) void skp_suppress_kernel(const SkpParams S) {
@@ -198,38 +194,9 @@ __global__ __launch_bounds__(SKP_BLOCK) void skp_suppress_kernel(const SkpParams
     surv = !gone;
   }
   S.idx[(long)b * S.GP + (long)blk * SKP_BLOCK + t] = surv ? 0 : -1;
-  skp_count(S.info + (long)b * SET_KPTS_INFO + 5, gone);
-  const int n = __popcll(__ballot(surv));
-  if ((t & 63) == 0) wcnt[t >> 6] = n;
-  __syncthreads();
-  if (t == 0) {
-    int s = 0;
-#pragma unroll
-    for (int w = 0; w < SKP_WAVES; ++w) s += wcnt[w];
-    S.bsum[(long)b * S.NBLK + blk] = s;
-  }
-}
-
-// exclusive prefix of v over the workgroup in thread order, and the sum in every thread; wt holds one int per wave
-__device__ __forceinline__ int skp_block_scan(int v, int* wt, int& sum) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int inc = v;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int up = __shfl_up(inc, off);
-    inc += lane >= off ? up : 0;
-  }
-  __syncthreads();
-  if (lane == 63) wt[wave] = inc;
-  __syncthreads();
-  int before = 0;
-  sum = 0;
-#pragma unroll
-  for (int w = 0; w < SKP_WAVES; ++w) {
-    before += w < wave ? wt[w] : 0;
-    sum += wt[w];
-  }
-  return before + inc - v;
+  wave_count_add(S.info + (long)b * SET_KPTS_INFO + 5, gone);
+  const int n = wg_count<SKP_WAVES>(surv, wcnt);
+  if (t == 0) S.bsum[(long)b * S.NBLK + blk] = n;
 }
 
 __global__ __launch_bounds__(SKP_BLOCK) void skp_scan_kernel(const SkpParams S) {
@@ -246,7 +213,7 @@ __global__ __launch_bounds__(SKP_BLOCK) void skp_scan_kernel(const SkpParams S) 
   int mine = 0, total;
 #pragma unroll
   for (int k = 0; k < PER; ++k) mine += bs[t * PER + k];
-  int before = skp_block_scan(mine, wt, total);
+  int before = wg_scan_exclusive<SKP_WAVES>(mine, wt, total);
   if (t == 0) {
     S.total[(long)b * S.V + v] = total;
     S.num_kpts[(long)b * S.V + v] = min(total, S.K);
@@ -295,7 +262,7 @@ __global__ __launch_bounds__(SKP_BLOCK) void skp_scan_kernel(const SkpParams S) 
     mine = 0;
 #pragma unroll
     for (int k = 0; k < PER; ++k) mine += bs[t * PER + k];
-    before = skp_block_scan(mine, wt, total);
+    before = wg_scan_exclusive<SKP_WAVES>(mine, wt, total);
   }
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
@@ -306,17 +273,14 @@ __global__ __launch_bounds__(SKP_BLOCK) void skp_scan_kernel(const SkpParams S) 
 
 __global__ __launch_bounds__(SKP_BLOCK) void skp_number_kernel(const SkpParams S) {
   __shared__ int wcnt[SKP_WAVES];
-  const int blk = blockIdx.x, b = blockIdx.y, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int blk = blockIdx.x, b = blockIdx.y, t = threadIdx.x;
   const int v = skp_view_of_block(S, blk);
   const long cell = (long)b * S.GP + (long)blk * SKP_BLOCK + t;
   const bool kept = S.idx[cell] == 0;
-  const u64 bal = __ballot(kept);
-  if (lane == 0) wcnt[wave] = __popcll(bal);
-  __syncthreads();
+  int in_block;  // kept cells of the block: not needed
+  const int before = wg_rank<SKP_WAVES>(kept, wcnt, in_block);
   if (!kept) return;
-  int rank = S.bsum[(long)b * S.NBLK + blk] + __popcll(bal & ((1ull << lane) - 1ull));
-#pragma unroll
-  for (int w = 0; w < SKP_WAVES; ++w) rank += w < wave ? wcnt[w] : 0;
+  const int rank = S.bsum[(long)b * S.NBLK + blk] + before;
   S.idx[cell] = rank < S.K ? rank : -1;
   if (rank < S.K) {  // the cut leaves at most K
     const u64 key = S.key[cell];
@@ -363,7 +327,7 @@ __global__ __launch_bounds__(SKP_ROWS) void skp_assign_kernel(const SkpParams S)
     ib = skp_assign(S, b, S.pv[p][1], r.b);
   }
   const bool have = ia >= 0 && ib >= 0;
-  skp_count(S.info + (long)b * SET_KPTS_INFO + 2, r.valid && !have);
+  wave_count_add(S.info + (long)b * SET_KPTS_INFO + 2, r.valid && !have);
   if (n >= S.N) return;
   const long pair = (long)b * S.P + p;
   S.inds[pair * S.N + n] = have ? make_int2(ia, ib) : make_int2(-1, -1);
@@ -388,9 +352,9 @@ __global__ __launch_bounds__(SKP_ROWS) void skp_finish_kernel(const SkpParams S)
     }
   }
   int* info = S.info + (long)b * SET_KPTS_INFO;
-  skp_count(info + 3, lost);
-  skp_count(info + 4, have && !lost);
-  skp_count(S.kept + pair, have && !lost);
+  wave_count_add(info + 3, lost);
+  wave_count_add(info + 4, have && !lost);
+  wave_count_add(S.kept + pair, have && !lost);
 }
 
 struct SkpLayout {
@@ -401,10 +365,10 @@ struct SkpLayout {
 SkpLayout skp_layout(int B, long gp, int P, int K) {
   SkpLayout L;
   size_t at = 0;
-  L.key = at, at += skp_align((size_t)B * gp * sizeof(u64));
-  L.idx = at, at += skp_align((size_t)B * gp * sizeof(int));
-  L.bsum = at, at += skp_align((size_t)B * (gp / SKP_BLOCK) * sizeof(int));
-  L.slot = at, at += skp_align((size_t)B * P * 2 * K * sizeof(u64));
+  L.key = at, at += align256((size_t)B * gp * sizeof(u64));
+  L.idx = at, at += align256((size_t)B * gp * sizeof(int));
+  L.bsum = at, at += align256((size_t)B * (gp / SKP_BLOCK) * sizeof(int));
+  L.slot = at, at += align256((size_t)B * P * 2 * K * sizeof(u64));
   L.bytes = at + 256;  // the base is aligned to 256 inside what the caller gives
   return L;
 }

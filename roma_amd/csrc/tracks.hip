@@ -26,10 +26,13 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "arena.h"
+#include "workgroup.h"
+
 namespace roma {
 namespace {
 
-constexpr int TRK_THREADS = 1024, TRK_WAVES = TRK_THREADS / 64;
+constexpr int TRK_THREADS = 1024, TRK_WAVES = TRK_THREADS / WAVE;
 constexpr int TRK_ARRAYS = 4;  // label, slot, mask, conflict
 
 struct TrkPairs {
@@ -52,26 +55,11 @@ struct TrkParams {
   TrkPairs pv;
 };
 
-size_t trk_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
-long trk_array_ints(int V, int K) { return (long)(trk_align(sizeof(int) * (size_t)V * K) / sizeof(int)); }
+long trk_array_ints(int V, int K) { return (long)(align256(sizeof(int) * (size_t)V * K) / sizeof(int)); }
 
 // A label as memory holds it.  Labels are lowered by atomics, which execute in L2; every read of one goes there too (a relaxed
 // agent-scope load bypasses the CU's L1), so no phase depends on what the L1 does with a line an atomic has rewritten.
 __device__ __forceinline__ int trk_label(const int* lab, int u) { return __hip_atomic_load(lab + u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// sum of v over the workgroup, the same in every thread; sh holds one int per wave
-__device__ __forceinline__ int trk_sum(int v, int* sh) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int w = 0; w < TRK_WAVES; ++w) s += sh[w];
-  return s;
-}
 
 __global__ __launch_bounds__(TRK_THREADS) void build_tracks_kernel(const TrkParams P) {
   __shared__ int nk[ROMA_TRACKS_MAX_VIEWS];
@@ -108,8 +96,8 @@ __global__ __launch_bounds__(TRK_THREADS) void build_tracks_kernel(const TrkPara
       ignored += ok ? 0 : 1;
     }
   }
-  used = trk_sum(used, sh);
-  ignored = trk_sum(ignored, sh);
+  used = wg_sum<TRK_WAVES>(used, sh);
+  ignored = wg_sum<TRK_WAVES>(ignored, sh);
 
   // labels: min-label hooking and pointer jumping
 #pragma unroll 1
@@ -201,7 +189,7 @@ __global__ __launch_bounds__(TRK_THREADS) void build_tracks_kernel(const TrkPara
     const int r = base + lane;
     const bool is = r < hi && trk_label(lab, r) == r && conf[r] == 0 && __popc(mask[r]) >= P.min_views;
     const unsigned long long bal = __ballot(is);
-    if (r < hi) slot[r] = is ? first + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
+    if (r < hi) slot[r] = is ? first + wave_rank(bal) : -1;
     first += __popcll(bal);
   }
 

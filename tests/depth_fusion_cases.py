@@ -137,6 +137,23 @@ def large_ref(max_points=None):
     return ref(large_case(), max_points=max_points)
 
 
+# ---- V = 8 at 184 x 180: 130 blocks a view, 1040 in all - the scan kernel's 1024 threads take two block counts each, the last ones none.
+# A chain of pairs joins the views, so the end views have one slot a pixel: min_support = 1
+WIDE_SEED = 19  # 18 puts a decision within 1.4e-11 of its threshold
+WIDE_PAIRS = [(v, v + 1) for v in range(7)]
+WIDE_CUT = 20000
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case():
+    return operator_case(8, 184, 180, WIDE_PAIRS, WIDE_SEED)
+
+
+@functools.lru_cache(maxsize=None)
+def wide_ref(max_points=None):
+    return ref(wide_case(), min_support=1, max_points=max_points)
+
+
 # ---- a ragged batch of 3 on the random shape: a problem that is not valid, one with a view switched off, one without a usable slot
 RAGGED_SEEDS = (13, 14, 15)
 RAGGED_VALID = (False, True, True)
@@ -322,6 +339,7 @@ def gpu_margins():
     yield "random without certainty", random_ref(0.01, 2, 1, 1, True, False)["margin"]
     yield "random not symmetric", random_ref(0.01, 2, 1, 1, False, True)["margin"]
     yield "large", large_ref()["margin"]
+    yield "wide", wide_ref()["margin"]
     for b, o in enumerate(ragged_refs()):
         yield f"ragged {b}", o["margin"]
     yield "colours", color_ref()["margin"]

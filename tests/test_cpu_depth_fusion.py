@@ -12,8 +12,8 @@ import pytest
 import torch
 
 from conftest import ROOT
-from depth_fusion_cases import (HAND_KW, RANDOM_PAIRS, chain_case, chain_ref_default, check_hand_made, dfr, gpu_margins, hand_made, operator_case,
-                                plane_distance, random_case, ref)
+from depth_fusion_cases import (HAND_KW, RANDOM_PAIRS, WIDE_CUT, chain_case, chain_ref_default, check_hand_made, dfr, gpu_margins, hand_made,
+                                operator_case, plane_distance, random_case, ref, wide_case, wide_ref)
 
 NEW_SYMBOLS = ["roma_op_fuse_depth_maps", "roma_op_fuse_depth_maps_workspace", "roma_op_relative_poses"]
 f32 = np.float32
@@ -207,6 +207,16 @@ def test_margins_of_every_case_the_gpu_file_compares():
     print(f"smallest margin {worst[1]:.3e} ({worst[0]})")
     for name, m in gpu_margins():
         assert m > 1e-9, (name, m)
+
+
+def test_wide_case_has_more_blocks_than_the_scan_has_threads():
+    """the case of the GPU file that gives every thread of the scan kernel two block counts: more than 1024 blocks of 256 pixels, a
+    total above the cut, points of the first and of the last view"""
+    c, o = wide_case(), wide_ref()
+    assert 1024 < c["V"] * -(-c["H"] * c["W"] // 256) <= 2048
+    views = o["source"][:o["count"], 0]
+    assert o["total"] > WIDE_CUT and (views == 0).any() and (views == 7).any()
+    assert wide_ref(WIDE_CUT)["count"] == WIDE_CUT and wide_ref(WIDE_CUT)["total"] == o["total"]
 
 
 def test_reference_chain_on_the_scene():

@@ -8,9 +8,9 @@ import numpy as np
 import pytest
 import torch
 
-from depth_fusion_cases import (CHAIN_SIZES, HAND_KW, RAGGED_VALID, RAGGED_VIEW_VALID, RANDOM_PARAMS, chain_case, chain_ref_default, check_hand_made,
-                                color_case, color_ref, dfr, hand_made, large_case, large_ref, ragged_batch, ragged_refs, random_case, random_ref,
-                                ref)
+from depth_fusion_cases import (CHAIN_SIZES, HAND_KW, RAGGED_VALID, RAGGED_VIEW_VALID, RANDOM_PARAMS, WIDE_CUT, chain_case, chain_ref_default,
+                                check_hand_made, color_case, color_ref, dfr, hand_made, large_case, large_ref, ragged_batch, ragged_refs, random_case,
+                                random_ref, ref, wide_case, wide_ref)
 
 pytestmark = pytest.mark.gpu
 
@@ -100,6 +100,18 @@ def test_large_grid_scan_crosses_many_workgroups_and_the_cut(built_lib):
     n = o["total"]
     assert int(d.counts) == n and np.isnan(d.points[n:].cpu().numpy()).all() and bool((d.source[n:] == -1).all())
     assert np.array_equal(_bits(d.points[:n]), _bits(o["points"][:n]))
+
+
+def test_scan_threads_take_two_block_counts_each(built_lib):
+    """V = 8 at 184 x 180: 1040 blocks of pixels for the 1024 threads of the scan kernel - two block counts a thread, none for the
+    last 504 threads; then max_points below total"""
+    c, o = wide_case(), wide_ref()
+    _same_as_ref(_run(c, min_support=1), o)
+    views = o["source"][:o["count"], 0]
+    assert o["total"] > WIDE_CUT and (views == 0).any() and (views == 7).any()
+    d = _run(c, min_support=1, max_points=WIDE_CUT)
+    _same_as_ref(d, wide_ref(WIDE_CUT), "cut")
+    assert int(d.total) == o["total"] and int(d.counts) == WIDE_CUT and np.array_equal(d.source.cpu().numpy(), o["source"][:WIDE_CUT])
 
 
 def test_ragged_batch_equals_single_calls_and_runs_are_identical(built_lib):
