@@ -287,10 +287,9 @@ struct ApRows {
   struct Row { float4 X; float2 x; };
   float4* px;
   float2* pi;
-  static size_t carve(ApRows& r, char* ws, size_t o, size_t rows) {
-    r.px = reinterpret_cast<float4*>(ws + o); o = align256(o + sizeof(float4) * rows);
-    r.pi = reinterpret_cast<float2*>(ws + o); o = align256(o + sizeof(float2) * rows);
-    return o;
+  static void carve(ApRows& r, Workspace256& ws, size_t rows) {
+    r.px = ws.take<float4>(rows);
+    r.pi = ws.take<float2>(rows);
   }
   __device__ ApRows at(long row) const { return {px + row, pi + row}; }
   __device__ Row row(int i, int n) const {

@@ -52,16 +52,14 @@ struct BaCarve {
   size_t bytes;
 };
 
-BaCarve ba_carve(void* ws, int B, int N) {
+BaCarve ba_carve(Workspace256 ws, int B, int N) {
   BaCarve c;
-  char* p = static_cast<char*>(ws);
   const size_t bn = (size_t)B * N;
-  size_t o = 0;
-  c.cur = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * 3 * bn);
-  c.trial = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * 3 * bn);
-  c.blk = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * BA_BLK * bn);
-  c.flag = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * bn);
-  c.bytes = o + 256;
+  c.cur = ws.take<double>(3 * bn);
+  c.trial = ws.take<double>(3 * bn);
+  c.blk = ws.take<double>(BA_BLK * bn);
+  c.flag = ws.take<int>(bn);
+  c.bytes = ws.bytes();
   return c;
 }
 
@@ -667,7 +665,7 @@ __global__ __launch_bounds__(LM_THREADS) void bundle_adjust_kernel(
 }  // namespace
 
 size_t bundle_adjust_workspace_bytes(int B, int V, int N) {
-  return B > 0 && V > 0 && N > 0 ? ba_carve(nullptr, B, N).bytes : 0;
+  return B > 0 && V > 0 && N > 0 ? ba_carve(Workspace256(), B, N).bytes : 0;
 }
 
 int bundle_adjust_launch(const double* points, const float* kpts, const double* K, const double* R_, const double* t,
@@ -682,7 +680,7 @@ int bundle_adjust_launch(const double* points, const float* kpts, const double* 
   ROMA_REQUIRE(thr > 0, "bundle_adjust: threshold must be positive (+inf: plain least squares)");  // false for NaN
   ROMA_REQUIRE(max_steps >= 0 && max_steps <= (1 << 16), "bundle_adjust: need 0 <= max_steps <= 65536");
   ROMA_REQUIRE(ws_bytes >= bundle_adjust_workspace_bytes(B, V, N), "bundle_adjust: workspace too small");
-  const BaCarve c = ba_carve(align_base<void*>(ws), B, N);
+  const BaCarve c = ba_carve(Workspace256(ws), B, N);
   hipLaunchKernelGGL(bundle_adjust_kernel, dim3(B), dim3(LM_THREADS), 0, s, points, reinterpret_cast<const float2*>(kpts), K, R_, t, hold,
                      counts, valid, V, N, thr, max_steps, out_points, out_r, out_t, out_mask, out_info, out_cost, c);
   ROMA_LAUNCH_CHECK();

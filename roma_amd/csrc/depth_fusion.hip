@@ -23,8 +23,9 @@
 
 #include <algorithm>
 
-#include "arena.h"
+#include "pair_views.h"
 #include "workgroup.h"
+#include "workspace.h"
 
 // nothing here is fused: tools/depth_fusion_ref.py evaluates the same expressions in the same order
 #pragma clang fp contract(off)
@@ -373,18 +374,12 @@ __global__ __launch_bounds__(64) void relative_poses_kernel(const RelParams Q) {
   }
 }
 
-struct FuseLayout {
-  size_t keep, bsum, bytes;
-};
-
-FuseLayout fuse_layout(int B, int V, int H, int W) {
+// the workspace regions of F; returns the bytes of the workspace
+size_t fuse_carve(Workspace256 ws, int B, int V, int H, int W, FuseParams& F) {
   const long n = (long)H * W, nb = (n + FUSE_BLOCK - 1) / FUSE_BLOCK;
-  FuseLayout L;
-  size_t at = 0;
-  L.keep = at, at += align256((size_t)B * V * n);
-  L.bsum = at, at += align256((size_t)B * V * nb * sizeof(int));
-  L.bytes = at + 256;  // the base is aligned to 256 inside what the caller gives
-  return L;
+  F.keep = ws.take<unsigned char>((size_t)B * V * n);
+  F.bsum = ws.take<int>((size_t)B * V * nb);
+  return ws.bytes();
 }
 
 bool fuse_sizes_ok(int B, int V, int H, int W) {
@@ -392,22 +387,12 @@ bool fuse_sizes_ok(int B, int V, int H, int W) {
          (long)H * W < (1l << 31) / ((long)B * V);
 }
 
-// pair_views: both views in range and different, no ordered pair twice
-int check_pairs(const char* op, const int* pair_views, int V, int P, unsigned char (*pv)[2]) {
-  for (int p = 0; p < P; ++p) {
-    const int a = pair_views[2 * p], c = pair_views[2 * p + 1];
-    ROMA_REQUIRE(a >= 0 && a < V && c >= 0 && c < V, std::string(op) + ": pair_views entry out of range [0, V)");
-    ROMA_REQUIRE(a != c, std::string(op) + ": pair_views joins a view to itself");
-    pv[p][0] = (unsigned char)a, pv[p][1] = (unsigned char)c;
-  }
-  return 0;
-}
-
 }  // namespace
 
 size_t fuse_depth_maps_workspace_bytes(int B, int V, int H, int W) {
   if (!fuse_sizes_ok(B, V, H, W)) return 0;
-  return fuse_layout(B, V, H, W).bytes;
+  FuseParams F;
+  return fuse_carve(Workspace256(), B, V, H, W, F);
 }
 
 int fuse_depth_maps_launch(const float* points, const unsigned char* flags, const float* certainty, const int* pair_views,
@@ -463,10 +448,7 @@ int fuse_depth_maps_launch(const float* points, const unsigned char* flags, cons
       const int v = F.pv[p][half];
       F.slot[v][F.nslots[v]++] = (unsigned char)(p * 2 + half);  // at most 2 (V - 1): no ordered pair occurs twice
     }
-  const FuseLayout L = fuse_layout(B, V, H, W);
-  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-  F.keep = reinterpret_cast<unsigned char*>(base + L.keep);
-  F.bsum = reinterpret_cast<int*>(base + L.bsum);
+  fuse_carve(Workspace256(ws), B, V, H, W, F);
   F.points = points, F.flags = flags, F.cert = certainty, F.cam = cameras, F.R = R, F.t = t, F.view_valid = view_valid, F.valid = valid;
   F.B = B, F.V = V, F.P = P, F.H = H, F.W = W, F.Wd = Wd;
   F.rel = rel_thresh;

@@ -967,15 +967,13 @@ struct PoseCarve {
   size_t bytes;
 };
 
-PoseCarve pose_carve(void* ws, int B, int N) {
+PoseCarve pose_carve(Workspace256 ws, int B, int N) {
   PoseCarve c;
-  char* p = static_cast<char*>(ws);
-  size_t o = 0;
   const size_t nblk = (N + 255) / 256;
-  c.st = reinterpret_cast<PoseState*>(p + o); o = align256(o + sizeof(PoseState) * B);
-  c.flags = reinterpret_cast<unsigned char*>(p + o); o = align256(o + (size_t)B * N);
-  c.partial = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * 4 * nblk * B);
-  c.bytes = o + 256;
+  c.st = ws.take<PoseState>(B);
+  c.flags = ws.take<unsigned char>((size_t)B * N);
+  c.partial = ws.take<int>(4 * nblk * B);
+  c.bytes = ws.bytes();
   return c;
 }
 
@@ -1023,7 +1021,7 @@ int essential_minimal_launch(const double* x0, const double* x1, int S, double* 
   return 0;
 }
 
-size_t recover_pose_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? pose_carve(nullptr, B, N).bytes : 0; }
+size_t recover_pose_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? pose_carve(Workspace256(), B, N).bytes : 0; }
 
 int recover_pose_launch(const double* E, const float* kpts_a, const float* kpts_b, const unsigned char* mask, const int* counts,
                         const double* K, int B, int N, double distance_thresh, int* out_n, double* out_r, double* out_t,
@@ -1032,7 +1030,7 @@ int recover_pose_launch(const double* E, const float* kpts_a, const float* kpts_
   ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), "recover_pose: need 0 < B <= 65536, 0 < N, B * N < 2^31");
   ROMA_REQUIRE(distance_thresh > 0, "recover_pose: distance_thresh must be positive");
   ROMA_REQUIRE(ws_bytes >= recover_pose_workspace_bytes(B, N), "recover_pose: workspace too small (roma_op_recover_pose_workspace)");
-  const PoseCarve c = pose_carve(align_base<void*>(ws), B, N);
+  const PoseCarve c = pose_carve(Workspace256(ws), B, N);
   const int nblk = (N + 255) / 256;
   hipLaunchKernelGGL(ess_decompose_kernel, dim3((B + 63) / 64), dim3(64), 0, s, E, counts, K, B, N, c.st);
   ROMA_LAUNCH_CHECK();

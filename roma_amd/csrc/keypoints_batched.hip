@@ -30,6 +30,7 @@
 #include <algorithm>
 
 #include "workgroup.h"
+#include "workspace.h"
 
 namespace roma {
 namespace {
@@ -299,30 +300,17 @@ long slices_of(long n, long per) { return std::max<long>(1, (n + per - 1) / per)
 
 bool sizes_ok(int B, long NA, long NB) { return B >= 1 && B <= 65535 && NA >= 0 && NA <= KP_MAX_POINTS && NB >= 0 && NB <= KP_MAX_POINTS; }
 
-struct Layout {
-  size_t p, c, min_a, min_b, offs, total;
-  long cnt_per;
-  int cnt_slices;
-};
-
-Layout layout(int B, long NA, long NB) {
-  Layout L{};
-  size_t off = 0;
-  auto take = [&off](size_t bytes) {
-    const size_t at = off;
-    off += (bytes + 15) & ~(size_t)15;
-    return at;
-  };
+// the count slices and the workspace regions of A; returns the bytes of the workspace
+size_t carve(Workspace16 ws, int B, long NA, long NB, KpParams& A) {
   const size_t b = (size_t)B, na = (size_t)NA, nb = (size_t)NB;
-  L.cnt_per = slice_points(NB, (long)B * blocks_of(NA), KP_COUNT_SLICES);
-  L.cnt_slices = (int)slices_of(NB, L.cnt_per);
-  L.p = take(b * na * 2 * sizeof(float));
-  L.c = take(b * na * sizeof(float));
-  L.min_a = take(b * na * sizeof(unsigned));
-  L.min_b = take(b * nb * sizeof(unsigned));
-  L.offs = take(b * na * (size_t)L.cnt_slices * sizeof(long long));
-  L.total = off;
-  return L;
+  A.cnt_per = slice_points(NB, (long)B * blocks_of(NA), KP_COUNT_SLICES);
+  A.cnt_slices = (int)slices_of(NB, A.cnt_per);
+  A.p = ws.take<float>(b * na * 2);
+  A.c = ws.take<float>(b * na);
+  A.min_a = ws.take<unsigned>(b * na);
+  A.min_b = ws.take<unsigned>(b * nb);
+  A.offs = ws.take<long long>(b * na * (size_t)A.cnt_slices);
+  return ws.bytes();
 }
 
 bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
@@ -331,7 +319,8 @@ bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p
 
 long match_keypoints_workspace_bytes(int B, long NA, long NB) {
   if (!sizes_ok(B, NA, NB)) return -1;
-  return (long)layout(B, NA, NB).total;
+  KpParams A;
+  return (long)carve(Workspace16(), B, NA, NB, A);
 }
 
 int match_keypoints_launch(const float* x_a, const float* x_b, const int* counts_a, const int* counts_b, const float* warp, long warp_bs,
@@ -356,11 +345,9 @@ int match_keypoints_launch(const float* x_a, const float* x_b, const int* counts
                    aligned(total, 8),
                "match_keypoints: a pointer is not aligned to its type");
   ROMA_REQUIRE(max_dist == max_dist && cert_th == cert_th, "match_keypoints: max_dist or cert_th is NaN");
-  const Layout L = layout(B, NA, NB);
-  ROMA_REQUIRE(workspace_bytes >= (long)L.total, "match_keypoints: workspace is too small (roma_op_match_keypoints_workspace)");
-
-  char* base = static_cast<char*>(workspace);
   KpParams A{};
+  ROMA_REQUIRE(workspace_bytes >= (long)carve(Workspace16(workspace), B, NA, NB, A),
+               "match_keypoints: workspace is too small (roma_op_match_keypoints_workspace)");
   A.xa = x_a, A.xb = x_b, A.counts_a = counts_a, A.counts_b = counts_b;
   A.warp = warp, A.warp_bs = warp_bs, A.warp_rs = warp_rs;
   A.cert = certainty, A.cert_bs = cert_bs, A.cert_rs = cert_rs;
@@ -371,10 +358,6 @@ int match_keypoints_launch(const float* x_a, const float* x_b, const int* counts
   A.blocks_a = (int)ga;
   A.nn_per_a = slice_points(NA, (long)B * (ga + gb), 1l << 30);
   A.nn_per_b = slice_points(NB, (long)B * (ga + gb), 1l << 30);
-  A.cnt_slices = L.cnt_slices, A.cnt_per = L.cnt_per;
-  A.p = reinterpret_cast<float*>(base + L.p), A.c = reinterpret_cast<float*>(base + L.c);
-  A.min_a = reinterpret_cast<unsigned*>(base + L.min_a), A.min_b = reinterpret_cast<unsigned*>(base + L.min_b);
-  A.offs = reinterpret_cast<long long*>(base + L.offs);
   A.inds = inds, A.kpts_a = kpts_a, A.kpts_b = kpts_b, A.counts = counts, A.total = total;
   const unsigned nn_slices = (unsigned)std::max(slices_of(NA, A.nn_per_a), slices_of(NB, A.nn_per_b));
 
@@ -385,11 +368,11 @@ int match_keypoints_launch(const float* x_a, const float* x_b, const int* counts
     hipLaunchKernelGGL(kp_nn_kernel, dim3((unsigned)(ga + gb), nn_slices, B), dim3(KP_THREADS), 0, s, A);
     ROMA_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(kp_pairs_kernel<0>, dim3((unsigned)ga, (unsigned)L.cnt_slices, B), dim3(KP_THREADS), 0, s, A);
+  hipLaunchKernelGGL(kp_pairs_kernel<0>, dim3((unsigned)ga, (unsigned)A.cnt_slices, B), dim3(KP_THREADS), 0, s, A);
   ROMA_LAUNCH_CHECK();
   hipLaunchKernelGGL(kp_scan_kernel, dim3(B), dim3(1024), 0, s, A);
   ROMA_LAUNCH_CHECK();
-  hipLaunchKernelGGL(kp_pairs_kernel<1>, dim3((unsigned)ga, (unsigned)L.cnt_slices, B), dim3(KP_THREADS), 0, s, A);
+  hipLaunchKernelGGL(kp_pairs_kernel<1>, dim3((unsigned)ga, (unsigned)A.cnt_slices, B), dim3(KP_THREADS), 0, s, A);
   ROMA_LAUNCH_CHECK();
   return 0;
 }

@@ -26,7 +26,7 @@
 #include "model_refine.h"
 
 #include "geometry.h"
-#include "lm_fit.h"  // and through it ransac.h: mat3, finite_row, align256, align_base; its fp-contract setting holds here as well
+#include "lm_fit.h"  // and through it ransac.h: mat3, finite_row, workspace.h; its fp-contract setting holds here as well
 
 namespace roma {
 namespace {
@@ -423,9 +423,18 @@ int refine_model_run(const double* M, const float2* ka, const float2* kb, const 
   return 0;
 }
 
+// the workspace is the pairs' states; returns its bytes
+size_t model_refine_carve(Workspace256 ws, int B, MrState*& st) {
+  st = ws.take<MrState>(B);
+  return ws.bytes();
+}
+
 }  // namespace
 
-size_t refine_model_workspace_bytes(int B, int N) { return B > 0 && N >= 0 ? align256(sizeof(MrState) * (size_t)B) + 256 : 0; }
+size_t refine_model_workspace_bytes(int B, int N) {
+  MrState* st;
+  return B > 0 && N >= 0 ? model_refine_carve(Workspace256(), B, st) : 0;
+}
 
 int refine_model_launch(int model, const double* M, const float* kpts_a, const float* kpts_b, const int* counts,
                         const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_m, unsigned char* out_mask,
@@ -439,7 +448,8 @@ int refine_model_launch(int model, const double* M, const float* kpts_a, const f
   ROMA_REQUIRE(max_steps >= 0 && max_steps <= (1 << 16), "refine_model: need 0 <= max_steps <= 65536");
   ROMA_REQUIRE(ws_bytes >= refine_model_workspace_bytes(B, N), "refine_model: workspace too small (roma_op_refine_model_workspace)");
   if (B == 0) return 0;
-  MrState* st = align_base<MrState*>(ws);
+  MrState* st;
+  model_refine_carve(Workspace256(ws), B, st);
   const float2* ka = reinterpret_cast<const float2*>(kpts_a);
   const float2* kb = reinterpret_cast<const float2*>(kpts_b);
   return model == RANSAC_HOMOGRAPHY

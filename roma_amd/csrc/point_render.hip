@@ -25,8 +25,8 @@
 
 #include <algorithm>
 
-#include "arena.h"
 #include "workgroup.h"
+#include "workspace.h"
 
 // nothing here is fused: tools/point_render_ref.py evaluates the same expressions in the same order
 #pragma clang fp contract(off)
@@ -213,12 +213,19 @@ bool render_sizes_ok(int B, int C, int H, int W) {
   return B >= 1 && C >= 1 && (long)B * C <= 65535 && H >= 1 && W >= 1 && render_pixels_ok(B, C, H, W);
 }
 
+// the workspace regions of P, one entry per pixel each; returns the bytes of the workspace
+size_t render_carve(Workspace256 ws, size_t npx, RenderParams& P) {
+  P.key = ws.take<u64>(npx);
+  P.dec = ws.take<unsigned char>(npx);
+  return ws.bytes();
+}
+
 }  // namespace
 
 size_t render_points_workspace_bytes(int B, int C, int H, int W) {
   if (!render_sizes_ok(B, C, H, W)) return 0;
-  const size_t npx = (size_t)B * C * H * W;
-  return align256(npx * sizeof(u64)) + align256(npx) + 256;  // the base is aligned to 256 inside what the caller gives
+  RenderParams P;
+  return render_carve(Workspace256(), (size_t)B * C * H * W, P);
 }
 
 int render_points_launch(const float* points, const unsigned char* colors, const int* counts, const unsigned char* valid,
@@ -246,9 +253,7 @@ int render_points_launch(const float* points, const unsigned char* colors, const
   ROMA_REQUIRE(ws && ws_bytes >= render_points_workspace_bytes(B, C, H, W), "render_points: workspace too small");
   RenderParams P = {};
   const size_t npx = (size_t)B * C * H * W;
-  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-  P.key = reinterpret_cast<u64*>(base);
-  P.dec = reinterpret_cast<unsigned char*>(base + align256(npx * sizeof(u64)));
+  render_carve(Workspace256(ws), npx, P);
   P.points = points, P.colors = colors, P.counts = counts, P.valid = valid, P.cam = cameras, P.R = R, P.t = t;
   P.B = B, P.N = N, P.C = C, P.H = H, P.W = W;
   P.radius = radius, P.occ_radius = occlusion_radius, P.occ_count = occlusion_count, P.fill_radius = fill_radius, P.fill_min = fill_min;

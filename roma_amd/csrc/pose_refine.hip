@@ -208,9 +208,18 @@ __global__ __launch_bounds__(256) void pose_refine_mask_kernel(const float2* __r
   mask[(long)b * N + i] = in ? 1 : 0;
 }
 
+// the workspace is the pairs' states; returns its bytes
+size_t pose_refine_carve(Workspace256 ws, int B, LmState*& st) {
+  st = ws.take<LmState>(B);
+  return ws.bytes();
+}
+
 }  // namespace
 
-size_t refine_pose_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? align256(sizeof(LmState) * (size_t)B) + 256 : 0; }
+size_t refine_pose_workspace_bytes(int B, int N) {
+  LmState* st;
+  return B > 0 && N > 0 ? pose_refine_carve(Workspace256(), B, st) : 0;
+}
 
 int refine_pose_launch(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
                        const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
@@ -220,7 +229,8 @@ int refine_pose_launch(const double* R, const double* t, const float* kpts_a, co
   ROMA_REQUIRE(thr > 0 && isfinite(thr), "refine_pose: threshold must be positive and finite");
   ROMA_REQUIRE(max_steps >= 0 && max_steps <= (1 << 16), "refine_pose: need 0 <= max_steps <= 65536");
   ROMA_REQUIRE(ws_bytes >= refine_pose_workspace_bytes(B, N), "refine_pose: workspace too small (roma_op_refine_pose_workspace)");
-  LmState* st = align_base<LmState*>(ws);
+  LmState* st;
+  pose_refine_carve(Workspace256(ws), B, st);
   const float2* ka = reinterpret_cast<const float2*>(kpts_a);
   const float2* kb = reinterpret_cast<const float2*>(kpts_b);
   hipLaunchKernelGGL(pose_refine_kernel, dim3(B), dim3(LM_THREADS), 0, s, R, t, ka, kb, counts, valid, N, thr, max_steps, out_r, out_t,

@@ -52,6 +52,7 @@
 
 #include "common.h"
 #include "sampling.h"
+#include "workspace.h"
 
 // nothing here is fused: the numpy restatements (tools/geometry_ref.py, tools/essential_ref.py) evaluate the same expressions;
 // the scoring is written with explicit fmaf
@@ -286,13 +287,6 @@ __device__ __forceinline__ void store_model(const double* m, long slot, const Sl
   o[2] = make_float4(mf[8], mf[9], mf[10], mf[11]);
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-template <typename T>
-T align_base(void* ws) {  // the caller's workspace need not be 256-aligned: every carve keeps 256 bytes of slack
-  return reinterpret_cast<T>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-}
-
 // ---- In, Rows and the sample load of the two-view models (H, F, E)
 struct PairIn {                 // kpts_a, kpts_b [B, N] pixel (E without a camera matrix: normalised) coordinates
   const float2* a;
@@ -303,10 +297,7 @@ struct PairIn {                 // kpts_a, kpts_b [B, N] pixel (E without a came
 struct PairRows {               // (xa, ya, xb, yb) normalised, [B * N]
   using Row = float4;
   float4* p;
-  static size_t carve(PairRows& r, char* ws, size_t o, size_t rows) {
-    r.p = reinterpret_cast<float4*>(ws + o);
-    return align256(o + sizeof(float4) * rows);
-  }
+  static void carve(PairRows& r, Workspace256& ws, size_t rows) { r.p = ws.take<float4>(rows); }
   __device__ PairRows at(long row) const { return {p + row}; }
   __device__ float4 row(int i, int n) const { return i < n ? p[i] : make_float4(NAN, NAN, NAN, NAN); }
 };
@@ -334,24 +325,24 @@ struct Carve {
   size_t bytes;
 };
 
+// the regions of the pipeline, named once: over Workspace256() for the size, over the caller's pointer for the launches
 template <class M, class Sc>
-Carve<M, Sc> carve(void* ws, int B, int N) {
-  constexpr int SL = M::SLOTS;
+Carve<M, Sc> carve(Workspace256 ws, int B, int N) {
+  const size_t hyp = (size_t)B * R, slots = hyp * M::SLOTS;
   Carve<M, Sc> c;
-  char* p = static_cast<char*>(ws);
-  size_t o = 0;
-  c.st = reinterpret_cast<PairState<M>*>(p + o); o = align256(o + sizeof(PairState<M>) * B);
-  o = M::Rows::carve(c.rows, p, o, (size_t)B * N);
-  c.sl.d = reinterpret_cast<double*>(p + o); o = align256(o + sizeof(double) * M::NM * SL * (size_t)B * R);
-  c.sl.f = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * 12 * SL * (size_t)B * R);
-  c.sl.n = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * (size_t)B * R);
-  c.sl.cnt = reinterpret_cast<int*>(p + o); o = align256(o + sizeof(int) * SL * (size_t)B * R);
-  c.bytes = Sc::carve(c.w, p, o, (size_t)B * R * SL, B) + 256;
+  c.st = ws.take<PairState<M>>(B);
+  M::Rows::carve(c.rows, ws, (size_t)B * N);
+  c.sl.d = ws.take<double>(M::NM * slots);
+  c.sl.f = ws.take<float>(12 * slots);
+  c.sl.n = ws.take<int>(hyp);
+  c.sl.cnt = ws.take<int>(slots);
+  Sc::carve(c.w, ws, slots, B);
+  c.bytes = ws.bytes();
   return c;
 }
 
 template <class M, class Sc>
-size_t workspace_bytes(int B, int N) { return B > 0 && N > 0 ? carve<M, Sc>(nullptr, B, N).bytes : 0; }
+size_t workspace_bytes(int B, int N) { return B > 0 && N > 0 ? carve<M, Sc>(Workspace256(), B, N).bytes : 0; }
 
 // ------------------------------------------------------------------------------------------------------------ shared by the models
 // The f32 scoring of a model is written once, as its residual terms linear in the model (Model::res_terms, NT of them): the
@@ -602,7 +593,7 @@ struct CountScoring {
   template <class M> static constexpr bool INFO_MIN = M::INFO > INFO_CORE;
   template <class M> static constexpr bool REFITS = M::REFINE_ITERS > 0;
   template <class M> static int steps(int refine) { return refine ? M::REFINE_ITERS : 0; }
-  static size_t carve(Ws&, char*, size_t o, size_t, int) { return o; }
+  static void carve(Ws&, Workspace256&, size_t, int) {}
 
   __device__ static Key worst() { return -1; }
   __device__ static bool better(Key a, Key b) { return a > b; }
@@ -677,10 +668,9 @@ struct MagsacScoring {
   template <class M> static constexpr bool INFO_MIN = true;
   template <class M> static constexpr bool REFITS = true;
   template <class M> static int steps(int lo_iters) { return lo_iters; }
-  static size_t carve(Ws& w, char* p, size_t o, size_t slots, int B) {
-    w.ms = reinterpret_cast<MagState*>(p + o); o = align256(o + sizeof(MagState) * B);
-    w.sc = reinterpret_cast<float*>(p + o); o = align256(o + sizeof(float) * slots);
-    return o;
+  static void carve(Ws& w, Workspace256& ws, size_t slots, int B) {
+    w.ms = ws.take<MagState>(B);
+    w.sc = ws.take<float>(slots);
   }
 
   __device__ static Key worst() { return INFINITY; }
@@ -978,7 +968,7 @@ template <class M, class Sc>
 int ransac_run(typename M::In in, const int* counts, const unsigned long long* seeds, const double* K, int B, int N, float thr,
                double conf, int max_iters, int opt, typename M::Out out_model, unsigned char* out_mask, unsigned char* out_ok,
                int* out_info, double* out_score, void* ws, hipStream_t s) {
-  const Carve<M, Sc> c = carve<M, Sc>(align_base<void*>(ws), B, N);
+  const Carve<M, Sc> c = carve<M, Sc>(Workspace256(ws), B, N);
   hipLaunchKernelGGL(ransac_norm_kernel<M>, dim3(B), dim3(256), 0, s, in, counts, K, N, thr, max_iters, c.st, c.rows);
   ROMA_LAUNCH_CHECK();
   if constexpr (Sc::INIT) {

@@ -24,6 +24,7 @@
 
 #include "sampling.h"
 #include "workgroup.h"
+#include "workspace.h"
 
 namespace roma {
 namespace {
@@ -324,34 +325,32 @@ bool sizes(long n, long num, int balanced, Sizes* z) {
   return z->k <= SAMPLE_BATCHED_MAX_K;
 }
 
-struct Layout {
-  size_t st1, st2, hist, cnt, keys1, sel, stage_idx, stage_m, stage_c, partial, keys2, total;
+struct Carve {  // the workspace; stage_*, partial and keys2 only in the balanced modes (NULL otherwise)
+  PairState *st1, *st2;
+  unsigned *hist, *cnt;
+  float *keys1, *stage_m, *stage_c, *partial, *keys2;
+  int *sel, *stage_idx;
+  size_t bytes;
 };
 
-Layout layout(int B, long n, const Sizes& z, int balanced) {
-  Layout L{};
-  size_t off = 0;
-  auto take = [&off](size_t bytes) {
-    const size_t at = off;
-    off += (bytes + 15) & ~(size_t)15;
-    return at;
-  };
+Carve carve(Workspace16 ws, int B, long n, const Sizes& z, int balanced) {
+  Carve c{};
   const size_t b = (size_t)B, k = (size_t)z.k;
-  L.st1 = take(b * sizeof(PairState));
-  L.st2 = take(b * sizeof(PairState));
-  L.hist = take(b * 2048 * sizeof(unsigned));
-  L.cnt = take(b * (size_t)z.chunks * sizeof(unsigned));
-  L.keys1 = take(b * (size_t)n * sizeof(float));
-  L.sel = take(b * k * sizeof(int));
+  c.st1 = ws.take<PairState>(b);
+  c.st2 = ws.take<PairState>(b);
+  c.hist = ws.take<unsigned>(b * 2048);
+  c.cnt = ws.take<unsigned>(b * (size_t)z.chunks);
+  c.keys1 = ws.take<float>(b * (size_t)n);
+  c.sel = ws.take<int>(b * k);
   if (balanced) {
-    L.stage_idx = take(b * k * sizeof(int));
-    L.stage_m = take(b * k * 4 * sizeof(float));
-    L.stage_c = take(b * k * sizeof(float));
-    L.partial = take(b * (size_t)z.slices * k * sizeof(float));
-    L.keys2 = take(b * k * sizeof(float));
+    c.stage_idx = ws.take<int>(b * k);
+    c.stage_m = ws.take<float>(b * k * 4);
+    c.stage_c = ws.take<float>(b * k);
+    c.partial = ws.take<float>(b * (size_t)z.slices * k);
+    c.keys2 = ws.take<float>(b * k);
   }
-  L.total = off;
-  return L;
+  c.bytes = ws.bytes();
+  return c;
 }
 
 // the k smallest of each pair's n keys into sel [B, k] (hist zero on entry and on exit; st holds remaining = k)
@@ -380,7 +379,7 @@ size_t sample_matches_workspace_bytes(int B, long n, long num, int balanced) {
   if (B <= 0 || n <= 0 || num <= 0) return 0;
   Sizes z;
   sizes(n, num, balanced, &z);
-  return layout(B, n, z, balanced).total;
+  return carve(Workspace16(), B, n, z, balanced).bytes;
 }
 
 int sample_matches_launch(const float* matches, const float* certainty, const unsigned long long* seeds, int B, long n, long num,
@@ -396,54 +395,42 @@ int sample_matches_launch(const float* matches, const float* certainty, const un
                "sample_matches: the first draw takes k = min(4 num, n) rows in the balanced modes (min(num, n) otherwise) and k > 65536 "
                "is not batched (num <= 16384 in the balanced modes); use sample() per pair");
   ROMA_REQUIRE(ws, "sample_matches: null pointer (workspace)");
-  const Layout L = layout(B, n, z, balanced);
-  ROMA_REQUIRE(ws_bytes >= L.total, "sample_matches: workspace too small (roma_op_sample_matches_workspace)");
+  const Carve c = carve(Workspace16(ws), B, n, z, balanced);
+  ROMA_REQUIRE(ws_bytes >= c.bytes, "sample_matches: workspace too small (roma_op_sample_matches_workspace)");
   ROMA_REQUIRE((reinterpret_cast<uintptr_t>(matches) & 15) == 0 && (reinterpret_cast<uintptr_t>(out_matches) & 15) == 0 &&
                    (reinterpret_cast<uintptr_t>(ws) & 15) == 0,
                "sample_matches: matches, out_matches and workspace must be 16-byte aligned");
-  char* base = static_cast<char*>(ws);
-  PairState* st1 = reinterpret_cast<PairState*>(base + L.st1);
-  PairState* st2 = reinterpret_cast<PairState*>(base + L.st2);
-  unsigned* hist = reinterpret_cast<unsigned*>(base + L.hist);
-  unsigned* cnt = reinterpret_cast<unsigned*>(base + L.cnt);
-  float* keys1 = reinterpret_cast<float*>(base + L.keys1);
-  int* sel = reinterpret_cast<int*>(base + L.sel);
   const long k = z.k, m = z.m;
   const unsigned gk = (unsigned)((k + 255) / 256);
 
-  hipLaunchKernelGGL(sample_init_kernel, dim3(8, B), dim3(256), 0, s, st1, st2, hist, (unsigned)k, (unsigned)m);
+  hipLaunchKernelGGL(sample_init_kernel, dim3(8, B), dim3(256), 0, s, c.st1, c.st2, c.hist, (unsigned)k, (unsigned)m);
   ROMA_LAUNCH_CHECK();
   hipLaunchKernelGGL(sample_keys_kernel, dim3((unsigned)((n + 255) / 256), B), dim3(256), 0, s, certainty, seeds, n, threshold, thresh,
-                     keys1, st1);
+                     c.keys1, c.st1);
   ROMA_LAUNCH_CHECK();
-  if (int e = select_launch(keys1, n, k, st1, hist, cnt, sel, B, s)) return e;
+  if (int e = select_launch(c.keys1, n, k, c.st1, c.hist, c.cnt, c.sel, B, s)) return e;
   if (!balanced) {  // the first draw is the sample (k = m): the filler already sorts last
-    hipLaunchKernelGGL(sample_order_gather_kernel, dim3(gk, B), dim3(256), 0, s, keys1, n, sel, k, matches, certainty,
-                       (const int*)nullptr, threshold, thresh, out_matches, out_certainty, (int*)nullptr, out_idx, out_first_idx, st1,
+    hipLaunchKernelGGL(sample_order_gather_kernel, dim3(gk, B), dim3(256), 0, s, c.keys1, n, c.sel, k, matches, certainty,
+                       (const int*)nullptr, threshold, thresh, out_matches, out_certainty, (int*)nullptr, out_idx, out_first_idx, c.st1,
                        out_counts, (int)m);
     ROMA_LAUNCH_CHECK();
     return 0;
   }
-  int* stage_idx = reinterpret_cast<int*>(base + L.stage_idx);
-  float* stage_m = reinterpret_cast<float*>(base + L.stage_m);
-  float* stage_c = reinterpret_cast<float*>(base + L.stage_c);
-  float* partial = reinterpret_cast<float*>(base + L.partial);
-  float* keys2 = reinterpret_cast<float*>(base + L.keys2);
-  hipLaunchKernelGGL(sample_order_gather_kernel, dim3(gk, B), dim3(256), 0, s, keys1, n, sel, k, matches, certainty, (const int*)nullptr,
-                     threshold, thresh, stage_m, stage_c, stage_idx, out_first_idx, (long long*)nullptr, st1, (int*)nullptr, (int)m);
+  hipLaunchKernelGGL(sample_order_gather_kernel, dim3(gk, B), dim3(256), 0, s, c.keys1, n, c.sel, k, matches, certainty, (const int*)nullptr,
+                     threshold, thresh, c.stage_m, c.stage_c, c.stage_idx, out_first_idx, (long long*)nullptr, c.st1, (int*)nullptr, (int)m);
   ROMA_LAUNCH_CHECK();
   {
     const float std_ = 0.1f, coef = -1.4426950408889634f / (2.0f * std_ * std_);
     ProfScope ps("sample_kde_kernel", 10.0 * (double)B * (double)k * (double)k, "flop", s);
-    hipLaunchKernelGGL(sample_kde_kernel, dim3(gk, (unsigned)z.slices, B), dim3(256), 0, s, stage_m, k, coef, partial, z.per);
+    hipLaunchKernelGGL(sample_kde_kernel, dim3(gk, (unsigned)z.slices, B), dim3(256), 0, s, c.stage_m, k, coef, c.partial, z.per);
     ROMA_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(sample_density_keys_kernel, dim3(gk, B), dim3(256), 0, s, partial, (int)z.slices, k, stage_c, seeds, keys2,
+  hipLaunchKernelGGL(sample_density_keys_kernel, dim3(gk, B), dim3(256), 0, s, c.partial, (int)z.slices, k, c.stage_c, seeds, c.keys2,
                      out_density);
   ROMA_LAUNCH_CHECK();
-  if (int e = select_launch(keys2, k, m, st2, hist, cnt, sel, B, s)) return e;
-  hipLaunchKernelGGL(sample_order_gather_kernel, dim3((unsigned)((m + 255) / 256), B), dim3(256), 0, s, keys2, k, sel, m, stage_m, stage_c,
-                     stage_idx, 0, 0.f, out_matches, out_certainty, (int*)nullptr, out_idx, (long long*)nullptr, st1, out_counts, (int)m);
+  if (int e = select_launch(c.keys2, k, m, c.st2, c.hist, c.cnt, c.sel, B, s)) return e;
+  hipLaunchKernelGGL(sample_order_gather_kernel, dim3((unsigned)((m + 255) / 256), B), dim3(256), 0, s, c.keys2, k, c.sel, m, c.stage_m, c.stage_c,
+                     c.stage_idx, 0, 0.f, out_matches, out_certainty, (int*)nullptr, out_idx, (long long*)nullptr, c.st1, out_counts, (int)m);
   ROMA_LAUNCH_CHECK();
   return 0;
 }

@@ -34,8 +34,9 @@
 
 #include <algorithm>
 
-#include "arena.h"
+#include "pair_views.h"
 #include "workgroup.h"
+#include "workspace.h"
 
 // nothing here is fused: tools/set_keypoints_ref.py evaluates the same expressions; the one fused multiply-add is written out
 #pragma clang fp contract(off)
@@ -357,20 +358,13 @@ __global__ __launch_bounds__(SKP_ROWS) void skp_finish_kernel(const SkpParams S)
   wave_count_add(S.kept + pair, have && !lost);
 }
 
-struct SkpLayout {
-  size_t key, idx, bsum, slot, bytes;
-};
-
-// the workspace for B problems of at most gp padded cells each
-SkpLayout skp_layout(int B, long gp, int P, int K) {
-  SkpLayout L;
-  size_t at = 0;
-  L.key = at, at += align256((size_t)B * gp * sizeof(u64));
-  L.idx = at, at += align256((size_t)B * gp * sizeof(int));
-  L.bsum = at, at += align256((size_t)B * (gp / SKP_BLOCK) * sizeof(int));
-  L.slot = at, at += align256((size_t)B * P * 2 * K * sizeof(u64));
-  L.bytes = at + 256;  // the base is aligned to 256 inside what the caller gives
-  return L;
+// the workspace regions of S for B problems of at most gp padded cells each; returns the bytes of the workspace
+size_t skp_carve(Workspace256 ws, int B, long gp, int P, int K, SkpParams& S) {
+  S.key = ws.take<u64>((size_t)B * gp);
+  S.idx = ws.take<int>((size_t)B * gp);
+  S.bsum = ws.take<int>((size_t)B * (gp / SKP_BLOCK));
+  S.slot = ws.take<u64>((size_t)B * P * 2 * K);
+  return ws.bytes();
 }
 
 long skp_padded_bound(int V, long G_total) { return ((G_total + SKP_BLOCK - 1) / SKP_BLOCK + V) * SKP_BLOCK; }
@@ -381,7 +375,8 @@ size_t keypoints_from_matches_workspace_bytes(int B, int V, int P, int N, long G
   if (B <= 0 || V <= 0 || V > ROMA_TRACKS_MAX_VIEWS || P < 0 || P > ROMA_TRACKS_MAX_PAIRS || G_total <= 0 || K <= 0 || K > ROMA_TRACKS_MAX_KPTS)
     return 0;
   if (G_total > (long)V * SET_KPTS_MAX_GRID || (long)B * skp_padded_bound(V, G_total) > SET_KPTS_MAX_CELLS) return 0;
-  return skp_layout(B, skp_padded_bound(V, G_total), P, K).bytes;
+  SkpParams S;
+  return skp_carve(Workspace256(), B, skp_padded_bound(V, G_total), P, K, S);
 }
 
 int keypoints_from_matches_launch(const float* matches, const float* certainty, const int* counts, const int* pair_views,
@@ -418,24 +413,13 @@ int keypoints_from_matches_launch(const float* matches, const float* certainty, 
   for (int v = V; v <= ROMA_TRACKS_MAX_VIEWS; ++v) S.blk0[v] = blocks;
   ROMA_REQUIRE((long)B * skp_padded_bound(V, gtot) <= SET_KPTS_MAX_CELLS,
                "keypoints_from_matches: B * (cells of all views + 1024 V) must not exceed 2^28; use a larger cell or fewer problems");
-  for (int p = 0; p < Pn; ++p) {  // checked whether or not a row will be read
-    const int a = pair_views[2 * p], c = pair_views[2 * p + 1];
-    ROMA_REQUIRE(a >= 0 && a < V && c >= 0 && c < V, "keypoints_from_matches: pair_views entry out of range [0, V)");
-    ROMA_REQUIRE(a != c, "keypoints_from_matches: pair_views joins a view to itself");
-    S.pv[p][0] = (unsigned char)a;
-    S.pv[p][1] = (unsigned char)c;
-  }
+  if (int rc = check_pairs("keypoints_from_matches", pair_views, V, Pn, S.pv)) return rc;  // whether or not a row will be read
   if (B == 0) return 0;
   ROMA_REQUIRE(ws && ws_bytes >= keypoints_from_matches_workspace_bytes(B, V, Pn, N, gtot, K), "keypoints_from_matches: workspace too small");
   // laid out for the cells there are: never more than the bound the workspace entry sizes for
   S.GP = (long)blocks * SKP_BLOCK;
   S.NBLK = blocks;
-  const SkpLayout L = skp_layout(B, S.GP, Pn, K);
-  char* base = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-  S.key = reinterpret_cast<u64*>(base + L.key);
-  S.idx = reinterpret_cast<int*>(base + L.idx);
-  S.bsum = reinterpret_cast<int*>(base + L.bsum);
-  S.slot = reinterpret_cast<u64*>(base + L.slot);
+  skp_carve(Workspace256(ws), B, S.GP, Pn, K, S);
   S.matches = reinterpret_cast<const float4*>(matches);
   S.cert = certainty;
   S.counts = counts;

@@ -26,8 +26,9 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "arena.h"
+#include "pair_views.h"
 #include "workgroup.h"
+#include "workspace.h"
 
 namespace roma {
 namespace {
@@ -56,6 +57,14 @@ struct TrkParams {
 };
 
 long trk_array_ints(int V, int K) { return (long)(align256(sizeof(int) * (size_t)V * K) / sizeof(int)); }
+
+// the workspace of P: TRK_ARRAYS padded arrays per problem; returns the bytes of the workspace
+size_t trk_carve(Workspace256 ws, int B, int V, int K, TrkParams& P) {
+  P.per_array = trk_array_ints(V, K);
+  P.per_problem = TRK_ARRAYS * P.per_array;
+  P.ws = ws.take<int>((size_t)B * P.per_problem);
+  return ws.bytes();
+}
 
 // A label as memory holds it.  Labels are lowered by atomics, which execute in L2; every read of one goes there too (a relaxed
 // agent-scope load bypasses the CU's L1), so no phase depends on what the L1 does with a line an atomic has rewritten.
@@ -231,7 +240,8 @@ __global__ __launch_bounds__(TRK_THREADS) void build_tracks_kernel(const TrkPara
 
 size_t build_tracks_workspace_bytes(int B, int V, int K, int P, int M) {
   if (B <= 0 || V <= 0 || K <= 0 || V > ROMA_TRACKS_MAX_VIEWS || K > ROMA_TRACKS_MAX_KPTS) return 0;
-  return (size_t)B * TRK_ARRAYS * trk_array_ints(V, K) * sizeof(int) + 256;
+  TrkParams T;
+  return trk_carve(Workspace256(), B, V, K, T);
 }
 
 int build_tracks_launch(const int* inds, const int* pair_views, const int* match_counts, const int* num_kpts, const float* x, int B,
@@ -251,13 +261,7 @@ int build_tracks_launch(const int* inds, const int* pair_views, const int* match
                    (reinterpret_cast<uintptr_t>(out_kpts) & 7) == 0,
                "build_tracks: inds, x and out_kpts must be 8-byte aligned");
   TrkParams P = {};
-  for (int p = 0; p < Pn; ++p) {  // checked whether or not a row will be read
-    const int a = pair_views[2 * p], c = pair_views[2 * p + 1];
-    ROMA_REQUIRE(a >= 0 && a < V && c >= 0 && c < V, "build_tracks: pair_views entry out of range [0, V)");
-    ROMA_REQUIRE(a != c, "build_tracks: pair_views joins a view to itself");
-    P.pv.v[p][0] = (unsigned char)a;
-    P.pv.v[p][1] = (unsigned char)c;
-  }
+  if (int rc = check_pairs("build_tracks", pair_views, V, Pn, P.pv.v)) return rc;  // whether or not a row will be read
   if (B == 0) return 0;
   ROMA_REQUIRE(K == 0 || (ws && ws_bytes >= build_tracks_workspace_bytes(B, V, K, Pn, M)), "build_tracks: workspace too small");
   P.inds = reinterpret_cast<const int2*>(inds);
@@ -268,9 +272,7 @@ int build_tracks_launch(const int* inds, const int* pair_views, const int* match
   P.tracks = out_tracks;
   P.kpts = reinterpret_cast<float2*>(out_kpts);
   P.counts = out_counts, P.total = out_total, P.info = out_info;
-  P.ws = reinterpret_cast<int*>((reinterpret_cast<uintptr_t>(ws) + 255) & ~(uintptr_t)255);
-  P.per_array = trk_array_ints(V, K);
-  P.per_problem = TRK_ARRAYS * P.per_array;
+  trk_carve(Workspace256(ws), B, V, K, P);
   ProfScope ps("build_tracks_kernel", (double)B * ((double)Pn * M + (double)V * K), "B", s);
   hipLaunchKernelGGL(build_tracks_kernel, dim3(B), dim3(TRK_THREADS), 0, s, P);
   ROMA_LAUNCH_CHECK();

@@ -24,6 +24,7 @@ fixtures are what travels to the GPU box.  Usage:
     python tools/make_goldens.py assets        # tests/golden/pair_{A,B}.png: the decoded pixels of assets/sacre_coeur_{A,B}.jpg
     python tools/make_goldens.py match_path    # RegressionMatcher.match(path, path) / match(PIL, PIL): the transform route
     python tools/make_goldens.py tinyroma_path # TinyRoMa.match(path, path) on the asset pair (A and B of different sizes)
+    ROMA_LIB_DIR=<a build> python tools/make_goldens.py workspace_sizes  # the roma_op_*_workspace byte counts of THAT build
 """
 import json
 import os
@@ -598,6 +599,64 @@ def vis_golden():
     print("visualize_reference.npz", {k: v.shape for k, v in out.items()})
 
 
+# roma_op_<entry>_workspace -> argument tuples.  Every entry: all ones; sizes at which no region is a multiple of 16 or 256
+# bytes; each refusal of its *_workspace_bytes (0, or -1 for match_keypoints); and, where the entry's limits allow a total
+# above 2^32 bytes, one such shape (fuse_depth_maps: B V H W < 2^31 keeps it below, so the largest legal one stands in).
+_PAIRS = [(1, 1), (3, 777), (7, 1001), (1, 255), (13, 4099), (64, 2049), (0, 5), (5, 0), (-1, 5), (5, -1), (0, 0),
+          (65536, 32767), (65536, 100000), (1 << 27, 1)]  # the last two: past what the launches take, 64-bit totals everywhere
+WORKSPACE_SHAPES = {
+    "ransac": _PAIRS, "magsac": _PAIRS, "essential": _PAIRS, "essential_magsac": _PAIRS, "recover_pose": _PAIRS,
+    "refine_pose": _PAIRS, "absolute_pose": _PAIRS, "refine_model": _PAIRS,  # refine_model: N = 0 is a legal size
+    "bundle_adjust": [(1, 1, 1), (3, 2, 777), (7, 8, 1001), (1, 3, 255), (13, 5, 4099), (2, 4, 31), (0, 2, 5), (2, 0, 5), (2, 2, 0),
+                      (-1, 2, 5), (2, -1, 5), (2, 2, -1), (1000, 8, 100000)],
+    # (B, V, K, P, M)
+    "build_tracks": [(1, 1, 1, 1, 1), (3, 2, 777, 1, 100), (7, 8, 1001, 28, 5000), (1, 3, 63, 3, 7), (13, 5, 4099, 10, 0),
+                     (2, 8, 65536, 64, 1), (0, 2, 5, 1, 1), (2, 0, 5, 1, 1), (2, 2, 0, 1, 1), (-1, 2, 5, 1, 1), (2, 9, 5, 1, 1),
+                     (2, 2, 65537, 1, 1), (2, 2, 5, -1, -1), (4096, 8, 65536, 28, 1)],
+    # (B, V, P, N, G_total, K)
+    "keypoints_from_matches": [(1, 1, 1, 1, 1, 1), (3, 2, 1, 777, 1025, 333), (7, 8, 28, 1001, 8 * 4097, 1001), (1, 3, 3, 0, 1023, 63),
+                               (13, 5, 0, 4099, 5 * 300 + 7, 4099), (2, 8, 64, 5, 8 << 22, 65536), (0, 2, 1, 5, 100, 5),
+                               (2, 0, 1, 5, 100, 5), (2, 9, 1, 5, 100, 5), (2, 2, -1, 5, 100, 5), (2, 2, 65, 5, 100, 5),
+                               (2, 2, 1, 5, 0, 5), (2, 2, 1, 5, 100, 0), (2, 2, 1, 5, 100, 65537), (2, 2, 1, 5, (2 << 22) + 1, 5),
+                               (8, 8, 1, 5, 8 << 22, 5), (7, 8, 1, 5, 8 << 22, 5), (60000, 2, 64, 5, 2000, 65536)],
+    # (B, V, H, W)
+    "fuse_depth_maps": [(1, 2, 1, 1), (3, 2, 37, 21), (7, 8, 101, 99), (1, 3, 17, 15), (13, 5, 63, 65), (2, 4, 255, 257), (0, 2, 5, 5),
+                        (65536, 2, 5, 5), (2, 1, 5, 5), (2, 9, 5, 5), (2, 2, 0, 5), (2, 2, 5, 0), (1, 2, 1, (1 << 30) + 1),
+                        (1, 2, 1 << 15, 1 << 15), (1, 2, 32767, 32769), (2, 8, 11585, 11585)],
+    # (B, C, H, W)
+    "render_points": [(1, 1, 1, 1), (3, 2, 37, 21), (7, 8, 101, 99), (1, 3, 17, 15), (13, 5, 63, 65), (2, 4, 255, 257), (0, 1, 5, 5),
+                      (1, 0, 5, 5), (256, 256, 5, 5), (1, 1, 0, 5), (1, 1, 5, 0), (1, 1, 26755, 26755), (1, 1, 26754, 26755),
+                      (1, 1, 26000, 27000)],
+    # (B, n, num, balanced)
+    "sample_matches": [(1, 1, 1, b) for b in (0, 1)] + [(3, 777, 100, b) for b in (0, 1)] + [(7, 100001, 5000, b) for b in (0, 1)] +
+                      [(1, 2049, 4000, b) for b in (0, 1)] + [(13, 4099, 1025, b) for b in (0, 1)] +
+                      [(2, 300000, 16384, 1), (2, 300000, 16385, 1), (2, 300000, 65537, 0), (0, 5, 5, 1), (5, 0, 5, 1), (5, 5, 0, 1),
+                       (-1, 5, 5, 0), (1024, 1 << 21, 10000, 0), (1024, 1 << 21, 10000, 1)],
+    # (B, NA, NB): the count slices change with the tiles of NB (1024 each, at most 8) and with B * ceil(NA / 256) workgroups
+    "match_keypoints": [(1, 1, 1), (1, 0, 0), (3, 777, 333), (1, 1000, 1024), (1, 1000, 1025), (1, 1000, 7168), (1, 1000, 7169),
+                        (1, 1000, 8192), (1, 1000, 8193), (1, 1000, 100001), (1, 256 * 127, 9001), (1, 256 * 128, 9001),
+                        (1, 256 * 128 + 1, 9001), (1, 256 * 146 + 1, 9001), (1, 256 * 512, 9001), (2, 256 * 512, 9001),
+                        (2, 256 * 512 + 1, 9001), (0, 5, 5), (65536, 5, 5), (5, -1, 5), (5, (1 << 20) + 1, 5), (5, 5, -1),
+                        (5, 5, (1 << 20) + 1), (200, 1 << 20, 1 << 20)],
+}
+
+
+def workspace_sizes_golden():
+    """What every roma_op_*_workspace entry of WORKSPACE_SHAPES returns, from both libraries of the build that ROMA_LIB_DIR
+    names (the parent commit's, when a change must keep the byte counts).  No reference and no GPU involved."""
+    from roma_amd import _lib
+    assert os.environ.get("ROMA_LIB_DIR"), "set ROMA_LIB_DIR to the build whose byte counts are the golden ones"
+    rows = []
+    for entry, shapes in WORKSPACE_SHAPES.items():
+        for args in shapes:
+            got = {fmt: int(getattr(_lib.load(fmt), f"roma_op_{entry}_workspace")(*args)) for fmt in ("bf16", "f16")}
+            rows.append({"entry": entry, "args": list(args), "bytes": got})
+    with open(os.path.join(GOLD, "workspace_sizes.json"), "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps(r) for r in rows) + "\n]\n")
+    big = sorted({r["entry"] for r in rows if r["bytes"]["bf16"] > 1 << 32})
+    print("workspace_sizes.json", len(rows), "rows; above 2^32 bytes:", big)
+
+
 if __name__ == "__main__":
     for what in sys.argv[1:]:
-        {"contract": contract, "ops": ops, "ops_nearest": ops_nearest, "tiny": tiny, "small": small, "full": full, "odd": odd, "mega": mega, "full8": full8, "full8_indoor": full8_indoor, "full_coarse": full_coarse, "kde": kde_golden, "keypoints": keypoints_golden, "keypoints_ties": keypoints_ties_golden, "vis": vis_golden, "tinyroma": tinyroma_golden, "tinyroma_xfeat": tinyroma_xfeat_golden, "forward": forward_golden, "assets": assets_golden, "match_path": match_path_golden, "tinyroma_path": tinyroma_path_golden}[what]()
+        {"workspace_sizes": workspace_sizes_golden, "contract": contract, "ops": ops, "ops_nearest": ops_nearest, "tiny": tiny, "small": small, "full": full, "odd": odd, "mega": mega, "full8": full8, "full8_indoor": full8_indoor, "full_coarse": full_coarse, "kde": kde_golden, "keypoints": keypoints_golden, "keypoints_ties": keypoints_ties_golden, "vis": vis_golden, "tinyroma": tinyroma_golden, "tinyroma_xfeat": tinyroma_xfeat_golden, "forward": forward_golden, "assets": assets_golden, "match_path": match_path_golden, "tinyroma_path": tinyroma_path_golden}[what]()
