@@ -450,8 +450,9 @@ int roma_op_recover_pose(const double* E, const float* kpts_a, const float* kpts
  * the others are copied through; thr in normalised units.  Outputs, all DEVICE: R f64 [B, 3, 3], t f64 [B, 3] (the input bits
  * when no step was accepted), mask u8 [B, N] (r^2 < thr^2 under the returned pose and positive depth in both cameras by
  * recoverPose's triangulation; zeros for a pair that is not fitted), info int32 [B, 4] = {accepted steps, cost evaluations,
- * active rows at the end, pair fitted}.  One workgroup per pair runs the whole loop in one launch: no host synchronisation,
- * bit-identical from run to run and independent of B.  workspace: device memory of roma_op_refine_pose_workspace(B, N) bytes. */
+ * active rows at the end, pair fitted (valid, at least 5 rows, finite pose)}.  One workgroup per pair runs the whole loop in
+ * one launch: no host synchronisation, bit-identical from run to run and independent of B.  workspace: device memory of
+ * roma_op_refine_pose_workspace(B, N) bytes. */
 long roma_op_refine_pose_workspace(int B, int N);
 int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
                         const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
@@ -507,9 +508,10 @@ int roma_op_lift_matches(const float* matches, const float* depth_a, const doubl
  * non-finite start or with fewer than two observations is not part of the problem.  Outputs, all DEVICE: points f64 [B, N, 3], R,
  * t (the input bits when no step was accepted, and always for a point outside the problem), mask u8 [B, V, N] (active under
  * the returned state; zeros for a problem that is not fitted), info int32 [B, 6] = {accepted steps, cost evaluations, active
- * rows at the end, points adjusted, free camera parameters, problem fitted}, cost f64 [B, 2] = {start, end}.  The workspace
- * (roma_op_bundle_adjust_workspace bytes, N <= 2^27, B V N < 2^31) holds the current and the trial points.  One workgroup per
- * problem runs the whole loop in one launch; bit-identical from run to run and independent of B. */
+ * rows at the end, points adjusted, free camera parameters, problem fitted}, cost f64 [B, 2] = {start, end} (NaN for a problem
+ * that is not evaluated).  The workspace (roma_op_bundle_adjust_workspace bytes, N <= 2^27, B V N < 2^31) holds the current and
+ * the trial points.  One workgroup per problem runs the whole loop in one launch; bit-identical from run to run and independent
+ * of B. */
 long roma_op_bundle_adjust_workspace(int B, int V, int N);
 int roma_op_bundle_adjust(const double* points, const float* kpts, const double* camera_matrices, const double* R, const double* t,
                           const unsigned char* hold, const int* counts, const unsigned char* valid, int B, int V, int N,

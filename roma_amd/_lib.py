@@ -4,6 +4,9 @@ The 16-bit storage format is a build-time property of the library (csrc/common.h
 libroma_hip.so, `load("f16")` binds libroma_hip_f16.so - the same sources compiled for IEEE binary16, the reference's
 default amp_dtype.  Both export the same symbols; f32-only operators live in either.
 
+The signatures are not restated here: `SIGNATURES` is read from include/roma_hip.h at import (`parse_header`), the
+declarations that the compiler holds every definition in csrc/ to.
+
 There is deliberately NO fallback: if the HIP library is missing or does not export a symbol
 the import fails loudly (the product path never routes through the CPU oracle).
 """
@@ -11,11 +14,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
+import torch
+
+_PKG = os.path.dirname(os.path.abspath(__file__))
 # ROMA_LIB_DIR: A/B runs of tools/ against another BUILD of the same two libraries (e.g. the previous commit's); the product
 # default is the in-tree build next to this file.  There is still no fallback: a missing library raises.
-_HERE = os.environ.get("ROMA_LIB_DIR", _HERE)
+_HERE = os.environ.get("ROMA_LIB_DIR", _PKG)
 LIB_PATH = os.path.join(_HERE, "libroma_hip.so")
 LIB_PATHS = {"bf16": LIB_PATH, "f16": os.path.join(_HERE, "libroma_hip_f16.so")}
 
@@ -36,139 +42,46 @@ class RomaForwardArgs(C.Structure):
                 ("flow", C.c_void_p * 5), ("cert", C.c_void_p * 5), ("feat", C.c_void_p * 5)]
 
 
-_vp, _i, _l, _f = C.c_void_p, C.c_int, C.c_long, C.c_float
+# C type -> ctypes.  `char*` / `const char*` are c_char_p and every other pointer c_void_p (_ctype); nothing else is known.
+_CTYPES = {"int": C.c_int, "long": C.c_long, "float": C.c_float, "double": C.c_double, "long long": C.c_longlong,
+           "unsigned long long": C.c_ulonglong, "roma_handle_t": C.c_void_p}
 
-# symbol -> (restype, argtypes); mirrors include/roma_hip.h one to one
-SIGNATURES = {
-    "roma_last_error": (C.c_char_p, []),
-    "roma_version": (C.c_char_p, []),
-    "roma_h16_format": (_i, []),
-    "roma_abi_stamp": (_i, []),
-    "roma_self_check": (_i, []),
-    "roma_create": (_i, [C.POINTER(RomaConfig), C.POINTER(_vp)]),
-    "roma_set_tensor": (_i, [_vp, C.c_char_p, _i, C.POINTER(C.c_int64), _vp, _i]),
-    "roma_finalize": (_i, [_vp]),
-    "roma_set_option": (_i, [_vp, C.c_char_p, _i]),
-    "roma_set_option_f": (_i, [_vp, C.c_char_p, C.c_double]),
-    "roma_match": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "roma_encoded_bytes": (_l, [_vp]),
-    "roma_encode": (_i, [_vp, _i, _vp, _vp, _vp, _l, _vp]),
-    "roma_match_encoded": (_i, [_vp, _i, _vp, _l, _i, C.POINTER(C.c_int), C.POINTER(C.c_int), _vp, _vp, _vp]),
-    "roma_forward": (_i, [_vp, _i, _vp, _vp, C.POINTER(RomaForwardArgs), _vp]),
-    "roma_debug_fetch": (_l, [_vp, C.c_char_p, _vp, _l]),
-    "roma_debug_trace": (_l, [_vp, _i, _vp, _l, C.c_char_p, _l]),
-    "roma_debug_inject": (_i, [_vp, C.c_char_p, _vp, _l]),
-    "roma_destroy": (_i, [_vp]),
-    "roma_tuning": (_i, [C.c_char_p, _i]),
-    "roma_tuning_describe": (_l, [C.c_char_p, _l]),
-    "roma_debug_gemm_trace": (_l, [_vp, _l]),
-    "roma_vit_forward": (_i, [_vp, _vp]),
-    "roma_op_convert_from_bf16": (_i, [_vp, _vp, _l, _vp]),
-    "roma_profile_enable": (_i, [_i]),
-    "roma_profile_report": (_l, [C.c_char_p, _l]),
-    "roma_op_local_corr": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_local_corr_window": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _l, _i, _i, _vp]),
-    "roma_op_local_corr_window_workspace": (_l, [_i, _i, _i, _i]),
-    "roma_op_local_corr_window_ws": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _l, _i, _i, _vp, _l, _vp]),
-    "roma_op_gemm": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _l, _l, _l, _vp, _vp, _vp, _l, _i, _f, _i, _i, _vp]),
-    "roma_op_conv3x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_conv3x3_slab": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_attention": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_qkv_scatter_gemm": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_layernorm": (_i, [_vp, _vp, _vp, _vp, _l, _i, _f, _i, _vp]),
-    "roma_op_layernorm_dt": (_i, [_vp, _i, _vp, _vp, _vp, _l, _i, _f, _i, _vp]),
-    "roma_op_gemm_res_bf16": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_cholesky_solve_t": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "roma_op_gp": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "roma_op_cls_to_flow": (_i, [_vp, _l, _vp, _vp, _l, _vp]),
-    "roma_op_resize_bilinear": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_refiner_input": (_i, [_vp, _l, _vp, _vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp]),
-    "roma_op_dwconv5x5": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_refiner_block": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_refiner_block_final": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_refiner_apply_delta": (_i, [_vp, _vp, _vp, _l, _f, _f, _vp]),
-    "roma_op_kde": (_i, [_vp, _l, _i, _f, _i, _vp, _vp]),
-    "roma_op_sample_warp_at": (_i, [_vp, _vp, _i, _i, _vp, _l, _vp, _vp, _vp]),
-    "roma_op_mutual_nn": (_i, [_vp, _l, _vp, _l, _vp, _f, _f, _vp, _vp, _vp, _vp]),
-    "roma_op_mutual_nn_count": (_i, [_vp, _l, _vp, _l, _vp, _f, _f, _vp, _vp, _vp, _vp]),
-    "roma_op_mutual_nn_fill": (_i, [_vp, _l, _vp, _l, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]),
-    "roma_op_fb_consistency": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp]),
-    "roma_op_visualize_warp": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "roma_op_multinomial_workspace": (_l, [_l, _l]),
-    "roma_op_multinomial": (_i, [_vp, _l, _l, C.c_ulonglong, _vp, _vp, _l, _vp]),
-    "roma_op_sample_matches_workspace": (_l, [_i, _l, _l, _i]),
-    "roma_op_sample_matches": (_i, [_vp, _vp, _vp, _i, _l, _l, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_ransac_workspace": (_l, [_i, _i]),
-    "roma_op_ransac": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_magsac_workspace": (_l, [_i, _i]),
-    "roma_op_magsac": (_i, [_i, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_essential_workspace": (_l, [_i, _i]),
-    "roma_op_essential": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_essential_magsac_workspace": (_l, [_i, _i]),
-    "roma_op_essential_magsac": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_essential_minimal": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
-    "roma_op_recover_pose_workspace": (_l, [_i, _i]),
-    "roma_op_recover_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_refine_pose_workspace": (_l, [_i, _i]),
-    "roma_op_refine_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_absolute_pose_workspace": (_l, [_i, _i]),
-    "roma_op_absolute_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _f, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_absolute_pose_minimal": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "roma_op_refine_absolute_pose": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
-    "roma_op_lift_matches": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "roma_op_bundle_adjust_workspace": (_l, [_i, _i, _i]),
-    "roma_op_bundle_adjust": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp,
-                                  _vp, _l, _vp]),
-    "roma_op_build_tracks_workspace": (_l, [_i, _i, _i, _i, _i]),
-    "roma_op_build_tracks": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_keypoints_from_matches_workspace": (_l, [_i, _i, _i, _i, _l, _i]),
-    "roma_op_keypoints_from_matches": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                           _vp, _l, _vp]),
-    "roma_op_triangulate_views": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _i, _i, _i,
-                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "roma_op_refine_model_workspace": (_l, [_i, _i]),
-    "roma_op_refine_model": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_triangulate": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _l, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double,
-                                C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "roma_op_depth_consistency": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
-    "roma_op_fuse_depth_maps_workspace": (_l, [_i, _i, _i, _i]),
-    "roma_op_fuse_depth_maps": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, _i, _i,
-                                    _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_relative_poses": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "roma_op_render_points_workspace": (_l, [_i, _i, _i, _i]),
-    "roma_op_render_points": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, _i, C.c_double, _i, _i,
-                                  _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_warp_kpts": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _l, _i, _i, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
-    "roma_op_dense_metrics_workspace": (_l, [_i, _i, _i]),
-    "roma_op_dense_metrics": (_i, [_vp, _l, _l, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double,
-                                  C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_pose_error": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _l, _vp, _vp]),
-    "roma_op_corner_error": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _l, _vp, _vp]),
-    "roma_op_error_log_append": (_i, [_vp, _i, _vp, _l, _vp, _vp]),
-    "roma_op_error_summary": (_i, [_vp, _l, _vp, _l, C.POINTER(C.c_double), _i, _vp, _vp, _vp, _vp, _vp]),
-    "roma_op_render_morph_frame_chunk": (_i, []),
-    "roma_op_render_morph_workspace": (_l, [_i, _i, _i, _l]),
-    "roma_op_render_morph": (_i, [_vp, _l, _l, _vp, _i, _vp, _vp, _l, _l, _f, _i, _l, _i, _i, _i, _i, _vp, _i, _vp, _l, _vp]),
-    "roma_op_match_keypoints_workspace": (_l, [_i, _l, _l]),
-    "roma_op_match_keypoints": (_i, [_vp, _vp, _vp, _vp, _vp, _l, _l, _vp, _l, _l, _vp, _l, _i, _l, _l, _i, _i, _f, _f, _l, _vp, _vp, _vp,
-                                    _vp, _vp, _vp, _l, _vp]),
-    "roma_op_preprocess_workspace": (_l, [_vp, _i, _vp, _i]),
-    "roma_op_preprocess": (_i, [_vp, C.c_longlong, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _vp]),
-    "roma_op_nchw_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "roma_op_tiny_pos_embed": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_gray_instnorm": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _vp]),
-    "roma_op_conv2d_nhwc": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_avgpool_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_add3": (_i, [_vp, _vp, _vp, _vp, _l, _vp]),
-    "roma_op_tiny_matcher_input": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_tiny_update": (_i, [_vp, _i, _vp, _l, _f, _f, _vp, _l, _vp]),
-    "roma_op_tiny_final": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
-    "roma_op_maxpool2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_pool_proj": (_i, [_vp, _vp, _vp, _vp, _l, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "roma_op_conv3x3_c3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "roma_op_conv3x3_c3_bf16": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
-    "roma_op_refiner_out": (_i, [_vp, _l, _i, _vp, _vp, _vp, _vp, _l, _i, _f, _f, _vp]),
-}
+
+def _ctype(text, named, decl):
+    """One return type (named = False) or one parameter with its name of the declaration `decl` as a ctypes type."""
+    words = re.findall(r"\w+|\*", text) if re.fullmatch(r"[\w\s*]+", text) else []  # no function pointer, no array
+    if "*" in words:
+        return C.c_char_p if [w for w in words[:words.index("*")] if w != "const"] == ["char"] else C.c_void_p
+    key = " ".join(w for w in (words[:-1] if named else words) if w != "const")
+    if key not in _CTYPES:
+        raise ImportError(f"roma_hip.h: no ctypes type for `{' '.join(text.split())}` in `{decl}`")
+    return _CTYPES[key]
+
+
+def parse_header(text):
+    """symbol -> (restype, argtypes) of every function that the C header `text` declares.  It reads the narrow subset of C
+    that include/roma_hip.h is written in and raises on anything else: it never guesses a type."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r"\b(typedef\s+struct|enum)\s*\{[^}]*\}[^;]*;|\btypedef\b[^;{]*;", " ", text)
+    text = re.sub(r'extern\s+"C"\s*\{|\}', " ", text)
+    sigs = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"([\w\s*]+?)\s*\b(\w+)\s*\((.*)\)", decl)
+        if not m:
+            raise ImportError(f"roma_hip.h: `{decl}` is not a function declaration")
+        ret, name, params = m.groups()
+        sigs[name] = (_ctype(ret, False, decl), [_ctype(p, True, decl) for p in params.split(",") if params.strip() != "void"])
+    return sigs
+
+
+# symbol -> (restype, argtypes), read from the one declaration of the C ABI.  The header travels with the package (it is looked
+# up next to it, whatever ROMA_LIB_DIR says); without it there is no binding.
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "roma_hip.h")
+if not os.path.exists(HEADER_PATH):
+    raise ImportError(f"{HEADER_PATH} not found - roma_amd reads the signatures of the C ABI from it")
+with open(HEADER_PATH) as _f:
+    SIGNATURES = parse_header(_f.read())
 
 _libs = {}
 
@@ -210,3 +123,17 @@ def check(rc: int, exc=RomaHipError, lib=None):
     if rc != 0:
         raise exc(last_error(lib))
     return rc
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+
+def _stream(dev):
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _device_tensor(x, name, module):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RomaHipError(f"roma_amd.{module}: {name} must be a tensor on a HIP device; there is no CPU fallback")
+    return x.detach()

@@ -11,18 +11,18 @@ OpenCV's adaptive iteration count) followed by a Levenberg-Marquardt fit of the 
 """
 from __future__ import annotations
 
+from functools import partial
+
 import torch
 
 from . import _lib
-from .geometry import _cameras, _counts, _front, _pose_tensor, _ptr, _seeds, _stream, _valid
+from ._lib import _ptr, _stream
+from .geometry import _cameras, _counts, _front, _pose_tensor, _seeds, _valid
 
-SLOTS = 4  # solutions of one P3P sample (csrc/absolute_pose.h)
+SLOTS = 4  # solutions of one P3P sample (csrc/absolute_pose.hip AP_SLOTS)
 
 
-def _device_tensor(x, name):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise _lib.RomaHipError(f"roma_amd.absolute_pose: {name} must be a tensor on a HIP device; there is no CPU fallback")
-    return x
+_device_tensor = partial(_lib._device_tensor, module="absolute_pose")
 
 
 def _rows(points3d, kpts):

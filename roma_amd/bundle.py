@@ -17,14 +17,16 @@ float64 by tools/bundle_ref.py.  x_cam = R X + t.
 """
 from __future__ import annotations
 
+from functools import partial
 from typing import NamedTuple
 
 import torch
 
 from . import _lib
-from .geometry import _counts, _ptr, _stream, _valid
+from ._lib import _ptr, _stream
+from .geometry import _counts, _valid
 
-MAX_VIEWS = 8  # csrc/bundle.h: ROMA_BA_MAX_VIEWS
+MAX_VIEWS = 8  # csrc/bundle.hip: ROMA_BA_MAX_VIEWS
 
 
 class BundleResult(NamedTuple):
@@ -47,10 +49,7 @@ class ViewsReconstruction(NamedTuple):
     cost: torch.Tensor     # [.., 2] float64: `bundle_adjust`'s truncated cost at the start and at the end
 
 
-def _device_tensor(x, name):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise _lib.RomaHipError(f"roma_amd.bundle: {name} must be a tensor on a HIP device; there is no CPU fallback")
-    return x
+_device_tensor = partial(_lib._device_tensor, module="bundle")
 
 
 def _view_cameras(K, B, V, dev):

@@ -25,14 +25,14 @@
 // abs_refine_kernel: lm_fit<AbsPoseFit> (lm_fit.h) on the normalised problem - 6 parameters (R <- exp([w]x) R, t' <- t' + dt),
 // two residuals per row p_xy / z - x_n, a row with z <= 0 or a non-finite value inactive - and the mask of the final pose.
 // lift_kernel: matches + depth map -> 3-D points in camera A's frame and pixel keypoints in B (depth_consistency's bilinear rule).
-#include "absolute_pose.h"
-
+#include "../../include/roma_hip.h"
 #include "lm_fit.h"
 
 namespace roma {
 namespace {
 
-constexpr int AP_SLOTS = ABSOLUTE_POSE_SLOTS;
+constexpr int ABSOLUTE_POSE_INFO = 5;  // ints per pair in roma_op_absolute_pose's out_info
+constexpr int AP_SLOTS = 4;            // solutions of one P3P sample
 constexpr int AP_BISECT = 48, AP_NEWTON = 3, AP_GN = 3;
 constexpr double AP_DEN_EPS = 1e-9;        // |D(v)| below which u = N / D is not formed
 constexpr double AP_COLLINEAR_EPS = 1e-4;  // |d12 x d13| / (|d12| |d13|) below which the 3-D sample is collinear
@@ -592,19 +592,24 @@ __global__ __launch_bounds__(256) void lift_kernel(const float* __restrict__ mat
 
 }  // namespace
 
-size_t absolute_pose_workspace_bytes(int B, int N) { return workspace_bytes<AbsPose, CountScoring>(B, N); }
+extern "C" long roma_op_absolute_pose_workspace(int B, int N) { return workspace_bytes<AbsPose, CountScoring>(B, N); }
 
-int absolute_pose_launch(const float* points3d, const float* kpts, const int* counts, const unsigned long long* seeds, const double* K,
-                         int B, int N, float thr, double conf, int max_iters, double* out_r, double* out_t, unsigned char* out_mask,
-                         unsigned char* out_ok, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_absolute_pose(const float* points3d, const float* kpts, const int* counts, const unsigned long long* seeds,
+                                     const double* K, int B, int N, float thr, double conf, int max_iters, double* out_r, double* out_t,
+                                     unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* ws, long workspace_bytes,
+                                     void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   if (check_args<CountScoring>("absolute_pose", "conf", points3d && kpts && seeds && out_r && out_t && out_mask && out_ok && out_info && ws,
-                               B, N, thr, conf, max_iters, 0, ws_bytes, absolute_pose_workspace_bytes(B, N)))
+                               B, N, thr, conf, max_iters, 0, ws_bytes, (size_t)roma_op_absolute_pose_workspace(B, N)))
     return -1;
   return ransac_run<AbsPose, CountScoring>({points3d, reinterpret_cast<const float2*>(kpts)}, counts, seeds, K, B, N, thr, conf,
                                            max_iters, 0, {out_r, out_t}, out_mask, out_ok, out_info, nullptr, ws, s);
 }
 
-int absolute_pose_minimal_launch(const double* X, const double* x, int S, double* out_r, double* out_t, int* out_n, hipStream_t s) {
+extern "C" int roma_op_absolute_pose_minimal(const double* X, const double* x, int S, double* out_r, double* out_t, int* out_n,
+                                             void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(X && x && out_r && out_t && out_n, "absolute_pose_minimal: null pointer");
   ROMA_REQUIRE(S > 0 && S <= (1 << 24), "absolute_pose_minimal: need 0 < S <= 2^24");
   hipLaunchKernelGGL(ap_minimal_kernel, dim3((S + 63) / 64), dim3(64), 0, s, X, x, S, out_r, out_t, out_n);
@@ -612,9 +617,10 @@ int absolute_pose_minimal_launch(const double* X, const double* x, int S, double
   return 0;
 }
 
-int refine_absolute_pose_launch(const double* R_, const double* t, const float* points3d, const float* kpts, const int* counts,
-                                const unsigned char* valid, const double* K, int B, int N, double thr, int max_steps, double* out_r,
-                                double* out_t, unsigned char* out_mask, int* out_info, hipStream_t s) {
+extern "C" int roma_op_refine_absolute_pose(const double* R_, const double* t, const float* points3d, const float* kpts, const int* counts,
+                                            const unsigned char* valid, const double* K, int B, int N, double thr, int max_steps,
+                                            double* out_r, double* out_t, unsigned char* out_mask, int* out_info, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(R_ && t && points3d && kpts && out_r && out_t && out_mask && out_info, "refine_absolute_pose: null pointer");
   ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16),
                "refine_absolute_pose: need 0 < B <= 65536, 0 < N, B * N < 2^31");
@@ -626,8 +632,9 @@ int refine_absolute_pose_launch(const double* R_, const double* t, const float* 
   return 0;
 }
 
-int lift_matches_launch(const float* matches, const float* depth, const double* K, int B, int N, int H, int W, int H_B, int W_B,
-                        float* out_points, float* out_kpts, hipStream_t s) {
+extern "C" int roma_op_lift_matches(const float* matches, const float* depth, const double* K, int B, int N, int H, int W, int H_B, int W_B,
+                                    float* out_points, float* out_kpts, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(matches && depth && K && out_points && out_kpts, "lift_matches: null pointer");
   ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), "lift_matches: need 0 < B <= 65536, 0 < N, B * N < 2^31");
   ROMA_REQUIRE(H > 0 && W > 0 && H_B > 0 && W_B > 0 && (long)B * H * W < (1l << 40), "lift_matches: need positive image sizes");

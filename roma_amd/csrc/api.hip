@@ -1,4 +1,6 @@
-// extern "C" boundary of libroma_hip (declarations + reference citations: include/roma_hip.h)
+// extern "C" boundary of libroma_hip (declarations + reference citations: include/roma_hip.h): the handle, the library-wide
+// calls and the operator entry points that translate their arguments (dtype codes, argument structs) for a launch function
+// the model calls too.  Every other operator defines its roma_op_* entry points in its own source file.
 #include <algorithm>
 #include <mutex>
 #include <map>
@@ -17,29 +19,8 @@
 #include "gp.h"
 #include "model.h"
 #include "refiner_block.h"
-#include "kde.h"
-#include "keypoints.h"
-#include "keypoints_batched.h"
-#include "tiny.h"
 #include "tuning.h"
 #include "vit.h"
-#include "sampling.h"
-#include "sample_batched.h"
-#include "absolute_pose.h"
-#include "bundle.h"
-#include "essential.h"
-#include "model_refine.h"
-#include "pose_refine.h"
-#include "geometry.h"
-#include "triangulate.h"
-#include "depth_fusion.h"
-#include "point_render.h"
-#include "tracks.h"
-#include "set_keypoints.h"
-#include "gt_warp.h"
-#include "metrics.h"
-#include "morph.h"
-#include "preprocess.h"
 
 namespace roma {
 static thread_local std::string g_err;
@@ -527,321 +508,6 @@ int roma_op_refiner_block_final(const void* in, float* delta, const float* dw_w,
 int roma_op_refiner_apply_delta(const float* delta, float* flow, float* cert, long M, float sx, float sy, void* stream) {
   ROMA_REQUIRE(delta && flow && cert && M >= 0, "roma_op_refiner_apply_delta: null pointer");
   return refiner_apply_delta_launch(delta, flow, cert, M, sx, sy, S(stream));
-}
-
-int roma_op_kde(const float* x, long n, int down, float std, int half_inputs, float* density, void* stream) {
-  return kde_launch(x, n, down, std, half_inputs, density, S(stream));
-}
-
-int roma_op_sample_warp_at(const float* warp, const float* cert, int H, int W, const float* xa, long n, float* xa_to_b,
-                           float* cert_a, void* stream) {
-  return sample_warp_at_launch(warp, cert, H, W, xa, n, xa_to_b, cert_a, S(stream));
-}
-
-int roma_op_mutual_nn(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
-                      int* match_b, void* ws_a, void* ws_b, void* stream) {
-  return mutual_nn_launch(a, na, b, nb, cert_a, cert_th, max_dist, match_b, static_cast<unsigned long long*>(ws_a),
-                          static_cast<unsigned long long*>(ws_b), S(stream));
-}
-
-int roma_op_mutual_nn_count(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
-                            void* ws_a, void* ws_b, long long* offsets, void* stream) {
-  return mutual_nn_count_launch(a, na, b, nb, cert_a, cert_th, max_dist, static_cast<unsigned long long*>(ws_a),
-                                static_cast<unsigned long long*>(ws_b), offsets, S(stream));
-}
-int roma_op_mutual_nn_fill(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
-                           const void* ws_a, const void* ws_b, long long* offsets, long long* pairs, void* stream) {
-  return mutual_nn_fill_launch(a, na, b, nb, cert_a, cert_th, max_dist, static_cast<const unsigned long long*>(ws_a),
-                               static_cast<const unsigned long long*>(ws_b), offsets, pairs, S(stream));
-}
-
-long roma_op_multinomial_workspace(long n, long k) { return (long)multinomial_workspace_bytes(n, k); }
-int roma_op_multinomial(const float* weights, long n, long k, unsigned long long seed, long long* out_indices, void* workspace,
-                        long workspace_bytes, void* stream) {
-  return multinomial_launch(weights, n, k, seed, out_indices, workspace, (size_t)workspace_bytes, S(stream));
-}
-// ---- RegressionMatcher.sample for a batch of pairs (sample_batched.hip)
-long roma_op_sample_matches_workspace(int B, long n, long num, int balanced) {
-  return (long)sample_matches_workspace_bytes(B, n, num, balanced);
-}
-int roma_op_sample_matches(const float* matches, const float* certainty, const unsigned long long* seeds, int B, long n, long num,
-                           int threshold, float thresh, int balanced, float* out_matches, float* out_certainty, int* out_counts,
-                           long long* out_idx, long long* out_first_idx, float* out_density, void* workspace, long workspace_bytes,
-                           void* stream) {
-  return sample_matches_launch(matches, certainty, seeds, B, n, num, threshold, thresh, balanced, out_matches, out_certainty, out_counts,
-                               out_idx, out_first_idx, out_density, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0),
-                               S(stream));
-}
-// ---- batched RANSAC (geometry.hip)
-long roma_op_ransac_workspace(int B, int N) { return (long)ransac_workspace_bytes(B, N); }
-int roma_op_ransac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
-                   int N, float threshold, double confidence, int max_iters, int refine, double* out_model, unsigned char* out_mask,
-                   unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes, void* stream) {
-  return ransac_launch(model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, refine, out_model, out_mask,
-                       out_ok, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-long roma_op_magsac_workspace(int B, int N) { return (long)magsac_workspace_bytes(B, N); }
-int roma_op_magsac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
-                   int N, float threshold, double confidence, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask,
-                   unsigned char* out_ok, int* out_info, double* out_score, void* workspace, long workspace_bytes, void* stream) {
-  return magsac_launch(model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, lo_iters, out_model, out_mask,
-                       out_ok, out_info, out_score, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-// ---- essential matrix and recoverPose (essential.hip)
-long roma_op_essential_workspace(int B, int N) { return (long)essential_workspace_bytes(B, N); }
-int roma_op_essential(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
-                      const double* camera_matrix, int B, int N, float threshold, double prob, int max_iters, double* out_e,
-                      unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* workspace, long workspace_bytes,
-                      void* stream) {
-  return essential_launch(kpts_a, kpts_b, counts, seeds, camera_matrix, B, N, threshold, prob, max_iters, out_e, out_mask, out_ok,
-                          out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-long roma_op_essential_magsac_workspace(int B, int N) { return (long)essential_magsac_workspace_bytes(B, N); }
-int roma_op_essential_magsac(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
-                             const double* camera_matrix, int B, int N, float threshold, double prob, int max_iters, int lo_iters,
-                             double* out_e, unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score,
-                             void* workspace, long workspace_bytes, void* stream) {
-  return essential_magsac_launch(kpts_a, kpts_b, counts, seeds, camera_matrix, B, N, threshold, prob, max_iters, lo_iters, out_e,
-                                 out_mask, out_ok, out_info, out_score, workspace,
-                                 (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-int roma_op_essential_minimal(const double* x0, const double* x1, int S_, double* out_e, int* out_n, void* stream) {
-  return essential_minimal_launch(x0, x1, S_, out_e, out_n, S(stream));
-}
-long roma_op_recover_pose_workspace(int B, int N) { return (long)recover_pose_workspace_bytes(B, N); }
-int roma_op_recover_pose(const double* E, const float* kpts_a, const float* kpts_b, const unsigned char* mask, const int* counts,
-                         const double* camera_matrix, int B, int N, double distance_thresh, int* out_n_good, double* out_r,
-                         double* out_t, unsigned char* out_mask, void* workspace, long workspace_bytes, void* stream) {
-  return recover_pose_launch(E, kpts_a, kpts_b, mask, counts, camera_matrix, B, N, distance_thresh, out_n_good, out_r, out_t,
-                             out_mask, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-// ---- relative-pose refinement (pose_refine.hip)
-long roma_op_refine_pose_workspace(int B, int N) { return (long)refine_pose_workspace_bytes(B, N); }
-int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
-                        const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
-                        unsigned char* out_mask, int* out_info, void* workspace, long workspace_bytes, void* stream) {
-  return refine_pose_launch(R, t, kpts_a, kpts_b, counts, valid, B, N, thr, max_steps, out_r, out_t, out_mask, out_info, workspace,
-                            (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-// ---- absolute pose: P3P RANSAC, refinement, lifting (absolute_pose.hip)
-long roma_op_absolute_pose_workspace(int B, int N) { return (long)absolute_pose_workspace_bytes(B, N); }
-int roma_op_absolute_pose(const float* points3d, const float* kpts, const int* counts, const unsigned long long* seeds,
-                          const double* camera_matrix, int B, int N, float threshold, double conf, int max_iters, double* out_r,
-                          double* out_t, unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* workspace,
-                          long workspace_bytes, void* stream) {
-  return absolute_pose_launch(points3d, kpts, counts, seeds, camera_matrix, B, N, threshold, conf, max_iters, out_r, out_t, out_mask,
-                              out_ok, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-int roma_op_absolute_pose_minimal(const double* X, const double* x, int S_, double* out_r, double* out_t, int* out_n, void* stream) {
-  return absolute_pose_minimal_launch(X, x, S_, out_r, out_t, out_n, S(stream));
-}
-int roma_op_refine_absolute_pose(const double* R, const double* t, const float* points3d, const float* kpts, const int* counts,
-                                 const unsigned char* valid, const double* camera_matrix, int B, int N, double thr, int max_steps,
-                                 double* out_r, double* out_t, unsigned char* out_mask, int* out_info, void* stream) {
-  return refine_absolute_pose_launch(R, t, points3d, kpts, counts, valid, camera_matrix, B, N, thr, max_steps, out_r, out_t, out_mask,
-                                     out_info, S(stream));
-}
-int roma_op_lift_matches(const float* matches, const float* depth_a, const double* camera_a, int B, int N, int H, int W, int H_b,
-                         int W_b, float* out_points, float* out_kpts_b, void* stream) {
-  return lift_matches_launch(matches, depth_a, camera_a, B, N, H, W, H_b, W_b, out_points, out_kpts_b, S(stream));
-}
-// ---- bundle adjustment: cameras and points together, Schur-complement LM (bundle.hip)
-long roma_op_bundle_adjust_workspace(int B, int V, int N) { return (long)bundle_adjust_workspace_bytes(B, V, N); }
-int roma_op_bundle_adjust(const double* points, const float* kpts, const double* camera_matrices, const double* R, const double* t,
-                          const unsigned char* hold, const int* counts, const unsigned char* valid, int B, int V, int N,
-                          double reproj_thresh, int max_steps, double* out_points, double* out_r, double* out_t, unsigned char* out_mask,
-                          int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream) {
-  return bundle_adjust_launch(points, kpts, camera_matrices, R, t, hold, counts, valid, B, V, N, reproj_thresh, max_steps, out_points,
-                              out_r, out_t, out_mask, out_info, out_cost, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0),
-                              S(stream));
-}
-// ---- multi-view tracks from pairwise index matches (tracks.hip) and their N-view triangulation (triangulate_views.hip)
-long roma_op_build_tracks_workspace(int B, int V, int K, int P, int M) { return (long)build_tracks_workspace_bytes(B, V, K, P, M); }
-int roma_op_build_tracks(const int* inds, const int* pair_views, const int* match_counts, const int* num_kpts, const float* x, int B,
-                         int V, int K, int P, int M, int max_tracks, int min_views, int* out_tracks, float* out_kpts, int* out_counts,
-                         int* out_total, int* out_info, void* workspace, long workspace_bytes, void* stream) {
-  return build_tracks_launch(inds, pair_views, match_counts, num_kpts, x, B, V, K, P, M, max_tracks, min_views, out_tracks, out_kpts,
-                             out_counts, out_total, out_info, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-// ---- detector-free keypoints: the dense matches of an image set to per-view keypoints and index matches (set_keypoints.hip)
-long roma_op_keypoints_from_matches_workspace(int B, int V, int P, int N, long G_total, int K) {
-  return (long)keypoints_from_matches_workspace_bytes(B, V, P, N, G_total, K);
-}
-int roma_op_keypoints_from_matches(const float* matches, const float* certainty, const int* counts, const int* pair_views,
-                                   const int* sizes, int B, int V, int P, int N, int cell, float radius, int max_kpts, int one_to_one,
-                                   float* out_kpts, float* out_score, int* out_num_kpts, int* out_total, int* out_inds, int* out_kept,
-                                   int* out_info, void* workspace, long workspace_bytes, void* stream) {
-  return keypoints_from_matches_launch(matches, certainty, counts, pair_views, sizes, B, V, P, N, cell, radius, max_kpts, one_to_one,
-                                       out_kpts, out_score, out_num_kpts, out_total, out_inds, out_kept, out_info, workspace,
-                                       (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-int roma_op_triangulate_views(const float* kpts, const double* camera_matrices, const double* R, const double* t,
-                              const unsigned char* view_valid, const int* counts, const unsigned char* valid, int B, int V, int N,
-                              double max_reproj, double min_parallax, double max_depth, int min_views, int gn_steps, int trim,
-                              double* out_points, float* out_reproj, unsigned char* out_used, float* out_parallax,
-                              unsigned char* out_flags, int* out_stats, void* stream) {
-  return triangulate_views_launch(kpts, camera_matrices, R, t, view_valid, counts, valid, B, V, N, max_reproj, min_parallax, max_depth,
-                                  min_views, gn_steps, trim, out_points, out_reproj, out_used, out_parallax, out_flags, out_stats,
-                                  S(stream));
-}
-// ---- homography / fundamental-matrix refinement (model_refine.hip)
-long roma_op_refine_model_workspace(int B, int N) { return (long)refine_model_workspace_bytes(B, N); }
-int roma_op_refine_model(int model, const double* M, const float* kpts_a, const float* kpts_b, const int* counts,
-                         const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_m, unsigned char* out_mask,
-                         int* out_info, double* out_cost, void* workspace, long workspace_bytes, void* stream) {
-  return refine_model_launch(model, M, kpts_a, kpts_b, counts, valid, B, N, thr, max_steps, out_m, out_mask, out_info, out_cost,
-                             workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-// ---- triangulation and depth consistency (triangulate.hip)
-int roma_op_triangulate(const float* matches, const float* certainty, const int* counts, const unsigned char* valid, const double* R,
-                        const double* t, const double* K_a, const double* K_b, int B, long n, int coords, int W_a, int H_a, int W_b,
-                        int H_b, int sym_w, double max_depth, double max_reproj, double min_parallax, double min_certainty,
-                        float* out_points, float* out_depth_other, float* out_reproj, float* out_parallax, unsigned char* out_flags,
-                        int* out_stats, void* stream) {
-  return triangulate_launch(matches, certainty, counts, valid, R, t, K_a, K_b, B, n, coords, W_a, H_a, W_b, H_b, sym_w, max_depth,
-                            max_reproj, min_parallax, min_certainty, out_points, out_depth_other, out_reproj, out_parallax, out_flags,
-                            out_stats, S(stream));
-}
-int roma_op_depth_consistency(const float* points, const unsigned char* flags, const double* R, const double* t, const double* K_a,
-                              const double* K_b, int W_a, int H_a, int W_b, int H_b, int B, int H, int W, double rel_thresh,
-                              unsigned char* out_consistent, float* out_err, void* stream) {
-  return depth_consistency_launch(points, flags, R, t, K_a, K_b, W_a, H_a, W_b, H_b, B, H, W, rel_thresh, out_consistent, out_err,
-                                  S(stream));
-}
-// ---- dense multi-view depth fusion and the relative poses of the pairs of a set of views (depth_fusion.hip)
-long roma_op_fuse_depth_maps_workspace(int B, int V, int H, int W) { return (long)fuse_depth_maps_workspace_bytes(B, V, H, W); }
-int roma_op_fuse_depth_maps(const float* points, const unsigned char* flags, const float* certainty, const int* pair_views,
-                            const double* cameras, const double* R, const double* t, const unsigned char* view_valid,
-                            const unsigned char* valid, const unsigned char* images, const long long* image_offsets,
-                            const int* image_sizes, int B, int V, int P, int H, int W, int symmetric, double rel_thresh,
-                            int min_support, int min_consistent, int max_violations, int dedupe, int max_points, float* out_depth,
-                            float* out_weight, unsigned char* out_support, unsigned char* out_seen, unsigned char* out_violated,
-                            unsigned char* out_state, float* out_points, unsigned char* out_colors, float* out_cloud_weight,
-                            int* out_source, int* out_counts, int* out_total, int* out_stats, void* workspace, long workspace_bytes,
-                            void* stream) {
-  return fuse_depth_maps_launch(points, flags, certainty, pair_views, cameras, R, t, view_valid, valid, images, image_offsets,
-                                image_sizes, B, V, P, H, W, symmetric, rel_thresh, min_support, min_consistent, max_violations, dedupe,
-                                max_points, out_depth, out_weight, out_support, out_seen, out_violated, out_state, out_points,
-                                out_colors, out_cloud_weight, out_source, out_counts, out_total, out_stats, workspace,
-                                (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-int roma_op_relative_poses(const double* R, const double* t, const int* pair_views, int B, int V, int P, double* out_R, double* out_t,
-                           void* stream) {
-  return relative_poses_launch(R, t, pair_views, B, V, P, out_R, out_t, S(stream));
-}
-// ---- point-cloud rendering: z-buffered splat, occlusion filter, hole fill (point_render.hip)
-long roma_op_render_points_workspace(int B, int C, int H, int W) { return (long)render_points_workspace_bytes(B, C, H, W); }
-int roma_op_render_points(const float* points, const unsigned char* colors, const int* counts, const unsigned char* valid,
-                          const double* cameras, const double* R, const double* t, int B, int N, int C, int H, int W, int radius,
-                          double near, double far, int occlusion_radius, double occlusion_rel, int occlusion_count, int fill_radius,
-                          int fill_min, int background, unsigned char* out_color, float* out_depth, int* out_index,
-                          unsigned char* out_mask, int* out_stats, void* workspace, long workspace_bytes, void* stream) {
-  return render_points_launch(points, colors, counts, valid, cameras, R, t, B, N, C, H, W, radius, near, far, occlusion_radius,
-                              occlusion_rel, occlusion_count, fill_radius, fill_min, background, out_color, out_depth, out_index,
-                              out_mask, out_stats, workspace, (size_t)(workspace_bytes > 0 ? workspace_bytes : 0), S(stream));
-}
-// ---- ground-truth warp from depth and dense EPE / PCK metrics (gt_warp.hip)
-int roma_op_warp_kpts(const void* kpts, int kpts_f64, int grid_h, int grid_w, const float* depth0, const float* depth1, const double* T,
-                      int t_rows, const double* K0, const double* K1, int B, long L, int H0, int W0, int H1, int W1, double rel_thresh,
-                      unsigned char* out_valid, float* out_prob, double* out_rel, double* out_warped, void* stream) {
-  return warp_kpts_launch(kpts, kpts_f64, grid_h, grid_w, depth0, depth1, T, t_rows, K0, K1, B, L, H0, W0, H1, W1, rel_thresh, out_valid,
-                          out_prob, out_rel, out_warped, S(stream));
-}
-long roma_op_dense_metrics_workspace(int B, int h, int w) { return dense_metrics_workspace_bytes(B, h, w); }
-int roma_op_dense_metrics(const float* matches, long batch_stride, long row_stride, const float* depth1, const float* depth2,
-                          const double* T, int t_rows, const double* K1, const double* K2, int B, int h, int w, int H1, int W1, int H2,
-                          int W2, double rel_thresh, double thr0, double thr1, double thr2, long long* out_n_valid,
-                          long long* out_n_below, double* out_gd_sum, double* out_epe, double* out_pck, float* out_prob, double* out_gd,
-                          void* workspace, long workspace_bytes, void* stream) {
-  return dense_metrics_launch(matches, batch_stride, row_stride, depth1, depth2, T, t_rows, K1, K2, B, h, w, H1, W1, H2, W2, rel_thresh,
-                              thr0, thr1, thr2, out_n_valid, out_n_below, out_gd_sum, out_epe, out_pck, out_prob, out_gd, workspace,
-                              workspace_bytes, S(stream));
-}
-// ---- pose / homography benchmark scoring: errors, the error log, accuracy and AUC (metrics.hip)
-int roma_op_pose_error(const double* R, const double* t, const unsigned char* ok, const double* T_gt, int t_rows, int B, double* out_err,
-                       double* log, long capacity, long long* state, void* stream) {
-  return pose_error_launch(R, t, ok, T_gt, t_rows, B, out_err, log, capacity, state, S(stream));
-}
-int roma_op_corner_error(const double* H_pred, const unsigned char* ok, const double* H_gt, const double* sizes, int B, double* out_err,
-                         double* log, long capacity, long long* state, void* stream) {
-  return corner_error_launch(H_pred, ok, H_gt, sizes, B, out_err, log, capacity, state, S(stream));
-}
-int roma_op_error_log_append(const double* values, int B, double* log, long capacity, long long* state, void* stream) {
-  return error_log_append_launch(values, B, log, capacity, state, S(stream));
-}
-int roma_op_error_summary(const double* errors, long n, const long long* state, long capacity, const double* thresholds, int T,
-                          long long* out_n, long long* out_below, double* out_acc, double* out_auc, void* stream) {
-  return error_summary_launch(errors, n, state, capacity, thresholds, T, out_n, out_below, out_acc, out_auc, S(stream));
-}
-// ---- warp morph rendering: the frames of a parallax animation in one enqueue (morph.hip)
-int roma_op_render_morph_frame_chunk(void) { return render_morph_frame_chunk(); }
-long roma_op_render_morph_workspace(int B, int im_h, int im_w, long T) { return render_morph_workspace_bytes(B, im_h, im_w, T); }
-int roma_op_render_morph(const float* warp, long warp_batch_stride, long warp_row_stride, const void* image, int image_u8, const double* ts,
-                         const float* certainty, long cert_batch_stride, long cert_row_stride, float background, int B, long T, int H,
-                         int W, int im_h, int im_w, void* out, int out_f32, void* workspace, long workspace_bytes, void* stream) {
-  return render_morph_launch(warp, warp_batch_stride, warp_row_stride, image, image_u8, ts, certainty, cert_batch_stride, cert_row_stride,
-                             background, B, T, H, W, im_h, im_w, out, out_f32, workspace, workspace_bytes, S(stream));
-}
-// ---- match_keypoints for a batch of warps: padded, counted, no host read (keypoints_batched.hip)
-long roma_op_match_keypoints_workspace(int B, long NA, long NB) { return match_keypoints_workspace_bytes(B, NA, NB); }
-int roma_op_match_keypoints(const float* x_a, const float* x_b, const int* counts_a, const int* counts_b, const float* warp,
-                            long warp_batch_stride, long warp_row_stride, const float* certainty, long cert_batch_stride,
-                            long cert_row_stride, const float* sizes, long sizes_batch_stride, int B, long NA, long NB, int H, int W,
-                            float max_dist, float cert_th, long M, int* inds, float* kpts_a, float* kpts_b, int* counts,
-                            long long* total, void* workspace, long workspace_bytes, void* stream) {
-  return match_keypoints_launch(x_a, x_b, counts_a, counts_b, warp, warp_batch_stride, warp_row_stride, certainty, cert_batch_stride,
-                                cert_row_stride, sizes, sizes_batch_stride, B, NA, NB, H, W, max_dist, cert_th, M, inds, kpts_a, kpts_b,
-                                counts, total, workspace, workspace_bytes, S(stream));
-}
-// ---- image preprocessing: Pillow-exact bicubic resize + normalisation (preprocess.hip)
-long roma_op_preprocess_workspace(const long long* desc_host, int n_images, const int* targets_hw, int n_targets) {
-  return preprocess_workspace_bytes(desc_host, n_images, targets_hw, n_targets);
-}
-int roma_op_preprocess(const unsigned char* src, long long src_bytes, const long long* desc_host, const long long* desc_dev,
-                       int n_images, const int* targets_hw, int n_targets, int normalize, float* out0, float* out1, void* workspace,
-                       void* stream) {
-  return preprocess_launch(src, src_bytes, desc_host, desc_dev, n_images, targets_hw, n_targets, normalize, out0, out1, workspace,
-                           S(stream));
-}
-// ---- Tiny RoMa matcher side (tiny.hip)
-int roma_op_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, void* stream) {
-  return nchw_to_nhwc_launch(in, out, B, C, H, W, S(stream));
-}
-int roma_op_tiny_pos_embed(const float* corr_volume, float* out, int B, int H1, int W1, int H0, int W0, int exact_softmax,
-                           void* stream) {
-  return tiny_pos_embed_launch(corr_volume, out, B, H1, W1, H0, W0, exact_softmax, S(stream));
-}
-int roma_op_gray_instnorm(const float* in, float* out, int B, int H, int W, int C, float eps, void* stream) {
-  return gray_instnorm_launch(in, out, B, H, W, C, eps, S(stream));
-}
-int roma_op_conv2d_nhwc(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int H, int W,
-                        int Cin, int Cout, int K, int stride, int pad, int relu, void* stream) {
-  return conv2d_nhwc_launch(in, w, bias, res, out, B, H, W, Cin, Cout, K, stride, pad, relu, S(stream));
-}
-int roma_op_avgpool_nhwc(const float* in, float* out, int B, int H, int W, int C, int k, void* stream) {
-  return avgpool_nhwc_launch(in, out, B, H, W, C, k, S(stream));
-}
-int roma_op_add3(const float* a, const float* b, const float* c, float* out, long n, void* stream) {
-  return add3_launch(a, b, c, out, n, S(stream));
-}
-int roma_op_tiny_matcher_input(const float* f0, const float* f1, const float* warp, int warp_channels, float* d, int B, int H,
-                               int W, int H1, int W1, int C, int Cp, void* stream) {
-  return tiny_matcher_input_launch(f0, f1, warp, warp_channels, d, B, H, W, H1, W1, C, Cp, S(stream));
-}
-int roma_op_tiny_update(const float* base, int base_channels, const float* delta, long ldd, float sx, float sy, float* out,
-                        long npix, void* stream) {
-  return tiny_update_launch(base, base_channels, delta, ldd, sx, sy, out, npix, S(stream));
-}
-int roma_op_tiny_final(const float* matches, float* warp, float* certainty, int B, int H, int W, void* stream) {
-  return tiny_final_launch(matches, warp, certainty, B, H, W, S(stream));
-}
-int roma_op_visualize_warp(const float* warp, const float* certainty, const float* im_a, const float* im_b, int H, int W,
-                           int symmetric, int im_h, int im_w, float* out, void* stream) {
-  return visualize_warp_launch(warp, certainty, im_a, im_b, H, W, symmetric, im_h, im_w, out, S(stream));
-}
-int roma_op_fb_consistency(const float* flow_fwd, const float* flow_bwd, int B, int H, int W, float th_n, float* out,
-                           void* stream) {
-  return fb_consistency_launch(flow_fwd, flow_bwd, B, H, W, th_n, out, S(stream));
 }
 
 int roma_op_maxpool2x2(const void* in, void* out, int B, int H, int W, int C, int dt, void* stream) {

@@ -33,13 +33,14 @@
 // of views are one pass over the points, V (V + 1) / 2 + 2 passes per step; a pass recomputes the two rows' Jacobians from the
 // point (3 doubles), Vi_j and g_j (9) and the cameras in LDS rather than staging W_j and W_j Vi_j (288 doubles a point at V = 8).  No
 // atomics; the order of every sum depends on LM_THREADS alone.
-#include "bundle.h"
-
+#include "../../include/roma_hip.h"
 #include "lm_fit.h"
 
 namespace roma {
 namespace {
 
+constexpr int ROMA_BA_MAX_VIEWS = 8;   // views of one problem: the reduced camera system is at most 48 x 48
+constexpr int BUNDLE_ADJUST_INFO = 6;  // ints per problem in roma_op_bundle_adjust's out_info
 constexpr int BA_V = ROMA_BA_MAX_VIEWS, BA_NS = 6 * BA_V;  // views, rows of S
 constexpr int BA_CAM = 12, BA_VW = 5;                      // doubles of a camera (R row-major, t) and of a view (fx, fy, cx, cy, thr^2)
 constexpr int BA_DIAG = 33, BA_PAIR = 36;                  // sums of a view's pass (block of S 21, diag U 6, reduced gradient 6) and of a pair's
@@ -664,14 +665,16 @@ __global__ __launch_bounds__(LM_THREADS) void bundle_adjust_kernel(
 
 }  // namespace
 
-size_t bundle_adjust_workspace_bytes(int B, int V, int N) {
+extern "C" long roma_op_bundle_adjust_workspace(int B, int V, int N) {
   return B > 0 && V > 0 && N > 0 ? ba_carve(Workspace256(), B, N).bytes : 0;
 }
 
-int bundle_adjust_launch(const double* points, const float* kpts, const double* K, const double* R_, const double* t,
-                         const unsigned char* hold, const int* counts, const unsigned char* valid, int B, int V, int N, double thr,
-                         int max_steps, double* out_points, double* out_r, double* out_t, unsigned char* out_mask, int* out_info,
-                         double* out_cost, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_bundle_adjust(const double* points, const float* kpts, const double* K, const double* R_, const double* t,
+                                     const unsigned char* hold, const int* counts, const unsigned char* valid, int B, int V, int N,
+                                     double thr, int max_steps, double* out_points, double* out_r, double* out_t, unsigned char* out_mask,
+                                     int* out_info, double* out_cost, void* ws, long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(points && kpts && R_ && t && out_points && out_r && out_t && out_mask && out_info && out_cost && ws,
                "bundle_adjust: null pointer");
   ROMA_REQUIRE(V >= 1 && V <= ROMA_BA_MAX_VIEWS, "bundle_adjust: need 1 <= V <= 8 views");
@@ -679,7 +682,7 @@ int bundle_adjust_launch(const double* points, const float* kpts, const double* 
                "bundle_adjust: need 0 < B <= 65535, 0 < N <= 2^27, B * V * N < 2^31");
   ROMA_REQUIRE(thr > 0, "bundle_adjust: threshold must be positive (+inf: plain least squares)");  // false for NaN
   ROMA_REQUIRE(max_steps >= 0 && max_steps <= (1 << 16), "bundle_adjust: need 0 <= max_steps <= 65536");
-  ROMA_REQUIRE(ws_bytes >= bundle_adjust_workspace_bytes(B, V, N), "bundle_adjust: workspace too small");
+  ROMA_REQUIRE(ws_bytes >= (size_t)roma_op_bundle_adjust_workspace(B, V, N), "bundle_adjust: workspace too small");
   const BaCarve c = ba_carve(Workspace256(ws), B, N);
   hipLaunchKernelGGL(bundle_adjust_kernel, dim3(B), dim3(LM_THREADS), 0, s, points, reinterpret_cast<const float2*>(kpts), K, R_, t, hold,
                      counts, valid, V, N, thr, max_steps, out_points, out_r, out_t, out_mask, out_info, out_cost, c);

@@ -16,13 +16,12 @@
 //   emit     the index of an emitted pixel is its block's prefix plus its rank inside the block (ballots, wave order): (view,
 //            row-major pixel) order whatever the schedule; the cloud and its padding are written
 // The only atomics are the integer counters of `stats`, one per workgroup that has something to count.
-#include "depth_fusion.h"
-
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "../../include/roma_hip.h"
 #include "pair_views.h"
 #include "workgroup.h"
 #include "workspace.h"
@@ -33,6 +32,10 @@
 namespace roma {
 namespace {
 
+constexpr int FUSE_MAX_VIEWS = 8, FUSE_MAX_PAIRS = 64;
+constexpr int FUSE_MAX_SLOTS = 2 * (FUSE_MAX_VIEWS - 1);  // hypotheses of one view: (i, j) and (j, i) may both occur
+constexpr int FUSE_STATS = 8;                              // ints per problem in roma_op_fuse_depth_maps' out_stats
+constexpr int FUSE_MAX_COLOR_VIEWS = 128;                  // B * V with a colour source: offsets and sizes travel in the kernel's arguments
 constexpr int FUSE_BLOCK = 256, FUSE_WAVES = FUSE_BLOCK / WAVE;
 constexpr int FUSE_SCAN = 1024, FUSE_SCAN_WAVES = FUSE_SCAN / WAVE;
 
@@ -389,20 +392,23 @@ bool fuse_sizes_ok(int B, int V, int H, int W) {
 
 }  // namespace
 
-size_t fuse_depth_maps_workspace_bytes(int B, int V, int H, int W) {
+extern "C" long roma_op_fuse_depth_maps_workspace(int B, int V, int H, int W) {
   if (!fuse_sizes_ok(B, V, H, W)) return 0;
   FuseParams F;
   return fuse_carve(Workspace256(), B, V, H, W, F);
 }
 
-int fuse_depth_maps_launch(const float* points, const unsigned char* flags, const float* certainty, const int* pair_views,
-                           const double* cameras, const double* R, const double* t, const unsigned char* view_valid,
-                           const unsigned char* valid, const unsigned char* images, const long long* image_offsets,
-                           const int* image_sizes, int B, int V, int P, int H, int W, int symmetric, double rel_thresh, int min_support,
-                           int min_consistent, int max_violations, int dedupe, int max_points, float* out_depth, float* out_weight,
-                           unsigned char* out_support, unsigned char* out_seen, unsigned char* out_violated, unsigned char* out_state,
-                           float* out_points, unsigned char* out_colors, float* out_cloud_weight, int* out_source, int* out_counts,
-                           int* out_total, int* out_stats, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_fuse_depth_maps(const float* points, const unsigned char* flags, const float* certainty, const int* pair_views,
+                                       const double* cameras, const double* R, const double* t, const unsigned char* view_valid,
+                                       const unsigned char* valid, const unsigned char* images, const long long* image_offsets,
+                                       const int* image_sizes, int B, int V, int P, int H, int W, int symmetric, double rel_thresh,
+                                       int min_support, int min_consistent, int max_violations, int dedupe, int max_points,
+                                       float* out_depth, float* out_weight, unsigned char* out_support, unsigned char* out_seen,
+                                       unsigned char* out_violated, unsigned char* out_state, float* out_points, unsigned char* out_colors,
+                                       float* out_cloud_weight, int* out_source, int* out_counts, int* out_total, int* out_stats, void* ws,
+                                       long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(points && flags && pair_views && cameras && R && t, "fuse_depth_maps: null pointer");
   ROMA_REQUIRE(out_depth && out_weight && out_support && out_seen && out_violated && out_state && out_points && out_cloud_weight &&
                    out_source && out_counts && out_total && out_stats,
@@ -441,7 +447,7 @@ int fuse_depth_maps_launch(const float* points, const unsigned char* flags, cons
     }
     C.images = images;
   }
-  ROMA_REQUIRE(ws && ws_bytes >= fuse_depth_maps_workspace_bytes(B, V, H, W), "fuse_depth_maps: workspace too small");
+  ROMA_REQUIRE(ws && ws_bytes >= (size_t)roma_op_fuse_depth_maps_workspace(B, V, H, W), "fuse_depth_maps: workspace too small");
   // the slots of every view: the halves on its grid, in ascending pair
   for (int p = 0; p < P; ++p)
     for (int half = 0; half < (symmetric ? 2 : 1); ++half) {
@@ -493,8 +499,9 @@ int fuse_depth_maps_launch(const float* points, const unsigned char* flags, cons
   return 0;
 }
 
-int relative_poses_launch(const double* R, const double* t, const int* pair_views, int B, int V, int P, double* out_R, double* out_t,
-                          hipStream_t s) {
+extern "C" int roma_op_relative_poses(const double* R, const double* t, const int* pair_views, int B, int V, int P, double* out_R,
+                                      double* out_t, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(R && t && pair_views && out_R && out_t, "relative_poses: null pointer");
   ROMA_REQUIRE(V >= 2 && V <= FUSE_MAX_VIEWS, "relative_poses: need 2 <= V <= 8 views");
   ROMA_REQUIRE(P >= 1 && P <= FUSE_MAX_PAIRS, "relative_poses: need 1 <= P <= 64 pairs");

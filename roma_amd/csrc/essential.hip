@@ -27,13 +27,17 @@
 // ess_pose_kernel (candidate with most good points, ties to the earlier one; R, t, n_good, mask).
 // As in the RANSAC pipeline, every flag and count of recoverPose's workspace is written with plain stores by one kernel and read
 // by a later launch on the same stream.  Results are bit-identical from run to run and independent of B.
-#include "essential.h"
+#include "../../include/roma_hip.h"
 #include "cheirality.h"
 #include "ransac.h"
 
 namespace roma {
 namespace {
 
+constexpr int ESSENTIAL_MAX_ROOTS = 10;       // real solutions of one five-point sample (tools/essential_ref.py: MAX_ROOTS)
+constexpr int ESSENTIAL_INFO = 5;             // ints per pair in roma_op_essential's out_info
+constexpr int ESSENTIAL_MAGSAC_INFO = 7;      // in roma_op_essential_magsac's
+constexpr int ESSENTIAL_MAGSAC_MAX_LO = 64;   // largest lo_iters
 constexpr int MAXR = ESSENTIAL_MAX_ROOTS;
 constexpr int G = 16;                     // lanes per hypothesis in the solver
 constexpr int GPB = 256 / G;              // hypotheses per solver workgroup
@@ -979,7 +983,7 @@ PoseCarve pose_carve(Workspace256 ws, int B, int N) {
 
 static_assert(MagsacScoring::MAX_STEPS == ESSENTIAL_MAGSAC_MAX_LO);
 
-// the check and launch behind essential_launch and essential_magsac_launch: `opt` is `lo_iters`, out_score NULL without scores
+// the check and launch behind roma_op_essential and roma_op_essential_magsac: `opt` is `lo_iters`, out_score NULL without scores
 template <class Sc>
 int e_launch(const char* op, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
              const double* K, int B, int N, float threshold, double prob, int max_iters, int opt, double* out_e,
@@ -994,26 +998,28 @@ int e_launch(const char* op, const float* kpts_a, const float* kpts_b, const int
 
 }  // namespace
 
-size_t essential_workspace_bytes(int B, int N) { return workspace_bytes<Essential, CountScoring>(B, N); }
+extern "C" long roma_op_essential_workspace(int B, int N) { return (long)workspace_bytes<Essential, CountScoring>(B, N); }
 
-int essential_launch(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, const double* K,
-                     int B, int N, float threshold, double prob, int max_iters, double* out_e, unsigned char* out_mask,
-                     unsigned char* out_ok, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_essential(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                                 const double* K, int B, int N, float threshold, double prob, int max_iters, double* out_e,
+                                 unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* ws, long ws_bytes, void* stream) {
   return e_launch<CountScoring>("essential", kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, 0, out_e, out_mask,
-                                out_ok, out_info, nullptr, ws, ws_bytes, s);
+                                out_ok, out_info, nullptr, ws, workspace_size(ws_bytes), static_cast<hipStream_t>(stream));
 }
 
-size_t essential_magsac_workspace_bytes(int B, int N) { return workspace_bytes<Essential, MagsacScoring>(B, N); }
+extern "C" long roma_op_essential_magsac_workspace(int B, int N) { return (long)workspace_bytes<Essential, MagsacScoring>(B, N); }
 
-int essential_magsac_launch(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
-                            const double* K, int B, int N, float threshold, double prob, int max_iters, int lo_iters, double* out_e,
-                            unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score, void* ws,
-                            size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_essential_magsac(const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                                        const double* K, int B, int N, float threshold, double prob, int max_iters, int lo_iters,
+                                        double* out_e, unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score,
+                                        void* ws, long ws_bytes, void* stream) {
   return e_launch<MagsacScoring>("essential_magsac", kpts_a, kpts_b, counts, seeds, K, B, N, threshold, prob, max_iters, lo_iters,
-                                 out_e, out_mask, out_ok, out_info, out_score, ws, ws_bytes, s);
+                                 out_e, out_mask, out_ok, out_info, out_score, ws, workspace_size(ws_bytes),
+                                 static_cast<hipStream_t>(stream));
 }
 
-int essential_minimal_launch(const double* x0, const double* x1, int S, double* out_e, int* out_n, hipStream_t s) {
+extern "C" int roma_op_essential_minimal(const double* x0, const double* x1, int S, double* out_e, int* out_n, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(x0 && x1 && out_e && out_n, "essential_minimal: null pointer");
   ROMA_REQUIRE(S > 0 && S <= (1 << 24), "essential_minimal: need 0 < S <= 2^24");
   hipLaunchKernelGGL(ess_minimal_kernel, dim3((S + GPB - 1) / GPB), dim3(256), 0, s, x0, x1, S, out_e, out_n);
@@ -1021,15 +1027,19 @@ int essential_minimal_launch(const double* x0, const double* x1, int S, double* 
   return 0;
 }
 
-size_t recover_pose_workspace_bytes(int B, int N) { return B > 0 && N > 0 ? pose_carve(Workspace256(), B, N).bytes : 0; }
+extern "C" long roma_op_recover_pose_workspace(int B, int N) {
+  return B > 0 && N > 0 ? (long)pose_carve(Workspace256(), B, N).bytes : 0;
+}
 
-int recover_pose_launch(const double* E, const float* kpts_a, const float* kpts_b, const unsigned char* mask, const int* counts,
-                        const double* K, int B, int N, double distance_thresh, int* out_n, double* out_r, double* out_t,
-                        unsigned char* out_mask, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_recover_pose(const double* E, const float* kpts_a, const float* kpts_b, const unsigned char* mask,
+                                    const int* counts, const double* K, int B, int N, double distance_thresh, int* out_n, double* out_r,
+                                    double* out_t, unsigned char* out_mask, void* ws, long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(E && kpts_a && kpts_b && out_n && out_r && out_t && out_mask && ws, "recover_pose: null pointer");
   ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), "recover_pose: need 0 < B <= 65536, 0 < N, B * N < 2^31");
   ROMA_REQUIRE(distance_thresh > 0, "recover_pose: distance_thresh must be positive");
-  ROMA_REQUIRE(ws_bytes >= recover_pose_workspace_bytes(B, N), "recover_pose: workspace too small (roma_op_recover_pose_workspace)");
+  ROMA_REQUIRE(ws_bytes >= (size_t)roma_op_recover_pose_workspace(B, N), "recover_pose: workspace too small (roma_op_recover_pose_workspace)");
   const PoseCarve c = pose_carve(Workspace256(ws), B, N);
   const int nblk = (N + 255) / 256;
   hipLaunchKernelGGL(ess_decompose_kernel, dim3((B + 63) / 64), dim3(64), 0, s, E, counts, K, B, N, c.st);

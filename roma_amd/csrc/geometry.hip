@@ -16,11 +16,16 @@
 //   wrefit      (MagsacScoring) the same with the rows weighted by the MAGSAC++ weights of the current model (one IRLS step).
 //   model_out   de-normalised in f64 (H = Tb^-1 H_n Ta, F = Tb^T F_n Ta), scaled so that [2, 2] = 1.  Info rows of RANSAC_INFO
 //               and MAGSAC_INFO ints.
+#include "../../include/roma_hip.h"
 #include "geometry.h"
 #include "ransac.h"
 
 namespace roma {
 namespace {
+
+constexpr int RANSAC_INFO = 6;                // ints per pair in roma_op_ransac's out_info
+constexpr int MAGSAC_INFO = RANSAC_INFO + 1;  // in roma_op_magsac's: the RANSAC_INFO entries and the LO steps accepted
+constexpr int MAGSAC_MAX_LO = 64;             // largest lo_iters
 
 constexpr double COLLINEAR_EPS = 1e-4;  // |sin| of a triple's angle below which the triple counts as collinear
 constexpr double CUBIC_EPS = 1e-12;     // relative size below which a leading coefficient of the cubic is zero
@@ -416,7 +421,7 @@ size_t hf_workspace_bytes(int B, int N) {  // one size for both models (the roma
   return std::max(workspace_bytes<Homography, Sc>(B, N), workspace_bytes<Fundamental, Sc>(B, N));
 }
 
-// the check and dispatch behind ransac_launch and magsac_launch: `opt` is `refine` or `lo_iters`, out_score NULL without scores
+// the check and dispatch behind roma_op_ransac and roma_op_magsac: `opt` is `refine` or `lo_iters`, out_score NULL without scores
 template <class Sc>
 int hf_launch(const char* op, int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
               int B, int N, float threshold, double confidence, int max_iters, int opt, double* out_model, unsigned char* out_mask,
@@ -434,22 +439,25 @@ int hf_launch(const char* op, int model, const float* kpts_a, const float* kpts_
 
 }  // namespace
 
-size_t ransac_workspace_bytes(int B, int N) { return hf_workspace_bytes<CountScoring>(B, N); }
+extern "C" long roma_op_ransac_workspace(int B, int N) { return (long)hf_workspace_bytes<CountScoring>(B, N); }
 
-int ransac_launch(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
-                  int N, float threshold, double confidence, int max_iters, int refine, double* out_model, unsigned char* out_mask,
-                  unsigned char* out_ok, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_ransac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                              int B, int N, float threshold, double confidence, int max_iters, int refine, double* out_model,
+                              unsigned char* out_mask, unsigned char* out_ok, int* out_info, void* ws, long ws_bytes, void* stream) {
   return hf_launch<CountScoring>("ransac", model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, refine,
-                                 out_model, out_mask, out_ok, out_info, nullptr, ws, ws_bytes, s);
+                                 out_model, out_mask, out_ok, out_info, nullptr, ws, workspace_size(ws_bytes),
+                                 static_cast<hipStream_t>(stream));
 }
 
-size_t magsac_workspace_bytes(int B, int N) { return hf_workspace_bytes<MagsacScoring>(B, N); }
+extern "C" long roma_op_magsac_workspace(int B, int N) { return (long)hf_workspace_bytes<MagsacScoring>(B, N); }
 
-int magsac_launch(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds, int B,
-                  int N, float threshold, double confidence, int max_iters, int lo_iters, double* out_model, unsigned char* out_mask,
-                  unsigned char* out_ok, int* out_info, double* out_score, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_magsac(int model, const float* kpts_a, const float* kpts_b, const int* counts, const unsigned long long* seeds,
+                              int B, int N, float threshold, double confidence, int max_iters, int lo_iters, double* out_model,
+                              unsigned char* out_mask, unsigned char* out_ok, int* out_info, double* out_score, void* ws,
+                              long ws_bytes, void* stream) {
   return hf_launch<MagsacScoring>("magsac", model, kpts_a, kpts_b, counts, seeds, B, N, threshold, confidence, max_iters, lo_iters,
-                                  out_model, out_mask, out_ok, out_info, out_score, ws, ws_bytes, s);
+                                  out_model, out_mask, out_ok, out_info, out_score, ws, workspace_size(ws_bytes),
+                                  static_cast<hipStream_t>(stream));
 }
 
 }  // namespace roma

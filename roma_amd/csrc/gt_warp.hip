@@ -14,12 +14,13 @@
 // The 30 doubles of a pair (K0^-1, R, t, K1) are formed by thread 0 of each workgroup and read from LDS into vector registers:
 // the float64 chain has more wave-uniform values than a wave has scalar registers (as triangulate_kernel had).  No float is added
 // atomically, nothing is read back.
-#include "gt_warp.h"
-
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
+
+#include "../../include/roma_hip.h"
+#include "common.h"
 
 // nothing here is fused: tools/gt_warp_ref.py evaluates the same expressions in the same order
 #pragma clang fp contract(off)
@@ -300,9 +301,10 @@ bool side_ok(int v) { return v >= 1 && v <= GW_MAX_SIDE; }
 
 }  // namespace
 
-int warp_kpts_launch(const void* kpts, int kpts_f64, int grid_h, int grid_w, const float* depth0, const float* depth1, const double* T,
-                     int t_rows, const double* K0, const double* K1, int B, long L, int H0, int W0, int H1, int W1, double rel_thresh,
-                     unsigned char* valid, float* prob, double* rel, double* warped, hipStream_t s) {
+extern "C" int roma_op_warp_kpts(const void* kpts, int kpts_f64, int grid_h, int grid_w, const float* depth0, const float* depth1,
+                                 const double* T, int t_rows, const double* K0, const double* K1, int B, long L, int H0, int W0, int H1,
+                                 int W1, double rel_thresh, unsigned char* valid, float* prob, double* rel, double* warped, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(depth0 && depth1 && T && K0 && K1 && warped, "warp_kpts: null pointer");
   ROMA_REQUIRE(B >= 0 && B <= 65535, "warp_kpts: B must lie in [0, 65535]");
   ROMA_REQUIRE(L >= 0, "warp_kpts: L must not be negative");
@@ -323,16 +325,17 @@ int warp_kpts_launch(const void* kpts, int kpts_f64, int grid_h, int grid_w, con
   return 0;
 }
 
-long dense_metrics_workspace_bytes(int B, int h, int w) {
+extern "C" long roma_op_dense_metrics_workspace(int B, int h, int w) {
   if (B < 0 || B > 65535 || h < 0 || w < 0 || h > GW_MAX_SIDE || w > GW_MAX_SIDE) return -1;
   return std::max<long>(16, (long)B * pair_blocks((long)h * w) * 5 * (long)sizeof(double));
 }
 
-int dense_metrics_launch(const float* matches, long batch_stride, long row_stride, const float* depth1, const float* depth2,
-                         const double* T, int t_rows, const double* K1, const double* K2, int B, int h, int w, int H1, int W1, int H2,
-                         int W2, double rel_thresh, double thr0, double thr1, double thr2, long long* n_valid, long long* n_below,
-                         double* gd_sum, double* epe, double* pck, float* prob, double* gd, void* workspace, long workspace_bytes,
-                         hipStream_t s) {
+extern "C" int roma_op_dense_metrics(const float* matches, long batch_stride, long row_stride, const float* depth1, const float* depth2,
+                                     const double* T, int t_rows, const double* K1, const double* K2, int B, int h, int w, int H1, int W1,
+                                     int H2, int W2, double rel_thresh, double thr0, double thr1, double thr2, long long* n_valid,
+                                     long long* n_below, double* gd_sum, double* epe, double* pck, float* prob, double* gd, void* workspace,
+                                     long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(matches && depth1 && depth2 && T && K1 && K2 && n_valid && n_below && gd_sum && epe && pck && workspace,
                "dense_metrics: null pointer");
   ROMA_REQUIRE(B >= 1 && B <= 65535, "dense_metrics: B must lie in [1, 65535]");
@@ -345,7 +348,7 @@ int dense_metrics_launch(const float* matches, long batch_stride, long row_strid
   ROMA_REQUIRE((reinterpret_cast<uintptr_t>(matches) & 15) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
                "dense_metrics: matches must be 16-byte and workspace 8-byte aligned");
   ROMA_REQUIRE(rel_thresh >= 0 && thr0 >= 0 && thr1 >= 0 && thr2 >= 0, "dense_metrics: a threshold is negative (or NaN)");
-  ROMA_REQUIRE(workspace_bytes >= dense_metrics_workspace_bytes(B, h, w), "dense_metrics: workspace is too small");
+  ROMA_REQUIRE(workspace_bytes >= roma_op_dense_metrics_workspace(B, h, w), "dense_metrics: workspace is too small");
   const unsigned blocks = pair_blocks((long)h * w);
   double* part_sum = static_cast<double*>(workspace);
   long long* part_cnt = reinterpret_cast<long long*>(part_sum + (long)B * blocks);

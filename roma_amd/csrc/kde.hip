@@ -1,12 +1,21 @@
-// All-pairs Gaussian KDE in 4-D (see kde.h).  VALU-bound: per pair 4 sub + 4 fma + 1 v_exp_f32 + 1 add.
+// Gaussian kernel density of the sampled matches (reference: romatch/utils/kde.py:4-12, used by
+// RegressionMatcher.sample, romatch/models/matcher.py:598-629):
+//     density[i] = sum_j exp(-||x_i - y_j||^2 / (2 std^2)),   y = x[::down]
+// x: [n, 4] f32 (A-coordinates, B-coordinates of a match).  The reference evaluates this with a 40 000 x 40 000 fp16
+// cdist (3.2 GB intermediate); here it is one all-pairs kernel with the reference points staged through LDS.
+// half_inputs != 0 rounds the coordinates to fp16 first (the reference's `x.half()`); distances, exp and the row sum
+// are always f32 (at least the reference's precision).
+//
+// All-pairs in 4-D, VALU-bound: per pair 4 sub + 4 fma + 1 v_exp_f32 + 1 add.
 //   * one thread per query point (registers), 256 queries per workgroup;
 //   * reference points stream through LDS in tiles of 1024 (16 KB, float4 each): every LDS read is a wave-wide
 //     broadcast of one 16-byte point, so the inner loop is 1 ds_read_b128 per 64 x 10 VALU operations;
 //   * the reference set is split over gridDim.y slices (atomicAdd of the partial sums) so that n = 40 000 still
 //     fills the 256 CUs (157 query blocks alone would leave 40 % of them idle).
-#include "kde.h"
-
 #include <algorithm>
+
+#include "../../include/roma_hip.h"
+#include "common.h"
 
 namespace roma {
 
@@ -49,7 +58,8 @@ __global__ __launch_bounds__(256) void kde_kernel(const float* __restrict__ x, l
   if (i < n) atomicAdd(density + i, acc);
 }
 
-int kde_launch(const float* x, long n, int down, float std, int half_inputs, float* density, hipStream_t s) {
+extern "C" int roma_op_kde(const float* x, long n, int down, float std, int half_inputs, float* density, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(x && density && n > 0, "kde: empty input");
   ROMA_REQUIRE(down >= 1 && std > 0.f, "kde: down must be >= 1 and std > 0");
   ROMA_REQUIRE((reinterpret_cast<uintptr_t>(x) & 15) == 0, "kde: points must be 16-byte aligned [n,4] f32");

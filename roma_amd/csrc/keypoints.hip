@@ -1,8 +1,15 @@
-// Keypoint matching helpers (see keypoints.h).  All-pairs work of at most ~1e8 pairs: VALU bound, microseconds.
-#include "keypoints.h"
-
+// RegressionMatcher.match_keypoints (romatch/models/matcher.py:732-773) on the device:
+//   1. sample_warp_at: x_A_to_B = grid_sample(warp[..., 2:4], x_A), cert_A = grid_sample(certainty, x_A)
+//      (bilinear, zeros padding, align_corners=False - the same tap rule as the refiner warp);
+//   2. mutual_nn: mutual nearest neighbours between x_A_to_B and x_B within max_dist, certainty above cert_th; its
+//      tie-complete form (mutual_nn_count / mutual_nn_fill) is torch.nonzero of the reference's mask (matcher.py:756-762), two calls
+//      around one host read;
+// and conf_from_fb_consistency (matcher.py:672-699), visualize_warp (matcher.py:936-986).
+// All-pairs work of at most ~1e8 pairs: VALU bound, microseconds.
 #include <algorithm>
 
+#include "../../include/roma_hip.h"
+#include "common.h"
 #include "workgroup.h"
 
 namespace roma {
@@ -38,8 +45,9 @@ __global__ __launch_bounds__(256) void sample_warp_at_kernel(const float* __rest
   cert_a[i] = c;
 }
 
-int sample_warp_at_launch(const float* warp, const float* cert, int H, int W, const float* xa, long n, float* xa_to_b,
-                          float* cert_a, hipStream_t s) {
+extern "C" int roma_op_sample_warp_at(const float* warp, const float* cert, int H, int W, const float* xa, long n, float* xa_to_b,
+                                      float* cert_a, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   if (n == 0) return 0;
   ROMA_REQUIRE(warp && cert && xa && xa_to_b && cert_a && H > 0 && W > 0 && n > 0, "sample_warp_at: bad arguments");
   ROMA_REQUIRE((reinterpret_cast<uintptr_t>(warp) & 15) == 0, "sample_warp_at: warp must be 16-byte aligned [H,W,4] f32");
@@ -103,8 +111,10 @@ __global__ __launch_bounds__(256) void mutual_nn_finalize_kernel(const unsigned 
   match_b[i] = out;
 }
 
-int mutual_nn_launch(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
-                     int* match_b, unsigned long long* ws_a, unsigned long long* ws_b, hipStream_t s) {
+extern "C" int roma_op_mutual_nn(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
+                                 int* match_b, void* ws_a_, void* ws_b_, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned long long* ws_a = static_cast<unsigned long long*>(ws_a_), *ws_b = static_cast<unsigned long long*>(ws_b_);
   if (na == 0) return 0;
   ROMA_REQUIRE(a && match_b && ws_a && ws_b && na > 0 && nb >= 0 && (b || nb == 0), "mutual_nn: bad arguments");
   ROMA_REQUIRE(na < (1l << 31) && nb < (1l << 31), "mutual_nn: too many points");
@@ -193,8 +203,10 @@ __global__ __launch_bounds__(1024) void scan_inclusive_kernel(long long* __restr
   }
 }
 
-int mutual_nn_count_launch(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
-                           unsigned long long* ws_a, unsigned long long* ws_b, long long* offs, hipStream_t s) {
+extern "C" int roma_op_mutual_nn_count(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
+                                       void* ws_a_, void* ws_b_, long long* offs, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  unsigned long long* ws_a = static_cast<unsigned long long*>(ws_a_), *ws_b = static_cast<unsigned long long*>(ws_b_);
   ROMA_REQUIRE(offs && na >= 0, "mutual_nn_count: bad arguments");
   if (na == 0) {
     ROMA_CHECK_HIP(hipMemsetAsync(offs, 0, sizeof(long long), s));
@@ -222,9 +234,10 @@ int mutual_nn_count_launch(const float* a, long na, const float* b, long nb, con
   return 0;
 }
 
-int mutual_nn_fill_launch(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
-                          const unsigned long long* ws_a, const unsigned long long* ws_b, long long* offs, long long* pairs,
-                          hipStream_t s) {
+extern "C" int roma_op_mutual_nn_fill(const float* a, long na, const float* b, long nb, const float* cert_a, float cert_th, float max_dist,
+                                      const void* ws_a_, const void* ws_b_, long long* offs, long long* pairs, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const unsigned long long* ws_a = static_cast<const unsigned long long*>(ws_a_), *ws_b = static_cast<const unsigned long long*>(ws_b_);
   if (na == 0 || nb == 0) return 0;
   ROMA_REQUIRE(a && b && ws_a && ws_b && offs && pairs, "mutual_nn_fill: bad arguments");
   hipLaunchKernelGGL(mutual_pairs_kernel<1>, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, a, na, b, nb, ws_a, ws_b, cert_a,
@@ -267,8 +280,9 @@ __global__ __launch_bounds__(256) void fb_consistency_kernel(const float* __rest
   out[idx] = sqrtf(dx * dx + dy * dy) < th_n ? 1.f : 0.f;
 }
 
-int fb_consistency_launch(const float* flow_fwd, const float* flow_bwd, int B, int H, int W, float th_n, float* out,
-                          hipStream_t s) {
+extern "C" int roma_op_fb_consistency(const float* flow_fwd, const float* flow_bwd, int B, int H, int W, float th_n, float* out,
+                                      void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(flow_fwd && flow_bwd && out && B > 0 && H > 0 && W > 0, "fb_consistency: bad arguments");
   const long total = (long)B * H * W;
   hipLaunchKernelGGL(fb_consistency_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, flow_fwd, flow_bwd, B, H, W,
@@ -312,8 +326,9 @@ __global__ __launch_bounds__(256) void visualize_warp_kernel(const float* __rest
   for (int c = 0; c < 3; ++c) out[(long)c * total + idx] = ce * rgb[c] + (1.f - ce);
 }
 
-int visualize_warp_launch(const float* warp, const float* cert, const float* im_a, const float* im_b, int H, int W,
-                          int symmetric, int im_h, int im_w, float* out, hipStream_t s) {
+extern "C" int roma_op_visualize_warp(const float* warp, const float* cert, const float* im_a, const float* im_b, int H, int W,
+                                      int symmetric, int im_h, int im_w, float* out, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(warp && cert && im_b && out && H > 0 && W > 0 && im_h > 0 && im_w > 0, "visualize_warp: bad arguments");
   ROMA_REQUIRE(!symmetric || im_a, "visualize_warp: symmetric warps need im_A as well");
   const int W2 = symmetric ? 2 * W : W;

@@ -22,13 +22,13 @@
 // its place in the batch, or the padding widths NA / NB (which only move the slice boundaries of commutative minima and of
 // counts that are added up in order).  A workgroup whose block of rows or slice lies beyond the pair's counts exits before
 // its first load of point data; rows at or beyond the counts are never read.
-#include "keypoints_batched.h"
-
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "../../include/roma_hip.h"
+#include "common.h"
 #include "workgroup.h"
 #include "workspace.h"
 
@@ -317,16 +317,18 @@ bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p
 
 }  // namespace
 
-long match_keypoints_workspace_bytes(int B, long NA, long NB) {
+extern "C" long roma_op_match_keypoints_workspace(int B, long NA, long NB) {
   if (!sizes_ok(B, NA, NB)) return -1;
   KpParams A;
   return (long)carve(Workspace16(), B, NA, NB, A);
 }
 
-int match_keypoints_launch(const float* x_a, const float* x_b, const int* counts_a, const int* counts_b, const float* warp, long warp_bs,
-                           long warp_rs, const float* certainty, long cert_bs, long cert_rs, const float* sizes, long sizes_bs, int B,
-                           long NA, long NB, int H, int W, float max_dist, float cert_th, long M, int* inds, float* kpts_a,
-                           float* kpts_b, int* counts, long long* total, void* workspace, long workspace_bytes, hipStream_t s) {
+extern "C" int roma_op_match_keypoints(const float* x_a, const float* x_b, const int* counts_a, const int* counts_b, const float* warp,
+                                       long warp_bs, long warp_rs, const float* certainty, long cert_bs, long cert_rs, const float* sizes,
+                                       long sizes_bs, int B, long NA, long NB, int H, int W, float max_dist, float cert_th, long M,
+                                       int* inds, float* kpts_a, float* kpts_b, int* counts, long long* total, void* workspace,
+                                       long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(B >= 1 && B <= 65535, "match_keypoints: B must lie in [1, 65535]");
   ROMA_REQUIRE(NA >= 0 && NA <= KP_MAX_POINTS && NB >= 0 && NB <= KP_MAX_POINTS, "match_keypoints: NA and NB must lie in [0, 2^20]");
   ROMA_REQUIRE(M >= 1 && M <= 0x7fffffffl, "match_keypoints: M (max_matches) must lie in [1, 2^31 - 1]");

@@ -16,10 +16,11 @@
 // barrier thread 0 stores count + B and adds what did not fit to dropped.  One workgroup per launch, so there is no other reader
 // or writer of the cursor inside a launch, and successive launches order themselves by the stream: no host value takes part, no
 // atomic is used.  No float is added atomically, nothing is read back.
-#include "metrics.h"
-
 #include <math.h>
 #include <stdint.h>
+
+#include "../../include/roma_hip.h"
+#include "common.h"
 
 // nothing here is fused: tools/metrics_ref.py evaluates the same expressions in the same order
 #pragma clang fp contract(off)
@@ -241,8 +242,9 @@ const char* log_fault(const double* log, long capacity, const long long* state) 
 
 }  // namespace
 
-int pose_error_launch(const double* R, const double* t, const unsigned char* ok, const double* T_gt, int t_rows, int B, double* err,
-                      double* log, long capacity, long long* state, hipStream_t s) {
+extern "C" int roma_op_pose_error(const double* R, const double* t, const unsigned char* ok, const double* T_gt, int t_rows, int B,
+                                  double* err, double* log, long capacity, long long* state, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(R && t && T_gt && err, "pose_error: null pointer");
   ROMA_REQUIRE(B >= 0 && B <= MT_MAX_B, "pose_error: B must lie in [0, 65535]");
   ROMA_REQUIRE(t_rows == 3 || t_rows == 4, "pose_error: t_rows must be 3 ([B, 3, 4]) or 4 ([B, 4, 4])");
@@ -256,8 +258,9 @@ int pose_error_launch(const double* R, const double* t, const unsigned char* ok,
   return 0;
 }
 
-int corner_error_launch(const double* H_pred, const unsigned char* ok, const double* H_gt, const double* sizes, int B, double* err,
-                        double* log, long capacity, long long* state, hipStream_t s) {
+extern "C" int roma_op_corner_error(const double* H_pred, const unsigned char* ok, const double* H_gt, const double* sizes, int B,
+                                    double* err, double* log, long capacity, long long* state, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(H_pred && H_gt && sizes && err, "corner_error: null pointer");
   ROMA_REQUIRE(B >= 0 && B <= MT_MAX_B, "corner_error: B must lie in [0, 65535]");
   ROMA_REQUIRE(aligned8(H_pred) && aligned8(H_gt) && aligned8(sizes) && aligned8(err),
@@ -271,7 +274,8 @@ int corner_error_launch(const double* H_pred, const unsigned char* ok, const dou
   return 0;
 }
 
-int error_log_append_launch(const double* values, int B, double* log, long capacity, long long* state, hipStream_t s) {
+extern "C" int roma_op_error_log_append(const double* values, int B, double* log, long capacity, long long* state, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(values && log && state, "error_log_append: null pointer");
   ROMA_REQUIRE(B >= 0 && B <= MT_MAX_B, "error_log_append: B must lie in [0, 65535]");
   ROMA_REQUIRE(aligned8(values), "error_log_append: values is not 8-byte aligned");
@@ -284,8 +288,9 @@ int error_log_append_launch(const double* values, int B, double* log, long capac
   return 0;
 }
 
-int error_summary_launch(const double* errors, long n, const long long* state, long capacity, const double* thresholds_host, int T,
-                         long long* out_n, long long* out_below, double* out_acc, double* out_auc, hipStream_t s) {
+extern "C" int roma_op_error_summary(const double* errors, long n, const long long* state, long capacity, const double* thresholds_host,
+                                     int T, long long* out_n, long long* out_below, double* out_acc, double* out_auc, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(thresholds_host && out_n && out_below && out_acc && out_auc, "error_summary: null pointer");
   ROMA_REQUIRE(T >= 1 && T <= MT_MAX_THRESHOLDS, "error_summary: the number of thresholds must lie in [1, 16]");
   if (state) {

@@ -23,8 +23,7 @@
 // model_refine_kernel<P>: one workgroup of LM_THREADS per pair runs the normalisation (summed like the loop's passes: results are
 // bit-identical from run to run, independent of B and of the pair's place in the batch), lm_fit<P> and the de-normalisation.
 // model_refine_mask_kernel<P>: grid (point blocks, pair): mask = active under the final model.
-#include "model_refine.h"
-
+#include "../../include/roma_hip.h"
 #include "geometry.h"
 #include "lm_fit.h"  // and through it ransac.h: mat3, finite_row, workspace.h; its fp-contract setting holds here as well
 
@@ -431,14 +430,17 @@ size_t model_refine_carve(Workspace256 ws, int B, MrState*& st) {
 
 }  // namespace
 
-size_t refine_model_workspace_bytes(int B, int N) {
+extern "C" long roma_op_refine_model_workspace(int B, int N) {
   MrState* st;
   return B > 0 && N >= 0 ? model_refine_carve(Workspace256(), B, st) : 0;
 }
 
-int refine_model_launch(int model, const double* M, const float* kpts_a, const float* kpts_b, const int* counts,
-                        const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_m, unsigned char* out_mask,
-                        int* out_info, double* out_cost, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_refine_model(int model, const double* M, const float* kpts_a, const float* kpts_b, const int* counts,
+                                    const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_m,
+                                    unsigned char* out_mask, int* out_info, double* out_cost, void* ws, long workspace_bytes,
+                                    void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(model == RANSAC_HOMOGRAPHY || model == RANSAC_FUNDAMENTAL,
                "refine_model: model must be 0 (homography) or 1 (fundamental)");
   ROMA_REQUIRE(M && kpts_a && kpts_b && out_m && out_mask && out_info && out_cost && ws, "refine_model: null pointer");
@@ -446,7 +448,7 @@ int refine_model_launch(int model, const double* M, const float* kpts_a, const f
   ROMA_REQUIRE(N >= 0 && (long)B * N < (1l << 31), "refine_model: need 0 <= N, B * N < 2^31");
   ROMA_REQUIRE(thr > 0, "refine_model: threshold must be positive (inf: no truncation)");
   ROMA_REQUIRE(max_steps >= 0 && max_steps <= (1 << 16), "refine_model: need 0 <= max_steps <= 65536");
-  ROMA_REQUIRE(ws_bytes >= refine_model_workspace_bytes(B, N), "refine_model: workspace too small (roma_op_refine_model_workspace)");
+  ROMA_REQUIRE(ws_bytes >= (size_t)roma_op_refine_model_workspace(B, N), "refine_model: workspace too small (roma_op_refine_model_workspace)");
   if (B == 0) return 0;
   MrState* st;
   model_refine_carve(Workspace256(ws), B, st);

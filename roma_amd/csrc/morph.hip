@@ -18,12 +18,13 @@
 // sum that skips it, and no texel that the tap does not cover (a NaN in the picture, say) can reach the pixel.
 // A frame whose first byte is not dword aligned (H W 3 is odd, say) and the last, partial wave of a frame are written byte by
 // byte from registers; the f32 form stores one coalesced dword per lane, pixel and channel.
-#include "morph.h"
-
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
+
+#include "../../include/roma_hip.h"
+#include "common.h"
 
 // nothing here is fused: tools/morph_ref.py evaluates the same float32 expressions in the same order
 #pragma clang fp contract(off)
@@ -226,16 +227,17 @@ bool overlap(const void* p, long bytes, const void* q, long bytes_q) {
 
 }  // namespace
 
-int render_morph_frame_chunk() { return MORPH_FRAME_CHUNK; }
+extern "C" int roma_op_render_morph_frame_chunk(void) { return MORPH_FRAME_CHUNK; }
 
-long render_morph_workspace_bytes(int B, int im_h, int im_w, long T) {
+extern "C" long roma_op_render_morph_workspace(int B, int im_h, int im_w, long T) {
   if (B < 1 || B > 65535 || !side_ok(im_h) || !side_ok(im_w) || T < 1 || T > MORPH_MAX_FRAMES) return -1;
   return texel_bytes(B, im_h, im_w) + T * 8;
 }
 
-int render_morph_launch(const float* warp, long warp_bs, long warp_rs, const void* image, int image_u8, const double* ts,
-                        const float* certainty, long cert_bs, long cert_rs, float background, int B, long T, int H, int W, int im_h,
-                        int im_w, void* out, int out_f32, void* workspace, long workspace_bytes, hipStream_t s) {
+extern "C" int roma_op_render_morph(const float* warp, long warp_bs, long warp_rs, const void* image, int image_u8, const double* ts,
+                                    const float* certainty, long cert_bs, long cert_rs, float background, int B, long T, int H, int W,
+                                    int im_h, int im_w, void* out, int out_f32, void* workspace, long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(warp && image && ts && out && workspace, "render_morph: null pointer");
   ROMA_REQUIRE(B >= 1 && B <= 65535, "render_morph: B must lie in [1, 65535]");
   ROMA_REQUIRE(T >= 1 && T <= MORPH_MAX_FRAMES, "render_morph: T (frames) must lie in [1, 65535 * 32]");
@@ -256,7 +258,7 @@ int render_morph_launch(const float* warp, long warp_bs, long warp_rs, const voi
                    (image_u8 || (reinterpret_cast<uintptr_t>(image) & 3) == 0) && (!out_f32 || (reinterpret_cast<uintptr_t>(out) & 3) == 0),
                "render_morph: ts, certainty, a float32 image or a float32 out is not aligned to its type");
   ROMA_REQUIRE(background == background, "render_morph: background is NaN");
-  const long need = render_morph_workspace_bytes(B, im_h, im_w, T);
+  const long need = roma_op_render_morph_workspace(B, im_h, im_w, T);
   ROMA_REQUIRE(workspace_bytes >= need, "render_morph: workspace is too small");
   // what is written must not share a byte with what is read, nor the two written buffers with each other
   const long out_bytes = (long)B * T * n * 3 * (out_f32 ? 4 : 1);

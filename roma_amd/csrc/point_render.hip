@@ -18,13 +18,13 @@
 //   fill     one thread per pixel, reads the decision bytes and the keys of the survivors: an empty or removed pixel with fill_min
 //            survivors in its window takes the smallest of their keys; then every output of the pixel is written
 // The only other atomics are the integer counters of `stats`, one per workgroup that has something to count.
-#include "point_render.h"
-
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "../../include/roma_hip.h"
+#include "common.h"
 #include "workgroup.h"
 #include "workspace.h"
 
@@ -36,6 +36,8 @@ namespace {
 
 typedef unsigned long long u64;
 
+constexpr int RENDER_MAX_RADIUS = 4;  // splat, occlusion and fill windows: at most 9 x 9
+constexpr int RENDER_STATS = 4;       // ints per frame in roma_op_render_points' out_stats
 constexpr int RND_BLOCK = 256, RND_WAVES = RND_BLOCK / WAVE;
 constexpr u64 RND_EMPTY = ~0ull;
 
@@ -222,17 +224,20 @@ size_t render_carve(Workspace256 ws, size_t npx, RenderParams& P) {
 
 }  // namespace
 
-size_t render_points_workspace_bytes(int B, int C, int H, int W) {
+extern "C" long roma_op_render_points_workspace(int B, int C, int H, int W) {
   if (!render_sizes_ok(B, C, H, W)) return 0;
   RenderParams P;
   return render_carve(Workspace256(), (size_t)B * C * H * W, P);
 }
 
-int render_points_launch(const float* points, const unsigned char* colors, const int* counts, const unsigned char* valid,
-                         const double* cameras, const double* R, const double* t, int B, int N, int C, int H, int W, int radius,
-                         double near, double far, int occlusion_radius, double occlusion_rel, int occlusion_count, int fill_radius,
-                         int fill_min, int background, unsigned char* out_color, float* out_depth, int* out_index,
-                         unsigned char* out_mask, int* out_stats, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_render_points(const float* points, const unsigned char* colors, const int* counts, const unsigned char* valid,
+                                     const double* cameras, const double* R, const double* t, int B, int N, int C, int H, int W, int radius,
+                                     double near, double far, int occlusion_radius, double occlusion_rel, int occlusion_count,
+                                     int fill_radius, int fill_min, int background, unsigned char* out_color, float* out_depth,
+                                     int* out_index, unsigned char* out_mask, int* out_stats, void* ws, long workspace_bytes,
+                                     void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(points && cameras && R && t, "render_points: null pointer");
   ROMA_REQUIRE(out_depth && out_index && out_mask && out_stats, "render_points: null pointer");
   ROMA_REQUIRE((colors != nullptr) == (out_color != nullptr), "render_points: colors and out_color go together");
@@ -250,7 +255,7 @@ int render_points_launch(const float* points, const unsigned char* colors, const
   ROMA_REQUIRE(background >= 0 && background <= 0xFFFFFF, "render_points: background is r | g << 8 | b << 16");
   if (B == 0) return 0;
   ROMA_REQUIRE(render_pixels_ok(B, C, H, W), "render_points: 3 * B * C * H * W must be below 2^31");
-  ROMA_REQUIRE(ws && ws_bytes >= render_points_workspace_bytes(B, C, H, W), "render_points: workspace too small");
+  ROMA_REQUIRE(ws && ws_bytes >= (size_t)roma_op_render_points_workspace(B, C, H, W), "render_points: workspace too small");
   RenderParams P = {};
   const size_t npx = (size_t)B * C * H * W;
   render_carve(Workspace256(ws), npx, P);

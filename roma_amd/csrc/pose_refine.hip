@@ -17,8 +17,7 @@
 // pose_refine_kernel: one workgroup of LM_THREADS per pair checks the start, runs lm_fit<PoseFit> and stores the pose.
 // pose_refine_mask_kernel: grid (point blocks, pair): mask = active under the final pose and in front of both cameras (the
 // linear triangulation of recoverPose, cheirality.h).
-#include "pose_refine.h"
-
+#include "../../include/roma_hip.h"
 #include "cheirality.h"
 #include "lm_fit.h"
 
@@ -216,19 +215,21 @@ size_t pose_refine_carve(Workspace256 ws, int B, LmState*& st) {
 
 }  // namespace
 
-size_t refine_pose_workspace_bytes(int B, int N) {
+extern "C" long roma_op_refine_pose_workspace(int B, int N) {
   LmState* st;
   return B > 0 && N > 0 ? pose_refine_carve(Workspace256(), B, st) : 0;
 }
 
-int refine_pose_launch(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
-                       const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
-                       unsigned char* out_mask, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_refine_pose(const double* R, const double* t, const float* kpts_a, const float* kpts_b, const int* counts,
+                                   const unsigned char* valid, int B, int N, double thr, int max_steps, double* out_r, double* out_t,
+                                   unsigned char* out_mask, int* out_info, void* ws, long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(R && t && kpts_a && kpts_b && out_r && out_t && out_mask && out_info && ws, "refine_pose: null pointer");
   ROMA_REQUIRE(B > 0 && N > 0 && (long)B * N < (1l << 31) && B <= (1 << 16), "refine_pose: need 0 < B <= 65536, 0 < N, B * N < 2^31");
   ROMA_REQUIRE(thr > 0 && isfinite(thr), "refine_pose: threshold must be positive and finite");
   ROMA_REQUIRE(max_steps >= 0 && max_steps <= (1 << 16), "refine_pose: need 0 <= max_steps <= 65536");
-  ROMA_REQUIRE(ws_bytes >= refine_pose_workspace_bytes(B, N), "refine_pose: workspace too small (roma_op_refine_pose_workspace)");
+  ROMA_REQUIRE(ws_bytes >= (size_t)roma_op_refine_pose_workspace(B, N), "refine_pose: workspace too small (roma_op_refine_pose_workspace)");
   LmState* st;
   pose_refine_carve(Workspace256(ws), B, st);
   const float2* ka = reinterpret_cast<const float2*>(kpts_a);

@@ -14,12 +14,13 @@
 // The workspace is laid out from the LARGEST image of the host descriptors (equal slots per image), so the kernels find every slot
 // from the image index alone; they read the sizes from the device descriptors and skip an image whose device descriptor does not fit
 // what the host planned for (it can then never read or write out of bounds).
-#include "preprocess.h"
-
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
+
+#include "../../include/roma_hip.h"
+#include "common.h"
 
 // the coefficient arithmetic is evaluated as written: tools/pil_resample_ref.py has the same expressions in the same order
 #pragma clang fp contract(off)
@@ -389,15 +390,16 @@ unsigned grid_x(long items, int slices) {
 
 }  // namespace
 
-long preprocess_workspace_bytes(const long long* desc_host, int n_images, const int* targets_hw, int n_targets) {
+extern "C" long roma_op_preprocess_workspace(const long long* desc_host, int n_images, const int* targets_hw, int n_targets) {
   Plan plan;
   if (preprocess_plan(desc_host, n_images, targets_hw, n_targets, -1, &plan) != 0) return -1;
   return plan.bytes;
 }
 
-int preprocess_launch(const unsigned char* src, long long src_bytes, const long long* desc_host, const long long* desc_dev,
-                      int n_images, const int* targets_hw, int n_targets, int normalize, float* out0, float* out1, void* workspace,
-                      hipStream_t s) {
+extern "C" int roma_op_preprocess(const unsigned char* src, long long src_bytes, const long long* desc_host, const long long* desc_dev,
+                                  int n_images, const int* targets_hw, int n_targets, int normalize, float* out0, float* out1,
+                                  void* workspace, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(src && desc_host && desc_dev && targets_hw && out0 && workspace, "preprocess: null pointer");
   ROMA_REQUIRE(n_targets != 2 || out1, "preprocess: null pointer (out1 with two targets)");
   ROMA_REQUIRE(src_bytes >= 0, "preprocess: src_bytes is negative");

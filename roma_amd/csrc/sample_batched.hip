@@ -16,18 +16,22 @@
 //     the count of positive weights, the cursor) give the same totals in any order.
 // The density is kde_kernel<true>'s loop (kde.hip): coordinates rounded to fp16, f32 accumulation, v_exp_f32 with
 // coef = -log2(e) / (2 * 0.1^2), 1024 reference rows per LDS tile read as wave-wide broadcasts.
-#include "sample_batched.h"
-
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "../../include/roma_hip.h"
 #include "sampling.h"
 #include "workgroup.h"
 #include "workspace.h"
 
 namespace roma {
 namespace {
+
+// the second draw of pair b runs on seeds[b] ^ SAMPLE_SECOND_DRAW_SEED (the multiplier of Knuth's MMIX generator)
+constexpr unsigned long long SAMPLE_SECOND_DRAW_SEED = 0x5851f42d4c957f2dull;
+// largest first-draw size: the all-pairs order of sampling.hip (ORDER_ALLPAIRS_MAX); its bitonic path is not batched
+constexpr long SAMPLE_BATCHED_MAX_K = 65536;
 
 struct PairState {      // one per pair and draw, at the head of the workspace
   unsigned prefix;      // bits of the k-th key fixed so far; after the third pass the key T itself
@@ -375,16 +379,19 @@ int select_launch(const float* keys, long n, long k, PairState* st, unsigned* hi
 
 }  // namespace
 
-size_t sample_matches_workspace_bytes(int B, long n, long num, int balanced) {
+extern "C" long roma_op_sample_matches_workspace(int B, long n, long num, int balanced) {
   if (B <= 0 || n <= 0 || num <= 0) return 0;
   Sizes z;
   sizes(n, num, balanced, &z);
   return carve(Workspace16(), B, n, z, balanced).bytes;
 }
 
-int sample_matches_launch(const float* matches, const float* certainty, const unsigned long long* seeds, int B, long n, long num,
-                          int threshold, float thresh, int balanced, float* out_matches, float* out_certainty, int* out_counts,
-                          long long* out_idx, long long* out_first_idx, float* out_density, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_sample_matches(const float* matches, const float* certainty, const unsigned long long* seeds, int B, long n,
+                                      long num, int threshold, float thresh, int balanced, float* out_matches, float* out_certainty,
+                                      int* out_counts, long long* out_idx, long long* out_first_idx, float* out_density, void* ws,
+                                      long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(matches && certainty && seeds && out_matches && out_certainty, "sample_matches: null pointer");
   ROMA_REQUIRE(B >= 0 && B <= 65535, "sample_matches: B must lie in [0, 65535]");
   ROMA_REQUIRE(n >= 0 && num >= 0, "sample_matches: n and num must not be negative");

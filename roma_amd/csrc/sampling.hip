@@ -14,9 +14,10 @@
 // spatially ordered one the compaction leaves.  k <= 40 000 in match(): an all-pairs rank (k^2 compares from LDS tiles) is
 // ~30 us and needs no sort; above 65 536 (sample(num = 100 000) asks for k = 400 000) the same order comes from a bitonic
 // network over the packed (key, index) words - see ORDER_ALLPAIRS_MAX.
-#include "sampling.h"
-
 #include <stdint.h>
+
+#include "../../include/roma_hip.h"
+#include "sampling.h"
 
 namespace roma {
 
@@ -189,17 +190,19 @@ __global__ __launch_bounds__(256) void race_unpack_kernel(const unsigned long lo
   if (i < k) out[i] = (long long)(comp[i] & 0xffffffffull);
 }
 
-size_t multinomial_workspace_bytes(long n, long k) {
+extern "C" long roma_op_multinomial_workspace(long n, long k) {
   size_t b = sizeof(SelState) + 2048 * sizeof(unsigned) + (size_t)n * sizeof(float) + (size_t)(k > 0 ? k : 0) * sizeof(long long) + 16;
   if (k > ORDER_ALLPAIRS_MAX) b += (size_t)order_pow2(k) * sizeof(unsigned long long) + 16;
   return b;
 }
 
-int multinomial_launch(const float* weights, long n, long k, unsigned long long seed, long long* out, void* ws, size_t ws_bytes,
-                       hipStream_t s) {
+extern "C" int roma_op_multinomial(const float* weights, long n, long k, unsigned long long seed, long long* out, void* ws,
+                                   long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = (size_t)workspace_bytes;
   ROMA_REQUIRE(weights && out && ws && n > 0 && k > 0 && k <= n, "multinomial: bad arguments (need 0 < k <= n)");
   ROMA_REQUIRE(n < (1l << 31), "multinomial: n too large");
-  ROMA_REQUIRE(ws_bytes >= multinomial_workspace_bytes(n, k), "multinomial: workspace too small (roma_op_multinomial_workspace)");
+  ROMA_REQUIRE(ws_bytes >= (size_t)roma_op_multinomial_workspace(n, k), "multinomial: workspace too small (roma_op_multinomial_workspace)");
   SelState* st = reinterpret_cast<SelState*>(ws);
   unsigned* hist = reinterpret_cast<unsigned*>(st + 1);
   float* keys = reinterpret_cast<float*>(hist + 2048);

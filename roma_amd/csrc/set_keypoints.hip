@@ -27,14 +27,14 @@
 //             the row key (bits of the certainty) << 32 | (0xFFFFFFFF - n) goes to the slots of both keypoints by atomicMax
 //   finish    one thread per row: a row stays if it holds both of its slots; kept and info are counted
 // Integer atomicAdd counts and atomicMax selections do not depend on the order of arrival.
-#include "set_keypoints.h"
-
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
 
+#include "../../include/roma_hip.h"
 #include "pair_views.h"
+#include "tracks.h"
 #include "workgroup.h"
 #include "workspace.h"
 
@@ -44,6 +44,11 @@
 namespace roma {
 namespace {
 
+constexpr int SET_KPTS_INFO = 6;              // ints per problem in roma_op_keypoints_from_matches' out_info
+constexpr int SET_KPTS_MAX_CELL = 64;         // pixels
+constexpr int SET_KPTS_MAX_SIZE = 65535;      // H and W of a view
+constexpr long SET_KPTS_MAX_GRID = 1l << 22;  // cells of one view
+constexpr long SET_KPTS_MAX_CELLS = 1l << 28; // B (G_total + 1024 V): the cells of a call with every view's grid padded to a block
 constexpr int SKP_BLOCK = 1024, SKP_WAVES = SKP_BLOCK / WAVE;  // cells per workgroup of the grid kernels, one thread each
 constexpr int SKP_ROWS = 256;                                // rows per workgroup of the row kernels
 constexpr int SKP_MAX_BLOCKS = (int)(SET_KPTS_MAX_GRID / SKP_BLOCK);  // blocks of one view: the scan keeps them in LDS
@@ -371,7 +376,7 @@ long skp_padded_bound(int V, long G_total) { return ((G_total + SKP_BLOCK - 1) /
 
 }  // namespace
 
-size_t keypoints_from_matches_workspace_bytes(int B, int V, int P, int N, long G_total, int K) {
+extern "C" long roma_op_keypoints_from_matches_workspace(int B, int V, int P, int N, long G_total, int K) {
   if (B <= 0 || V <= 0 || V > ROMA_TRACKS_MAX_VIEWS || P < 0 || P > ROMA_TRACKS_MAX_PAIRS || G_total <= 0 || K <= 0 || K > ROMA_TRACKS_MAX_KPTS)
     return 0;
   if (G_total > (long)V * SET_KPTS_MAX_GRID || (long)B * skp_padded_bound(V, G_total) > SET_KPTS_MAX_CELLS) return 0;
@@ -379,10 +384,12 @@ size_t keypoints_from_matches_workspace_bytes(int B, int V, int P, int N, long G
   return skp_carve(Workspace256(), B, skp_padded_bound(V, G_total), P, K, S);
 }
 
-int keypoints_from_matches_launch(const float* matches, const float* certainty, const int* counts, const int* pair_views,
-                                  const int* sizes, int B, int V, int Pn, int N, int cell, float radius, int K, int one_to_one,
-                                  float* out_kpts, float* out_score, int* out_num_kpts, int* out_total, int* out_inds, int* out_kept,
-                                  int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_keypoints_from_matches(const float* matches, const float* certainty, const int* counts, const int* pair_views,
+                                              const int* sizes, int B, int V, int Pn, int N, int cell, float radius, int K, int one_to_one,
+                                              float* out_kpts, float* out_score, int* out_num_kpts, int* out_total, int* out_inds,
+                                              int* out_kept, int* out_info, void* ws, long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(out_kpts && out_score && out_num_kpts && out_total && out_info && sizes, "keypoints_from_matches: null pointer");
   ROMA_REQUIRE(V >= 2 && V <= ROMA_TRACKS_MAX_VIEWS, "keypoints_from_matches: need 2 <= V <= 8 views");
   ROMA_REQUIRE(B >= 0 && B <= 65535, "keypoints_from_matches: B must lie in [0, 65535]");
@@ -415,7 +422,7 @@ int keypoints_from_matches_launch(const float* matches, const float* certainty, 
                "keypoints_from_matches: B * (cells of all views + 1024 V) must not exceed 2^28; use a larger cell or fewer problems");
   if (int rc = check_pairs("keypoints_from_matches", pair_views, V, Pn, S.pv)) return rc;  // whether or not a row will be read
   if (B == 0) return 0;
-  ROMA_REQUIRE(ws && ws_bytes >= keypoints_from_matches_workspace_bytes(B, V, Pn, N, gtot, K), "keypoints_from_matches: workspace too small");
+  ROMA_REQUIRE(ws && ws_bytes >= (size_t)roma_op_keypoints_from_matches_workspace(B, V, Pn, N, gtot, K), "keypoints_from_matches: workspace too small");
   // laid out for the cells there are: never more than the bound the workspace entry sizes for
   S.GP = (long)blocks * SKP_BLOCK;
   S.NBLK = blocks;

@@ -8,9 +8,10 @@
 //   matches += delta * to_normalized (tiny.py:292, 300) -> tiny_update_kernel
 //   F.interpolate(bilinear) (tiny.py:294, 222-236) -> resize_bilinear_kernel (elementwise.hip)
 //   warp = cat(grid, flow), sigmoid(certainty) (tiny.py:237-238) -> tiny_final_kernel
-#include "tiny.h"
-
 #include <algorithm>
+
+#include "../../include/roma_hip.h"
+#include "common.h"
 
 namespace roma {
 
@@ -29,7 +30,8 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
   }
 }
 
-int nchw_to_nhwc_launch(const float* in, float* out, int B, int C, int H, int W, hipStream_t s) {
+extern "C" int roma_op_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(in && out && B > 0 && C > 0 && H > 0 && W > 0, "nchw_to_nhwc: bad arguments");
   const long total = (long)B * C * H * W;
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)std::min<long>((total + 255) / 256, 65536)), dim3(256), 0, s, in, out, B, C,
@@ -86,7 +88,8 @@ __global__ __launch_bounds__(256) void tiny_pos_embed_kernel(const float* __rest
 
 __global__ void tiny_pos_embed_exact_kernel(const float* __restrict__ cv, float* __restrict__ out, int B, int H1, int W1, long N0);
 
-int tiny_pos_embed_launch(const float* cv, float* out, int B, int H1, int W1, int H0, int W0, int exact_softmax, hipStream_t s) {
+extern "C" int roma_op_tiny_pos_embed(const float* cv, float* out, int B, int H1, int W1, int H0, int W0, int exact_softmax, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(cv && out && B > 0 && H1 > 0 && W1 > 0 && H0 > 0 && W0 > 0, "tiny_pos_embed: bad arguments");
   const long total = (long)B * H0 * W0;
   if (exact_softmax) {
@@ -136,8 +139,9 @@ __global__ __launch_bounds__(256) void tiny_matcher_input_kernel(const float* __
   }
 }
 
-int tiny_matcher_input_launch(const float* f0, const float* f1, const float* warp, int warp_channels, float* d, int B, int H,
-                              int W, int H1, int W1, int C, int Cp, hipStream_t s) {
+extern "C" int roma_op_tiny_matcher_input(const float* f0, const float* f1, const float* warp, int warp_channels, float* d, int B, int H,
+                                          int W, int H1, int W1, int C, int Cp, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(f0 && f1 && warp && d && B > 0 && H > 0 && W > 0 && H1 > 0 && W1 > 0, "tiny_matcher_input: bad arguments");
   ROMA_REQUIRE(warp_channels >= 2 && Cp >= 2 * C + 2, "tiny_matcher_input: Cp must hold 2 C + 2 channels");
   const long total = (long)B * H * W * Cp;
@@ -158,8 +162,9 @@ __global__ __launch_bounds__(256) void tiny_update_kernel(const float* __restric
   out[p * 3 + 2] = b2 + delta[p * ldd + 2];
 }
 
-int tiny_update_launch(const float* base, int base_channels, const float* delta, long ldd, float sx, float sy, float* out,
-                       long npix, hipStream_t s) {
+extern "C" int roma_op_tiny_update(const float* base, int base_channels, const float* delta, long ldd, float sx, float sy, float* out,
+                                   long npix, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(base && delta && out && npix > 0 && (base_channels == 2 || base_channels == 3) && ldd >= 3,
                "tiny_update: bad arguments");
   hipLaunchKernelGGL(tiny_update_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, base, base_channels, delta, ldd, sx,
@@ -239,7 +244,8 @@ __global__ __launch_bounds__(1024) void gray_instnorm_kernel(const float* __rest
   for (long p = threadIdx.x; p < HW; p += 1024) ob[p] = (gray(p) - mean) * inv;
 }
 
-int gray_instnorm_launch(const float* in, float* out, int B, int H, int W, int C, float eps, hipStream_t s) {
+extern "C" int roma_op_gray_instnorm(const float* in, float* out, int B, int H, int W, int C, float eps, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(in && out && B > 0 && H > 0 && W > 0 && C > 0, "gray_instnorm: bad arguments");
   hipLaunchKernelGGL(gray_instnorm_kernel, dim3((unsigned)B), dim3(1024), 0, s, in, out, C, (long)H * W, eps);
   ROMA_LAUNCH_CHECK();
@@ -293,8 +299,9 @@ __global__ __launch_bounds__(256) void conv2d_nhwc_kernel(const float* __restric
   }
 }
 
-int conv2d_nhwc_launch(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int H, int W,
-                       int Cin, int Cout, int K, int stride, int pad, int relu, hipStream_t s) {
+extern "C" int roma_op_conv2d_nhwc(const float* in, const float* w, const float* bias, const float* res, float* out, int B, int H, int W,
+                                   int Cin, int Cout, int K, int stride, int pad, int relu, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(in && w && out && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv2d_nhwc: bad arguments");
   ROMA_REQUIRE((K == 1 || K == 3) && (stride == 1 || stride == 2) && pad >= 0 && pad <= 1, "conv2d_nhwc: 1x1 / 3x3, stride 1 / 2, padding 0 / 1");
   ROMA_REQUIRE(Cout % 4 == 0, "conv2d_nhwc: Cout must be a multiple of 4");
@@ -329,7 +336,8 @@ __global__ __launch_bounds__(256) void avgpool_nhwc_kernel(const float* __restri
   }
 }
 
-int avgpool_nhwc_launch(const float* in, float* out, int B, int H, int W, int C, int k, hipStream_t s) {
+extern "C" int roma_op_avgpool_nhwc(const float* in, float* out, int B, int H, int W, int C, int k, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(in && out && B > 0 && C > 0 && k > 0 && H >= k && W >= k, "avgpool_nhwc: bad arguments");
   const int Ho = H / k, Wo = W / k;
   const long total = (long)B * Ho * Wo * C;
@@ -349,7 +357,8 @@ __global__ __launch_bounds__(256) void add3_kernel(const float* __restrict__ a, 
   }
 }
 
-int add3_launch(const float* a, const float* b, const float* c, float* out, long n, hipStream_t s) {
+extern "C" int roma_op_add3(const float* a, const float* b, const float* c, float* out, long n, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(a && b && out && n > 0, "add3: bad arguments");
   hipLaunchKernelGGL(add3_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 1 << 20)), dim3(256), 0, s, a, b, c, out, n);
   ROMA_LAUNCH_CHECK();
@@ -370,7 +379,8 @@ __global__ __launch_bounds__(256) void tiny_final_kernel(const float* __restrict
   cert[idx] = z < -87.f ? expf(z) : 1.f / (1.f + expf(-z));
 }
 
-int tiny_final_launch(const float* matches, float* warp, float* cert, int B, int H, int W, hipStream_t s) {
+extern "C" int roma_op_tiny_final(const float* matches, float* warp, float* cert, int B, int H, int W, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(matches && warp && cert && B > 0 && H > 0 && W > 0, "tiny_final: bad arguments");
   const long total = (long)B * H * W;
   hipLaunchKernelGGL(tiny_final_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, matches, warp, cert, B, H, W);

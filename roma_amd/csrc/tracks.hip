@@ -21,18 +21,20 @@
 //   numbers   every wave walks one contiguous segment of the ids, 64 at a time; the roots that are tracks are counted by ballot,
 //             the waves' totals are added in wave order, a second walk writes the track number into slot[root].
 //   fill      tracks = -1 and kpts = NaN everywhere, then every keypoint of a track below max_tracks writes its own cell.
-#include "tracks.h"
-
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/roma_hip.h"
+#include "common.h"
 #include "pair_views.h"
+#include "tracks.h"
 #include "workgroup.h"
 #include "workspace.h"
 
 namespace roma {
 namespace {
 
+constexpr int BUILD_TRACKS_INFO = 4;  // ints per problem in roma_op_build_tracks' out_info
 constexpr int TRK_THREADS = 1024, TRK_WAVES = TRK_THREADS / WAVE;
 constexpr int TRK_ARRAYS = 4;  // label, slot, mask, conflict
 
@@ -238,15 +240,17 @@ __global__ __launch_bounds__(TRK_THREADS) void build_tracks_kernel(const TrkPara
 
 }  // namespace
 
-size_t build_tracks_workspace_bytes(int B, int V, int K, int P, int M) {
+extern "C" long roma_op_build_tracks_workspace(int B, int V, int K, int P, int M) {
   if (B <= 0 || V <= 0 || K <= 0 || V > ROMA_TRACKS_MAX_VIEWS || K > ROMA_TRACKS_MAX_KPTS) return 0;
   TrkParams T;
   return trk_carve(Workspace256(), B, V, K, T);
 }
 
-int build_tracks_launch(const int* inds, const int* pair_views, const int* match_counts, const int* num_kpts, const float* x, int B,
-                        int V, int K, int Pn, int M, int T, int min_views, int* out_tracks, float* out_kpts, int* out_counts,
-                        int* out_total, int* out_info, void* ws, size_t ws_bytes, hipStream_t s) {
+extern "C" int roma_op_build_tracks(const int* inds, const int* pair_views, const int* match_counts, const int* num_kpts, const float* x,
+                                    int B, int V, int K, int Pn, int M, int T, int min_views, int* out_tracks, float* out_kpts,
+                                    int* out_counts, int* out_total, int* out_info, void* ws, long workspace_bytes, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t ws_bytes = workspace_size(workspace_bytes);
   ROMA_REQUIRE(out_tracks && out_counts && out_total && out_info, "build_tracks: null pointer");
   ROMA_REQUIRE(V >= 2 && V <= ROMA_TRACKS_MAX_VIEWS, "build_tracks: need 2 <= V <= 8 views");
   ROMA_REQUIRE(B >= 0 && B <= 65535, "build_tracks: B must lie in [0, 65535]");
@@ -263,7 +267,7 @@ int build_tracks_launch(const int* inds, const int* pair_views, const int* match
   TrkParams P = {};
   if (int rc = check_pairs("build_tracks", pair_views, V, Pn, P.pv.v)) return rc;  // whether or not a row will be read
   if (B == 0) return 0;
-  ROMA_REQUIRE(K == 0 || (ws && ws_bytes >= build_tracks_workspace_bytes(B, V, K, Pn, M)), "build_tracks: workspace too small");
+  ROMA_REQUIRE(K == 0 || (ws && ws_bytes >= (size_t)roma_op_build_tracks_workspace(B, V, K, Pn, M)), "build_tracks: workspace too small");
   P.inds = reinterpret_cast<const int2*>(inds);
   P.match_counts = match_counts;
   P.num_kpts = num_kpts;

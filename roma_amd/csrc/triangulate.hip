@@ -10,12 +10,14 @@
 // the pair as the grid's y axis, so the pose and the cameras of a pair are wave-uniform loads.  No LDS, no workspace.  The only
 // atomics are the integer counters of `stats`, whose totals do not depend on arrival order: every output is bit-identical from
 // run to run and independent of B and of where the pair sits in the batch.
-#include "triangulate.h"
-
 #include <math.h>
 #include <stdint.h>
 
 #include <algorithm>
+
+#include "../../include/roma_hip.h"
+#include "common.h"
+#include "triangulate.h"
 
 // nothing here is fused: tools/triangulate_ref.py evaluates the same expressions in the same order
 #pragma clang fp contract(off)
@@ -307,11 +309,12 @@ unsigned grid_x(long n, int B) {
 
 }  // namespace
 
-int triangulate_launch(const float* matches, const float* certainty, const int* counts, const unsigned char* valid, const double* R,
-                       const double* t, const double* K_a, const double* K_b, int B, long n, int coords, int W_a, int H_a, int W_b,
-                       int H_b, int sym_w, double max_depth, double max_reproj, double min_parallax, double min_certainty,
-                       float* points, float* depth_other, float* reproj, float* parallax, unsigned char* flags, int* stats,
-                       hipStream_t s) {
+extern "C" int roma_op_triangulate(const float* matches, const float* certainty, const int* counts, const unsigned char* valid,
+                                   const double* R, const double* t, const double* K_a, const double* K_b, int B, long n, int coords,
+                                   int W_a, int H_a, int W_b, int H_b, int sym_w, double max_depth, double max_reproj, double min_parallax,
+                                   double min_certainty, float* points, float* depth_other, float* reproj, float* parallax,
+                                   unsigned char* flags, int* stats, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(matches && R && t && points && flags, "triangulate: null pointer");
   ROMA_REQUIRE(B >= 0 && B <= 65535, "triangulate: B must lie in [0, 65535]");
   ROMA_REQUIRE(n >= 0, "triangulate: n must not be negative");
@@ -334,9 +337,10 @@ int triangulate_launch(const float* matches, const float* certainty, const int* 
   return 0;
 }
 
-int depth_consistency_launch(const float* points, const unsigned char* flags, const double* R, const double* t, const double* K_a,
-                             const double* K_b, int W_a, int H_a, int W_b, int H_b, int B, int H, int W, double rel_thresh,
-                             unsigned char* consistent, float* err, hipStream_t s) {
+extern "C" int roma_op_depth_consistency(const float* points, const unsigned char* flags, const double* R, const double* t,
+                                         const double* K_a, const double* K_b, int W_a, int H_a, int W_b, int H_b, int B, int H, int W,
+                                         double rel_thresh, unsigned char* consistent, float* err, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(points && flags && R && t && consistent, "depth_consistency: null pointer");
   ROMA_REQUIRE(B >= 0 && B <= 65535, "depth_consistency: B must lie in [0, 65535]");
   ROMA_REQUIRE(H >= 0 && W >= 0, "depth_consistency: H and W must not be negative");

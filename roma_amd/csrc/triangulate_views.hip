@@ -14,11 +14,13 @@
 // One thread per point; the views of the problem (pose, centre, camera, threshold) are staged once per workgroup in LDS and the
 // observations are re-read from memory where they are used, so no per-thread array is indexed by a view.  `stats` is added over
 // the workgroup in lane and wave order, then by one integer atomic per counter: bit-identical from run to run.
-#include "tracks.h"
-#include "triangulate.h"
-
 #include <math.h>
 #include <stdint.h>
+
+#include "../../include/roma_hip.h"
+#include "common.h"
+#include "tracks.h"
+#include "triangulate.h"
 
 // nothing here is fused: tools/triangulate_views_ref.py evaluates the same expressions in the same order
 #pragma clang fp contract(off)
@@ -26,6 +28,8 @@
 namespace roma {
 namespace {
 
+constexpr int TRIANGULATE_VIEWS_STATS = 8;    // ints per problem in roma_op_triangulate_views' out_stats
+constexpr int TRIANGULATE_VIEWS_MAX_GN = 10;  // Gauss-Newton steps per fit
 constexpr int TV_THREADS = 256, TV_WAVES = TV_THREADS / 64;
 constexpr int TV_VIEW = 20;  // doubles of a view in LDS: R (9, row-major), t (3), centre (3), fx, fy, cx, cy, thr
 constexpr int TV_T = 9, TV_C = 12, TV_FX = 15, TV_FY = 16, TV_CX = 17, TV_CY = 18, TV_THR = 19;
@@ -343,11 +347,12 @@ __global__ __launch_bounds__(TV_THREADS) void triangulate_views_kernel(const TvP
 
 }  // namespace
 
-int triangulate_views_launch(const float* kpts, const double* K, const double* R, const double* t, const unsigned char* view_valid,
-                             const int* counts, const unsigned char* valid, int B, int V, int N, double max_reproj,
-                             double min_parallax, double max_depth, int min_views, int gn_steps, int trim, double* out_points,
-                             float* out_reproj, unsigned char* out_used, float* out_parallax, unsigned char* out_flags,
-                             int* out_stats, hipStream_t s) {
+extern "C" int roma_op_triangulate_views(const float* kpts, const double* K, const double* R, const double* t,
+                                         const unsigned char* view_valid, const int* counts, const unsigned char* valid, int B, int V,
+                                         int N, double max_reproj, double min_parallax, double max_depth, int min_views, int gn_steps,
+                                         int trim, double* out_points, float* out_reproj, unsigned char* out_used, float* out_parallax,
+                                         unsigned char* out_flags, int* out_stats, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
   ROMA_REQUIRE(kpts && R && t && out_points && out_reproj && out_used && out_parallax && out_flags && out_stats,
                "triangulate_views: null pointer");
   ROMA_REQUIRE(V >= 2 && V <= ROMA_TRACKS_MAX_VIEWS, "triangulate_views: need 2 <= V <= 8 views");

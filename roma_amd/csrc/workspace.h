@@ -35,4 +35,7 @@ class Workspace {
 using Workspace256 = Workspace<256, true>;   // the geometry operators
 using Workspace16 = Workspace<16, false>;    // sample_matches, match_keypoints
 
+// the `long workspace_bytes` of an entry point as a size: a negative count is an empty workspace, which the operator refuses
+inline size_t workspace_size(long workspace_bytes) { return workspace_bytes > 0 ? (size_t)workspace_bytes : 0; }
+
 }  // namespace roma

@@ -7,15 +7,17 @@ float64 by tools/depth_fusion_ref.py; the result is bit-identical from run to ru
 only, one enqueue for a batch of problems, nothing read back."""
 from __future__ import annotations
 
+from functools import partial
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from .geometry import _ptr, _stream, _valid
+from ._lib import _ptr, _stream
+from .geometry import _valid
 
-MAX_VIEWS, MAX_PAIRS = 8, 64          # csrc/depth_fusion.h: FUSE_MAX_VIEWS, FUSE_MAX_PAIRS
+MAX_VIEWS, MAX_PAIRS = 8, 64          # csrc/depth_fusion.hip: FUSE_MAX_VIEWS, FUSE_MAX_PAIRS
 MAX_SLOTS = 2 * (MAX_VIEWS - 1)       # FUSE_MAX_SLOTS
 MAX_COLOR_VIEWS = 128                 # FUSE_MAX_COLOR_VIEWS: B * V with a colour source
 KEPT, DUPLICATE = 1, 2                # bits of `state`
@@ -37,10 +39,7 @@ class DenseFusion(NamedTuple):
     stats: torch.Tensor         # [.., 8] int32: pixels with a hypothesis, fused, kept, duplicates, emitted, with a violation, 0, 0
 
 
-def _device_tensor(x, name):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise _lib.RomaHipError(f"roma_amd.depth_fusion: {name} must be a tensor on a HIP device; there is no CPU fallback")
-    return x
+_device_tensor = partial(_lib._device_tensor, module="depth_fusion")
 
 
 def _pairs(pair_views, V, unique):

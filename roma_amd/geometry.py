@@ -23,11 +23,10 @@ Levenberg-Marquardt on the truncated Sampson error, as the reference's PoseLib b
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
+from ._lib import _ptr, _stream
 
 HOMOGRAPHY, FUNDAMENTAL = 0, 1
 SAMPLE_SIZE = {HOMOGRAPHY: 4, FUNDAMENTAL: 7}
@@ -88,14 +87,6 @@ def _seeds(seed, B, dev):
     return seeds.to(dev).contiguous()  # read as uint64 by the kernels
 
 
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else 0)
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def _single(kpts):
     """the single-pair form of the public functions: [N, 2] keypoints"""
     return isinstance(kpts, torch.Tensor) and kpts.dim() == 2
@@ -110,7 +101,7 @@ def _valid(valid, B, dev):
     return valid
 
 
-MAGSAC_MAX_LO = 64  # csrc/geometry.h, csrc/essential.h
+MAGSAC_MAX_LO = 64  # csrc/geometry.hip, csrc/essential.hip
 # roma_op_<op>: (info columns, score columns, what the confidence argument is called)
 ROBUST_OPS = {"ransac": (6, 0, "confidence"), "magsac": (7, 2, "confidence"), "essential": (5, 0, "prob"),
               "essential_magsac": (7, 2, "prob")}
@@ -308,7 +299,7 @@ def find_fundamental(kpts_A, kpts_B, ransac_reproj_threshold=3.0, confidence=0.9
 
 
 # ---------------------------------------------------------------------------------------------------- essential matrix and pose
-ESSENTIAL_MAX_ROOTS = 10  # solutions of one five-point sample (csrc/essential.h)
+ESSENTIAL_MAX_ROOTS = 10  # solutions of one five-point sample (csrc/essential.hip)
 
 
 def essential(kpts_A, kpts_B, camera_matrix=None, prob=0.999, threshold=1.0, max_iters=1000, seed=None, counts=None):

@@ -11,12 +11,13 @@ bit-identical from run to run and independent of the batch a pair sits in."""
 from __future__ import annotations
 
 from collections import namedtuple
+from functools import partial
 
 import numpy as np
 import torch
 
 from . import _lib
-from .geometry import _ptr, _stream
+from ._lib import _ptr, _stream
 
 DenseMetrics = namedtuple("DenseMetrics", "n_valid n_below gd_sum epe pck prob gd", defaults=(None, None))
 
@@ -56,10 +57,7 @@ def _small_shape(x, name, B, shapes):
     return x
 
 
-def _device_tensor(x, name):
-    if not x.is_cuda:
-        raise _lib.RomaHipError(f"roma_amd.gt_warp: {name} must be a tensor on a HIP device; there is no CPU fallback")
-    return x.detach()
+_device_tensor = partial(_lib._device_tensor, module="gt_warp")
 
 
 def _small(x, name, dev):

@@ -14,7 +14,7 @@ from collections import namedtuple
 import torch
 
 from . import _lib
-from .geometry import _ptr, _stream
+from ._lib import _ptr, _stream
 
 MAX_POINTS = 1 << 20  # keypoints per pair and side that one call takes
 

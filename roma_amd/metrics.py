@@ -38,7 +38,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .geometry import _ptr, _stream
+from ._lib import _ptr, _stream
 
 PoseError = namedtuple("PoseError", "e_t e_R e_pose")
 ErrorSummary = namedtuple("ErrorSummary", "n dropped below acc auc")

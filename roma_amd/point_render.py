@@ -9,15 +9,17 @@ fill_radius pixels."""
 from __future__ import annotations
 
 import math
+from functools import partial
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from .geometry import _ptr, _stream, _valid
+from ._lib import _ptr, _stream
+from .geometry import _valid
 
-MAX_RADIUS = 4                      # csrc/point_render.h: RENDER_MAX_RADIUS
+MAX_RADIUS = 4                      # csrc/point_render.hip: RENDER_MAX_RADIUS
 HIT, REMOVED, FILLED = 1, 2, 4      # bits of `mask`
 
 
@@ -29,10 +31,7 @@ class PointRender(NamedTuple):
     stats: torch.Tensor            # [.., C, 4] int32: usable rows whose cell lies inside the image, pixels hit, removed, filled
 
 
-def _device_tensor(x, name):
-    if not x.is_cuda:
-        raise _lib.RomaHipError(f"roma_amd.point_render: {name} must be a tensor on a HIP device; there is no CPU fallback")
-    return x.detach()
+_device_tensor = partial(_lib._device_tensor, module="point_render")
 
 
 def orbit_cameras(R0, t0, centre, angles, axis=(0.0, 1.0, 0.0), device="cuda"):

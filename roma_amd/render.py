@@ -9,12 +9,13 @@ the host, and every output is bit-identical from run to run and independent of t
 from __future__ import annotations
 
 import math
+from functools import partial
 
 import numpy as np
 import torch
 
 from . import _lib
-from .geometry import _ptr, _stream
+from ._lib import _ptr, _stream
 
 FRAME_CHUNK = 32  # frames one workgroup renders from the warp rows it loaded (roma_op_render_morph_frame_chunk)
 
@@ -27,10 +28,7 @@ def morph_times(n=200):
     return (1 + np.cos(np.linspace(0, 2 * np.pi, n))) / 2
 
 
-def _device_tensor(x, name):
-    if not x.is_cuda:
-        raise _lib.RomaHipError(f"roma_amd.render: {name} must be a tensor on a HIP device; there is no CPU fallback")
-    return x.detach()
+_device_tensor = partial(_lib._device_tensor, module="render")
 
 
 def _times(ts):

@@ -38,7 +38,7 @@ def multinomial(weights: torch.Tensor, num_samples: int, generator=None) -> torc
 
 
 SAMPLE_MODES = ("threshold_balanced", "threshold", "balanced", "plain")  # the substrings decide, as in the reference
-MAX_FIRST_DRAW = 65536  # csrc/sample_batched.h SAMPLE_BATCHED_MAX_K
+MAX_FIRST_DRAW = 65536  # csrc/sample_batched.hip SAMPLE_BATCHED_MAX_K
 
 
 def sample_matches(matches: torch.Tensor, certainty: torch.Tensor, num: int = 10000, sample_mode: str = "threshold_balanced",

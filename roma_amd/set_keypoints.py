@@ -14,10 +14,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .geometry import _ptr, _stream
+from ._lib import _ptr, _stream
 from .tracks import MAX_KPTS, MAX_VIEWS, _device_tensor, _pairs
 
-MAX_CELL = 64          # csrc/set_keypoints.h: SET_KPTS_MAX_CELL
+MAX_CELL = 64          # csrc/set_keypoints.hip: SET_KPTS_MAX_CELL
 MAX_SIZE = 65535       # SET_KPTS_MAX_SIZE
 MAX_GRID = 1 << 22     # SET_KPTS_MAX_GRID, cells of one view
 MAX_CELLS = 1 << 28    # SET_KPTS_MAX_CELLS, B (G_total + 1024 V)

@@ -24,13 +24,14 @@ builder).  Tracks are numbered by their smallest node, so the result depends on 
 rows or pairs, on duplicates, or on the schedule.  Restated by tools/tracks_ref.py."""
 from __future__ import annotations
 
+from functools import partial
 from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
-from .geometry import _ptr, _stream
+from ._lib import _ptr, _stream
 
 MAX_VIEWS = 8        # csrc/tracks.h: ROMA_TRACKS_MAX_VIEWS
 MAX_KPTS = 1 << 16   # ROMA_TRACKS_MAX_KPTS, keypoints per view
@@ -45,10 +46,7 @@ class Tracks(NamedTuple):
     info: torch.Tensor             # [.., 4] int32: rows used, rows ignored, components of >= 2 keypoints, components dropped
 
 
-def _device_tensor(x, name):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise _lib.RomaHipError(f"roma_amd.tracks: {name} must be a tensor on a HIP device; there is no CPU fallback")
-    return x
+_device_tensor = partial(_lib._device_tensor, module="tracks")
 
 
 def _pairs(pair_views, V):

@@ -14,18 +14,20 @@ from __future__ import annotations
 
 import math
 from collections import namedtuple
+from functools import partial
 
 import torch
 
 from . import _lib
-from .geometry import _cameras, _counts, _pair_batch, _pose_tensor, _ptr, _stream, _valid
+from ._lib import _ptr, _stream
+from .geometry import _cameras, _counts, _pair_batch, _pose_tensor, _valid
 
 SKIPPED, DEGENERATE, CHEIRALITY, REPROJ, PARALLAX, CERTAINTY = 1, 2, 4, 8, 16, 32  # bits of `flags` (csrc/triangulate.h)
 
 Triangulation = namedtuple("Triangulation", "points depth_other reproj parallax flags valid stats")
 ViewsTriangulation = namedtuple("ViewsTriangulation", "points reproj used parallax flags valid stats")
 MAX_VIEWS = 8   # csrc/tracks.h: ROMA_TRACKS_MAX_VIEWS
-MAX_GN = 10     # TRIANGULATE_VIEWS_MAX_GN
+MAX_GN = 10     # csrc/triangulate_views.hip: TRIANGULATE_VIEWS_MAX_GN
 
 
 class WarpTriangulation(dict):
@@ -33,10 +35,7 @@ class WarpTriangulation(dict):
     __getattr__ = dict.__getitem__
 
 
-def _device_tensor(x, name):
-    if not isinstance(x, torch.Tensor) or not x.is_cuda:
-        raise _lib.RomaHipError(f"roma_amd.triangulation: {name} must be a tensor on a HIP device; there is no CPU fallback")
-    return x
+_device_tensor = partial(_lib._device_tensor, module="triangulation")
 
 
 def _thresholds(max_depth, max_reproj, min_parallax, min_certainty):

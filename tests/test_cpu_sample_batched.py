@@ -98,8 +98,8 @@ def test_uniforms_are_the_devices_integers():
             assert u[i] == ((r >> 41) + 0.5) / 8388608.0
         assert np.all((u > 0) & (u < 1)) and np.all(u * 8388608.0 - 0.5 == np.round(u * 8388608.0 - 0.5))
     assert sr.SECOND_DRAW_SEED == 0x5851f42d4c957f2d
-    header = open(os.path.join(ROOT, "roma_amd", "csrc", "sample_batched.h")).read()
-    assert "0x5851f42d4c957f2d" in header
+    source = open(os.path.join(ROOT, "roma_amd", "csrc", "sample_batched.hip")).read()
+    assert "SAMPLE_SECOND_DRAW_SEED = 0x5851f42d4c957f2dull" in source
 
 
 def test_tie_rule_draw_order_and_filler():

@@ -189,7 +189,7 @@ def test_host_tensors_raise(scene_dev):
 def test_nothing_is_written_outside_the_frames(scene_dev, frames, out_f32):
     """the C entry point on an output over-allocated by one frame row of guard values on each side: 0xAB bytes (uint8) or NaN"""
     from roma_amd import _lib
-    from roma_amd.geometry import _ptr, _stream
+    from roma_amd._lib import _ptr, _stream
     s = scene_dev
     T = int(s["ts"].shape[0])
     n_out = cases.B * T * cases.H * cases.W * 3

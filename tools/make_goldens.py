@@ -25,6 +25,7 @@ fixtures are what travels to the GPU box.  Usage:
     python tools/make_goldens.py match_path    # RegressionMatcher.match(path, path) / match(PIL, PIL): the transform route
     python tools/make_goldens.py tinyroma_path # TinyRoMa.match(path, path) on the asset pair (A and B of different sizes)
     ROMA_LIB_DIR=<a build> python tools/make_goldens.py workspace_sizes  # the roma_op_*_workspace byte counts of THAT build
+    python tools/make_goldens.py abi_signatures  # the C ABI as roma_amd/_lib.py binds it: rewritten on purpose with an ABI change
 """
 import json
 import os
@@ -657,6 +658,33 @@ def workspace_sizes_golden():
     print("workspace_sizes.json", len(rows), "rows; above 2^32 bytes:", big)
 
 
+# ctypes type code -> class.  Where long and long long are both 64 bits (every platform the libraries build for) ctypes has ONE
+# type for the two, code "l" / "L": a `long long` then reads "long", and "L" can only be `unsigned long long` (the ABI has no
+# unsigned long).  "q" / "Q" are what a platform with a 32-bit long would report.
+ABI_CLASSES = {"i": "int", "l": "long", "q": "longlong", "L": "ulonglong", "Q": "ulonglong", "f": "float", "d": "double",
+               "z": "cstr", "P": "ptr"}
+
+
+def abi_classes(signatures):
+    """roma_amd._lib.SIGNATURES as {name: {"ret": class, "args": [class, ...]}}: the scalars by ctypes type code, c_char_p "cstr",
+    every other pointer flavour (c_void_p, POINTER(...)) "ptr"."""
+    import ctypes
+
+    def cls(t):
+        return "ptr" if issubclass(t, ctypes._Pointer) else ABI_CLASSES[t._type_]
+    return {name: {"ret": cls(res), "args": [cls(a) for a in args]} for name, (res, args) in signatures.items()}
+
+
+def abi_signatures_golden():
+    """The C ABI as the ctypes binding declares it, one row per exported function.  A change of the ABI has to rewrite this
+    file on purpose, next to ROMA_ABI_VERSION.  No reference, no library and no GPU involved."""
+    from roma_amd import _lib
+    rows = abi_classes(_lib.SIGNATURES)
+    with open(os.path.join(GOLD, "abi_signatures.json"), "w") as f:
+        f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in sorted(rows.items())) + "\n}\n")
+    print("abi_signatures.json", len(rows), "entries")
+
+
 if __name__ == "__main__":
     for what in sys.argv[1:]:
-        {"workspace_sizes": workspace_sizes_golden, "contract": contract, "ops": ops, "ops_nearest": ops_nearest, "tiny": tiny, "small": small, "full": full, "odd": odd, "mega": mega, "full8": full8, "full8_indoor": full8_indoor, "full_coarse": full_coarse, "kde": kde_golden, "keypoints": keypoints_golden, "keypoints_ties": keypoints_ties_golden, "vis": vis_golden, "tinyroma": tinyroma_golden, "tinyroma_xfeat": tinyroma_xfeat_golden, "forward": forward_golden, "assets": assets_golden, "match_path": match_path_golden, "tinyroma_path": tinyroma_path_golden}[what]()
+        {"abi_signatures": abi_signatures_golden, "workspace_sizes": workspace_sizes_golden, "contract": contract, "ops": ops, "ops_nearest": ops_nearest, "tiny": tiny, "small": small, "full": full, "odd": odd, "mega": mega, "full8": full8, "full8_indoor": full8_indoor, "full_coarse": full_coarse, "kde": kde_golden, "keypoints": keypoints_golden, "keypoints_ties": keypoints_ties_golden, "vis": vis_golden, "tinyroma": tinyroma_golden, "tinyroma_xfeat": tinyroma_xfeat_golden, "forward": forward_golden, "assets": assets_golden, "match_path": match_path_golden, "tinyroma_path": tinyroma_path_golden}[what]()

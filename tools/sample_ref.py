@@ -12,7 +12,7 @@ The device's definition, term for term (include/roma_hip.h):
 be driven from the device's."""
 import numpy as np
 
-SECOND_DRAW_SEED = 0x5851f42d4c957f2d  # csrc/sample_batched.h SAMPLE_SECOND_DRAW_SEED
+SECOND_DRAW_SEED = 0x5851f42d4c957f2d  # csrc/sample_batched.hip SAMPLE_SECOND_DRAW_SEED
 KEY_MAX = 3.0e38
 MASK = (1 << 64) - 1
 
