@@ -11,6 +11,8 @@ from .sampling import multinomial, sample_matches  # noqa: F401
 from .geometry import (essential_magsac, essential_minimal, estimate_pose, estimate_pose_uncalibrated, find_essential,  # noqa: F401
                        find_fundamental, find_homography, magsac, recover_pose, refine_fundamental, refine_homography, refine_pose)
 from .absolute_pose import absolute_pose_minimal, estimate_absolute_pose, lift_matches, refine_absolute_pose  # noqa: F401
+from .registration import (Similarity, TrajectoryError, align_points, apply_similarity, depth_rows, fit_similarity,  # noqa: F401
+                           refine_similarity, register_depth_maps, similarity_minimal, trajectory_error)
 from .bundle import BundleResult, ViewsReconstruction, bundle_adjust, reconstruct_pair, reconstruct_views  # noqa: F401
 from .triangulation import ViewsTriangulation, depth_consistency, triangulate, triangulate_views, triangulate_warp  # noqa: F401
 from .tracks import Tracks, build_tracks  # noqa: F401
@@ -32,6 +34,8 @@ __all__ = ["pose_error", "compute_pose_error", "homography_corner_error", "pose_
            "multinomial", "sample_matches", "find_homography", "find_fundamental", "find_essential", "recover_pose", "refine_pose", "estimate_pose",
            "refine_homography", "refine_fundamental", "estimate_pose_uncalibrated", "essential_minimal", "magsac", "essential_magsac",
            "estimate_absolute_pose", "absolute_pose_minimal", "refine_absolute_pose", "lift_matches",
+           "Similarity", "TrajectoryError", "align_points", "similarity_minimal", "refine_similarity", "fit_similarity",
+           "apply_similarity", "depth_rows", "register_depth_maps", "trajectory_error",
            "bundle_adjust", "reconstruct_pair", "BundleResult", "build_tracks", "Tracks", "triangulate_views", "ViewsTriangulation",
            "reconstruct_views", "ViewsReconstruction", "keypoints_from_matches", "SetKeypoints",
            "fuse_depth_maps", "relative_poses", "DenseFusion",

@@ -5,7 +5,8 @@ libroma_hip.so, `load("f16")` binds libroma_hip_f16.so - the same sources compil
 default amp_dtype.  Both export the same symbols; f32-only operators live in either.
 
 The signatures are not restated here: `SIGNATURES` is read from include/roma_hip.h at import (`parse_header`), the
-declarations that the compiler holds every definition in csrc/ to.
+declarations that the compiler holds every definition in csrc/ to; `EXTENSIONS` likewise from the headers of the operator
+families declared outside it (include/roma_hip_registration.h).
 
 There is deliberately NO fallback: if the HIP library is missing or does not export a symbol
 the import fails loudly (the product path never routes through the CPU oracle).
@@ -82,6 +83,19 @@ if not os.path.exists(HEADER_PATH):
     raise ImportError(f"{HEADER_PATH} not found - roma_amd reads the signatures of the C ABI from it")
 with open(HEADER_PATH) as _f:
     SIGNATURES = parse_header(_f.read())
+# the operator families declared in headers of their own (include/roma_hip_registration.h): a second table, bound by load()
+# like the first.  SIGNATURES stays the table of roma_hip.h alone, the one ROMA_ABI_VERSION counts.
+EXTENSION_HEADERS = [os.path.join(os.path.dirname(_PKG), "include", "roma_hip_registration.h")]
+EXTENSIONS = {}
+for _path in EXTENSION_HEADERS:
+    if not os.path.exists(_path):
+        raise ImportError(f"{_path} not found - roma_amd reads the signatures of the C ABI from it")
+    with open(_path) as _f:
+        _sigs = parse_header(_f.read())
+    _twice = sorted(set(_sigs) & (set(SIGNATURES) | set(EXTENSIONS)))
+    if _twice:
+        raise ImportError(f"{_path} declares {_twice} a second time")
+    EXTENSIONS.update(_sigs)
 
 _libs = {}
 
@@ -99,7 +113,7 @@ def load(fmt: str = "bf16"):
         raise ImportError(f"{path} not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(roma_amd has no CPU fallback)")
     lib = C.CDLL(path)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **EXTENSIONS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -26,6 +26,7 @@ fixtures are what travels to the GPU box.  Usage:
     python tools/make_goldens.py tinyroma_path # TinyRoMa.match(path, path) on the asset pair (A and B of different sizes)
     ROMA_LIB_DIR=<a build> python tools/make_goldens.py workspace_sizes  # the roma_op_*_workspace byte counts of THAT build
     python tools/make_goldens.py abi_signatures  # the C ABI as roma_amd/_lib.py binds it: rewritten on purpose with an ABI change
+    python tools/make_goldens.py abi_signatures_registration  # the same for include/roma_hip_registration.h (_lib.EXTENSIONS)
 """
 import json
 import os
@@ -685,6 +686,15 @@ def abi_signatures_golden():
     print("abi_signatures.json", len(rows), "entries")
 
 
+def abi_signatures_registration_golden():
+    """The registration operators of the C ABI (include/roma_hip_registration.h) as roma_amd/_lib.py binds them (EXTENSIONS)."""
+    from roma_amd import _lib
+    rows = abi_classes(_lib.EXTENSIONS)
+    with open(os.path.join(GOLD, "abi_signatures_registration.json"), "w") as f:
+        f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in sorted(rows.items())) + "\n}\n")
+    print("abi_signatures_registration.json", len(rows), "entries")
+
+
 if __name__ == "__main__":
     for what in sys.argv[1:]:
-        {"abi_signatures": abi_signatures_golden, "workspace_sizes": workspace_sizes_golden, "contract": contract, "ops": ops, "ops_nearest": ops_nearest, "tiny": tiny, "small": small, "full": full, "odd": odd, "mega": mega, "full8": full8, "full8_indoor": full8_indoor, "full_coarse": full_coarse, "kde": kde_golden, "keypoints": keypoints_golden, "keypoints_ties": keypoints_ties_golden, "vis": vis_golden, "tinyroma": tinyroma_golden, "tinyroma_xfeat": tinyroma_xfeat_golden, "forward": forward_golden, "assets": assets_golden, "match_path": match_path_golden, "tinyroma_path": tinyroma_path_golden}[what]()
+        {"abi_signatures": abi_signatures_golden, "abi_signatures_registration": abi_signatures_registration_golden, "workspace_sizes": workspace_sizes_golden, "contract": contract, "ops": ops, "ops_nearest": ops_nearest, "tiny": tiny, "small": small, "full": full, "odd": odd, "mega": mega, "full8": full8, "full8_indoor": full8_indoor, "full_coarse": full_coarse, "kde": kde_golden, "keypoints": keypoints_golden, "keypoints_ties": keypoints_ties_golden, "vis": vis_golden, "tinyroma": tinyroma_golden, "tinyroma_xfeat": tinyroma_xfeat_golden, "forward": forward_golden, "assets": assets_golden, "match_path": match_path_golden, "tinyroma_path": tinyroma_path_golden}[what]()
