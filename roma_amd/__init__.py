@@ -19,6 +19,8 @@ from .tracks import Tracks, build_tracks  # noqa: F401
 from .set_keypoints import SetKeypoints, keypoints_from_matches  # noqa: F401
 from .depth_fusion import DenseFusion, fuse_depth_maps, relative_poses  # noqa: F401
 from .point_render import PointRender, orbit_cameras, render_points  # noqa: F401
+from .tsdf import (Mesh, TSDFVolume, extract_mesh, integrate_depth_maps, mesh_from_fusion, points_bounds, tsdf_bounds,  # noqa: F401
+                   tsdf_volume, write_ply)
 from .preprocess import preprocess_images  # noqa: F401
 from .encoded import EncodedImages, all_pairs, pack_layout  # noqa: F401
 from .gt_warp import DenseMetrics, dense_metrics, get_gt_warp, warp_kpts  # noqa: F401
@@ -40,5 +42,7 @@ __all__ = ["pose_error", "compute_pose_error", "homography_corner_error", "pose_
            "reconstruct_views", "ViewsReconstruction", "keypoints_from_matches", "SetKeypoints",
            "fuse_depth_maps", "relative_poses", "DenseFusion",
            "render_points", "orbit_cameras", "PointRender",
+           "tsdf_volume", "tsdf_bounds", "points_bounds", "integrate_depth_maps", "extract_mesh", "mesh_from_fusion", "write_ply",
+           "TSDFVolume", "Mesh",
            "EncodedImages", "all_pairs", "pack_layout",
            "TinyRoMa", "tiny_roma_v1_outdoor"]

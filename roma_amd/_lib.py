@@ -5,8 +5,8 @@ libroma_hip.so, `load("f16")` binds libroma_hip_f16.so - the same sources compil
 default amp_dtype.  Both export the same symbols; f32-only operators live in either.
 
 The signatures are not restated here: `SIGNATURES` is read from include/roma_hip.h at import (`parse_header`), the
-declarations that the compiler holds every definition in csrc/ to; `EXTENSIONS` likewise from the headers of the operator
-families declared outside it (include/roma_hip_registration.h).
+declarations that the compiler holds every definition in csrc/ to; `EXTENSIONS` likewise from the header of the registration
+operators (include/roma_hip_registration.h) and `TSDF` from that of the volumetric ones (include/roma_hip_tsdf.h).
 
 There is deliberately NO fallback: if the HIP library is missing or does not export a symbol
 the import fails loudly (the product path never routes through the CPU oracle).
@@ -96,6 +96,15 @@ for _path in EXTENSION_HEADERS:
     if _twice:
         raise ImportError(f"{_path} declares {_twice} a second time")
     EXTENSIONS.update(_sigs)
+# the volumetric operators (include/roma_hip_tsdf.h): a third table.  EXTENSIONS stays the registration one, entry by entry.
+TSDF_HEADER = os.path.join(os.path.dirname(_PKG), "include", "roma_hip_tsdf.h")
+if not os.path.exists(TSDF_HEADER):
+    raise ImportError(f"{TSDF_HEADER} not found - roma_amd reads the signatures of the C ABI from it")
+with open(TSDF_HEADER) as _f:
+    TSDF = parse_header(_f.read())
+_twice = sorted(set(TSDF) & (set(SIGNATURES) | set(EXTENSIONS)))
+if _twice:
+    raise ImportError(f"{TSDF_HEADER} declares {_twice} a second time")
 
 _libs = {}
 
@@ -113,7 +122,7 @@ def load(fmt: str = "bf16"):
         raise ImportError(f"{path} not found - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                           "(roma_amd has no CPU fallback)")
     lib = C.CDLL(path)
-    for name, (res, args) in {**SIGNATURES, **EXTENSIONS}.items():
+    for name, (res, args) in {**SIGNATURES, **EXTENSIONS, **TSDF}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

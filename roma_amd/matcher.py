@@ -516,6 +516,21 @@ class RegressionMatcher:
         flags = torch.as_strided(flg, (P, H, Wd), (H * Wd, Wd, 1), flg.storage_offset())
         return fuse_depth_maps(points, flags, certainty, pairs, K_grid, R, t, symmetric=symmetric, images=images, view_valid=view_valid, **kw)
 
+    def mesh_image_set(self, warp, certainty, pairs, K, R, t, sizes, images=None, view_valid=None, mesh=None, **kw):
+        """`fuse_image_set` with the same arguments, then `roma_amd.mesh_from_fusion` on its fused depth maps: the warps of an image
+        set and the poses of its views to one coloured triangle mesh - composition only, nothing read back.  mesh: a dict of
+        keywords for `mesh_from_fusion` (dims, trunc_voxels, margin, min_weight, max_vertices, max_faces, ..); **kw goes to
+        `fuse_image_set`.  Returns (Mesh, TSDFVolume, DenseFusion); the volume can take further views, `integrate_depth_maps`."""
+        from .bundle import _view_cameras
+        from .tsdf import mesh_from_fusion
+        fusion = self.fuse_image_set(warp, certainty, pairs, K, R, t, sizes, images=images, view_valid=view_valid, **kw)
+        H, W = int(fusion.depth.shape[-2]), int(fusion.depth.shape[-1])
+        K_img = _view_cameras(K, 1, len(sizes), warp.device)[0]
+        K_grid = torch.stack([torch.stack((K_img[v, 0] * (W / int(w_img)), K_img[v, 1] * (H / int(h_img)), K_img[v, 2]))
+                              for v, (h_img, w_img) in enumerate(sizes)])
+        out, volume = mesh_from_fusion(fusion, K_grid, R, t, images, view_valid=view_valid, **(mesh or {}))
+        return out, volume, fusion
+
     def dense_reconstruct_image_set(self, images, K, norm_thresh, reproj_thresh, *, pairs=None, num=5000, seed=None, max_tracks=None,
                                     fusion=None, **kw):
         """2 .. 8 decoded images to a dense reconstruction - `reconstruct_image_set`'s steps with the warp and the certainty kept,

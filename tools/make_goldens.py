@@ -27,6 +27,7 @@ fixtures are what travels to the GPU box.  Usage:
     ROMA_LIB_DIR=<a build> python tools/make_goldens.py workspace_sizes  # the roma_op_*_workspace byte counts of THAT build
     python tools/make_goldens.py abi_signatures  # the C ABI as roma_amd/_lib.py binds it: rewritten on purpose with an ABI change
     python tools/make_goldens.py abi_signatures_registration  # the same for include/roma_hip_registration.h (_lib.EXTENSIONS)
+    python tools/make_goldens.py abi_signatures_tsdf  # the same for include/roma_hip_tsdf.h (_lib.TSDF)
 """
 import json
 import os
@@ -695,6 +696,15 @@ def abi_signatures_registration_golden():
     print("abi_signatures_registration.json", len(rows), "entries")
 
 
+def abi_signatures_tsdf_golden():
+    """The volumetric operators of the C ABI (include/roma_hip_tsdf.h) as roma_amd/_lib.py binds them (TSDF)."""
+    from roma_amd import _lib
+    rows = abi_classes(_lib.TSDF)
+    with open(os.path.join(GOLD, "abi_signatures_tsdf.json"), "w") as f:
+        f.write("{\n" + ",\n".join(f"{json.dumps(k)}: {json.dumps(v)}" for k, v in sorted(rows.items())) + "\n}\n")
+    print("abi_signatures_tsdf.json", len(rows), "entries")
+
+
 if __name__ == "__main__":
     for what in sys.argv[1:]:
-        {"abi_signatures": abi_signatures_golden, "abi_signatures_registration": abi_signatures_registration_golden, "workspace_sizes": workspace_sizes_golden, "contract": contract, "ops": ops, "ops_nearest": ops_nearest, "tiny": tiny, "small": small, "full": full, "odd": odd, "mega": mega, "full8": full8, "full8_indoor": full8_indoor, "full_coarse": full_coarse, "kde": kde_golden, "keypoints": keypoints_golden, "keypoints_ties": keypoints_ties_golden, "vis": vis_golden, "tinyroma": tinyroma_golden, "tinyroma_xfeat": tinyroma_xfeat_golden, "forward": forward_golden, "assets": assets_golden, "match_path": match_path_golden, "tinyroma_path": tinyroma_path_golden}[what]()
+        {"abi_signatures": abi_signatures_golden, "abi_signatures_registration": abi_signatures_registration_golden, "abi_signatures_tsdf": abi_signatures_tsdf_golden, "workspace_sizes": workspace_sizes_golden, "contract": contract, "ops": ops, "ops_nearest": ops_nearest, "tiny": tiny, "small": small, "full": full, "odd": odd, "mega": mega, "full8": full8, "full8_indoor": full8_indoor, "full_coarse": full_coarse, "kde": kde_golden, "keypoints": keypoints_golden, "keypoints_ties": keypoints_ties_golden, "vis": vis_golden, "tinyroma": tinyroma_golden, "tinyroma_xfeat": tinyroma_xfeat_golden, "forward": forward_golden, "assets": assets_golden, "match_path": match_path_golden, "tinyroma_path": tinyroma_path_golden}[what]()
